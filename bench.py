@@ -7,11 +7,17 @@ on the synthetic 20,000 genes x 200 samples matrix of BASELINE config 3, inputs 
 HBM. `value` = sum over steps of the pooled bulk-ESS (min over the six hyper-parameters and lp__) divided
 by the summed wall time (barrier + device synchronise on both sides, max over ranks). Chains are the
 sharded unit (weak scaling: chains/GPU fixed); there is no collective on the data path. The timed fits run the
-library's defaults (pipelined rounds, three chain groups on their own streams); the `roofline` sample comes from one
-more fit on a single in-order stream, from HIP events attached to the merged launch's dispatches (hipExtLaunchKernel: the
-kernel's own duration, as a kernel trace sees it).
+library's defaults (pipelined rounds, three chain groups on their own streams).
+
+A plain run does only what the headline needs: set-up, warm-up fits, the timed fits and their pooled ESS, the result
+line. Everything else moves behind --full: the gene-level ESS median, the posterior-predictive kernel's object, the fits
+of cfg3 as named (one chain per GPU), the `roofline` (in chains mode sampled from one more fit on a single in-order
+stream, from HIP events attached to the merged launch's dispatches -- hipExtLaunchKernel: the kernel's own duration, as a
+kernel trace sees it), the CPU baselines and the outlier-call concordance. --dump-outputs DIR writes what the last timed
+fit returned (rank 0) as .npy files, so that two builds can be compared output for output on the same seeded inputs.
 
     python bench.py --gpus 1 --steps 2 --warmup 1
+    python bench.py --gpus 1 --steps 2 --warmup 1 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 """
@@ -48,6 +54,13 @@ def main():
                     help="shards mode: how the ranks' partial sums meet every leapfrog -- direct: peer-mapped buffers written by the "
                          "state machines inside the merged launch of a pipelined round (no collective call); rccl: an RCCL "
                          "all-reduce between the launches of the three-launch round")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything besides the headline (the objects below that a plain run leaves "
+                         "null): the options from --no-cpu-baseline on apply to such a run only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed fit returned on rank 0 as DIR/<name>.npy (float64): "
+                         "a fixed, seeded sample of the draws' columns, the adapted inverse metric at the same columns and the "
+                         "per-iteration diagnostics")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--no-cpu-full-cfg2", action="store_true",
@@ -64,6 +77,8 @@ def main():
                     help="fits of the configuration AS BASELINE cfg3 names it (1 chain per GPU), reported beside the headline "
                          "(0 = skip); outside the timed region of the headline")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     from ppcseq_amd import _lib, distributed as D
@@ -156,6 +171,7 @@ def main():
     ess_detail, depth_mean, div_total = None, [], 0
     step_ms, stuck_fits = [], 0
     xchg_wait = (0.0, 0)
+    ess_gene_median, outputs = None, None
     for k in range(args.steps):
         barrier()
         t0 = time.perf_counter()
@@ -176,11 +192,12 @@ def main():
             lp = D.all_gather_chains(lp, device=dev)
             ge = D.all_gather_chains(ge, device=dev)
         per = [ess_bulk(hyp[:, :, j]) for j in range(6)] + [ess_bulk(lp)]
-        # also the median over gene-level parameters (a sample of 128 intercepts and 128 sigma_raw; this rank's chains)
-        gsel = np.unique(np.linspace(0, model_G - 1, 128).astype(int))
-        gcols = [3 + int(g) for g in gsel] + [Dm - 3 - model_G + int(g) for g in gsel]
-        gene_draws = fit.columns(gcols)
-        ess_gene_median = float(np.median([ess_bulk(gene_draws[:, :, j]) for j in range(gene_draws.shape[2])]))
+        if args.full:
+            # also the median over gene-level parameters (a sample of 128 intercepts and 128 sigma_raw; this rank's chains)
+            gsel = np.unique(np.linspace(0, model_G - 1, 128).astype(int))
+            gcols = [3 + int(g) for g in gsel] + [Dm - 3 - model_G + int(g) for g in gsel]
+            gene_draws = fit.columns(gcols)
+            ess_gene_median = float(np.median([ess_bulk(gene_draws[:, :, j]) for j in range(gene_draws.shape[2])]))
         tot_ess += float(np.nanmin(per))
         ess_detail = per
         tot_time += dt
@@ -199,17 +216,23 @@ def main():
         if xchg is not None:
             xw_us, xn = fit.xchg_timing()
             xchg_wait = (xchg_wait[0] + xw_us * xn, xchg_wait[1] + xn)
+        if rank == 0 and k == args.steps - 1 and args.dump_outputs:
+            outputs = fit_outputs(fit, dg)
         # the posterior-predictive kernel on this fit's draws (outside the timed region; rank 0, last step)
-        if rank == 0 and k == args.steps - 1 and not args.no_ppc and args.mode == "chains":
+        if rank == 0 and k == args.steps - 1 and args.full and not args.no_ppc and args.mode == "chains":
             ppc_obj = ppc_object(fit, K, S, C)
         fit.close()
+    if outputs is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in outputs.items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
 
     launch_used = model.get_launch()           # (lanes per gene, workgroups) of the timed fits' log-likelihood launches
     # BASELINE cfg3 as named: 8 chains, ONE per GPU (at N GPUs: N chains). A lone chain leaves the GPU mostly idle (a
     # leapfrog round costs the same for 1 chain as for 8), so this line scales strongly with nothing to gain from it; it is
     # reported for completeness, never as `value`.
     as_named = None
-    if args.mode == "chains" and args.as_named_steps > 0:
+    if args.full and args.mode == "chains" and args.as_named_steps > 0:
         t_an, ess_an = 0.0, 0.0
         for k in range(args.as_named_steps):
             barrier()
@@ -232,7 +255,7 @@ def main():
     # The same fit on ONE in-order stream: the merged launch's own start / stop events then time that launch alone, which is what
     # the roofline object needs (with chain groups on several streams another group's kernels share the chip with it).
     single = None
-    if args.mode == "chains" and args.single_stream_steps > 0:
+    if args.full and args.mode == "chains" and args.single_stream_steps > 0:
         model.set_rounds(stream_groups=1)
         try:
             t_g, ess_g = 0.0, 0.0
@@ -265,7 +288,7 @@ def main():
         E = 0
         b_grad = 4.0 * G * S + 16.0 * (C + 1) * G + 8.0 * S * (C + 1) + 4.0 * E
         roof = None
-        if kA_n > 0:
+        if args.full and kA_n > 0:
             ms = kA_ms / kA_n
             chains_per_launch = kA_chains / kA_n
             if args.mode == "shards":
@@ -288,7 +311,7 @@ def main():
                             "WRITE_SIZE of the PMC passes is far below the algorithmic bytes), and the kernel is bound by fp64 "
                             "vector issue, not by HBM (profiles/ README: instructions per cell, VALU busy share)."}
         cpu = None
-        if not args.no_cpu_baseline and world == 1:        # reported at N = 1 only (rank 0's host cores)
+        if args.full and not args.no_cpu_baseline and world == 1:        # reported at N = 1 only (rank 0's host cores)
             cpu = cpu_baseline(arrays, K, tot_ess, tot_grad, args)
         out = {
             "metric": "effective samples/sec (whole node) for NB hierarchical fit",
@@ -304,7 +327,7 @@ def main():
                        "mode": args.mode, "chains_total": nch * world if args.mode == "chains" else nch, "lanes_per_gene": launch_used[0], "loglik_workgroups": launch_used[1],
                        "ess_estimator": "rank-normalised split-chain bulk-ESS, min over 6 hyper-parameters and lp__",
                        "ess_last_step": [round(float(x), 1) for x in ess_detail],
-                       "ess_median_intercept_sigma_raw_rank0_chains": round(ess_gene_median, 1),
+                       "ess_median_intercept_sigma_raw_rank0_chains": None if ess_gene_median is None else round(ess_gene_median, 1),
                        "grad_evals": tot_grad, "mean_treedepth": round(float(np.mean(depth_mean)), 2),
                        "divergent_after_warmup": div_total,
                        "ms_per_step_min_max": [round(min(step_ms), 1), round(max(step_ms), 1)] if step_ms else None,
@@ -320,7 +343,7 @@ def main():
                                             "(100 MHz wall clock), rank 0; it runs beside the log-likelihood workgroups of the same launch, so it is "
                                             "not added to the round. One rank: no exchange takes place"} if args.mode == "shards" else {})},
             "roofline": roof, "ppc": ppc_obj, "cpu_baseline": cpu, "as_named_cfg3_one_chain_per_gpu": as_named, "single_stream": single,
-            "concordance": None if (args.no_cpu_baseline or world > 1) else outlier_concordance(),
+            "concordance": outlier_concordance() if (args.full and not args.no_cpu_baseline and world == 1) else None, "full": args.full,
         }
         if cpu is not None and not args.no_cpu_full_cfg2 and world == 1:
             # the one CPU / GPU pair that is MEASURED end to end (whole fits of cfg2), beside the extrapolated cfg3 figure
@@ -337,6 +360,22 @@ def main():
         import torch.distributed as dist
         dist.barrier()
         dist.destroy_process_group()
+
+
+def fit_outputs(fit, dg, budget_bytes=48 << 20):
+    """What a caller of the timed path receives from one fit, as float64 arrays for --dump-outputs. The kept draws of every
+    parameter are too large at cfg3 (8 x 250 x 41 006 doubles), so the draws and the adapted inverse metric are taken at a
+    fixed, seeded sample of the columns that always holds the six hyper-parameters; the sample fits in `budget_bytes`."""
+    D = fit.D
+    hyper = np.unique([0, 1, 2, D - 3, D - 2, D - 1])
+    rest = np.setdiff1d(np.arange(D), hyper)
+    n_cols = budget_bytes // (8 * fit.chains * (fit.n_keep + 1))
+    pick = np.random.default_rng(20253).choice(rest, size=int(min(rest.size, max(0, n_cols - hyper.size))), replace=False)
+    cols = np.sort(np.concatenate([hyper, pick]))
+    out = {"draws_columns": cols.astype(np.float64), "draws": fit.columns(cols),
+           "inv_metric": fit.inv_metric()[:, cols]}
+    out.update({k: v.astype(np.float64) for k, v in dg.items()})
+    return out
 
 
 def pmc_traffic(chains_per_launch):

@@ -11,7 +11,7 @@ set -e
 R=${1:-r04}
 OUT=gpurun_out/shards_$R
 mkdir -p $OUT
-A="--mode shards --genes 50000 --samples 500 --chains-per-gpu 4 --steps 1 --warmup 0 --no-cpu-baseline --as-named-steps 0"
+A="--full --mode shards --genes 50000 --samples 500 --chains-per-gpu 4 --steps 1 --warmup 0 --no-cpu-baseline --as-named-steps 0"
 python3 bench.py $A 2> $OUT/one.err | grep '^{' > $OUT/${R}_bench_cfg4_shards_1gpu.json
 PPCX_DIST_BACKEND=gloo python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus 2 $A 2> $OUT/two.err | grep '^{' > $OUT/${R}_bench_cfg4_shards_2ranks_1gpu.json
 python3 bench.py $A --exchange rccl 2> $OUT/rccl.err | grep '^{' > $OUT/${R}_bench_cfg4_shards_rccl_1gpu.json
