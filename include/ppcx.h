@@ -121,6 +121,16 @@ PPCX_API int ppcx_fit_from_draws(ppcx_model* m, int chains, int n_keep, const do
 PPCX_API int ppcx_fit_get_draws(ppcx_fit* f, double* out);
 /* selected columns of the kept draws, [chains*n_keep][n_cols] */
 PPCX_API int ppcx_fit_get_columns(ppcx_fit* f, int n_cols, const int32_t* cols, double* out);
+/* Per-column summary of the kept draws (rstan::monitor, and the checks rstan::sampling runs after a fit: R-hat > 1.05, bulk or
+ * tail ESS < 100 x chains). out[i][PPCX_SUMMARY_FIELDS] for column cols[i] (-1 = lp__): mean, sd (ddof 1), q05, q50, q95 (type 7)
+ * over all draws; the rank-normalised split R-hat (the larger of the bulk and the folded one); the bulk ESS of the rank-normalised
+ * split chains; the tail ESS (the smaller of those of 1[x <= q05] and 1[x <= q95]) -- Vehtari, Gelman, Simpson, Carpenter, Buerkner
+ * (2021). A column with a non-finite draw is NaN throughout; one without variance, or with fewer than 4 draws per chain, has NaN
+ * R-hat and ESS. NUTS fits of every entry point and ppcx_fit_from_draws fits (which hold no lp__); an ADVI fit, a column out of
+ * range, -1 on a fit without lp__ or more than 128 chains: PPCX_ERR_ARG (PPCX_ERR_LIMIT for the chains). Synchronous on the
+ * model's stream; the same bits on every call.                                                                              */
+#define PPCX_SUMMARY_FIELDS 8   /* mean, sd, q05, q50, q95, rhat, ess_bulk, ess_tail */
+PPCX_API int ppcx_fit_summary(ppcx_fit* f, int n_cols, const int32_t* cols, double* out);
 /* lp: [chains][n_keep]; the rest [chains][iter] (warmup included); any pointer may be NULL */
 PPCX_API int ppcx_fit_get_diagnostics(ppcx_fit* f, double* lp, double* stepsize, int32_t* treedepth,
                              int32_t* n_leapfrog, int32_t* divergent, double* accept);

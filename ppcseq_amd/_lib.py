@@ -23,9 +23,10 @@ EXPORTS = [
     "ppcx_fit_nuts_comm", "ppcx_advi_config_default", "ppcx_fit_advi", "ppcx_fit_advi_info", "ppcx_fit_advi_iterative",
     "ppcx_guard_decision", "ppcx_device_memory", "ppcx_fit_get_ppc_timing",
     "ppcx_xchg_create", "ppcx_xchg_handle", "ppcx_xchg_connect", "ppcx_xchg_connect_local", "ppcx_xchg_set_timeout", "ppcx_xchg_destroy",
-    "ppcx_fit_nuts_xchg", "ppcx_fit_get_xchg_timing", "ppcx_fit_get_inv_metric",
+    "ppcx_fit_nuts_xchg", "ppcx_fit_get_xchg_timing", "ppcx_fit_get_inv_metric", "ppcx_fit_summary",
 ]
 ABI_VERSION = 400           # include/ppcx.h PPCX_VERSION this binding was written for
+SUMMARY_FIELDS = ("mean", "sd", "q05", "q50", "q95", "rhat", "ess_bulk", "ess_tail")   # PPCX_SUMMARY_FIELDS, in order
 
 
 class PpcxError(RuntimeError):
@@ -92,6 +93,7 @@ def load() -> C.CDLL:
     lib.ppcx_fit_from_draws.argtypes = [C.c_void_p, C.c_int, C.c_int, dp, C.POINTER(C.c_void_p)]
     lib.ppcx_fit_get_draws.argtypes = [C.c_void_p, dp]
     lib.ppcx_fit_get_columns.argtypes = [C.c_void_p, C.c_int, ip, dp]
+    lib.ppcx_fit_summary.argtypes = [C.c_void_p, C.c_int, ip, dp]
     lib.ppcx_fit_get_diagnostics.argtypes = [C.c_void_p, dp, dp, ip, ip, ip, dp]
     lib.ppcx_fit_get_timing.argtypes = [C.c_void_p, dp, C.POINTER(C.c_longlong), dp, C.POINTER(C.c_longlong), dp]
     lib.ppcx_fit_get_kernel_times.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(C.c_longlong)]
@@ -435,6 +437,19 @@ class Fit:
         out = np.zeros((self.chains, self.n_keep, cols.size))
         _check(load().ppcx_fit_get_columns(self._h, int(cols.size), _p(cols, C.c_int32), _p(out, C.c_double)))
         return out
+
+    def summary(self, cols=None, lp=True):
+        """Per-column summary on the device (include/ppcx.h ppcx_fit_summary; rstan::monitor): a dict of 1-D float64 arrays
+        mean, sd, q05, q50, q95, rhat, ess_bulk, ess_tail, and `column` (the column index, -1 for lp__). cols=None: all D
+        columns; lp: lp__ last."""
+        cols = np.arange(self.D) if cols is None else np.asarray(cols, dtype=np.int64).ravel()
+        cols = np.ascontiguousarray(np.concatenate([cols, [-1]]) if lp else cols, dtype=np.int32)
+        out = np.zeros((cols.size, len(SUMMARY_FIELDS)))
+        if cols.size:
+            _check(load().ppcx_fit_summary(self._h, int(cols.size), _p(cols, C.c_int32), _p(out, C.c_double)))
+        res = {k: out[:, i].copy() for i, k in enumerate(SUMMARY_FIELDS)}
+        res["column"] = cols.astype(np.int64)
+        return res
 
     def diagnostics(self):
         lp = np.zeros((self.chains, self.n_keep))

@@ -11,8 +11,8 @@ LIB = os.path.join(HERE, "libppcx.so")
 # the testing build (-DPPCX_TESTING: fault injection, forced cell paths, kernel-level timing; csrc/ppcx_testing.h) lives
 # with the tests, not in the package
 TESTING_LIB = os.path.join(os.path.dirname(HERE), "tests", "libppcx_testing.so")
-SOURCES = ["ppcx_kernels.hip", "ppcx_capi.hip"]
-HEADERS = ["ppcx_math.h", "ppcx_disp.h", "ppcx_model.h", "ppcx_nuts.h", "ppcx_gene.h", "ppcx_kernels.h", "ppcx_testing.h",
+SOURCES = ["ppcx_kernels.hip", "ppcx_summary.hip", "ppcx_capi.hip"]
+HEADERS = ["ppcx_math.h", "ppcx_disp.h", "ppcx_model.h", "ppcx_nuts.h", "ppcx_gene.h", "ppcx_kernels.h", "ppcx_summary.h", "ppcx_testing.h",
            os.path.join("..", "..", "include", "ppcx.h")]
 
 
@@ -37,7 +37,7 @@ def _compile(lib: str, extra, verbose: bool) -> None:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objs = []
     procs = []
-    for s in SOURCES:                            # the two translation units side by side
+    for s in SOURCES:                            # the translation units side by side
         o = lib + "." + s + ".o"
         objs.append(o)
         cmd = [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden", "-Wno-unused-result"] + CODEGEN_FLAGS + extra + \

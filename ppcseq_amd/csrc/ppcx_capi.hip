@@ -17,6 +17,7 @@
 #include <vector>
 #include "../../include/ppcx.h"
 #include "ppcx_kernels.h"
+#include "ppcx_summary.h"
 
 using namespace ppcx;
 
@@ -95,6 +96,7 @@ struct ppcx_fit {
   double ppc_ms = 0; long long ppc_draws = 0;  // last ppcx_fit_ppc: kernel time (HIP events) and NB draws generated
   long long xchg_ticks = 0, xchg_count = 0;    // direct exchange: 100 MHz ticks the chains' state machines waited for peers, exchanges
   std::vector<double> inv_metric;              // [chains][D] diagonal of the adapted inverse metric (host; ppcx_fit_get_inv_metric)
+  bool advi = false;                           // draws of an ADVI approximation (independent: ppcx_fit_summary refuses them)
 };
 
 extern "C" int ppcx_version(void) { return PPCX_VERSION; }
@@ -1571,7 +1573,7 @@ extern "C" int ppcx_fit_advi(ppcx_model* m, const ppcx_advi_config* cfg, ppcx_fi
   }
   // ---- output_samples draws from the fitted approximation (kept as a one-chain fit)
   ppcx_fit* f = new ppcx_fit();
-  fit_attach(f, m); f->chains = 1; f->n_keep = cfg->output_samples; f->iter = iters_done;
+  fit_attach(f, m); f->chains = 1; f->n_keep = cfg->output_samples; f->iter = iters_done; f->advi = true;
   memset(&f->cfg, 0, sizeof f->cfg);
 #define AHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ppcx_fit_free(f); return fail(PPCX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
   AHIP(hipMalloc(&f->d_draws, sizeof(double) * (size_t)cfg->output_samples * D));
@@ -1792,6 +1794,51 @@ extern "C" int ppcx_fit_get_columns(ppcx_fit* f, int n_cols, const int32_t* cols
   if (e != hipSuccess) rc = fail(PPCX_ERR_HIP, hipGetErrorString(e));
   (void)hipFree(d_cols); (void)hipFree(d_out);
   return rc;
+}
+// Fit summary (rstan::monitor): the columns go through column-major scratch in batches of at most kSummaryScratchBytes (never a
+// second copy of all the draws), one workgroup per column (ppcx_summary.hip)
+constexpr size_t kSummaryScratchBytes = (size_t)256 << 20;
+extern "C" int ppcx_fit_summary(ppcx_fit* f, int n_cols, const int32_t* cols, double* out) {
+  if (!f || !cols || !out || n_cols < 1) return fail(PPCX_ERR_ARG, "bad arguments");
+  if (f->advi) return fail(PPCX_ERR_ARG, "an ADVI fit has independent draws: R-hat and ESS are not defined for it (rstan::vb reports neither)");
+  const int D = f->m->d.D, M = f->chains, n = f->n_keep;
+  for (int i = 0; i < n_cols; ++i) {
+    if (cols[i] < -1 || cols[i] >= D) return fail(PPCX_ERR_ARG, "column out of range");
+    if (cols[i] == -1 && !f->d_lp) return fail(PPCX_ERR_ARG, "this fit holds no lp__ (a fit over draws produced elsewhere)");
+  }
+  if (M < 1 || n < 1) return fail(PPCX_ERR_ARG, "fit holds no kept draws");
+  if (M > kSummaryMaxChains) return fail(PPCX_ERR_LIMIT, "ppcx_fit_summary takes at most 128 chains");
+  HIPCHK(hipSetDevice(f->m->device));
+  hipStream_t st = f->m->stream;
+  const long rows = (long)M * n;
+  const bool lds = summary_lds_bytes(M, n) > 0;
+  const long slice = summary_slice_doubles(M, n);
+  // per batch: the columns ([batch][M n]) and, on the global path, a slice per workgroup
+  int batch = (int)std::max<size_t>(1, kSummaryScratchBytes / 2 / (sizeof(double) * (size_t)rows));
+  if (batch > n_cols) batch = n_cols;
+  int nslices = lds ? 0 : (int)std::max<size_t>(1, kSummaryScratchBytes / 2 / (sizeof(double) * (size_t)slice));
+  if (nslices > batch) nslices = batch;
+  if (nslices > 2048) nslices = 2048;
+  int* d_cols = nullptr; double *d_x = nullptr, *d_out = nullptr, *d_scr = nullptr;
+  hipError_t e = hipMalloc(&d_cols, sizeof(int) * (size_t)n_cols);
+  if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(double) * SUM_FIELDS * (size_t)n_cols);
+  if (e == hipSuccess) e = hipMalloc(&d_x, sizeof(double) * (size_t)rows * batch);
+  if (e == hipSuccess && !lds) e = hipMalloc(&d_scr, sizeof(double) * (size_t)slice * nslices);
+  if (e == hipSuccess) e = hipMemcpy(d_cols, cols, sizeof(int) * (size_t)n_cols, hipMemcpyHostToDevice);
+  for (int b0 = 0; e == hipSuccess && b0 < n_cols; b0 += batch) {
+    const int nb = n_cols - b0 < batch ? n_cols - b0 : batch;
+    e = launch_summary_gather_kernel(f->d_draws, f->d_lp, rows, D, d_cols + b0, nb, d_x, st);
+    if (e != hipSuccess) break;
+    SummaryArgs a;
+    a.x = d_x; a.n_cols = nb; a.M = M; a.n = n; a.npad = summary_npad(M, n);
+    a.out = d_out + (size_t)b0 * SUM_FIELDS; a.scratch = d_scr; a.slice = slice;
+    e = launch_summary_kernel(a, lds ? nb : nslices, st);
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = hipMemcpy(out, d_out, sizeof(double) * SUM_FIELDS * (size_t)n_cols, hipMemcpyDeviceToHost);
+  (void)hipFree(d_cols); (void)hipFree(d_x); (void)hipFree(d_out); (void)hipFree(d_scr);
+  if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
+  return PPCX_OK;
 }
 extern "C" int ppcx_fit_get_diagnostics(ppcx_fit* f, double* lp, double* stepsize, int32_t* treedepth,
                                         int32_t* n_leapfrog, int32_t* divergent, double* accept) {

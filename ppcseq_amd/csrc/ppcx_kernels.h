@@ -162,6 +162,23 @@ hipError_t launch_ppc_wave_kernel(const PpcArgs& a, const double* T, int nblocks
 hipError_t launch_disp_build_kernel(const int* counts, int G, int S, const int* genes, int n_genes, const DispFit& fit, double* table, hipStream_t st);
 hipError_t launch_gather_kernel(const double* draws, long n_rows, int D, const int* cols, int n_cols, double* out, hipStream_t st);
 hipError_t launch_fill_kernel(double* p, long n, double val, hipStream_t st);
+
+// the fit summary (ppcx_summary.hip, statistics in ppcx_summary.h): columns of up to kSummaryLdsDraws draws are summarised in
+// LDS (sort buffer + sequences: 128 KB at most), longer ones on a slice of global scratch per workgroup
+constexpr int kSummaryLdsDraws = 8192;
+constexpr int kSummaryMaxChains = 128;
+struct SummaryArgs {
+  const double* x;              // [n_cols][M n] the columns, chain-major (ppcx_summary_gather_kernel)
+  int n_cols, M, n;
+  int npad;                     // summary_npad(M, n): the sort buffer
+  double* out;                  // [n_cols][SUM_FIELDS]
+  double* scratch; long slice;  // null: LDS path; else [grid][slice] doubles (summary_slice_doubles)
+};
+int summary_npad(int M, int n);
+long summary_slice_doubles(int M, int n);
+size_t summary_lds_bytes(int M, int n);       // 0: the columns are too long for the LDS path
+hipError_t launch_summary_gather_kernel(const double* draws, const double* lp, long rows, int D, const int* cols, int n_cols, double* out, hipStream_t st);
+hipError_t launch_summary_kernel(const SummaryArgs& a, int nblocks, hipStream_t st);
 hipError_t launch_xchg_abort_kernel(const XchgArgs& x, hipStream_t st);      // tells every peer that this rank has left the fit
 
 }  // namespace ppcx

@@ -1,0 +1,244 @@
+// ppcx_summary.hip -- gfx950 kernels of the fit summary (ppcx_fit_summary, include/ppcx.h): per column of the kept draws the
+// plain summary, the rank-normalised split R-hat and the bulk / tail ESS (the statistics: ppcx_summary.h).
+//
+//   ppcx_summary_gather_kernel  a batch of columns of the draws [M n][D] (or lp__) into column-major scratch [batch][M n],
+//                               32 x 33 LDS tiles: reads along the columns, writes along the draws, both coalesced.
+//   ppcx_summary_kernel<LDS>    one workgroup per column: bitonic sort of the split values, average ranks by binary search of
+//                               the sorted copy (exact for ties, no index array), Blom z, the sequences' means and variances
+//                               (one wavefront per sequence), the autocovariances in chunks of kSummaryLags lags as far as
+//                               Geyer's truncation asks for them. LDS = true: the sort buffer and the sequence values live in
+//                               LDS (columns of up to kSummaryLdsDraws draws); LDS = false: the same code on a slice of a
+//                               global scratch buffer per workgroup (longer columns; a workgroup's own stores are visible to
+//                               its waves after the barrier, as in the posterior-predictive kernel's global path).
+// A column's result depends on its draws only (fixed reduction orders): the same bits on every call and in both paths.
+#include <hip/hip_runtime.h>
+#include "ppcx_summary.h"
+#include "ppcx_kernels.h"
+
+namespace ppcx {
+
+constexpr int kSummaryThreads = 256;
+constexpr int kSummaryWaves = kSummaryThreads / 64;
+constexpr int kSummaryLags = 16;              // autocovariance lags per chunk (even: a chunk holds whole Geyer pairs)
+
+__global__ __launch_bounds__(256) void ppcx_summary_gather_kernel(const double* draws, const double* lp, long rows, int D,
+                                                                  const int* cols, int n_cols, double* out) {
+  __shared__ double tile[32][33];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;          // 32 x 8
+  const long r0 = (long)blockIdx.x * 32; const int c0 = blockIdx.y * 32;
+  for (int r = ty; r < 32; r += 8) {
+    const long row = r0 + r; const int c = c0 + tx;
+    double v = 0.0;
+    if (row < rows && c < n_cols) { const int col = cols[c]; v = col < 0 ? lp[row] : draws[row * D + col]; }
+    tile[r][tx] = v;
+  }
+  __syncthreads();
+  for (int r = ty; r < 32; r += 8) {
+    const int c = c0 + r; const long row = r0 + tx;
+    if (row < rows && c < n_cols) out[(long)c * rows + row] = tile[tx][r];
+  }
+}
+
+__device__ __forceinline__ double summary_wave_sum(double v) {
+#pragma unroll
+  for (int msk = 1; msk < 64; msk <<= 1) v += __shfl_xor(v, msk, 64);
+  return v;                                    // the same bits in every lane
+}
+// sum over the workgroup in a fixed order; every thread gets it. red: kSummaryWaves doubles of LDS
+__device__ double summary_block_sum(double v, double* red) {
+  v = summary_wave_sum(v);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  double s = 0.0;
+  for (int w = 0; w < kSummaryWaves; ++w) s += red[w];
+  return s;
+}
+__device__ bool summary_block_any(bool b) { return __syncthreads_or(b ? 1 : 0) != 0; }
+
+// ascending bitonic sort of s[0 .. npad) (npad a power of two; the caller pads with +inf)
+__device__ void summary_sort(double* s, int npad) {
+  for (int k = 2; k <= npad; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = threadIdx.x; i < (npad >> 1); i += kSummaryThreads) {
+        const int lo = 2 * j * (i / j) + (i % j), hi = lo + j;
+        const bool up = (lo & k) == 0;
+        const double a = s[lo], b = s[hi];
+        if ((a > b) == up) { s[lo] = b; s[hi] = a; }
+      }
+      __syncthreads();
+    }
+  }
+}
+__device__ __forceinline__ int summary_pow2(long n) { int p = 1; while (p < n) p <<= 1; return p; }
+
+struct SummaryShared {
+  double red[kSummaryWaves];
+  double rho[kSummaryLags];
+  double part[kSummaryWaves][kSummaryLags];
+  double seq_mean[2 * kSummaryMaxChains];
+  double seq_var[2 * kSummaryMaxChains];
+};
+
+// R-hat of the m sequences z[j n' .. (j + 1) n'), and with want_ess their ESS (z is then centred in place). One wavefront per
+// sequence for the means and variances; the autocovariances summed over all sequences in chunks of kSummaryLags lags.
+__device__ double summary_sequences(double* z, int m, int nh, bool want_ess, double* ess, SummaryShared& sh) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int j = wave; j < m; j += kSummaryWaves) {
+    const double* q = z + (long)j * nh;
+    double s = 0.0;
+    for (int i = lane; i < nh; i += 64) s += q[i];
+    const double mu = summary_wave_sum(s) / nh;
+    double v = 0.0;
+    for (int i = lane; i < nh; i += 64) { const double d = q[i] - mu; v += d * d; }
+    v = summary_wave_sum(v) / (nh - 1.0);
+    if (lane == 0) { sh.seq_mean[j] = mu; sh.seq_var[j] = v; }
+  }
+  __syncthreads();
+  double mm = 0.0, mv = 0.0;
+  for (int j = 0; j < m; ++j) { mm += sh.seq_mean[j]; mv += sh.seq_var[j]; }
+  mm /= m; mv /= m;
+  double vm = 0.0;
+  for (int j = 0; j < m; ++j) vm += (sh.seq_mean[j] - mm) * (sh.seq_mean[j] - mm);
+  vm /= (m - 1.0);
+  const double rh = rhat_from(vm, mv, nh);
+  if (!want_ess) return rh;
+  const double vp = var_plus_of(vm, mv, nh);
+  if (!(vp > 0.0)) { *ess = NAN; __syncthreads(); return rh; }
+  const long N = (long)m * nh;
+  for (long k = threadIdx.x; k < N; k += kSummaryThreads) z[k] -= sh.seq_mean[k / nh];
+  __syncthreads();
+  Geyer g;                                      // every thread runs the same scalar recurrence on the same values
+  bool started = false;
+  for (int t0 = 0; ; t0 += kSummaryLags) {
+    double acc[kSummaryLags];
+#pragma unroll
+    for (int l = 0; l < kSummaryLags; ++l) acc[l] = 0.0;
+    for (long k = threadIdx.x; k < N; k += kSummaryThreads) {
+      const int i = (int)(k % nh);
+      const double c = z[k];
+#pragma unroll
+      for (int l = 0; l < kSummaryLags; ++l) if (i + t0 + l < nh) acc[l] += c * z[k + t0 + l];
+    }
+#pragma unroll
+    for (int l = 0; l < kSummaryLags; ++l) {
+      const double v = summary_wave_sum(acc[l]);
+      if (lane == 0) sh.part[wave][l] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < kSummaryLags) {
+      double s = 0.0;
+      for (int w = 0; w < kSummaryWaves; ++w) s += sh.part[w][threadIdx.x];
+      sh.rho[threadIdx.x] = rho_of(s / (double)N, mv, vp);
+    }
+    __syncthreads();
+    if (!started) { g.start(nh, sh.rho[1]); started = true; }
+    while (g.wants() && g.next() + 1 < t0 + kSummaryLags) { const int t = g.next() - t0; g.feed(sh.rho[t], sh.rho[t + 1]); }
+    const bool more = g.wants();
+    __syncthreads();                            // rho is rewritten by the next chunk
+    if (!more) break;
+  }
+  *ess = g.ess(N);
+  return rh;
+}
+
+template <bool LDS>
+__global__ __launch_bounds__(kSummaryThreads) void ppcx_summary_kernel(SummaryArgs a) {
+  extern __shared__ double lds[];
+  __shared__ SummaryShared sh;
+  const long Mn = (long)a.M * a.n;
+  const int nh = a.n / 2, m = 2 * a.M;
+  const long N = (long)m * nh;
+  double* S = LDS ? lds : a.scratch + (long)blockIdx.x * a.slice;     // [npad] the sort buffer
+  double* Z = S + a.npad;                                              // [N] the sequences
+  for (int c = blockIdx.x; c < a.n_cols; c += gridDim.x) {
+    const double* x = a.x + (long)c * Mn;
+    double* out = a.out + (long)c * SUM_FIELDS;
+    // ---- plain summary over all M n draws
+    double s = 0.0; bool bad = false;
+    for (long i = threadIdx.x; i < Mn; i += kSummaryThreads) { const double v = x[i]; bad = bad || !isfinite(v); s += v; }
+    bad = summary_block_any(bad);
+    const double mean = summary_block_sum(s, sh.red) / (double)Mn;
+    if (bad) {
+      if (threadIdx.x < SUM_FIELDS) out[threadIdx.x] = NAN;
+      continue;
+    }
+    double ss = 0.0;
+    for (long i = threadIdx.x; i < Mn; i += kSummaryThreads) { const double d = x[i] - mean; ss += d * d; }
+    ss = summary_block_sum(ss, sh.red);
+    double q05 = 0.0, q50 = 0.0, q95 = 0.0;
+    if (N != Mn || nh < 2) {                    // odd n (the split values drop the middle draws) or nothing to split
+      const int np = summary_pow2(Mn);
+      for (long i = threadIdx.x; i < np; i += kSummaryThreads) S[i] = i < Mn ? x[i] : INFINITY;
+      __syncthreads();
+      summary_sort(S, np);
+      q05 = quantile7_sorted(S, Mn, 0.05); q50 = quantile7_sorted(S, Mn, 0.5); q95 = quantile7_sorted(S, Mn, 0.95);
+      __syncthreads();
+    }
+    double rhat = NAN, ess_bulk = NAN, ess_tail = NAN;
+    if (nh >= 2) {
+      const int np = summary_pow2(N);
+      for (long k = threadIdx.x; k < np; k += kSummaryThreads) S[k] = k < N ? x[split_source(k, nh, a.n)] : INFINITY;
+      __syncthreads();
+      summary_sort(S, np);
+      const double sq05 = quantile7_sorted(S, N, 0.05), med = quantile7_sorted(S, N, 0.5), sq95 = quantile7_sorted(S, N, 0.95);
+      if (N == Mn) { q05 = sq05; q50 = med; q95 = sq95; }
+      if (S[0] < S[N - 1]) {
+        for (long k = threadIdx.x; k < N; k += kSummaryThreads) Z[k] = blom_z(average_rank(S, N, x[split_source(k, nh, a.n)]), N);
+        __syncthreads();
+        const double rb = summary_sequences(Z, m, nh, true, &ess_bulk, sh);
+        __syncthreads();                        // S and Z are rewritten below
+        for (long k = threadIdx.x; k < np; k += kSummaryThreads) S[k] = k < N ? fabs(x[split_source(k, nh, a.n)] - med) : INFINITY;
+        __syncthreads();
+        summary_sort(S, np);
+        for (long k = threadIdx.x; k < N; k += kSummaryThreads) Z[k] = blom_z(average_rank(S, N, fabs(x[split_source(k, nh, a.n)] - med)), N);
+        __syncthreads();
+        const double rf = summary_sequences(Z, m, nh, false, nullptr, sh);
+        rhat = fmax(rb, rf);
+        __syncthreads();
+        double e05 = NAN, e95 = NAN;
+        for (long k = threadIdx.x; k < N; k += kSummaryThreads) Z[k] = x[split_source(k, nh, a.n)] <= sq05 ? 1.0 : 0.0;
+        __syncthreads();
+        summary_sequences(Z, m, nh, true, &e05, sh);
+        __syncthreads();
+        for (long k = threadIdx.x; k < N; k += kSummaryThreads) Z[k] = x[split_source(k, nh, a.n)] <= sq95 ? 1.0 : 0.0;
+        __syncthreads();
+        summary_sequences(Z, m, nh, true, &e95, sh);
+        ess_tail = isnan(e05) ? e95 : (isnan(e95) ? e05 : (e05 < e95 ? e05 : e95));
+      }
+    }
+    if (threadIdx.x == 0) {
+      out[SUM_MEAN] = mean; out[SUM_SD] = sqrt(ss / ((double)Mn - 1.0));
+      out[SUM_Q05] = q05; out[SUM_Q50] = q50; out[SUM_Q95] = q95;
+      out[SUM_RHAT] = rhat; out[SUM_ESS_BULK] = ess_bulk; out[SUM_ESS_TAIL] = ess_tail;
+    }
+    __syncthreads();                            // S, Z and the shared block are reused by the next column
+  }
+}
+
+// ---- launch helpers (host)
+static int summary_pow2_host(long n) { int p = 1; while (p < n) p <<= 1; return p; }
+int summary_npad(int M, int n) { return summary_pow2_host((long)M * n); }
+long summary_slice_doubles(int M, int n) { return (long)summary_npad(M, n) + 2L * M * (n / 2) + 1; }
+size_t summary_lds_bytes(int M, int n) { return (long)M * n <= kSummaryLdsDraws ? sizeof(double) * (size_t)summary_slice_doubles(M, n) : 0; }
+hipError_t launch_summary_gather_kernel(const double* draws, const double* lp, long rows, int D, const int* cols, int n_cols, double* out, hipStream_t st) {
+  const dim3 grid((unsigned)((rows + 31) / 32), (unsigned)((n_cols + 31) / 32));
+  hipLaunchKernelGGL(ppcx_summary_gather_kernel, grid, dim3(256), 0, st, draws, lp, rows, D, cols, n_cols, out);
+  return hipGetLastError();
+}
+hipError_t launch_summary_kernel(const SummaryArgs& a, int nblocks, hipStream_t st) {
+  if (a.scratch) {
+    hipLaunchKernelGGL(ppcx_summary_kernel<false>, dim3(nblocks), dim3(kSummaryThreads), 0, st, a);
+    return hipGetLastError();
+  }
+  const size_t lds = summary_lds_bytes(a.M, a.n);
+  if (lds > 64u * 1024u) {
+    hipError_t e = hipFuncSetAttribute((const void*)ppcx_summary_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(ppcx_summary_kernel<true>, dim3(nblocks), dim3(kSummaryThreads), lds, st, a);
+  return hipGetLastError();
+}
+
+}  // namespace ppcx

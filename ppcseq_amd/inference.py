@@ -61,6 +61,7 @@ class InferenceResult:
     fit: object = None          # the device-resident Fit when pass_fit
     diagnostics: dict = field(default_factory=dict)
     counts_rng: np.ndarray | None = None
+    convergence: dict | None = None   # check_convergence: Fit.summary of alpha_sub_1 (and lp__ where the fit holds it)
 
     def to_frame(self):
         import pandas as pd
@@ -93,6 +94,37 @@ def hmc_warnings(diagnostics, warmup, max_treedepth=10):
     return msgs
 
 
+RHAT_THRESHOLD = 1.05          # rstan::throw_sampler_warnings
+ESS_PER_CHAIN = 100            # bulk / tail ESS below 100 x chains
+
+
+def convergence_warnings(summary, chains):
+    """What rstan::sampling adds after a fit (throw_sampler_warnings, rstan >= 2.21) from a summary of the saved parameters
+    (Fit.summary): the largest rank-normalised R-hat above 1.05, a bulk or a tail ESS below 100 x chains. NaN entries (a column
+    without variance) are ignored. Returns the messages, like hmc_warnings."""
+    msgs = []
+    rhat = np.asarray(summary["rhat"], dtype=np.float64)
+    bulk = np.asarray(summary["ess_bulk"], dtype=np.float64)
+    tail = np.asarray(summary["ess_tail"], dtype=np.float64)
+    more = "Running the chains for more iterations may help. See\nhttps://mc-stan.org/misc/warnings.html"
+    with np.errstate(invalid="ignore"):
+        if np.any(rhat > RHAT_THRESHOLD):
+            msgs.append(f"The largest R-hat is {round(float(np.nanmax(rhat)), 2)}, indicating chains have not mixed.\n{more}#r-hat")
+        if np.any(bulk < ESS_PER_CHAIN * chains):
+            msgs.append("Bulk Effective Samples Size (ESS) is too low, indicating posterior means and medians may be unreliable.\n"
+                        f"{more}#bulk-ess")
+        if np.any(tail < ESS_PER_CHAIN * chains):
+            msgs.append("Tail Effective Samples Size (ESS) is too low, indicating posterior variances and tail quantiles may be "
+                        f"unreliable.\n{more}#tail-ess")
+    return msgs
+
+
+def _warn_convergence(summary, chains):
+    import warnings
+    for msg in convergence_warnings(summary, chains):
+        warnings.warn(msg, RuntimeWarning, stacklevel=3)
+
+
 def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                  approximate_posterior_inference=False,
                  approximate_posterior_analysis=False,
@@ -109,7 +141,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                  model=None,
                  chains=None,
                  devices=None,
-                 launch=None):
+                 launch=None,
+                 check_convergence=False):
     """One inference pass (discovery or test) of ppcseq on the GPU.
 
     counts            G x S integer matrix, genes ordered with the `how_many_to_check` checked genes first
@@ -124,6 +157,10 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                       torch.distributed: ppcseq_amd.distributed.do_inference.
     launch            (lanes_per_gene, workgroups) pins the log-likelihood launch (0 = automatic); by default it follows the number of
                       chains per launch, and results agree to rounding, not bit for bit, between geometries
+    check_convergence the checks rstan::sampling runs after a NUTS fit: R-hat and bulk / tail ESS of alpha_sub_1 and lp__ (the
+                      parameters the reference saves besides counts_rng) on the device (Fit.summary), kept as
+                      `res.convergence` and reported as RuntimeWarning (convergence_warnings). devices=[...]: over the pooled
+                      chains, alpha_sub_1 only (the pooled fit holds no lp__). Not for an ADVI pass.
     Returns an InferenceResult.
     """
     counts = np.asarray(counts)
@@ -145,13 +182,16 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
     warmup = 150                                                    # R/utilities.R:1503
 
     excl = _to_cell_ids(to_exclude, S)
+    if check_convergence and approximate_posterior_inference:
+        raise ValueError("check_convergence needs a NUTS pass: the draws of an ADVI fit are independent (rstan::vb reports no "
+                         "R-hat or ESS)")
     if devices is not None and len(devices) > 1 and (save_generated_quantities or pass_fit or model is not None or approximate_posterior_inference):
         raise ValueError("devices=[...] splits the chains of a NUTS fit over several devices and pools their draws: it cannot "
                          "be combined with save_generated_quantities, pass_fit, a caller's model or approximate_posterior_inference")
     if devices is not None and len(devices) > 1 and not approximate_posterior_inference:
         return _do_inference_devices(counts, X, exposure_rate, K, list(devices), chains, n_iter, warmup, excl,
                                      lambda_mu_mu, approximate_posterior_analysis, adj_prob_theshold,
-                                     how_many_posterior_draws, truncation_compensation, seed, launch)
+                                     how_many_posterior_draws, truncation_compensation, seed, launch, check_convergence)
     if devices is not None and len(devices) >= 1 and model is None:
         device = devices[0]
     own_model = model is None
@@ -190,6 +230,9 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
             import warnings
             for msg in hmc_warnings(res.diagnostics, warmup):
                 warnings.warn(msg, RuntimeWarning, stacklevel=2)
+            if check_convergence:
+                res.convergence = fit.summary(np.arange(off_alpha1, off_alpha1 + K), lp=True)
+                _warn_convergence(res.convergence, chains)
         res.counts_rng = rng
         if pass_fit:
             res.fit = fit
@@ -241,11 +284,12 @@ def checked_columns(G, C, K):
 
 
 def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, approximate_posterior_analysis,
-                   adj_prob_theshold, how_many_posterior_draws, truncation_compensation, seed, device=0):
+                   adj_prob_theshold, how_many_posterior_draws, truncation_compensation, seed, device=0, convergence=False):
     """Credible intervals, slopes and flags from the pooled draws of all chains (rstan::summary over merged chains,
     R/utilities.R:685-703): `draws_checked` is [chains, n_keep, len(checked_columns)] in global chain order. The
     posterior-predictive kernel runs on a model that holds the K checked genes only -- cell ids g*S+s and draw indices are
-    those of the full model, so the result is what a single fit of all the chains gives, bit for bit."""
+    those of the full model, so the result is what a single fit of all the chains gives, bit for bit. convergence: also the
+    summary of alpha_sub_1 over the pooled chains (res.convergence; Fit.summary)."""
     counts = np.asarray(counts)
     X = np.asarray(X, dtype=np.float64).reshape(counts.shape[1], -1)
     small = _lib.Model(counts[:K], X, exposure_rate, K, lambda_mu_mu=lambda_mu_mu, device=device)
@@ -258,18 +302,20 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
             else:
                 ci = fit.ppc(truncation_compensation, p, 1 - p, seed=seed, n_gen=0, resample=False)
             slope = fit.columns(np.arange(3 + K, 3 + 2 * K)).reshape(-1, K).mean(axis=0) if K else np.zeros(0)
+            conv = fit.summary(np.arange(3 + K, 3 + 2 * K), lp=False) if convergence else None
         finally:
             fit.close()
     finally:
         small.close()
     res = _post_process(counts[:K], ci, slope, X)
     res.total_draws = counts.shape[1] * K * int(how_many_posterior_draws)
+    res.convergence = conv
     return res
 
 
 def _do_inference_devices(counts, X, exposure_rate, K, devices, chains, n_iter, warmup, excl, lambda_mu_mu,
                           approximate_posterior_analysis, adj_prob_theshold, how_many_posterior_draws,
-                          truncation_compensation, seed, launch=None):
+                          truncation_compensation, seed, launch=None, check_convergence=False):
     """Chains split over several devices of this process (one host thread per device; the C ABI allows different handles
     on different threads), pooled summary on the first device."""
     import threading
@@ -310,6 +356,8 @@ def _do_inference_devices(counts, X, exposure_rate, K, devices, chains, n_iter, 
     res = pooled_summary(counts, X, exposure_rate, K, pooled, lambda_mu_mu=lambda_mu_mu,
                          approximate_posterior_analysis=approximate_posterior_analysis, adj_prob_theshold=adj_prob_theshold,
                          how_many_posterior_draws=how_many_posterior_draws, truncation_compensation=truncation_compensation,
-                         seed=seed, device=devices[0])
+                         seed=seed, device=devices[0], convergence=check_convergence)
     res.chains, res.iter = chains, n_iter
+    if check_convergence:
+        _warn_convergence(res.convergence, chains)
     return res

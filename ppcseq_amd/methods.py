@@ -116,7 +116,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                       approximate_posterior_inference=True, approximate_posterior_analysis=True,
                       draws_after_tail=10, save_generated_quantities=False, additional_parameters_to_save=(),
                       cores=None, pass_fit=False, do_check_only_on_detrimental=None, tol_rel_obj=0.01,
-                      just_discovery=False, seed=None, adj_prob_theshold_2=None, device=0, devices=None, launch=None, _pass=None):
+                      just_discovery=False, seed=None, adj_prob_theshold_2=None, device=0, devices=None, launch=None, _pass=None,
+                      check_convergence=False):
     """Mirror of ppcseq::identify_outliers (R/methods.R:74-367): same arguments, same defaults.
 
     data is a tidy pandas DataFrame (one row per transcript x sample); column arguments are strings. As in the
@@ -134,6 +135,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
     pooled chains. Not with save_generated_quantities / pass_fit (the draws then live on several devices). One process per GPU
     over torch.distributed: ppcseq_amd.distributed.identify_outliers. `launch` = (lanes_per_gene, workgroups) pins the
     log-likelihood launch of both passes (results are bit-identical across device counts only at equal lanes per gene).
+    `check_convergence` = True (NUTS only): both passes run rstan::sampling's R-hat / ESS checks (inference.do_inference); their
+    summaries go to out.attrs["convergence_discovery"] and ["convergence_test"], failures are RuntimeWarnings.
     """
     import os
     import pandas as pd
@@ -153,6 +156,10 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
         warnings.warn("ppcseq says: There are not transcripts with the category .to_check. NULL is returned.")
         return pd.DataFrame({transcript: [], "sample_wise_data": [], "ppc samples failed": [],
                              "tot deleterious_outliers": []})
+    if check_convergence and approximate_posterior_inference:
+        raise ValueError("check_convergence needs NUTS (approximate_posterior_inference = False): ADVI draws are independent")
+    if check_convergence and _pass is not None:
+        raise ValueError("check_convergence is not available for passes over several ranks")
     if approximate_posterior_inference and save_generated_quantities:
         raise ValueError("Variational Bayes does not support tidybayes needed for save_generated_quantities, use sampling")
     pfp = percent_false_positive_genes
@@ -230,6 +237,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
     where = {} if _pass is not None else (dict(devices=list(devices)) if multi else dict(model=model))
     if _pass is None:
         where.update(approximate_posterior_inference=approximate_posterior_inference, pass_fit=pass_fit, launch=launch)
+        if check_convergence:
+            where.update(check_convergence=True)
     try:
         # ---- pass 1: discovery (R/methods.R:268-286); always the full posterior analysis
         res1 = run_pass(counts, X, exposure_rate, K,
@@ -237,7 +246,10 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                             adj_prob_theshold=adj_prob_theshold_1, how_many_posterior_draws=draws_1,
                             seed=seed, **where)
         if just_discovery:
-            return res1.to_frame()
+            out1 = res1.to_frame()
+            if check_convergence:
+                out1.attrs["convergence_discovery"] = res1.convergence
+            return out1
         # ---- cells to exclude (R/methods.R:292-300)
         flag = res1.deleterious_outliers if (do_check_only_on_detrimental and res1.deleterious_outliers is not None) else ~res1.ppc
         gg, ss = np.nonzero(flag)
@@ -278,6 +290,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
     out.attrs.update(total_draws=res2.total_draws, transcript_column=transcript, abundance_column=abundance,
                      sample_column=sample, formula=formula, seed=seed,
                      diagnostics_discovery=res1.diagnostics, diagnostics_test=res2.diagnostics)
+    if check_convergence:
+        out.attrs["convergence_discovery"], out.attrs["convergence_test"] = res1.convergence, res2.convergence
     if pass_fit:                                                           # R/methods.R:353-357: attrs "fit 1" / "fit 2"
         out.attrs["fit 1"], out.attrs["fit 2"] = res1.fit, res2.fit        # device-resident; the library keeps the model
     return out                                                             # alive until both fits are closed
