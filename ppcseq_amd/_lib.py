@@ -116,6 +116,12 @@ def load() -> C.CDLL:
         lib.ppcx_testing_set.argtypes = [C.c_char_p, C.c_longlong]
         lib.ppcx_testing_set_nccl_provider.argtypes = [C.c_char_p]
         lib.ppcx_testing_bench_kernel.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, C.POINTER(C.c_int)]
+    # the element-wise math and table read-back hooks: bound only where the testing build has them, so that a testing build of
+    # an older source still loads (its hooks above keep working; testing_eval_math / testing_disp_table then raise)
+    if hasattr(lib, "ppcx_testing_eval_math"):
+        lib.ppcx_testing_eval_math.argtypes = [C.c_int, C.c_int, dp, dp, ip, dp, dp]
+    if hasattr(lib, "ppcx_testing_get_disp_table"):
+        lib.ppcx_testing_get_disp_table.argtypes = [C.c_void_p, dp]
     lib.ppcx_fit_free.restype = None
     lib.ppcx_advi_config_default.argtypes = [C.POINTER(AdviConfig)]
     lib.ppcx_advi_config_default.restype = None
@@ -156,6 +162,30 @@ def testing_set_nccl_provider(path: str):
     if not hasattr(lib, "ppcx_testing_set_nccl_provider"):
         raise PpcxError(f"{LIB_PATH} is not the testing build")
     _check(lib.ppcx_testing_set_nccl_provider(path.encode() if path else None))
+
+
+# function ids of ppcx_testing_eval_math (csrc/ppcx_testing.h PPCX_MATH_*)
+TESTING_MATH = ("fast_rcp", "fast_log", "fast_exp", "table_log", "window_log", "stirling_tails", "stirling_excess",
+                "log_erfc_ratio", "cell", "cell_win", "cell_y", "cell_win_y")
+
+
+def testing_eval_math(fn: str, a, b=None, y=None):
+    """(out0, out1) of one of the device's building blocks at every element of a, b, y (testing build only;
+    csrc/ppcx_testing.h ppcx_testing_eval_math)."""
+    lib = load()
+    if not hasattr(lib, "ppcx_testing_eval_math"):
+        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before ppcx_testing_math.hip existed: rebuild it "
+                        "(`python -m ppcseq_amd.build --testing --force`)")
+    a = np.ascontiguousarray(a, dtype=np.float64).ravel()
+    n = a.size
+    b = np.ascontiguousarray(np.zeros(n) if b is None else np.broadcast_to(b, (n,)), dtype=np.float64)
+    y = np.ascontiguousarray(np.zeros(n) if y is None else np.broadcast_to(y, (n,)), dtype=np.int32)
+    o0, o1 = np.zeros(n), np.zeros(n)
+    rc = lib.ppcx_testing_eval_math(TESTING_MATH.index(fn), n, _p(a, C.c_double), _p(b, C.c_double), _p(y, C.c_int32),
+                                    _p(o0, C.c_double), _p(o1, C.c_double))
+    if rc != 0:
+        raise PpcxError(f"ppcx_testing_eval_math({fn}) failed with code {rc}")
+    return o0, o1
 
 
 def device_count() -> int:
@@ -244,6 +274,16 @@ class Model:
         a, b = C.c_int(), C.c_int()
         _check(load().ppcx_model_get_launch(self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def testing_disp_table(self):
+        """The dispersion tables the device built, [G][panel][function][12] (ppcx_disp.h layout; testing build only)."""
+        lib = load()
+        if not hasattr(lib, "ppcx_testing_get_disp_table"):
+            raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before ppcx_testing_get_disp_table existed: "
+                            "rebuild it (`python -m ppcseq_amd.build --testing --force`)")
+        out = np.zeros((self.G, 32, 2, 12))
+        _check(lib.ppcx_testing_get_disp_table(self._h, _p(out, C.c_double)))
+        return out
 
     def log_prob_grad(self, u):
         u = np.ascontiguousarray(u, dtype=np.float64)

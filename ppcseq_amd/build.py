@@ -12,6 +12,7 @@ LIB = os.path.join(HERE, "libppcx.so")
 # with the tests, not in the package
 TESTING_LIB = os.path.join(os.path.dirname(HERE), "tests", "libppcx_testing.so")
 SOURCES = ["ppcx_kernels.hip", "ppcx_summary.hip", "ppcx_capi.hip"]
+TESTING_SOURCES = ["ppcx_testing_math.hip"]      # the device's building blocks one by one (csrc/ppcx_testing.h): testing build only
 HEADERS = ["ppcx_math.h", "ppcx_disp.h", "ppcx_model.h", "ppcx_nuts.h", "ppcx_gene.h", "ppcx_kernels.h", "ppcx_summary.h", "ppcx_testing.h",
            os.path.join("..", "..", "include", "ppcx.h")]
 
@@ -26,18 +27,22 @@ HEADERS = ["ppcx_math.h", "ppcx_disp.h", "ppcx_model.h", "ppcx_nuts.h", "ppcx_ge
 CODEGEN_FLAGS = ["-fno-slp-vectorize"]
 
 
-def _stale(lib: str) -> bool:
+def _sources(extra):
+    return SOURCES + (TESTING_SOURCES if "-DPPCX_TESTING" in extra else [])
+
+
+def _stale(lib: str, extra=()) -> bool:
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + HEADERS)
+    return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in _sources(extra) + HEADERS)
 
 
 def _compile(lib: str, extra, verbose: bool) -> None:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objs = []
     procs = []
-    for s in SOURCES:                            # the translation units side by side
+    for s in _sources(extra):                    # the translation units side by side
         o = lib + "." + s + ".o"
         objs.append(o)
         cmd = [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden", "-Wno-unused-result"] + CODEGEN_FLAGS + extra + \
@@ -60,7 +65,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
 
 
 def build_testing(force: bool = False, verbose: bool = False) -> str:
-    if force or _stale(TESTING_LIB):
+    if force or _stale(TESTING_LIB, ["-DPPCX_TESTING"]):
         _compile(TESTING_LIB, ["-DPPCX_TESTING"], verbose)
     return TESTING_LIB
 
@@ -71,7 +76,7 @@ def build_all(force: bool = False, verbose: bool = False):
     jobs = []
     if force or _stale(LIB):
         jobs.append((LIB, []))
-    if force or _stale(TESTING_LIB):
+    if force or _stale(TESTING_LIB, ["-DPPCX_TESTING"]):
         jobs.append((TESTING_LIB, ["-DPPCX_TESTING"]))
     errs = []
 

@@ -1052,6 +1052,13 @@ extern "C" int ppcx_testing_sm_trace(double* out6) {
   g_sm_rounds = 0;
   return PPCX_OK;
 }
+extern "C" int ppcx_testing_get_disp_table(ppcx_model* m, double* out) {
+  if (!m || !out) return fail(PPCX_ERR_ARG, "bad arguments");
+  HIPCHK(hipSetDevice(m->device));
+  HIPCHK(hipStreamSynchronize(m->stream));
+  HIPCHK(hipMemcpy(out, m->d_disp, sizeof(double) * (size_t)m->d.G * kDispGeneDoubles, hipMemcpyDeviceToHost));
+  return PPCX_OK;
+}
 extern "C" int ppcx_testing_bench_kernel(ppcx_model* m, int which, int nchains, int warm_rounds, int reps, int n_merge,
                                          double* ms_per_launch, int* cmd_type) {
   if (!m || nchains < 1 || reps < 1 || !ms_per_launch || which < 0 || which > PPCX_BENCH_GENE_NEW_TRANSITION) return fail(PPCX_ERR_ARG, "bad arguments");

@@ -156,6 +156,7 @@ PPCX_HD double window_log(double x, const double* wt) {
 
 // exp(x) for |x| < 700 by x = k ln2 + r, |r| <= ln2/2 and the rational form of Sun's fdlibm e_exp.c
 // (public domain algorithm; error < 1 ulp): c = r - r^2 P(r^2), exp(r) = 1 + r + r c / (2 - c).
+// Below -708 the result is subnormal: the final scaling by 2^k rounds it to the subnormal spacing (down to -746).
 PPCX_HD double fast_exp(double x) {
   const double kf = rint(x * 1.44269504088896338700e+00);
   const double hi = fma(kf, -6.93147180369123816490e-01, x);
@@ -241,14 +242,18 @@ PPCX_HD void stirling_excess(double phi, double lnphi, const double* tab, bool a
 // ---------------------------------------------------------------------------------------------
 // log erfc(x) and  R(x) = exp(-x^2)/erfc(x)  (the inverse Mills-type ratio the skew-normal
 // gradient needs). Written as Stan Math's skew_normal_lpdf evaluates it -- log(erfc(.)) directly --
-// so that where erfc underflows (x > ~26.5) the density is log(0) = -inf exactly as in the reference:
+// so that where erfc underflows (x > ~27.2) the density is log(0) = -inf exactly as in the reference:
 // such points are rejected as initial values and count as divergent proposals, the same as in Stan.
+// The ratio is exp(-x^2)/erfc(x) wherever erfc(x) > 0: up to x = 27.2, erfc subnormal from 26.55 on, where
+// exp(-x^2) ~ x sqrt(pi) erfc(x) is subnormal too (fast_exp rounds it to the subnormal spacing); x^2 >= 746 only where
+// erfc(x) = 2 (ratio 0) or erfc(x) = 0. Where erfc(x) = 0 the ratio is NaN, as 0/0 is in Stan.
 // ---------------------------------------------------------------------------------------------
 PPCX_HD void log_erfc_and_ratio(double x, double* log_erfc, double* ratio) {
   const double e = erfc(x);
   *log_erfc = e > 0.0 ? fast_log(e) : -INFINITY;            // log(0) = -inf, as libm's log gives it
   const double x2 = x * x;
-  *ratio = (x2 < 700.0 ? fast_exp(-x2) : 0.0) / e;          // e = 0 only for x > 26.5: 0/0 = NaN, as exp(-x^2)/erfc(x) there
+  const double ex = x2 < 746.0 ? fast_exp(-x2) : 0.0;
+  *ratio = e > 0.0 ? ex / e : NAN;
 }
 
 PPCX_HD double log_sum_exp(double a, double b) {

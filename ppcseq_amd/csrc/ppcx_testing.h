@@ -29,6 +29,19 @@ PPCX_API int ppcx_testing_bench_kernel(ppcx_model* m, int which, int nchains, in
                                        double* ms_per_launch, int* cmd_type);
 /* mean microseconds per round of a chain's state machine by phase since the last call (ppcx_capi.hip) */
 PPCX_API int ppcx_testing_sm_trace(double* out6);
+/* The device's scalar building blocks element by element (ppcx_testing_math.hip): out0[i], out1[i] of function `fn` at a[i],
+ * b[i], y[i]; the log tables are in LDS, the cells run with their gfx950 assembly.
+ *   FAST_RCP / FAST_LOG / FAST_EXP / TABLE_LOG / WINDOW_LOG (ppcx_math.h): out0 = f(a)
+ *   STIRLING_TAILS: out0, out1 = lg_tail, dg_tail of r = a          STIRLING_EXCESS: dlt, dps of phi = a, ln phi = b, any_small = y
+ *   LOG_ERFC_RATIO: log erfc(a), exp(-a^2)/erfc(a)
+ *   CELL / CELL_WIN (ppcx_model.h cell_eval / cell_eval_win with one = 1): ln w, 1/w of w = fma(a, b, 1), count y
+ *   CELL_Y / CELL_WIN_Y: the same cells' y ln w and y / w accumulations */
+enum { PPCX_MATH_FAST_RCP = 0, PPCX_MATH_FAST_LOG = 1, PPCX_MATH_FAST_EXP = 2, PPCX_MATH_TABLE_LOG = 3, PPCX_MATH_WINDOW_LOG = 4,
+       PPCX_MATH_STIRLING_TAILS = 5, PPCX_MATH_STIRLING_EXCESS = 6, PPCX_MATH_LOG_ERFC_RATIO = 7, PPCX_MATH_CELL = 8,
+       PPCX_MATH_CELL_WIN = 9, PPCX_MATH_CELL_Y = 10, PPCX_MATH_CELL_WIN_Y = 11, PPCX_MATH_COUNT = 12 };
+PPCX_API int ppcx_testing_eval_math(int fn, int n, const double* a, const double* b, const int* y, double* out0, double* out1);
+/* the model's dispersion tables as the device built them: G x 768 doubles (ppcx_disp.h layout) */
+PPCX_API int ppcx_testing_get_disp_table(ppcx_model* m, double* out);
 #ifdef __cplusplus
 }
 #endif

@@ -274,3 +274,41 @@ extern "C" __attribute__((visibility("default")))
 int emul_nb2_log_rng(double eta, double phi, unsigned long long seed, unsigned cell, unsigned draw) {
   return nb2_log_rng(eta, phi, seed32(seed), cell, draw);
 }
+
+// the host twin of the testing build's ppcx_testing_eval_math (ppcseq_amd/csrc/ppcx_testing_math.hip): the same functions and
+// function ids (ppcx_testing.h PPCX_MATH_*), here their #else branches
+extern "C" __attribute__((visibility("default")))
+int emul_eval_math(int fn, int n, const double* a, const double* b, const int32_t* y, double* out0, double* out1) {
+  GeneParams<2> gp;
+  gp.coef[0] = gp.coef[1] = 0.0; gp.sigma_raw = 0.0; gp.phi = 1.0; gp.invphi = 1.0;
+  for (int i = 0; i < n; ++i) {
+    const double x = a[i], x2 = b[i];
+    double r0 = 0.0, r1 = 0.0;
+    CellAcc<2> acc; acc.zero();
+    switch (fn) {
+      case 0: r0 = fast_rcp(x); break;
+      case 1: r0 = fast_log(x); break;
+      case 2: r0 = fast_exp(x); break;
+      case 3: r0 = table_log(x, log_table()); break;
+      case 4: r0 = window_log(x, window_table()); break;
+      case 5: stirling_tails(x, &r0, &r1); break;
+      case 6: stirling_excess(x, x2, log_table(), y[i] != 0, &r0, &r1); break;
+      case 7: log_erfc_and_ratio(x, &r0, &r1); break;
+      case 8: (void)cell_eval<2, false>(y[i], x, x2, gp, log_table(), acc); r0 = acc.SL; r1 = acc.Sq; break;
+      case 9: (void)cell_eval_win<2, false>(y[i], x, x2, 1.0, gp, window_table(), acc); r0 = acc.SL; r1 = acc.Sq; break;
+      case 10: (void)cell_eval<2, false>(y[i], x, x2, gp, log_table(), acc); r0 = acc.SA; r1 = acc.SYq; break;
+      case 11: (void)cell_eval_win<2, false>(y[i], x, x2, 1.0, gp, window_table(), acc); r0 = acc.SA; r1 = acc.SYq; break;
+      default: return -1;
+    }
+    out0[i] = r0; out1[i] = r1;
+  }
+  return 0;
+}
+
+// the dispersion table of one row as the host builds it (kDispGeneDoubles doubles, ppcx_disp.h layout)
+extern "C" __attribute__((visibility("default")))
+int emul_disp_build(const int32_t* row, int S, double* out) {
+  DispFit fit; disp_fit_init(fit);
+  disp_build_gene_host(fit, row, S, out);
+  return 0;
+}

@@ -36,13 +36,15 @@ def test_test_hooks_are_not_in_the_shipped_library():
     environment switches."""
     from ppcseq_amd import build
     lib = ctypes.CDLL(build.build())
-    for name in ("ppcx_testing_set", "ppcx_testing_set_nccl_provider", "ppcx_testing_bench_kernel", "ppcx_bench_gene_kernel"):
+    for name in ("ppcx_testing_set", "ppcx_testing_set_nccl_provider", "ppcx_testing_bench_kernel", "ppcx_bench_gene_kernel",
+                 "ppcx_testing_eval_math", "ppcx_testing_get_disp_table"):
         assert not hasattr(lib, name), name
     blob = open(build.build(), "rb").read()
     for s in (b"PPCX_TEST_FAIL", b"PPCX_RCCL_LIB", b"PPCX_TWO_GROUP", b"PPCX_NO_TAIL_TIERS", b"PPCX_PLAN_IGNORE_TIERS", b"injected failure"):
         assert s not in blob, s
     tlib = ctypes.CDLL(build.build_testing())
-    for name in ("ppcx_testing_set", "ppcx_testing_set_nccl_provider", "ppcx_testing_bench_kernel"):
+    for name in ("ppcx_testing_set", "ppcx_testing_set_nccl_provider", "ppcx_testing_bench_kernel", "ppcx_testing_eval_math",
+                 "ppcx_testing_get_disp_table"):
         assert hasattr(tlib, name), name
     for name in _declared():                     # the testing build is the product plus the hooks
         assert hasattr(tlib, name), name
