@@ -131,6 +131,22 @@ PPCX_API int ppcx_fit_get_columns(ppcx_fit* f, int n_cols, const int32_t* cols, 
  * model's stream; the same bits on every call.                                                                              */
 #define PPCX_SUMMARY_FIELDS 8   /* mean, sd, q05, q50, q95, rhat, ess_bulk, ess_tail */
 PPCX_API int ppcx_fit_summary(ppcx_fit* f, int n_cols, const int32_t* cols, double* out);
+/* The Pareto-k diagnostic of an ADVI fit (what rstan::vb reports from rstan 2.21 on: Pareto-smoothed importance sampling on the
+ * log ratios log_p - log_g of the output draws, and a khat column in its summary). Only fits of ppcx_fit_advi /
+ * ppcx_fit_advi_iterative; a NUTS fit, a ppcx_fit_from_draws fit or a column out of range: PPCX_ERR_ARG.
+ *   ppcx_fit_get_approximation  mu and omega (log sd) of the fitted mean-field approximation, D values each (either may be NULL).
+ *   ppcx_fit_get_log_ratios     log_p (the model's log density, without constants, as the ELBO evaluates it; under the model's
+ *                               exclusions when first asked) and log_g = -1/2 sum_d ((theta_d - mu_d) exp(-omega_d))^2 (Stan's
+ *                               calc_log_g: the terms common to every draw cancel) at each kept draw, n_keep values each.
+ *                               Evaluated once per fit, on the first call of this or ppcx_fit_psis, and kept on the device.
+ *   ppcx_fit_psis               khat[i] of column cols[i]: -1 = the log ratios r themselves (the overall k-hat rstan warns on:
+ *                               > 0.7 resampling unreliable, > 1 disabled), d = 1/2 log1p(theta_d^2) + r (rstan's per-parameter
+ *                               khat). r = -Inf where log_p is not finite: such draws take no part. Fewer than 5 tail draws or a
+ *                               constant tail: +Inf; a non-finite theta_d: NaN. Synchronous on the model's stream; the same
+ *                               bits on every call. More than 1.86 million kept draws: PPCX_ERR_LIMIT.                      */
+PPCX_API int ppcx_fit_get_approximation(ppcx_fit* f, double* mu, double* omega);
+PPCX_API int ppcx_fit_get_log_ratios(ppcx_fit* f, double* log_p, double* log_g);
+PPCX_API int ppcx_fit_psis(ppcx_fit* f, int n_cols, const int32_t* cols, double* khat);
 /* lp: [chains][n_keep]; the rest [chains][iter] (warmup included); any pointer may be NULL */
 PPCX_API int ppcx_fit_get_diagnostics(ppcx_fit* f, double* lp, double* stepsize, int32_t* treedepth,
                              int32_t* n_leapfrog, int32_t* divergent, double* accept);

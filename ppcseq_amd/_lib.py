@@ -24,6 +24,7 @@ EXPORTS = [
     "ppcx_guard_decision", "ppcx_device_memory", "ppcx_fit_get_ppc_timing",
     "ppcx_xchg_create", "ppcx_xchg_handle", "ppcx_xchg_connect", "ppcx_xchg_connect_local", "ppcx_xchg_set_timeout", "ppcx_xchg_destroy",
     "ppcx_fit_nuts_xchg", "ppcx_fit_get_xchg_timing", "ppcx_fit_get_inv_metric", "ppcx_fit_summary",
+    "ppcx_fit_get_approximation", "ppcx_fit_get_log_ratios", "ppcx_fit_psis",
 ]
 ABI_VERSION = 400           # include/ppcx.h PPCX_VERSION this binding was written for
 SUMMARY_FIELDS = ("mean", "sd", "q05", "q50", "q95", "rhat", "ess_bulk", "ess_tail")   # PPCX_SUMMARY_FIELDS, in order
@@ -94,6 +95,9 @@ def load() -> C.CDLL:
     lib.ppcx_fit_get_draws.argtypes = [C.c_void_p, dp]
     lib.ppcx_fit_get_columns.argtypes = [C.c_void_p, C.c_int, ip, dp]
     lib.ppcx_fit_summary.argtypes = [C.c_void_p, C.c_int, ip, dp]
+    lib.ppcx_fit_get_approximation.argtypes = [C.c_void_p, dp, dp]
+    lib.ppcx_fit_get_log_ratios.argtypes = [C.c_void_p, dp, dp]
+    lib.ppcx_fit_psis.argtypes = [C.c_void_p, C.c_int, ip, dp]
     lib.ppcx_fit_get_diagnostics.argtypes = [C.c_void_p, dp, dp, ip, ip, ip, dp]
     lib.ppcx_fit_get_timing.argtypes = [C.c_void_p, dp, C.POINTER(C.c_longlong), dp, C.POINTER(C.c_longlong), dp]
     lib.ppcx_fit_get_kernel_times.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(C.c_longlong)]
@@ -122,6 +126,8 @@ def load() -> C.CDLL:
         lib.ppcx_testing_eval_math.argtypes = [C.c_int, C.c_int, dp, dp, ip, dp, dp]
     if hasattr(lib, "ppcx_testing_get_disp_table"):
         lib.ppcx_testing_get_disp_table.argtypes = [C.c_void_p, dp]
+    if hasattr(lib, "ppcx_testing_psis"):
+        lib.ppcx_testing_psis.argtypes = [C.c_int, C.c_int, dp, dp, dp]
     lib.ppcx_fit_free.restype = None
     lib.ppcx_advi_config_default.argtypes = [C.POINTER(AdviConfig)]
     lib.ppcx_advi_config_default.restype = None
@@ -186,6 +192,22 @@ def testing_eval_math(fn: str, a, b=None, y=None):
     if rc != 0:
         raise PpcxError(f"ppcx_testing_eval_math({fn}) failed with code {rc}")
     return o0, o1
+
+
+def testing_psis(lr, cols=None):
+    """k-hat of the PSIS kernel on host-given values (testing build only; csrc/ppcx_testing.h ppcx_testing_psis): lr [n] log
+    ratios, cols [n, n_cols] parameter draws or None. Returns [n_cols + 1]: the columns' k-hat, then that of lr itself."""
+    lib = load()
+    if not hasattr(lib, "ppcx_testing_psis"):
+        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before ppcx_testing_psis existed: rebuild it "
+                        "(`python -m ppcseq_amd.build --testing --force`)")
+    lr = np.ascontiguousarray(lr, dtype=np.float64).ravel()
+    n = lr.size
+    cols = np.zeros((n, 0)) if cols is None else np.ascontiguousarray(cols, dtype=np.float64).reshape(n, -1)
+    out = np.zeros(cols.shape[1] + 1)
+    _check(lib.ppcx_testing_psis(n, int(cols.shape[1]), _p(lr, C.c_double), _p(cols, C.c_double) if cols.size else None,
+                                 _p(out, C.c_double)))
+    return out
 
 
 def device_count() -> int:
@@ -490,6 +512,29 @@ class Fit:
         res = {k: out[:, i].copy() for i, k in enumerate(SUMMARY_FIELDS)}
         res["column"] = cols.astype(np.int64)
         return res
+
+    def approximation(self):
+        """(mu, omega) of an ADVI fit's mean-field approximation, D values each (include/ppcx.h ppcx_fit_get_approximation)."""
+        mu, om = np.zeros(self.D), np.zeros(self.D)
+        _check(load().ppcx_fit_get_approximation(self._h, _p(mu, C.c_double), _p(om, C.c_double)))
+        return mu, om
+
+    def log_ratios(self):
+        """(log_p, log_g) at each kept draw of an ADVI fit (ppcx_fit_get_log_ratios); the log ratios are log_p - log_g."""
+        lp, lg = np.zeros(self.n_keep), np.zeros(self.n_keep)
+        _check(load().ppcx_fit_get_log_ratios(self._h, _p(lp, C.c_double), _p(lg, C.c_double)))
+        return lp, lg
+
+    def psis(self, cols=None, overall=True):
+        """Pareto-k diagnostic of an ADVI fit on the device (ppcx_fit_psis; what rstan::vb reports): a dict of `khat` and
+        `column` (the column index, -1 for the log ratios themselves). cols=None: all D columns; overall: the k-hat of the log
+        ratios last, as column -1."""
+        cols = np.arange(self.D) if cols is None else np.asarray(cols, dtype=np.int64).ravel()
+        cols = np.ascontiguousarray(np.concatenate([cols, [-1]]) if overall else cols, dtype=np.int32)
+        out = np.zeros(cols.size)
+        if cols.size:
+            _check(load().ppcx_fit_psis(self._h, int(cols.size), _p(cols, C.c_int32), _p(out, C.c_double)))
+        return {"khat": out, "column": cols.astype(np.int64)}
 
     def diagnostics(self):
         lp = np.zeros((self.chains, self.n_keep))

@@ -18,6 +18,7 @@
 #include "../../include/ppcx.h"
 #include "ppcx_kernels.h"
 #include "ppcx_summary.h"
+#include "ppcx_psis.h"
 
 using namespace ppcx;
 
@@ -40,6 +41,8 @@ struct TestHooks {
   int slope_cost_permille = 0;                       // plan: cost of a pass with slope genes relative to a plain one (0: built-in)
   int trim_slack_permille = -1;                      // plan: slack of a chain group's trimmed launch (-1: built-in)
   int trim_extra_passes = 0;                         // plan: passes per wavefront of a trimmed launch beyond the fewest possible
+  int psis_slots = 0;                                // Pareto-k diagnostic: draws evaluated per launch for log_p (0: built-in)
+  long long psis_scratch_bytes = 0;                  // ... bound of its column scratch per batch (0: built-in)
   std::string rccl_lib;                              // another provider of the nccl* entry points (tests/loopback)
 };
 static TestHooks g_test;
@@ -97,6 +100,9 @@ struct ppcx_fit {
   long long xchg_ticks = 0, xchg_count = 0;    // direct exchange: 100 MHz ticks the chains' state machines waited for peers, exchanges
   std::vector<double> inv_metric;              // [chains][D] diagonal of the adapted inverse metric (host; ppcx_fit_get_inv_metric)
   bool advi = false;                           // draws of an ADVI approximation (independent: ppcx_fit_summary refuses them)
+  double *d_mu = nullptr, *d_omega = nullptr;  // ADVI: the fitted approximation [D] each (ppcx_fit_get_approximation)
+  double *d_log_p = nullptr, *d_log_g = nullptr, *d_r = nullptr;   // ADVI: log densities and log ratios at the kept draws
+                                               // [n_keep] each, made by the first ppcx_fit_get_log_ratios / ppcx_fit_psis
 };
 
 extern "C" int ppcx_version(void) { return PPCX_VERSION; }
@@ -1029,6 +1035,8 @@ extern "C" int ppcx_testing_set(const char* key, long long value) {
   else if (k == "slope_cost_permille") g_test.slope_cost_permille = (int)value;
   else if (k == "trim_slack_permille") g_test.trim_slack_permille = (int)value;
   else if (k == "trim_extra_passes") g_test.trim_extra_passes = (int)value;
+  else if (k == "psis_slots") g_test.psis_slots = (int)value;
+  else if (k == "psis_scratch_bytes") g_test.psis_scratch_bytes = value;
   else return fail(PPCX_ERR_ARG, "unknown test hook " + k);
   return PPCX_OK;
 }
@@ -1154,6 +1162,7 @@ extern "C" void ppcx_fit_free(ppcx_fit* f) {
   (void)hipSetDevice(m->device);
   (void)hipFree(f->d_draws); (void)hipFree(f->d_lp); (void)hipFree(f->d_stepsize); (void)hipFree(f->d_accept);
   (void)hipFree(f->d_treedepth); (void)hipFree(f->d_nleap); (void)hipFree(f->d_div);
+  (void)hipFree(f->d_mu); (void)hipFree(f->d_omega); (void)hipFree(f->d_log_p); (void)hipFree(f->d_log_g); (void)hipFree(f->d_r);
   delete f;
   if (--m->live_fits == 0 && m->destroy_requested) ppcx_model_destroy(m);
 }
@@ -1593,6 +1602,10 @@ extern "C" int ppcx_fit_advi(ppcx_model* m, const ppcx_advi_config* cfg, ppcx_fi
     if ((rc = advi_launch(r, ADVI_DRAW, nb, 0.0, 0, 0, r.draw_id, f->d_draws, row)) != PPCX_OK) { ppcx_fit_free(f); return rc; }
     r.draw_id += nb;
   }
+  // the approximation itself (mu, omega of every coordinate), for the Pareto-k diagnostic (ppcx_fit_psis)
+  AHIP(hipMalloc(&f->d_mu, sizeof(double) * (size_t)D));
+  AHIP(hipMalloc(&f->d_omega, sizeof(double) * (size_t)D));
+  AHIP(launch_psis_approx_kernel(d, w.vecs + (size_t)V_SQ * w.Dpad, w.vecs + (size_t)V_SG * w.Dpad, w.hyper_vecs[0], f->d_mu, f->d_omega, st));
   AHIP(hipStreamSynchronize(st));
   f->grad_evals = (long long)r.draw_id; f->seconds = 0; f->advi_elbo = elbo; f->advi_eta = eta_best; f->advi_converged = converged ? 1 : 0;
   *out = f;
@@ -1847,6 +1860,109 @@ extern "C" int ppcx_fit_summary(ppcx_fit* f, int n_cols, const int32_t* cols, do
   if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
   return PPCX_OK;
 }
+// ---- the Pareto-k diagnostic of an ADVI fit (rstan::vb, rstan >= 2.21: PSIS on log_p - log_g of the output draws)
+static int psis_fit_check(ppcx_fit* f) {
+  if (!f) return fail(PPCX_ERR_ARG, "fit is NULL");
+  if (!f->advi || !f->d_mu) return fail(PPCX_ERR_ARG, "the Pareto-k diagnostic needs an ADVI fit (a NUTS fit, or one over draws "
+                                                      "produced elsewhere, holds no approximation)");
+  HIPCHK(hipSetDevice(f->m->device));            // every allocation and launch below belongs to the fit's device
+  return PPCX_OK;
+}
+constexpr int kPsisSlots = 32;                   // draws evaluated per launch for log_p (8 .. 64 measured on cfg3)
+static int psis_slots() {
+#ifdef PPCX_TESTING
+  if (g_test.psis_slots > 0) return g_test.psis_slots < 256 ? g_test.psis_slots : 256;   // the stage / record kernels' bound
+#endif
+  return kPsisSlots;
+}
+static size_t psis_scratch_bytes() {
+#ifdef PPCX_TESTING
+  if (g_test.psis_scratch_bytes > 0) return (size_t)g_test.psis_scratch_bytes;
+#endif
+  return kPsisScratchBytes;
+}
+// log_p at every kept draw through the gradient evaluation the ELBO runs (stage -> log-likelihood -> close -> reduce -> record),
+// log_g and r; once per fit, cached on the device
+static int psis_ratios(ppcx_fit* f) {
+  ppcx_model* m = f->m;
+  HIPCHK(hipSetDevice(m->device));
+  if (f->d_r) return PPCX_OK;
+  const int n = f->n_keep, D = m->d.D;
+  const int slots = psis_slots();
+  const int nslot = n < slots ? n : slots;
+  choose_launch(m, nslot);
+  Work w;
+  int rc = work_alloc(w, m, nslot);
+  if (rc != PPCX_OK) return rc;
+  double *lp = nullptr, *lg = nullptr, *rr = nullptr;
+  hipError_t e = hipMalloc(&lp, sizeof(double) * (size_t)n);
+  if (e == hipSuccess) e = hipMalloc(&lg, sizeof(double) * (size_t)n);
+  if (e == hipSuccess) e = hipMalloc(&rr, sizeof(double) * (size_t)n);
+  AdviRun r; r.m = m; r.w = &w;
+  for (int row0 = 0; e == hipSuccess && rc == PPCX_OK && row0 < n; row0 += nslot) {
+    const int nb = n - row0 < nslot ? n - row0 : nslot;
+    e = launch_psis_stage_kernel(m->d, f->d_draws, row0, nb, w.vecs, w.Dpad, w.cmds[0], w.stream);
+    if (e == hipSuccess && (rc = advi_eval(r, nb)) == PPCX_OK) e = launch_psis_record_kernel(m->d, w.cmds[0], w.red, nb, lp + row0, w.stream);
+  }
+  if (e == hipSuccess && rc == PPCX_OK) e = launch_psis_log_g_kernel(f->d_draws, n, D, f->d_mu, f->d_omega, lp, lg, rr, w.stream);
+  const hipError_t es = hipStreamSynchronize(w.stream);
+  if (e == hipSuccess) e = es;
+  if (e != hipSuccess || rc != PPCX_OK) {
+    (void)hipFree(lp); (void)hipFree(lg); (void)hipFree(rr);
+    return rc != PPCX_OK ? rc : fail(PPCX_ERR_HIP, std::string("log ratios: ") + hipGetErrorString(e));
+  }
+  f->d_log_p = lp; f->d_log_g = lg; f->d_r = rr;
+  return PPCX_OK;
+}
+extern "C" int ppcx_fit_get_approximation(ppcx_fit* f, double* mu, double* omega) {
+  int rc = psis_fit_check(f);
+  if (rc != PPCX_OK) return rc;
+  const size_t bytes = sizeof(double) * (size_t)f->m->d.D;
+  if (mu) HIPCHK(hipMemcpy(mu, f->d_mu, bytes, hipMemcpyDeviceToHost));
+  if (omega) HIPCHK(hipMemcpy(omega, f->d_omega, bytes, hipMemcpyDeviceToHost));
+  return PPCX_OK;
+}
+extern "C" int ppcx_fit_get_log_ratios(ppcx_fit* f, double* log_p, double* log_g) {
+  int rc = psis_fit_check(f);
+  if (rc == PPCX_OK) rc = psis_ratios(f);
+  if (rc != PPCX_OK) return rc;
+  const size_t bytes = sizeof(double) * (size_t)f->n_keep;
+  if (log_p) HIPCHK(hipMemcpy(log_p, f->d_log_p, bytes, hipMemcpyDeviceToHost));
+  if (log_g) HIPCHK(hipMemcpy(log_g, f->d_log_g, bytes, hipMemcpyDeviceToHost));
+  return PPCX_OK;
+}
+extern "C" int ppcx_fit_psis(ppcx_fit* f, int n_cols, const int32_t* cols, double* khat) {
+  int rc = psis_fit_check(f);
+  if (rc != PPCX_OK) return rc;
+  if (!cols || !khat || n_cols < 1) return fail(PPCX_ERR_ARG, "bad arguments");
+  const int D = f->m->d.D;
+  for (int i = 0; i < n_cols; ++i) if (cols[i] < -1 || cols[i] >= D) return fail(PPCX_ERR_ARG, "column out of range");
+  if (psis_tail_len(f->n_keep) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "ppcx_fit_psis takes at most 1.86 million draws");
+  if ((rc = psis_ratios(f)) != PPCX_OK) return rc;
+  hipError_t e = psis_columns(f->d_draws, f->d_r, f->n_keep, D, n_cols, cols, khat, psis_scratch_bytes(), f->m->stream);
+  if (e != hipSuccess) return fail(PPCX_ERR_HIP, std::string("ppcx_fit_psis: ") + hipGetErrorString(e));
+  return PPCX_OK;
+}
+#ifdef PPCX_TESTING
+// testing build only (ppcx_testing.h): the PSIS kernel on host-given columns, on the current device
+extern "C" int ppcx_testing_psis(int n, int n_cols, const double* lr, const double* cols, double* khat) {
+  if (n < 1 || n_cols < 0 || !lr || (n_cols > 0 && !cols) || !khat) return fail(PPCX_ERR_ARG, "bad arguments");
+  if (psis_tail_len(n) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "too many draws");
+  const int D = n_cols > 0 ? n_cols : 1;
+  std::vector<int> ids(n_cols + 1);
+  for (int i = 0; i < n_cols; ++i) ids[i] = i;
+  ids[n_cols] = -1;
+  double *d_draws = nullptr, *d_r = nullptr;
+  hipError_t e = hipMalloc(&d_draws, sizeof(double) * (size_t)n * D);
+  if (e == hipSuccess) e = hipMalloc(&d_r, sizeof(double) * (size_t)n);
+  if (e == hipSuccess && n_cols > 0) e = hipMemcpy(d_draws, cols, sizeof(double) * (size_t)n * n_cols, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_r, lr, sizeof(double) * (size_t)n, hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = psis_columns(d_draws, d_r, n, D, n_cols + 1, ids.data(), khat, psis_scratch_bytes(), nullptr);
+  (void)hipFree(d_draws); (void)hipFree(d_r);
+  if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
+  return PPCX_OK;
+}
+#endif
 extern "C" int ppcx_fit_get_diagnostics(ppcx_fit* f, double* lp, double* stepsize, int32_t* treedepth,
                                         int32_t* n_leapfrog, int32_t* divergent, double* accept) {
   if (!f) return fail(PPCX_ERR_ARG, "fit is NULL");

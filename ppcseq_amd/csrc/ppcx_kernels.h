@@ -179,6 +179,34 @@ long summary_slice_doubles(int M, int n);
 size_t summary_lds_bytes(int M, int n);       // 0: the columns are too long for the LDS path
 hipError_t launch_summary_gather_kernel(const double* draws, const double* lp, long rows, int D, const int* cols, int n_cols, double* out, hipStream_t st);
 hipError_t launch_summary_kernel(const SummaryArgs& a, int nblocks, hipStream_t st);
+
+// the Pareto-k diagnostic of an ADVI fit (ppcx_psis.hip, statistic in ppcx_psis.h): the M + 1 largest values of a column are
+// selected and sorted in LDS (kPsisMaxSel of them at most: columns of up to 1.86 million draws); columns of up to kPsisLdsDraws
+// draws are staged in LDS, longer ones transformed in place in the column scratch
+constexpr int kPsisLdsDraws = 4096;
+constexpr int kPsisMaxSel = 4096;
+constexpr size_t kPsisScratchBytes = (size_t)256 << 20;
+struct PsisArgs {
+  double* x;                    // [n_cols][n] the columns (ppcx_summary_gather_kernel; column -1: r); rewritten on the long path
+  const double* r;              // [n] the log ratios
+  const int* cols;              // [n_cols] column ids, -1: r itself
+  int n_cols; long n;
+  int sel_pad;                  // psis_sel_pad(n): the selection buffer
+  double* out;                  // [n_cols] k-hat
+};
+int psis_sel_pad(long n);       // power of two >= M + 1 for n draws
+hipError_t launch_psis_approx_kernel(const Dims& d, const double* sq, const double* sg, const double* hyper, double* mu, double* omega,
+                                     hipStream_t st);
+hipError_t launch_psis_stage_kernel(const Dims& d, const double* draws, long row0, int n_slots, double* vecs, long Dpad, Cmd* cmds,
+                                    hipStream_t st);
+hipError_t launch_psis_record_kernel(const Dims& d, const Cmd* cmds, const double* red, int n_slots, double* log_p, hipStream_t st);
+hipError_t launch_psis_log_g_kernel(const double* draws, long rows, int D, const double* mu, const double* omega, const double* log_p,
+                                    double* log_g, double* r, hipStream_t st);
+hipError_t launch_psis_kernel(const PsisArgs& a, hipStream_t st);
+// k-hat of the columns `cols` (host; -1: r) of draws [n][D] and r [n] (device), through column scratch of at most scratch_bytes
+// per batch (kPsisScratchBytes in the product); synchronous
+hipError_t psis_columns(const double* draws, const double* r, long n, int D, int n_cols, const int* cols, double* khat,
+                        size_t scratch_bytes, hipStream_t st);
 hipError_t launch_xchg_abort_kernel(const XchgArgs& x, hipStream_t st);      // tells every peer that this rank has left the fit
 
 }  // namespace ppcx

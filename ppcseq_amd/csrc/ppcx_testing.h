@@ -13,7 +13,9 @@ extern "C" {
  * models created afterwards),
  * "slope_cost_permille", "trim_slack_permille", "trim_extra_passes" (the launch plan's cost of a pass with slopes / slack of
  * a chain group's trimmed launch, per mille / passes per wavefront of such a launch beyond the fewest possible; -1 or 0:
- * built-in; plans made afterwards). */
+ * built-in; plans made afterwards),
+ * "psis_slots", "psis_scratch_bytes" (the Pareto-k diagnostic: draws per launch of the log_p evaluation, bound of the column
+ * scratch per batch; 0: built-in). */
 PPCX_API int ppcx_testing_set(const char* key, long long value);
 /* path of a shared object that provides ncclGetUniqueId / ncclCommInitRank / ncclCommDestroy / ncclAllReduce /
  * ncclGetErrorString instead of librccl (before the first communicator is created) */
@@ -42,6 +44,10 @@ enum { PPCX_MATH_FAST_RCP = 0, PPCX_MATH_FAST_LOG = 1, PPCX_MATH_FAST_EXP = 2, P
 PPCX_API int ppcx_testing_eval_math(int fn, int n, const double* a, const double* b, const int* y, double* out0, double* out1);
 /* the model's dispersion tables as the device built them: G x 768 doubles (ppcx_disp.h layout) */
 PPCX_API int ppcx_testing_get_disp_table(ppcx_model* m, double* out);
+/* The Pareto-k kernel of ppcx_fit_psis on host-given values, on the current device (ppcx_psis.hip): lr [n] the log ratios,
+ * cols [n][n_cols] row-major parameter draws; khat [n_cols + 1]: the k-hat of 1/2 log1p(cols[:, i]^2) + lr for i < n_cols,
+ * then that of lr itself. */
+PPCX_API int ppcx_testing_psis(int n, int n_cols, const double* lr, const double* cols, double* khat);
 #ifdef __cplusplus
 }
 #endif

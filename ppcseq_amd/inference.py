@@ -62,6 +62,7 @@ class InferenceResult:
     diagnostics: dict = field(default_factory=dict)
     counts_rng: np.ndarray | None = None
     convergence: dict | None = None   # check_convergence: Fit.summary of alpha_sub_1 (and lp__ where the fit holds it)
+    approximation: dict | None = None  # check_approximation: Fit.psis of alpha_sub_1 and the overall k-hat (column -1, last)
 
     def to_frame(self):
         import pandas as pd
@@ -119,6 +120,30 @@ def convergence_warnings(summary, chains):
     return msgs
 
 
+KHAT_UNRELIABLE = 0.7          # rstan::vb: Pareto k above which resampling is unreliable
+KHAT_DISABLED = 1.0            # ... and above which it is disabled
+
+
+def approximation_warnings(khat):
+    """What rstan::vb (rstan >= 2.21) tells its user about the quality of an ADVI fit from the Pareto k diagnostic of the log
+    ratios log_p - log_g of its draws (Fit.psis): above 0.7 resampling is unreliable, above 1 it is disabled. `khat` is a number
+    or an array (the largest non-NaN value is reported: do_inference passes the overall k-hat only, as rstan warns on it). NaN
+    (a column with a non-finite draw) reports nothing. Returns the messages, like convergence_warnings."""
+    k = np.asarray(khat, dtype=np.float64).ravel()
+    k = k[~np.isnan(k)]
+    if k.size == 0:
+        return []
+    top = float(k.max())
+    shown = "Inf" if math.isinf(top) else f"{round(top, 2)}"
+    if top > KHAT_DISABLED:
+        return [f"Pareto k diagnostic value is {shown}. Resampling is disabled. Decreasing tol_rel_obj may help if variational "
+                "algorithm has terminated prematurely. Otherwise consider using sampling instead."]
+    if top > KHAT_UNRELIABLE:
+        return [f"Pareto k diagnostic value is {shown}. Resampling is unreliable. Increasing the number of draws or decreasing "
+                "tol_rel_obj may help."]
+    return []
+
+
 def _warn_convergence(summary, chains):
     import warnings
     for msg in convergence_warnings(summary, chains):
@@ -142,7 +167,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                  chains=None,
                  devices=None,
                  launch=None,
-                 check_convergence=False):
+                 check_convergence=False,
+                 check_approximation=False):
     """One inference pass (discovery or test) of ppcseq on the GPU.
 
     counts            G x S integer matrix, genes ordered with the `how_many_to_check` checked genes first
@@ -161,6 +187,10 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                       parameters the reference saves besides counts_rng) on the device (Fit.summary), kept as
                       `res.convergence` and reported as RuntimeWarning (convergence_warnings). devices=[...]: over the pooled
                       chains, alpha_sub_1 only (the pooled fit holds no lp__). Not for an ADVI pass.
+    check_approximation what rstan::vb reports after an ADVI fit: the Pareto k diagnostic (PSIS) of the log ratios log_p - log_g
+                      of the output draws and the per-parameter k-hat of alpha_sub_1, on the device (Fit.psis), kept as
+                      `res.approximation` (the overall k-hat last, column -1) and reported as RuntimeWarning from the
+                      overall k-hat (approximation_warnings). Not for a NUTS pass.
     Returns an InferenceResult.
     """
     counts = np.asarray(counts)
@@ -185,6 +215,9 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
     if check_convergence and approximate_posterior_inference:
         raise ValueError("check_convergence needs a NUTS pass: the draws of an ADVI fit are independent (rstan::vb reports no "
                          "R-hat or ESS)")
+    if check_approximation and not approximate_posterior_inference:
+        raise ValueError("check_approximation needs an ADVI pass (approximate_posterior_inference = True): the Pareto k "
+                         "diagnostic judges the variational approximation")
     if devices is not None and len(devices) > 1 and (save_generated_quantities or pass_fit or model is not None or approximate_posterior_inference):
         raise ValueError("devices=[...] splits the chains of a NUTS fit over several devices and pools their draws: it cannot "
                          "be combined with save_generated_quantities, pass_fit, a caller's model or approximate_posterior_inference")
@@ -226,6 +259,11 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
         res.total_draws = S * K * int(how_many_posterior_draws)   # R/utilities.R:1544
         res.chains, res.iter = chains, n_iter
         res.diagnostics = fit.advi_info() if approximate_posterior_inference else fit.diagnostics()
+        if approximate_posterior_inference and check_approximation:
+            import warnings
+            res.approximation = fit.psis(np.arange(off_alpha1, off_alpha1 + K), overall=True)
+            for msg in approximation_warnings(res.approximation["khat"][-1]):
+                warnings.warn(msg, RuntimeWarning, stacklevel=2)
         if not approximate_posterior_inference:
             import warnings
             for msg in hmc_warnings(res.diagnostics, warmup):
