@@ -147,6 +147,22 @@ PPCX_API int ppcx_fit_summary(ppcx_fit* f, int n_cols, const int32_t* cols, doub
 PPCX_API int ppcx_fit_get_approximation(ppcx_fit* f, double* mu, double* omega);
 PPCX_API int ppcx_fit_get_log_ratios(ppcx_fit* f, double* log_p, double* log_g);
 PPCX_API int ppcx_fit_psis(ppcx_fit* f, int n_cols, const int32_t* cols, double* khat);
+/* PSIS-LOO per observed cell of a NUTS fit (what rstan::loo(fit) / loo::loo(log_lik, r_eff) report per observation, without
+ * the MCSE). Every count is one observation: cell (g, s) of a gene g in genes[0 .. n_genes) and a sample s. NUTS fits of every
+ * entry point and ppcx_fit_from_draws fits; an ADVI fit, a gene out of range or a bad r_eff: PPCX_ERR_ARG. Synchronous on the
+ * model's stream; the same bits on every call, whatever other genes are requested.
+ *   ppcx_fit_get_log_lik  log_lik = neg_binomial_2_log_lpmf(y | exposure_s + X_s alpha_g, exp(-sigma_raw_g)) with every constant
+ *                         kept, out [chains][n_keep][n_genes][S]; cells excluded by the model hold theirs too.
+ *   ppcx_fit_loo          out [n_genes][S][PPCX_LOO_FIELDS]: elpd_loo, p_loo, looic, khat of loo's PSIS on r = -log_lik over
+ *                         the kept draws, tail length ceil(min(0.2 N, 3 sqrt(N / r_eff))); r_eff NULL (all 1) or [n_genes][S],
+ *                         each finite and > 0. A cell excluded by the model at the time of the call is already held out:
+ *                         elpd_loo = lpd (its exact held-out predictive density), p_loo = 0, khat = NaN. A NaN log_lik or one of
+ *                         -Inf: the cell is NaN; fewer than 5 tail draws or a constant tail: khat = +Inf and raw weights.
+ *                         The log-likelihood matrix is never materialised. A tail of more than 4 095 draws (1.86 million
+ *                         kept draws at r_eff = 1, fewer at smaller r_eff): PPCX_ERR_LIMIT.                                  */
+#define PPCX_LOO_FIELDS 4       /* elpd_loo, p_loo, looic, khat */
+PPCX_API int ppcx_fit_get_log_lik(ppcx_fit* f, int n_genes, const int32_t* genes, double* out);
+PPCX_API int ppcx_fit_loo(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double* out);
 /* lp: [chains][n_keep]; the rest [chains][iter] (warmup included); any pointer may be NULL */
 PPCX_API int ppcx_fit_get_diagnostics(ppcx_fit* f, double* lp, double* stepsize, int32_t* treedepth,
                              int32_t* n_leapfrog, int32_t* divergent, double* accept);

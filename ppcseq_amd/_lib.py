@@ -24,10 +24,11 @@ EXPORTS = [
     "ppcx_guard_decision", "ppcx_device_memory", "ppcx_fit_get_ppc_timing",
     "ppcx_xchg_create", "ppcx_xchg_handle", "ppcx_xchg_connect", "ppcx_xchg_connect_local", "ppcx_xchg_set_timeout", "ppcx_xchg_destroy",
     "ppcx_fit_nuts_xchg", "ppcx_fit_get_xchg_timing", "ppcx_fit_get_inv_metric", "ppcx_fit_summary",
-    "ppcx_fit_get_approximation", "ppcx_fit_get_log_ratios", "ppcx_fit_psis",
+    "ppcx_fit_get_approximation", "ppcx_fit_get_log_ratios", "ppcx_fit_psis", "ppcx_fit_get_log_lik", "ppcx_fit_loo",
 ]
 ABI_VERSION = 400           # include/ppcx.h PPCX_VERSION this binding was written for
 SUMMARY_FIELDS = ("mean", "sd", "q05", "q50", "q95", "rhat", "ess_bulk", "ess_tail")   # PPCX_SUMMARY_FIELDS, in order
+LOO_FIELDS = ("elpd_loo", "p_loo", "looic", "khat")                                      # PPCX_LOO_FIELDS, in order
 
 
 class PpcxError(RuntimeError):
@@ -98,6 +99,8 @@ def load() -> C.CDLL:
     lib.ppcx_fit_get_approximation.argtypes = [C.c_void_p, dp, dp]
     lib.ppcx_fit_get_log_ratios.argtypes = [C.c_void_p, dp, dp]
     lib.ppcx_fit_psis.argtypes = [C.c_void_p, C.c_int, ip, dp]
+    lib.ppcx_fit_get_log_lik.argtypes = [C.c_void_p, C.c_int, ip, dp]
+    lib.ppcx_fit_loo.argtypes = [C.c_void_p, C.c_int, ip, dp, dp]
     lib.ppcx_fit_get_diagnostics.argtypes = [C.c_void_p, dp, dp, ip, ip, ip, dp]
     lib.ppcx_fit_get_timing.argtypes = [C.c_void_p, dp, C.POINTER(C.c_longlong), dp, C.POINTER(C.c_longlong), dp]
     lib.ppcx_fit_get_kernel_times.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(C.c_longlong)]
@@ -128,6 +131,8 @@ def load() -> C.CDLL:
         lib.ppcx_testing_get_disp_table.argtypes = [C.c_void_p, dp]
     if hasattr(lib, "ppcx_testing_psis"):
         lib.ppcx_testing_psis.argtypes = [C.c_int, C.c_int, dp, dp, dp]
+    if hasattr(lib, "ppcx_testing_loo"):
+        lib.ppcx_testing_loo.argtypes = [C.c_int, C.c_int, dp, ip, dp, dp]
     lib.ppcx_fit_free.restype = None
     lib.ppcx_advi_config_default.argtypes = [C.POINTER(AdviConfig)]
     lib.ppcx_advi_config_default.restype = None
@@ -210,6 +215,36 @@ def testing_psis(lr, cols=None):
     return out
 
 
+def testing_loo(ll, excluded=None, r_eff=None):
+    """PSIS-LOO kernel on host-given log-likelihood columns (testing build only; csrc/ppcx_testing.h ppcx_testing_loo): ll
+    [n_draws, n_cells], excluded / r_eff None or [n_cells]. Returns [n_cells, 4]: elpd_loo, p_loo, looic, khat."""
+    lib = load()
+    if not hasattr(lib, "ppcx_testing_loo"):
+        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before ppcx_testing_loo existed: rebuild it "
+                        "(`python -m ppcseq_amd.build --testing --force`)")
+    ll = np.asarray(ll, dtype=np.float64)
+    ll = ll.reshape(ll.shape[0], -1)
+    n, nc = ll.shape
+    cols = np.ascontiguousarray(ll.T)
+    ex = None if excluded is None else np.ascontiguousarray(excluded, dtype=np.int32).ravel()
+    re = None if r_eff is None else np.ascontiguousarray(r_eff, dtype=np.float64).ravel()
+    out = np.zeros((nc, len(LOO_FIELDS)))
+    _check(lib.ppcx_testing_loo(n, nc, _p(cols, C.c_double), _p(ex, C.c_int32) if ex is not None else None,
+                                _p(re, C.c_double) if re is not None else None, _p(out, C.c_double)))
+    return out
+
+
+def loo_estimates(pointwise, excluded):
+    """loo's `estimates` for elpd_loo, p_loo and looic over the non-excluded cells: {name: (sum, sqrt(n var))}, var of ddof 1"""
+    keep = ~np.asarray(excluded, bool)
+    out = {}
+    for name in LOO_FIELDS[:3]:
+        v = np.asarray(pointwise[name], dtype=np.float64)[keep]
+        se = float(np.sqrt(v.size * np.var(v, ddof=1))) if v.size > 1 else float("nan")
+        out[name] = (float(np.sum(v)), se)
+    return out
+
+
 def device_count() -> int:
     return int(load().ppcx_device_count())
 
@@ -247,6 +282,7 @@ class Model:
             raise ValueError("exposure_rate must have length S")
         excl = np.ascontiguousarray(excl if excl is not None else np.zeros(0), dtype=np.int32)
         self.X, self.exposure_rate = X, exposure_rate
+        self.excl = excl.copy()                  # the cells excluded now (Fit.loo holds them out)
         h = C.c_void_p()
         self.shard = shard
         if shard is None:
@@ -276,6 +312,7 @@ class Model:
     def set_exclusions(self, excl):
         excl = np.ascontiguousarray(excl if excl is not None else np.zeros(0), dtype=np.int32)
         _check(load().ppcx_model_set_exclusions(self._h, int(excl.size), _p(excl, C.c_int32)))
+        self.excl = excl.copy()
 
     def set_launch(self, lanes_per_gene=0, workgroups=0):
         """Pin the log-likelihood kernel's lanes per gene (a power of two <= 64) and/or its number of persistent
@@ -535,6 +572,43 @@ class Fit:
         if cols.size:
             _check(load().ppcx_fit_psis(self._h, int(cols.size), _p(cols, C.c_int32), _p(out, C.c_double)))
         return {"khat": out, "column": cols.astype(np.int64)}
+
+    def _genes(self, genes):
+        G = self.model.G
+        g = np.arange(G) if genes is None else np.asarray(genes, dtype=np.int64).ravel()
+        return np.ascontiguousarray(g, dtype=np.int32)
+
+    def log_lik(self, genes=None):
+        """The cells' log-likelihood at every kept draw (include/ppcx.h ppcx_fit_get_log_lik; what a Stan log_lik block holds):
+        [chains, n_keep, n_genes, S]. genes=None: all G genes. Excluded cells hold theirs too."""
+        g = self._genes(genes)
+        out = np.zeros((self.chains, self.n_keep, g.size, self.model.S))
+        if g.size:
+            _check(load().ppcx_fit_get_log_lik(self._h, int(g.size), _p(g, C.c_int32), _p(out, C.c_double)))
+        return out
+
+    def loo(self, genes=None, r_eff=None):
+        """PSIS-LOO per observed cell on the device (ppcx_fit_loo; rstan::loo / loo::loo(log_lik, r_eff)): a dict of the
+        pointwise elpd_loo, p_loo, looic and khat, [n_genes, S] each, `excluded` (the cells the model holds out now: elpd_loo is
+        their exact held-out density, p_loo 0, khat NaN), `genes`, `n_draws`, and `estimates`: {elpd_loo, p_loo, looic: (sum, se)} over the
+        non-excluded cells as loo reports them. genes=None: all G genes; r_eff None (all 1) or [n_genes, S]."""
+        g = self._genes(genes)
+        S = self.model.S
+        out = np.zeros((g.size, S, len(LOO_FIELDS)))
+        re = None
+        if r_eff is not None:
+            re = np.ascontiguousarray(np.broadcast_to(np.asarray(r_eff, dtype=np.float64), (g.size, S)))
+        if g.size:
+            _check(load().ppcx_fit_loo(self._h, int(g.size), _p(g, C.c_int32), _p(re, C.c_double) if re is not None else None,
+                                       _p(out, C.c_double)))
+        res = {k: out[:, :, i].copy() for i, k in enumerate(LOO_FIELDS)}
+        excl = np.zeros(self.model.G * S, bool)
+        excl[np.asarray(self.model.excl, dtype=np.int64)] = True
+        res["excluded"] = excl.reshape(self.model.G, S)[g]
+        res["genes"] = g.astype(np.int64)
+        res["n_draws"] = self.chains * self.n_keep
+        res["estimates"] = loo_estimates(res, res["excluded"])
+        return res
 
     def diagnostics(self):
         lp = np.zeros((self.chains, self.n_keep))

@@ -19,6 +19,7 @@
 #include "ppcx_kernels.h"
 #include "ppcx_summary.h"
 #include "ppcx_psis.h"
+#include "ppcx_loo.h"
 
 using namespace ppcx;
 
@@ -43,6 +44,7 @@ struct TestHooks {
   int trim_extra_passes = 0;                         // plan: passes per wavefront of a trimmed launch beyond the fewest possible
   int psis_slots = 0;                                // Pareto-k diagnostic: draws evaluated per launch for log_p (0: built-in)
   long long psis_scratch_bytes = 0;                  // ... bound of its column scratch per batch (0: built-in)
+  long long loo_scratch_bytes = 0;                   // PSIS-LOO: bound of the gene table / column scratch per batch (0: built-in)
   std::string rccl_lib;                              // another provider of the nccl* entry points (tests/loopback)
 };
 static TestHooks g_test;
@@ -71,6 +73,7 @@ struct ppcx_model {
   std::map<std::pair<int, int>, Plan> plans;   // (chains in the launch, resident workgroups it may use) -> ranges
   std::mutex plan_mutex;
   std::vector<int32_t> counts_host;            // original counts (exclusions are re-applied on a copy)
+  std::vector<char> excluded_host;             // [G][S] the cells excluded now (ppcx_fit_loo holds them out)
   std::vector<double> X_host, expo_host;
   int* d_counts = nullptr;
   double *d_E = nullptr, *d_expo = nullptr, *d_X = nullptr, *d_Sy = nullptr, *d_SyE = nullptr, *d_SyX = nullptr, *d_SX = nullptr, *d_ncell = nullptr, *d_Lg1 = nullptr;
@@ -355,6 +358,8 @@ static int upload_counts(ppcx_model* m, int n_excl, const int32_t* excl) {
     drop_plans(m);
   }
   HIPCHK(hipMemcpy(m->d_counts, cnt.data(), sizeof(int32_t) * cnt.size(), hipMemcpyHostToDevice));
+  m->excluded_host.assign(cnt.size(), 0);
+  for (size_t i = 0; i < cnt.size(); ++i) m->excluded_host[i] = cnt[i] < 0;
   // the dispersion tables of all genes from the counts now on the device (a few milliseconds; excluded cells are left out of them)
   {
     const hipError_t e = launch_disp_build_kernel(m->d_counts, G, S, nullptr, G, m->fit, m->d_disp, m->stream);
@@ -1037,6 +1042,7 @@ extern "C" int ppcx_testing_set(const char* key, long long value) {
   else if (k == "trim_extra_passes") g_test.trim_extra_passes = (int)value;
   else if (k == "psis_slots") g_test.psis_slots = (int)value;
   else if (k == "psis_scratch_bytes") g_test.psis_scratch_bytes = value;
+  else if (k == "loo_scratch_bytes") g_test.loo_scratch_bytes = value;
   else return fail(PPCX_ERR_ARG, "unknown test hook " + k);
   return PPCX_OK;
 }
@@ -1959,6 +1965,80 @@ extern "C" int ppcx_testing_psis(int n, int n_cols, const double* lr, const doub
   if (e == hipSuccess) e = hipMemcpy(d_r, lr, sizeof(double) * (size_t)n, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = psis_columns(d_draws, d_r, n, D, n_cols + 1, ids.data(), khat, psis_scratch_bytes(), nullptr);
   (void)hipFree(d_draws); (void)hipFree(d_r);
+  if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
+  return PPCX_OK;
+}
+#endif
+// ---- PSIS-LOO per observed cell of a NUTS fit (rstan::loo / loo::loo on the cells' log-likelihood)
+static size_t loo_scratch_bytes() {
+#ifdef PPCX_TESTING
+  if (g_test.loo_scratch_bytes > 0) return (size_t)g_test.loo_scratch_bytes;
+#endif
+  return kPsisScratchBytes;
+}
+// the fit, the genes and the cells' counts (an excluded cell as -(y + 1)); sets the fit's device
+static int loo_prepare(ppcx_fit* f, int n_genes, const int32_t* genes, std::vector<int>& yenc) {
+  if (!f) return fail(PPCX_ERR_ARG, "fit is NULL");
+  if (f->advi) return fail(PPCX_ERR_ARG, "PSIS-LOO needs the draws of a NUTS fit (loo_approximate_posterior for ADVI fits is "
+                                         "not available)");
+  if (!genes || n_genes < 1) return fail(PPCX_ERR_ARG, "bad arguments");
+  if ((long)f->chains * f->n_keep < 1) return fail(PPCX_ERR_ARG, "fit holds no kept draws");
+  const ppcx_model* m = f->m;
+  const int G = m->d.G, S = m->d.S;
+  for (int i = 0; i < n_genes; ++i) if (genes[i] < 0 || genes[i] >= G) return fail(PPCX_ERR_ARG, "gene out of range");
+  yenc.resize((size_t)n_genes * S);
+  for (int i = 0; i < n_genes; ++i)
+    for (int s = 0; s < S; ++s) {
+      const size_t c = (size_t)genes[i] * S + s;
+      const int y = m->counts_host[c];
+      yenc[(size_t)i * S + s] = m->excluded_host[c] ? -y - 1 : y;
+    }
+  HIPCHK(hipSetDevice(m->device));
+  return PPCX_OK;
+}
+extern "C" int ppcx_fit_get_log_lik(ppcx_fit* f, int n_genes, const int32_t* genes, double* out) {
+  std::vector<int> yenc;
+  int rc = loo_prepare(f, n_genes, genes, yenc);
+  if (rc != PPCX_OK) return rc;
+  if (!out) return fail(PPCX_ERR_ARG, "bad arguments");
+  ppcx_model* m = f->m;
+  hipError_t e = loo_fit_log_lik(f->d_draws, (long)f->chains * f->n_keep, m->d, m->d_expo, m->d_X, n_genes, genes, yenc.data(), out,
+                                 loo_scratch_bytes(), m->stream);
+  if (e != hipSuccess) return fail(PPCX_ERR_HIP, std::string("ppcx_fit_get_log_lik: ") + hipGetErrorString(e));
+  return PPCX_OK;
+}
+static int loo_check_reff(const double* r_eff, long n) {
+  for (long i = 0; r_eff && i < n; ++i)
+    if (!(isfinite(r_eff[i]) && r_eff[i] > 0.0)) return fail(PPCX_ERR_ARG, "r_eff must be finite and > 0");
+  return PPCX_OK;
+}
+static double loo_reff_min(const double* r_eff, long n) {
+  double mn = 1.0;
+  for (long i = 0; r_eff && i < n; ++i) mn = i == 0 || r_eff[i] < mn ? r_eff[i] : mn;
+  return mn;
+}
+extern "C" int ppcx_fit_loo(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double* out) {
+  std::vector<int> yenc;
+  int rc = loo_prepare(f, n_genes, genes, yenc);
+  if (rc != PPCX_OK) return rc;
+  if (!out) return fail(PPCX_ERR_ARG, "bad arguments");
+  ppcx_model* m = f->m;
+  const long n = (long)f->chains * f->n_keep, ncells = (long)n_genes * m->d.S;
+  if ((rc = loo_check_reff(r_eff, ncells)) != PPCX_OK) return rc;
+  if (loo_tail_len(n, loo_reff_min(r_eff, ncells)) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "ppcx_fit_loo: the tail exceeds 4095 draws");
+  hipError_t e = loo_fit_cells(f->d_draws, n, m->d, m->d_expo, m->d_X, n_genes, genes, yenc.data(), r_eff, out, loo_scratch_bytes(),
+                               m->stream);
+  if (e != hipSuccess) return fail(PPCX_ERR_HIP, std::string("ppcx_fit_loo: ") + hipGetErrorString(e));
+  return PPCX_OK;
+}
+#ifdef PPCX_TESTING
+// testing build only (ppcx_testing.h): the LOO kernel on host-given columns, on the current device
+extern "C" int ppcx_testing_loo(int n, int n_cols, const double* ll, const int32_t* excluded, const double* r_eff, double* out) {
+  if (n < 1 || n_cols < 1 || !ll || !out) return fail(PPCX_ERR_ARG, "bad arguments");
+  int rc = loo_check_reff(r_eff, n_cols);
+  if (rc != PPCX_OK) return rc;
+  if (loo_tail_len(n, loo_reff_min(r_eff, n_cols)) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "too many draws");
+  hipError_t e = loo_columns(ll, n, n_cols, excluded, r_eff, out, loo_scratch_bytes(), nullptr);
   if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
   return PPCX_OK;
 }

@@ -207,6 +207,35 @@ hipError_t launch_psis_kernel(const PsisArgs& a, hipStream_t st);
 // per batch (kPsisScratchBytes in the product); synchronous
 hipError_t psis_columns(const double* draws, const double* r, long n, int D, int n_cols, const int* cols, double* khat,
                         size_t scratch_bytes, hipStream_t st);
+// PSIS-LOO per observed cell of a NUTS fit (ppcx_loo.hip, statistic in ppcx_loo.h): one workgroup per cell; the cell's ratios
+// live in LDS up to kPsisLdsDraws draws, beyond that in a global scratch of at most the scratch bound per batch; the gene
+// table T of a batch of genes is bounded the same way
+struct LooArgs {
+  const double* T = nullptr;    // [genes][C + 1][n] (ppcx_loo_table_kernel), or null: host-given columns
+  const int* y = nullptr;       // [cells] the counts, an excluded cell as -(y + 1)
+  const double* expo = nullptr; // [S] exposure
+  const double* X = nullptr;    // [C][S] design, column-major
+  int S = 1, C = 1;
+  const double* cols = nullptr; // [cells][n] log-likelihood columns (testing build), instead of T
+  const int* excl = nullptr;    // [cells] excluded flags of the given columns (null: none)
+  const double* r_eff = nullptr;   // [cells] relative efficiencies (null: 1)
+  long n = 0;                   // draws
+  int cell0 = 0, n_cells = 0;   // first cell of the launch; cells of the table / columns
+  double* scratch = nullptr;    // [launch's cells][n] the long path's ratios
+  int sel_pad = 0;              // loo_sel_pad: the selection buffer
+  double* out = nullptr;        // [cells][kLooFields]
+};
+int loo_sel_pad(long n, double r_eff_min);     // power of two >= M + 1 for n draws at the smallest r_eff
+// LOO of the cells of genes[0 .. n_genes) (host) for draws [n][D] (device); yenc, r_eff (null or [cells]) and out host;
+// synchronous
+hipError_t loo_fit_cells(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
+                         const int* genes, const int* yenc, const double* r_eff, double* out, size_t scratch_bytes, hipStream_t st);
+// the log-likelihood matrix of those cells, [n][cells] (host out); synchronous
+hipError_t loo_fit_log_lik(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
+                           const int* genes, const int* yenc, double* out, size_t scratch_bytes, hipStream_t st);
+// LOO of host-given columns cols [n_cols][n] (testing build); synchronous
+hipError_t loo_columns(const double* cols, long n, int n_cols, const int* excl, const double* r_eff, double* out,
+                       size_t scratch_bytes, hipStream_t st);
 hipError_t launch_xchg_abort_kernel(const XchgArgs& x, hipStream_t st);      // tells every peer that this rank has left the fit
 
 }  // namespace ppcx

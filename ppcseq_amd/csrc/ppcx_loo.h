@@ -1,0 +1,131 @@
+// ppcx_loo.h -- PSIS-LOO per observed cell of a NUTS fit (ppcx_fit_loo, ppcx_fit_get_log_lik): what rstan::loo(fit) and
+// loo::loo(log_lik, r_eff) report per observation. Vehtari, Gelman, Gabry (2017), "Practical Bayesian model evaluation using
+// leave-one-out cross-validation and WAIC"; the tail fit is ppcx_psis.h's (Vehtari, Simpson, Gelman, Yao, Gabry 2024).
+//
+// Shared by the gfx950 kernels (ppcx_loo.hip) and the CPU check (tests/loo_host): the blocks below are `__host__ __device__`;
+// loo_cell_host at the end is their sequential composition, the kernel composes them with workgroup-parallel loops.
+//
+// Log-likelihood of a non-excluded or excluded cell (g, s) at draw theta:
+//   ll = neg_binomial_2_log_lpmf(y | eta, phi) with every constant kept, eta = exposure_s + X_s . alpha_g,
+//   phi = exp(-sigma_raw_g): what a Stan `generated quantities { log_lik }` block holds. With t = eta + sigma_raw, w = 1 + e^t
+//   (ppcx_disp.h):  ll = y eta - y - (y + phi) ln w + Fh - lgamma(y + 1),  Fh = lgamma(y + phi) - lgamma(phi) + y sigma_raw + y
+//   the cell's own Fh (disp_point / disp_cell), never the per-gene tables (they hold sums over a gene).
+//
+// PSIS-LOO of one cell from its column ll[0 .. n) (loo's psis() on the log ratios r = -ll, then loo's pointwise columns):
+//   a NaN ratio, or +Inf (ll = -Inf): every field NaN. A ratio of -Inf (ll = +Inf) takes no part; N = the other draws.
+//   1. M = ceil(min(0.2 N, 3 sqrt(N / r_eff))) (r_eff = 1 unless the caller gives one).
+//   2. In the frame shifted by the largest ratio mx: the tail is the M largest ratios, the cutoff c the (M + 1)-th largest.
+//      M < 5, or the M tail values all equal: k-hat = +Inf and the raw weights. Otherwise ppcx_psis.h steps 2 - 4 give k-hat
+//      and theta^; sigma = -k / theta^ with the mean k BEFORE the adjustment. Where k-hat is finite and sigma > 0, the j-th
+//      smallest tail ratio (j = 1 .. M) is replaced by log(qgpd((j - 1/2) / M; k-hat, sigma) + exp(c - mx)),
+//      qgpd(p) = sigma expm1(-k-hat log1p(-p)) / k-hat; otherwise the raw tail stays.
+//   3. every log weight lw is truncated at 0 (the largest raw one); the weights are normalised by logsumexp(lw).
+//   4. elpd_loo = logsumexp(lw + ll) - logsumexp(lw); lpd = logsumexp(ll) - log N; p_loo = lpd - elpd_loo;
+//      looic = -2 elpd_loo; khat = k-hat.
+//   Tied ratios have equal ll, so which of them receives which smoothed weight does not change any sum.
+// An excluded cell (not in the likelihood at the time of the call) is already held out: elpd_loo = lpd, p_loo = 0,
+// looic = -2 lpd, khat = NaN (a NaN ll: all NaN; ll = +Inf takes no part).
+// Every reduction runs in a fixed order: a cell's fields depend on its own column only.
+#pragma once
+#include <stdint.h>
+#include "ppcx_math.h"
+#include "ppcx_disp.h"
+#include "ppcx_psis.h"
+
+namespace ppcx {
+
+constexpr int kLooFields = 4;                  // elpd_loo, p_loo, looic, khat (include/ppcx.h PPCX_LOO_FIELDS)
+
+// ln(1 + e^t) for every t
+PPCX_HD double loo_log1pexp(double t) {
+  PPCX_NO_CONTRACT
+  return t > 0.0 ? t + log1p(exp(-t)) : log1p(exp(t));
+}
+// the cell's log-likelihood at one draw (y >= 0)
+PPCX_HD double loo_ll(int y, double eta, double sigma_raw) {
+  PPCX_NO_CONTRACT
+  const DispPoint p = disp_point(sigma_raw);
+  double F, Dh;
+  disp_cell(y, p, &F, &Dh);
+  const double yd = (double)y;
+  const double lw = loo_log1pexp(eta + sigma_raw);
+  return yd * eta - yd - (yd + p.phi) * lw + F - lgamma_int1(yd);
+}
+// tail length M of N draws at relative efficiency r_eff (step 1; for r_eff = 1 the same bits as psis_tail_len)
+PPCX_HD int loo_tail_len(long N, double r_eff) {
+  const double a = 0.2 * (double)N, b = 3.0 * sqrt((double)N / r_eff);
+  return (int)ceil(a < b ? a : b);
+}
+// the smoothed log weight of tail position j = 1 .. M (shifted frame), given k-hat, sigma and exp(cutoff - mx)
+PPCX_HD double loo_smoothed(int j, int M, double khat, double sigma, double ec) {
+  PPCX_NO_CONTRACT
+  const double p = ((double)j - 0.5) / (double)M;
+  const double q = sigma * expm1(-khat * log1p(-p)) / khat;
+  return log(q + ec);
+}
+// whether the tail is replaced (step 2)
+PPCX_HD bool loo_smooth_ok(double khat, double sigma) { return isfinite(khat) && sigma > 0.0; }
+
+}  // namespace ppcx
+
+#if !defined(__HIP_DEVICE_COMPILE__)
+#include <algorithm>
+#include <vector>
+namespace ppcx {
+inline double loo_logsumexp_host(const std::vector<double>& v) {
+  double mx = -INFINITY;
+  for (double x : v) mx = x > mx ? x : mx;
+  if (mx == -INFINITY) return -INFINITY;
+  double s = 0.0;
+  for (double x : v) s += exp(x - mx);
+  return mx + log(s);
+}
+// the whole spec for one cell, sequentially, for the CPU check: out[kLooFields]
+inline void loo_cell_host(const double* ll, long n, double r_eff, bool excluded, double* out) {
+  std::vector<double> l;
+  l.reserve((size_t)n);
+  for (long i = 0; i < n; ++i) {
+    const double r = -ll[i];
+    if (isnan(r) || (!excluded && r == INFINITY)) { out[0] = out[1] = out[2] = out[3] = NAN; return; }
+    if (r != -INFINITY) l.push_back(ll[i]);
+  }
+  const long N = (long)l.size();
+  const double lpd = N > 0 ? loo_logsumexp_host(l) - log((double)N) : NAN;
+  if (excluded) { out[0] = lpd; out[1] = 0.0; out[2] = -2.0 * lpd; out[3] = NAN; return; }
+  // ratios sorted ascending, each with its draw's ll (tied ratios have equal ll)
+  std::vector<double> r(N);
+  for (long i = 0; i < N; ++i) r[i] = -l[i];
+  std::sort(r.begin(), r.end());
+  const double mx = r[N - 1];
+  std::vector<double> lw(N);
+  for (long i = 0; i < N; ++i) lw[i] = r[i] - mx;
+  const int M = loo_tail_len(N, r_eff);
+  double khat = INFINITY;
+  if (M >= 5 && M < N && r[N - M] != mx) {
+    const double c = r[N - M - 1], ec = exp(c - mx);
+    std::vector<double> x(M);
+    for (int i = 0; i < M; ++i) x[i] = exp(r[N - M + i] - mx) - ec;
+    const int m = psis_grid_size(M);
+    const double xstar = x[psis_xstar_index(M) - 1];
+    std::vector<double> th(m), el(m);
+    for (int j = 0; j < m; ++j) {
+      th[j] = psis_theta(j + 1, m, x[M - 1], xstar);
+      double a = 0.0;
+      for (int i = 0; i < M; ++i) a += log1p(-th[j] * x[i]);
+      el[j] = psis_ell(th[j], a / M, M);
+    }
+    const double t = psis_theta_hat(th.data(), el.data(), m);
+    double a = 0.0;
+    for (int i = 0; i < M; ++i) a += log1p(-t * x[i]);
+    const double k = a / M, sigma = -k / t;
+    khat = psis_adjust(k, M);
+    if (loo_smooth_ok(khat, sigma))
+      for (int j = 1; j <= M; ++j) lw[N - M + j - 1] = loo_smoothed(j, M, khat, sigma, ec);
+  }
+  std::vector<double> a(N);
+  for (long i = 0; i < N; ++i) { lw[i] = lw[i] > 0.0 ? 0.0 : lw[i]; a[i] = lw[i] - r[i]; }
+  const double elpd = loo_logsumexp_host(a) - loo_logsumexp_host(lw);
+  out[0] = elpd; out[1] = lpd - elpd; out[2] = -2.0 * elpd; out[3] = khat;
+}
+}  // namespace ppcx
+#endif

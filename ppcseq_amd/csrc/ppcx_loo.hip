@@ -1,0 +1,311 @@
+// ppcx_loo.hip -- gfx950 kernels of PSIS-LOO per observed cell (ppcx_fit_loo, ppcx_fit_get_log_lik, include/ppcx.h; the
+// statistic: ppcx_loo.h).
+//
+//   ppcx_loo_table_kernel  the per-draw parameters of the requested genes, transposed: T[g][c][draw], c = 0 intercept,
+//                          1 .. C - 1 slopes (0 for a gene without slopes), C sigma_raw. One thread per (draw, gene), 32 x 32
+//                          tiles through LDS so that both the reads (along the genes) and the writes (along the draws) are
+//                          coalesced -- ppcx_ppc_table_kernel's layout, for a gene list and without truncation compensation.
+//   ppcx_loo_ll_kernel     the log-likelihood matrix itself, [draw][cell] (ppcx_fit_get_log_lik): one thread per (draw, cell).
+//   ppcx_loo_kernel        one workgroup per cell: the cell's n log-likelihoods from T (the S cells of a gene read the same rows
+//                          of T, through L2), as ratios r = -ll in LDS (up to kPsisLdsDraws draws) or in the workgroup's slice
+//                          of a bounded global scratch; the M + 1 largest selected exactly and sorted (ppcx_psis_dev.h, the
+//                          radix selection of the Pareto-k kernel), the profile fit, the smoothed tail and three logsumexp
+//                          reductions (lpd; the weights; the weights times the likelihood). The testing build runs it on
+//                          host-given columns too.
+// Every reduction runs in a fixed order and a cell reads nothing of another cell: its fields are the same bits whatever else is
+// requested and however the work is batched. The G S x n matrix is never materialised for LOO.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include "ppcx_psis_dev.h"
+#include "ppcx_loo.h"
+#include "ppcx_kernels.h"
+
+namespace ppcx {
+
+__global__ __launch_bounds__(256) void ppcx_loo_table_kernel(const double* draws, long n_draws, Dims d, const int* genes,
+                                                             int n_genes, double* T) {
+  __shared__ double tile[32][33];
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;          // 32 x 8
+  const long j0 = (long)blockIdx.x * 32; const int g0 = blockIdx.y * 32;
+  const int ncol = d.C + 1;
+  for (int c = 0; c < ncol; ++c) {
+    for (int r = ty; r < 32; r += 8) {
+      const long j = j0 + r; const int gi = g0 + tx;
+      double v = 0.0;
+      if (j < n_draws && gi < n_genes) {
+        const double* u = draws + j * (long)d.D;
+        const int g = genes[gi];
+        if (c == 0) v = u[d.off_intercept + g];
+        else if (c < d.C) v = g < d.K ? u[coef_index(d, c, g)] : 0.0;
+        else v = u[d.off_sigma_raw + g];
+      }
+      tile[r][tx] = v;
+    }
+    __syncthreads();
+    for (int r = ty; r < 32; r += 8) {
+      const int gi = g0 + r; const long j = j0 + tx;
+      if (j < n_draws && gi < n_genes) T[((long)gi * ncol + c) * n_draws + j] = tile[tx][r];
+    }
+    __syncthreads();
+  }
+}
+
+// log-likelihood of cell (gene gi of the table, sample s) at draw j, count y >= 0
+__device__ __forceinline__ double loo_cell_ll(const LooArgs& a, int gi, int s, long j, int y) {
+  const double* Tg = a.T + (long)gi * (a.C + 1) * a.n;
+  double eta = a.expo[s] + a.X[s] * Tg[j];
+  for (int cc = 1; cc < a.C; ++cc) eta += a.X[(long)cc * a.S + s] * Tg[(long)cc * a.n + j];
+  return loo_ll(y, eta, Tg[(long)a.C * a.n + j]);
+}
+
+__global__ __launch_bounds__(256) void ppcx_loo_ll_kernel(LooArgs a, long j0, long n_rows, double* out) {
+  const long n_cells = (long)a.n_cells;
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= n_rows * n_cells) return;
+  const long jr = t / n_cells;
+  const int cell = (int)(t - jr * n_cells);
+  const int gi = cell / a.S, s = cell - gi * a.S;
+  const int ye = a.y[cell];
+  out[t] = loo_cell_ll(a, gi, s, j0 + jr, ye < 0 ? -ye - 1 : ye);
+}
+
+struct LooTerms { double a, b; };                // running max or sum of the two logsumexps: a over lw + ll, b over lw
+
+template <bool LDS, bool COLS>
+__global__ __launch_bounds__(kPsisThreads) void ppcx_loo_kernel(LooArgs a) {
+  extern __shared__ uint64_t lds_u[];
+  __shared__ PsisShared sh;
+  const int tid = threadIdx.x;
+  const long n = a.n;
+  uint64_t* K = lds_u;                                   // [sel_pad] keys of the M + 1 largest ratios
+  double* X = reinterpret_cast<double*>(lds_u + a.sel_pad);            // [sel_pad] the tail's exceedances
+  double* V = LDS ? X + a.sel_pad : a.scratch + (long)blockIdx.x * n;  // the cell's ratios r = -ll
+  const int cell = a.cell0 + blockIdx.x;                 // of this launch's cells (the table's genes, or the given columns)
+  int y = 0; bool excluded;
+  if (COLS) excluded = a.excl && a.excl[cell] != 0;
+  else { const int ye = a.y[cell]; excluded = ye < 0; y = excluded ? -ye - 1 : ye; }
+  const int gi = COLS ? 0 : cell / a.S, s = COLS ? 0 : cell - gi * a.S;
+  double* o = a.out + (long)cell * kLooFields;
+  // ---- the ratios; NaN / +Inf; N (the -Inf ratios take no part); the largest ratio and the largest ll
+  bool bad = false; double cnt = 0.0, rmax = -INFINITY, lmax = -INFINITY;
+  for (long i = tid; i < n; i += kPsisThreads) {
+    const double ll = COLS ? a.cols[(long)cell * n + i] : loo_cell_ll(a, gi, s, i, y);
+    const double r = -ll;
+    bad = bad || isnan(r) || (!excluded && r == INFINITY);
+    if (r != -INFINITY) { cnt += 1.0; rmax = fmax(rmax, r); lmax = fmax(lmax, ll); }
+    V[i] = r;
+  }
+  bad = __syncthreads_or(bad ? 1 : 0) != 0;
+  if (bad) {
+    if (tid == 0) o[0] = o[1] = o[2] = o[3] = NAN;
+    return;
+  }
+  const long N = (long)psis_block_sum(cnt, sh.red);
+  rmax = psis_block_max(rmax, sh.red);
+  lmax = psis_block_max(lmax, sh.red);
+  // ---- lpd = logsumexp(ll) - log N
+  double sl = 0.0;
+  for (long i = tid; i < n; i += kPsisThreads) { const double r = V[i]; if (r != -INFINITY) sl += exp(-r - lmax); }
+  sl = psis_block_sum(sl, sh.red);
+  const double lpd = N > 0 ? (lmax == -INFINITY ? -INFINITY : lmax + log(sl)) - log((double)N) : NAN;
+  if (excluded) {                                        // already held out: the exact held-out predictive density
+    if (tid == 0) { o[0] = lpd; o[1] = 0.0; o[2] = -2.0 * lpd; o[3] = NAN; }
+    return;
+  }
+  // ---- the tail: M + 1 largest, the profile fit, k-hat and sigma
+  const double mx = rmax;
+  const double reff = a.r_eff ? a.r_eff[cell] : 1.0;
+  const int M = loo_tail_len(N, reff);
+  double khat = INFINITY, sigma = 0.0, ec = 0.0;
+  bool smooth = false;
+  uint64_t prefix = 0; int n_extra = 0;
+  if (M >= 5 && (long)M < N) {
+    int want;
+    prefix = psis_select_top(V, n, M, K, a.sel_pad, sh, &want);
+    if (psis_unkey(K[1]) != mx) {
+      const double cut = psis_unkey(K[0]);
+      ec = exp(cut - mx);
+      for (int i = tid; i < M; i += kPsisThreads) X[i] = exp(psis_unkey(K[i + 1]) - mx) - ec;
+      __syncthreads();
+      double theta_hat, k_mean;
+      psis_fit_tail(X, M, sh, &theta_hat, &k_mean);
+      khat = psis_adjust(k_mean, M);
+      sigma = -k_mean / theta_hat;
+      smooth = loo_smooth_ok(khat, sigma);
+      if (smooth) {                                      // copies of the cutoff outside the tail: all of them but want - 1
+        double eq = 0.0;
+        for (long i = tid; i < n; i += kPsisThreads) eq += psis_key(V[i]) == prefix ? 1.0 : 0.0;
+        n_extra = (int)psis_block_sum(eq, sh.red) - (want - 1);
+      }
+    }
+  }
+  // ---- logsumexp(lw + ll) and logsumexp(lw): a raw draw has lw = r - mx (<= 0), a tail draw the smoothed value truncated at 0
+  auto terms = [&](bool sum, LooTerms mxv) {
+    LooTerms t{sum ? 0.0 : -INFINITY, sum ? 0.0 : -INFINITY};
+    auto add = [&](double lw, double r, double mult) {
+      const double va = lw - r;
+      if (sum) { t.a += mult * exp(va - mxv.a); t.b += mult * exp(lw - mxv.b); }
+      else { t.a = fmax(t.a, va); t.b = fmax(t.b, lw); }
+    };
+    for (long i = tid; i < n; i += kPsisThreads) {
+      const double r = V[i];
+      if (r == -INFINITY || (smooth && psis_key(r) >= prefix)) continue;
+      add(r - mx, r, 1.0);
+    }
+    if (smooth) {
+      for (int j = tid; j < M; j += kPsisThreads) {
+        const double sm = loo_smoothed(j + 1, M, khat, sigma, ec);
+        add(sm > 0.0 ? 0.0 : sm, psis_unkey(K[j + 1]), 1.0);
+      }
+      if (tid == 0 && n_extra > 0) { const double c = psis_unkey(prefix); add(c - mx, c, (double)n_extra); }
+    }
+    return t;
+  };
+  LooTerms m0 = terms(false, LooTerms{0.0, 0.0});
+  m0.a = psis_block_max(m0.a, sh.red);
+  m0.b = psis_block_max(m0.b, sh.red);
+  LooTerms s0 = terms(true, m0);
+  s0.a = psis_block_sum(s0.a, sh.red);
+  s0.b = psis_block_sum(s0.b, sh.red);
+  const double elpd = (m0.a + log(s0.a)) - (m0.b + log(s0.b));
+  if (tid == 0) { o[0] = elpd; o[1] = lpd - elpd; o[2] = -2.0 * elpd; o[3] = khat; }
+}
+
+// ---- launch helpers (host)
+static int loo_pow2(long n) { int p = 1; while (p < n) p <<= 1; return p; }
+int loo_sel_pad(long n, double r_eff_min) { return loo_pow2((long)loo_tail_len(n, r_eff_min) + 1); }
+hipError_t launch_loo_table_kernel(const double* draws, long n_draws, const Dims& d, const int* genes, int n_genes, double* T,
+                                   hipStream_t st) {
+  dim3 grid((unsigned)((n_draws + 31) / 32), (unsigned)((n_genes + 31) / 32));
+  hipLaunchKernelGGL(ppcx_loo_table_kernel, grid, dim3(256), 0, st, draws, n_draws, d, genes, n_genes, T);
+  return hipGetLastError();
+}
+hipError_t launch_loo_ll_kernel(const LooArgs& a, long j0, long n_rows, double* out, hipStream_t st) {
+  const long total = n_rows * (long)a.n_cells;
+  hipLaunchKernelGGL(ppcx_loo_ll_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a, j0, n_rows, out);
+  return hipGetLastError();
+}
+hipError_t launch_loo_kernel(const LooArgs& a, int n_blocks, hipStream_t st) {
+  const bool lds = a.n <= kPsisLdsDraws, cols = a.cols != nullptr;
+  const size_t bytes = sizeof(double) * (2 * (size_t)a.sel_pad + (lds ? (size_t)a.n : 0));
+  const void* fn = lds ? (cols ? (const void*)ppcx_loo_kernel<true, true> : (const void*)ppcx_loo_kernel<true, false>)
+                       : (cols ? (const void*)ppcx_loo_kernel<false, true> : (const void*)ppcx_loo_kernel<false, false>);
+  if (bytes > 64u * 1024u) {
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) return e;
+  }
+  if (lds && cols) hipLaunchKernelGGL((ppcx_loo_kernel<true, true>), dim3(n_blocks), dim3(kPsisThreads), bytes, st, a);
+  else if (lds) hipLaunchKernelGGL((ppcx_loo_kernel<true, false>), dim3(n_blocks), dim3(kPsisThreads), bytes, st, a);
+  else if (cols) hipLaunchKernelGGL((ppcx_loo_kernel<false, true>), dim3(n_blocks), dim3(kPsisThreads), bytes, st, a);
+  else hipLaunchKernelGGL((ppcx_loo_kernel<false, false>), dim3(n_blocks), dim3(kPsisThreads), bytes, st, a);
+  return hipGetLastError();
+}
+
+// Cells of a launch in batches: all at once where the ratios live in LDS, else as many as the scratch bound holds
+static hipError_t loo_cells(LooArgs a, int n_cells, size_t scratch_bytes, hipStream_t st) {
+  hipError_t e = hipSuccess;
+  int batch = n_cells;
+  if (a.n > kPsisLdsDraws) {
+    batch = (int)std::max<size_t>(1, scratch_bytes / (sizeof(double) * (size_t)a.n));
+    if (batch > n_cells) batch = n_cells;
+    e = hipMalloc(&a.scratch, sizeof(double) * (size_t)a.n * batch);
+  }
+  for (int c0 = 0; e == hipSuccess && c0 < n_cells; c0 += batch) {
+    a.cell0 = c0;
+    e = launch_loo_kernel(a, n_cells - c0 < batch ? n_cells - c0 : batch, st);
+  }
+  const hipError_t es = hipStreamSynchronize(st);      // nothing is freed under a running kernel
+  if (e == hipSuccess) e = es;
+  (void)hipFree(a.scratch);
+  return e;
+}
+
+hipError_t loo_fit_cells(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
+                         const int* genes, const int* yenc, const double* r_eff, double* out, size_t scratch_bytes,
+                         hipStream_t st) {
+  const int S = d.S, ncol = d.C + 1;
+  double rmin = 1.0;
+  for (long i = 0; r_eff && i < (long)n_genes * S; ++i) rmin = std::min(rmin, r_eff[i]);
+  int gb = (int)std::max<size_t>(1, scratch_bytes / (sizeof(double) * (size_t)ncol * (size_t)n));
+  if (gb > n_genes) gb = n_genes;
+  int *d_genes = nullptr, *d_y = nullptr; double *d_T = nullptr, *d_reff = nullptr, *d_out = nullptr;
+  const size_t ncells = (size_t)n_genes * S;
+  hipError_t e = hipMalloc(&d_genes, sizeof(int) * (size_t)n_genes);
+  if (e == hipSuccess) e = hipMalloc(&d_y, sizeof(int) * ncells);
+  if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(double) * kLooFields * ncells);
+  if (e == hipSuccess) e = hipMalloc(&d_T, sizeof(double) * (size_t)ncol * (size_t)n * gb);
+  if (e == hipSuccess && r_eff) e = hipMalloc(&d_reff, sizeof(double) * ncells);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_genes, genes, sizeof(int) * (size_t)n_genes, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_y, yenc, sizeof(int) * ncells, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && r_eff) e = hipMemcpyAsync(d_reff, r_eff, sizeof(double) * ncells, hipMemcpyHostToDevice, st);
+  for (int g0 = 0; e == hipSuccess && g0 < n_genes; g0 += gb) {
+    const int ng = n_genes - g0 < gb ? n_genes - g0 : gb;
+    e = launch_loo_table_kernel(draws, n, d, d_genes + g0, ng, d_T, st);
+    if (e != hipSuccess) break;
+    LooArgs a;
+    a.T = d_T; a.y = d_y + (size_t)g0 * S; a.expo = expo; a.X = X; a.S = S; a.C = d.C; a.n = n;
+    a.r_eff = d_reff ? d_reff + (size_t)g0 * S : nullptr; a.out = d_out + (size_t)g0 * S * kLooFields;
+    a.n_cells = ng * S; a.sel_pad = loo_sel_pad(n, rmin);
+    e = loo_cells(a, ng * S, scratch_bytes, st);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(double) * kLooFields * ncells, hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = es;
+  (void)hipFree(d_genes); (void)hipFree(d_y); (void)hipFree(d_T); (void)hipFree(d_reff); (void)hipFree(d_out);
+  return e;
+}
+
+hipError_t loo_fit_log_lik(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
+                           const int* genes, const int* yenc, double* out, size_t scratch_bytes, hipStream_t st) {
+  const int S = d.S, ncol = d.C + 1;
+  const size_t ncells = (size_t)n_genes * S;
+  int *d_genes = nullptr, *d_y = nullptr; double *d_T = nullptr, *d_buf = nullptr;
+  // the whole table of the requested genes, then the matrix in row blocks of at most scratch_bytes
+  long rows = (long)std::max<size_t>(1, scratch_bytes / (sizeof(double) * ncells));
+  if (rows > n) rows = n;
+  hipError_t e = hipMalloc(&d_genes, sizeof(int) * (size_t)n_genes);
+  if (e == hipSuccess) e = hipMalloc(&d_y, sizeof(int) * ncells);
+  if (e == hipSuccess) e = hipMalloc(&d_T, sizeof(double) * (size_t)ncol * (size_t)n * n_genes);
+  if (e == hipSuccess) e = hipMalloc(&d_buf, sizeof(double) * ncells * (size_t)rows);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_genes, genes, sizeof(int) * (size_t)n_genes, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_y, yenc, sizeof(int) * ncells, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = launch_loo_table_kernel(draws, n, d, d_genes, n_genes, d_T, st);
+  LooArgs a;
+  a.T = d_T; a.y = d_y; a.expo = expo; a.X = X; a.S = S; a.C = d.C; a.n = n; a.n_cells = (int)ncells;
+  for (long j0 = 0; e == hipSuccess && j0 < n; j0 += rows) {
+    const long nr = n - j0 < rows ? n - j0 : rows;
+    e = launch_loo_ll_kernel(a, j0, nr, d_buf, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(out + (size_t)j0 * ncells, d_buf, sizeof(double) * ncells * (size_t)nr, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+  }
+  const hipError_t es = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = es;
+  (void)hipFree(d_genes); (void)hipFree(d_y); (void)hipFree(d_T); (void)hipFree(d_buf);
+  return e;
+}
+
+hipError_t loo_columns(const double* cols, long n, int n_cols, const int* excl, const double* r_eff, double* out,
+                       size_t scratch_bytes, hipStream_t st) {
+  double rmin = 1.0;
+  for (int i = 0; r_eff && i < n_cols; ++i) rmin = std::min(rmin, r_eff[i]);
+  double *d_cols = nullptr, *d_reff = nullptr, *d_out = nullptr; int* d_excl = nullptr;
+  hipError_t e = hipMalloc(&d_cols, sizeof(double) * (size_t)n * n_cols);
+  if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(double) * kLooFields * (size_t)n_cols);
+  if (e == hipSuccess && excl) e = hipMalloc(&d_excl, sizeof(int) * (size_t)n_cols);
+  if (e == hipSuccess && r_eff) e = hipMalloc(&d_reff, sizeof(double) * (size_t)n_cols);
+  if (e == hipSuccess) e = hipMemcpyAsync(d_cols, cols, sizeof(double) * (size_t)n * n_cols, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && excl) e = hipMemcpyAsync(d_excl, excl, sizeof(int) * (size_t)n_cols, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess && r_eff) e = hipMemcpyAsync(d_reff, r_eff, sizeof(double) * (size_t)n_cols, hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) {
+    LooArgs a;
+    a.cols = d_cols; a.excl = d_excl; a.r_eff = d_reff; a.n = n; a.n_cells = n_cols; a.out = d_out; a.sel_pad = loo_sel_pad(n, rmin);
+    e = loo_cells(a, n_cols, scratch_bytes, st);
+  }
+  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(double) * kLooFields * (size_t)n_cols, hipMemcpyDeviceToHost, st);
+  const hipError_t es = hipStreamSynchronize(st);
+  if (e == hipSuccess) e = es;
+  (void)hipFree(d_cols); (void)hipFree(d_reff); (void)hipFree(d_out); (void)hipFree(d_excl);
+  return e;
+}
+
+}  // namespace ppcx

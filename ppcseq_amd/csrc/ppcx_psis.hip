@@ -16,17 +16,14 @@
 //                             statistics of a full sort --, then the m-point profile fit: one wavefront per grid point, a
 //                             fixed-order reduction, and theta^ and k-hat as the header composes them. Columns of up to
 //                             kPsisLdsDraws draws are staged in LDS, longer ones are transformed in place in the scratch.
+// The selection, the sort and the profile fit are in ppcx_psis_dev.h, shared with the PSIS-LOO kernel (ppcx_loo.hip).
 // Every reduction runs in a fixed order: a column's k-hat depends on its values only, the same bits on every call.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include "ppcx_psis.h"
+#include "ppcx_psis_dev.h"
 #include "ppcx_kernels.h"
 
 namespace ppcx {
-
-constexpr int kPsisThreads = 256;
-constexpr int kPsisWaves = kPsisThreads / 64;
-constexpr int kPsisMaxGrid = 96;              // 30 + floor(sqrt(kPsisMaxSel - 1)) = 93 grid points at most
 
 __global__ __launch_bounds__(256) void ppcx_psis_approx_kernel(Dims d, const double* sq, const double* sg, const double* hyper,
                                                                double* mu, double* omega) {
@@ -64,23 +61,6 @@ __global__ void ppcx_psis_record_kernel(Dims d, const Cmd* cmds, const double* r
   log_p[c] = hyper_close(d, cm.hy, cm.hyp_q, r[PT_LP], r + PT_H0, g6);
 }
 
-__device__ __forceinline__ double psis_wave_sum(double v) {
-#pragma unroll
-  for (int msk = 1; msk < 64; msk <<= 1) v += __shfl_xor(v, msk, 64);
-  return v;                                    // the same bits in every lane
-}
-// sum over the workgroup in a fixed order; every thread gets it. red: kPsisWaves doubles of LDS
-__device__ double psis_block_sum(double v, double* red) {
-  v = psis_wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < kPsisWaves; ++w) s += red[w];
-  return s;
-}
-
 __global__ __launch_bounds__(kPsisThreads) void ppcx_psis_log_g_kernel(const double* draws, int D, const double* mu,
                                                                        const double* omega, const double* log_p, double* log_g,
                                                                        double* r) {
@@ -100,33 +80,11 @@ __global__ __launch_bounds__(kPsisThreads) void ppcx_psis_log_g_kernel(const dou
   }
 }
 
-// ascending bitonic sort of the keys s[0 .. npad) (npad a power of two)
-__device__ void psis_sort(uint64_t* s, int npad) {
-  for (int k = 2; k <= npad; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < (npad >> 1); i += kPsisThreads) {
-        const int lo = 2 * j * (i / j) + (i % j), hi = lo + j;
-        const bool up = (lo & k) == 0;
-        const uint64_t a = s[lo], b = s[hi];
-        if ((a > b) == up) { s[lo] = b; s[hi] = a; }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-struct PsisShared {
-  int hist[256];
-  double red[kPsisWaves];
-  double theta[kPsisMaxGrid], ell[kPsisMaxGrid];
-  uint64_t prefix; int want, pos; double theta_hat;
-};
-
 template <bool LDS>
 __global__ __launch_bounds__(kPsisThreads) void ppcx_psis_kernel(PsisArgs a) {
   extern __shared__ uint64_t lds_u[];
   __shared__ PsisShared sh;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x;
   const long n = a.n;
   uint64_t* K = lds_u;                                   // [sel_pad] keys of the M + 1 largest values
   double* X = reinterpret_cast<double*>(lds_u + a.sel_pad);            // [sel_pad] the tail's exceedances
@@ -149,48 +107,8 @@ __global__ __launch_bounds__(kPsisThreads) void ppcx_psis_kernel(PsisArgs a) {
       __syncthreads();
       continue;
     }
-    // ---- the (M + 1)-th largest key: eight passes of 8 bits from the top
-    uint64_t prefix = 0, mask = 0; int want = M + 1;
-    for (int shift = 56; shift >= 0; shift -= 8) {
-      sh.hist[tid] = 0;                                  // kPsisThreads == 256 bins
-      __syncthreads();
-      for (long i0 = 0; i0 < n; i0 += kPsisThreads) {    // wave-uniform trip count
-        const long i = i0 + tid;
-        bool part = false; int dg = 0;
-        if (i < n) {
-          const uint64_t k = psis_key(V[i]);
-          part = (k & mask) == prefix;
-          dg = (int)((k >> shift) & 255);
-        }
-        const unsigned long long act = __ballot(part);
-        if (act) {                                       // one atomic per wavefront where its values share the digit
-          const int first = __ffsll((long long)act) - 1;
-          const int d0 = __shfl(dg, first, 64);
-          if (__all(!part || dg == d0)) { if (lane == first) atomicAdd(&sh.hist[d0], __popcll(act)); }
-          else if (part) atomicAdd(&sh.hist[dg], 1);
-        }
-      }
-      __syncthreads();
-      if (tid == 0) {
-        int cum = 0, b = 255;
-        for (; b > 0; --b) { if (cum + sh.hist[b] >= want) break; cum += sh.hist[b]; }
-        sh.want = want - cum;
-        sh.prefix = prefix | ((uint64_t)b << shift);
-      }
-      __syncthreads();
-      prefix = sh.prefix; want = sh.want; mask |= (uint64_t)255 << shift;
-    }
-    // ---- the M + 1 largest: the keys above the threshold, then `want` copies of it, sorted
-    const int n_gt = M + 1 - want;
-    if (tid == 0) sh.pos = 0;
-    __syncthreads();
-    for (long i = tid; i < n; i += kPsisThreads) {
-      const uint64_t k = psis_key(V[i]);
-      if (k > prefix) K[atomicAdd(&sh.pos, 1)] = k;
-    }
-    for (int p = n_gt + tid; p < a.sel_pad; p += kPsisThreads) K[p] = p <= M ? prefix : ~(uint64_t)0;
-    __syncthreads();
-    psis_sort(K, a.sel_pad);
+    int want;
+    (void)psis_select_top(V, n, M, K, a.sel_pad, sh, &want);
     const double cut = psis_unkey(K[0]), mx = psis_unkey(K[M]);
     if (psis_unkey(K[1]) == mx) {                        // the M tail values are all equal
       if (tid == 0) a.out[c] = INFINITY;
@@ -201,23 +119,9 @@ __global__ __launch_bounds__(kPsisThreads) void ppcx_psis_kernel(PsisArgs a) {
     for (int i = tid; i < M; i += kPsisThreads) X[i] = exp(psis_unkey(K[i + 1]) - mx) - ec;
     __syncthreads();
     // ---- the profile fit: one wavefront per grid point
-    const int m = psis_grid_size(M);
-    const double x_max = X[M - 1], xstar = X[psis_xstar_index(M) - 1];
-    for (int j = wave; j < m; j += kPsisWaves) {
-      const double th = psis_theta(j + 1, m, x_max, xstar);
-      double s = 0.0;
-      for (int i = lane; i < M; i += 64) s += log1p(-th * X[i]);
-      s = psis_wave_sum(s);
-      if (lane == 0) { sh.theta[j] = th; sh.ell[j] = psis_ell(th, s / M, M); }
-    }
-    __syncthreads();
-    if (tid == 0) sh.theta_hat = psis_theta_hat(sh.theta, sh.ell, m);
-    __syncthreads();
-    const double t = sh.theta_hat;
-    double s = 0.0;
-    for (int i = tid; i < M; i += kPsisThreads) s += log1p(-t * X[i]);
-    s = psis_block_sum(s, sh.red);
-    if (tid == 0) a.out[c] = psis_adjust(s / M, M);
+    double theta_hat, k_mean;
+    psis_fit_tail(X, M, sh, &theta_hat, &k_mean);
+    if (tid == 0) a.out[c] = psis_adjust(k_mean, M);
     __syncthreads();                                     // K, X, V and the shared block are reused by the next column
   }
 }

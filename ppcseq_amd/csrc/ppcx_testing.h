@@ -15,7 +15,9 @@ extern "C" {
  * a chain group's trimmed launch, per mille / passes per wavefront of such a launch beyond the fewest possible; -1 or 0:
  * built-in; plans made afterwards),
  * "psis_slots", "psis_scratch_bytes" (the Pareto-k diagnostic: draws per launch of the log_p evaluation, bound of the column
- * scratch per batch; 0: built-in). */
+ * scratch per batch; 0: built-in),
+ * "loo_scratch_bytes" (PSIS-LOO: bound of the gene table, of the long columns' scratch and of the exported log-likelihood
+ * block per batch; 0: built-in). */
 PPCX_API int ppcx_testing_set(const char* key, long long value);
 /* path of a shared object that provides ncclGetUniqueId / ncclCommInitRank / ncclCommDestroy / ncclAllReduce /
  * ncclGetErrorString instead of librccl (before the first communicator is created) */
@@ -48,6 +50,9 @@ PPCX_API int ppcx_testing_get_disp_table(ppcx_model* m, double* out);
  * cols [n][n_cols] row-major parameter draws; khat [n_cols + 1]: the k-hat of 1/2 log1p(cols[:, i]^2) + lr for i < n_cols,
  * then that of lr itself. */
 PPCX_API int ppcx_testing_psis(int n, int n_cols, const double* lr, const double* cols, double* khat);
+/* The PSIS-LOO kernel of ppcx_fit_loo on host-given log-likelihood columns, on the current device (ppcx_loo.hip): ll [n_cols][n]
+ * (column-major: a cell's n draws contiguous), excluded NULL or [n_cols] flags, r_eff NULL or [n_cols]; out [n_cols][4]. */
+PPCX_API int ppcx_testing_loo(int n, int n_cols, const double* ll, const int32_t* excluded, const double* r_eff, double* out);
 #ifdef __cplusplus
 }
 #endif

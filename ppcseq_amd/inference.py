@@ -63,6 +63,7 @@ class InferenceResult:
     counts_rng: np.ndarray | None = None
     convergence: dict | None = None   # check_convergence: Fit.summary of alpha_sub_1 (and lp__ where the fit holds it)
     approximation: dict | None = None  # check_approximation: Fit.psis of alpha_sub_1 and the overall k-hat (column -1, last)
+    loo: dict | None = None            # check_loo: Fit.loo of the checked genes' cells ([K, S] arrays and loo's estimates)
 
     def to_frame(self):
         import pandas as pd
@@ -144,6 +145,29 @@ def approximation_warnings(khat):
     return []
 
 
+def loo_threshold(n_draws):
+    """loo (>= 2.7): the Pareto k above which PSIS-LOO of an observation is unreliable at n_draws draws,
+    min(1 - 1 / log10(n_draws), 0.7) -- 0.7 from 2 154 draws on"""
+    return min(1.0 - 1.0 / math.log10(n_draws), 0.7)
+
+
+def loo_warnings(khat, n_draws):
+    """What loo tells its user after PSIS-LOO when any observation's k-hat exceeds loo_threshold(n_draws) (Fit.loo's khat,
+    any shape; NaN -- an excluded cell or one with a non-finite log-likelihood -- reports nothing). Returns the messages, like
+    convergence_warnings."""
+    k = np.asarray(khat, dtype=np.float64).ravel()
+    k = k[~np.isnan(k)]
+    if k.size and float(k.max()) > loo_threshold(n_draws):
+        return ["Some Pareto k diagnostic values are too high. See help('pareto-k-diagnostic') for details."]
+    return []
+
+
+def _warn_loo(loo, n_draws):
+    import warnings
+    for msg in loo_warnings(loo["khat"], n_draws):
+        warnings.warn(msg, RuntimeWarning, stacklevel=3)
+
+
 def _warn_convergence(summary, chains):
     import warnings
     for msg in convergence_warnings(summary, chains):
@@ -168,7 +192,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                  devices=None,
                  launch=None,
                  check_convergence=False,
-                 check_approximation=False):
+                 check_approximation=False,
+                 check_loo=False):
     """One inference pass (discovery or test) of ppcseq on the GPU.
 
     counts            G x S integer matrix, genes ordered with the `how_many_to_check` checked genes first
@@ -191,6 +216,10 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                       of the output draws and the per-parameter k-hat of alpha_sub_1, on the device (Fit.psis), kept as
                       `res.approximation` (the overall k-hat last, column -1) and reported as RuntimeWarning from the
                       overall k-hat (approximation_warnings). Not for a NUTS pass.
+    check_loo         what rstan::loo(fit) reports next: PSIS-LOO of every checked cell (elpd_loo, p_loo, looic, khat; loo's
+                      estimates over the cells not excluded) on the device (Fit.loo), kept as `res.loo` and reported as
+                      RuntimeWarning when a k-hat is too high (loo_warnings). An excluded cell holds its exact held-out
+                      density. devices=[...]: over the pooled chains. Not for an ADVI pass.
     Returns an InferenceResult.
     """
     counts = np.asarray(counts)
@@ -218,13 +247,16 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
     if check_approximation and not approximate_posterior_inference:
         raise ValueError("check_approximation needs an ADVI pass (approximate_posterior_inference = True): the Pareto k "
                          "diagnostic judges the variational approximation")
+    if check_loo and approximate_posterior_inference:
+        raise ValueError("check_loo needs a NUTS pass: PSIS-LOO of an ADVI fit (loo_approximate_posterior) is not available")
     if devices is not None and len(devices) > 1 and (save_generated_quantities or pass_fit or model is not None or approximate_posterior_inference):
         raise ValueError("devices=[...] splits the chains of a NUTS fit over several devices and pools their draws: it cannot "
                          "be combined with save_generated_quantities, pass_fit, a caller's model or approximate_posterior_inference")
     if devices is not None and len(devices) > 1 and not approximate_posterior_inference:
         return _do_inference_devices(counts, X, exposure_rate, K, list(devices), chains, n_iter, warmup, excl,
                                      lambda_mu_mu, approximate_posterior_analysis, adj_prob_theshold,
-                                     how_many_posterior_draws, truncation_compensation, seed, launch, check_convergence)
+                                     how_many_posterior_draws, truncation_compensation, seed, launch, check_convergence,
+                                     check_loo)
     if devices is not None and len(devices) >= 1 and model is None:
         device = devices[0]
     own_model = model is None
@@ -271,6 +303,9 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
             if check_convergence:
                 res.convergence = fit.summary(np.arange(off_alpha1, off_alpha1 + K), lp=True)
                 _warn_convergence(res.convergence, chains)
+            if check_loo:
+                res.loo = fit.loo(np.arange(K))
+                _warn_loo(res.loo, fit.chains * fit.n_keep)
         res.counts_rng = rng
         if pass_fit:
             res.fit = fit
@@ -322,15 +357,22 @@ def checked_columns(G, C, K):
 
 
 def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, approximate_posterior_analysis,
-                   adj_prob_theshold, how_many_posterior_draws, truncation_compensation, seed, device=0, convergence=False):
+                   adj_prob_theshold, how_many_posterior_draws, truncation_compensation, seed, device=0, convergence=False,
+                   loo=False, excl=None):
     """Credible intervals, slopes and flags from the pooled draws of all chains (rstan::summary over merged chains,
     R/utilities.R:685-703): `draws_checked` is [chains, n_keep, len(checked_columns)] in global chain order. The
     posterior-predictive kernel runs on a model that holds the K checked genes only -- cell ids g*S+s and draw indices are
     those of the full model, so the result is what a single fit of all the chains gives, bit for bit. convergence: also the
-    summary of alpha_sub_1 over the pooled chains (res.convergence; Fit.summary)."""
+    summary of alpha_sub_1 over the pooled chains (res.convergence; Fit.summary). loo: also PSIS-LOO of the checked cells over
+    the pooled chains (res.loo; Fit.loo); the small model then carries the checked genes' cells of `excl` (0-based cell ids of
+    the full model), so that the cells excluded from the fit are held out."""
     counts = np.asarray(counts)
     X = np.asarray(X, dtype=np.float64).reshape(counts.shape[1], -1)
-    small = _lib.Model(counts[:K], X, exposure_rate, K, lambda_mu_mu=lambda_mu_mu, device=device)
+    small_excl = None
+    if loo and excl is not None:
+        e = np.asarray(excl, dtype=np.int64).ravel()
+        small_excl = e[e < K * counts.shape[1]].astype(np.int32)
+    small = _lib.Model(counts[:K], X, exposure_rate, K, lambda_mu_mu=lambda_mu_mu, device=device, excl=small_excl)
     try:
         fit = small.fit_from_draws(draws_checked)
         try:
@@ -341,6 +383,7 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
                 ci = fit.ppc(truncation_compensation, p, 1 - p, seed=seed, n_gen=0, resample=False)
             slope = fit.columns(np.arange(3 + K, 3 + 2 * K)).reshape(-1, K).mean(axis=0) if K else np.zeros(0)
             conv = fit.summary(np.arange(3 + K, 3 + 2 * K), lp=False) if convergence else None
+            loo_res = fit.loo(np.arange(K)) if loo and K else None
         finally:
             fit.close()
     finally:
@@ -348,12 +391,13 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
     res = _post_process(counts[:K], ci, slope, X)
     res.total_draws = counts.shape[1] * K * int(how_many_posterior_draws)
     res.convergence = conv
+    res.loo = loo_res
     return res
 
 
 def _do_inference_devices(counts, X, exposure_rate, K, devices, chains, n_iter, warmup, excl, lambda_mu_mu,
                           approximate_posterior_analysis, adj_prob_theshold, how_many_posterior_draws,
-                          truncation_compensation, seed, launch=None, check_convergence=False):
+                          truncation_compensation, seed, launch=None, check_convergence=False, check_loo=False):
     """Chains split over several devices of this process (one host thread per device; the C ABI allows different handles
     on different threads), pooled summary on the first device."""
     import threading
@@ -394,8 +438,10 @@ def _do_inference_devices(counts, X, exposure_rate, K, devices, chains, n_iter, 
     res = pooled_summary(counts, X, exposure_rate, K, pooled, lambda_mu_mu=lambda_mu_mu,
                          approximate_posterior_analysis=approximate_posterior_analysis, adj_prob_theshold=adj_prob_theshold,
                          how_many_posterior_draws=how_many_posterior_draws, truncation_compensation=truncation_compensation,
-                         seed=seed, device=devices[0], convergence=check_convergence)
+                         seed=seed, device=devices[0], convergence=check_convergence, loo=check_loo, excl=excl)
     res.chains, res.iter = chains, n_iter
     if check_convergence:
         _warn_convergence(res.convergence, chains)
+    if check_loo and res.loo is not None:
+        _warn_loo(res.loo, pooled.shape[0] * pooled.shape[1])
     return res
