@@ -20,6 +20,7 @@
 #include "ppcx_summary.h"
 #include "ppcx_psis.h"
 #include "ppcx_loo.h"
+#include "ppcx_columns.h"
 
 using namespace ppcx;
 
@@ -1806,24 +1807,17 @@ extern "C" int ppcx_fit_get_columns(ppcx_fit* f, int n_cols, const int32_t* cols
   HIPCHK(hipSetDevice(f->m->device));
   const long rows = (long)f->chains * f->n_keep;
   if (rows == 0) return PPCX_OK;
-  int* d_cols = nullptr; double* d_out = nullptr;
-  HIPCHK(hipMalloc(&d_cols, sizeof(int) * n_cols));
-  hipError_t e = hipMalloc(&d_out, sizeof(double) * (size_t)rows * n_cols);
-  if (e != hipSuccess) { (void)hipFree(d_cols); return fail(PPCX_ERR_HIP, hipGetErrorString(e)); }
-  int rc = PPCX_OK;
-  do {
-    if ((e = hipMemcpy(d_cols, cols, sizeof(int) * n_cols, hipMemcpyHostToDevice)) != hipSuccess) break;
-    if ((e = launch_gather_kernel(f->d_draws, rows, D, d_cols, n_cols, d_out, f->m->stream)) != hipSuccess) break;
-    if ((e = hipStreamSynchronize(f->m->stream)) != hipSuccess) break;
-    e = hipMemcpy(out, d_out, sizeof(double) * (size_t)rows * n_cols, hipMemcpyDeviceToHost);
-  } while (0);
-  if (e != hipSuccess) rc = fail(PPCX_ERR_HIP, hipGetErrorString(e));
-  (void)hipFree(d_cols); (void)hipFree(d_out);
-  return rc;
+  hipStream_t st = f->m->stream;
+  DeviceBuffer<int> d_cols; DeviceBuffer<double> d_out;
+  hipError_t e = d_cols.upload(cols, (size_t)n_cols, st);
+  if (e == hipSuccess) e = d_out.alloc((size_t)rows * n_cols);
+  if (e == hipSuccess) e = launch_gather_kernel(f->d_draws, rows, D, d_cols.p, n_cols, d_out.p, st);
+  if (e == hipSuccess) e = d_out.download(out, (size_t)rows * n_cols, st);
+  if ((e = finish(e, st)) != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
+  return PPCX_OK;
 }
 // Fit summary (rstan::monitor): the columns go through column-major scratch in batches of at most kSummaryScratchBytes (never a
 // second copy of all the draws), one workgroup per column (ppcx_summary.hip)
-constexpr size_t kSummaryScratchBytes = (size_t)256 << 20;
 extern "C" int ppcx_fit_summary(ppcx_fit* f, int n_cols, const int32_t* cols, double* out) {
   if (!f || !cols || !out || n_cols < 1) return fail(PPCX_ERR_ARG, "bad arguments");
   if (f->advi) return fail(PPCX_ERR_ARG, "an ADVI fit has independent draws: R-hat and ESS are not defined for it (rstan::vb reports neither)");
@@ -1835,34 +1829,7 @@ extern "C" int ppcx_fit_summary(ppcx_fit* f, int n_cols, const int32_t* cols, do
   if (M < 1 || n < 1) return fail(PPCX_ERR_ARG, "fit holds no kept draws");
   if (M > kSummaryMaxChains) return fail(PPCX_ERR_LIMIT, "ppcx_fit_summary takes at most 128 chains");
   HIPCHK(hipSetDevice(f->m->device));
-  hipStream_t st = f->m->stream;
-  const long rows = (long)M * n;
-  const bool lds = summary_lds_bytes(M, n) > 0;
-  const long slice = summary_slice_doubles(M, n);
-  // per batch: the columns ([batch][M n]) and, on the global path, a slice per workgroup
-  int batch = (int)std::max<size_t>(1, kSummaryScratchBytes / 2 / (sizeof(double) * (size_t)rows));
-  if (batch > n_cols) batch = n_cols;
-  int nslices = lds ? 0 : (int)std::max<size_t>(1, kSummaryScratchBytes / 2 / (sizeof(double) * (size_t)slice));
-  if (nslices > batch) nslices = batch;
-  if (nslices > 2048) nslices = 2048;
-  int* d_cols = nullptr; double *d_x = nullptr, *d_out = nullptr, *d_scr = nullptr;
-  hipError_t e = hipMalloc(&d_cols, sizeof(int) * (size_t)n_cols);
-  if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(double) * SUM_FIELDS * (size_t)n_cols);
-  if (e == hipSuccess) e = hipMalloc(&d_x, sizeof(double) * (size_t)rows * batch);
-  if (e == hipSuccess && !lds) e = hipMalloc(&d_scr, sizeof(double) * (size_t)slice * nslices);
-  if (e == hipSuccess) e = hipMemcpy(d_cols, cols, sizeof(int) * (size_t)n_cols, hipMemcpyHostToDevice);
-  for (int b0 = 0; e == hipSuccess && b0 < n_cols; b0 += batch) {
-    const int nb = n_cols - b0 < batch ? n_cols - b0 : batch;
-    e = launch_summary_gather_kernel(f->d_draws, f->d_lp, rows, D, d_cols + b0, nb, d_x, st);
-    if (e != hipSuccess) break;
-    SummaryArgs a;
-    a.x = d_x; a.n_cols = nb; a.M = M; a.n = n; a.npad = summary_npad(M, n);
-    a.out = d_out + (size_t)b0 * SUM_FIELDS; a.scratch = d_scr; a.slice = slice;
-    e = launch_summary_kernel(a, lds ? nb : nslices, st);
-  }
-  if (e == hipSuccess) e = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = hipMemcpy(out, d_out, sizeof(double) * SUM_FIELDS * (size_t)n_cols, hipMemcpyDeviceToHost);
-  (void)hipFree(d_cols); (void)hipFree(d_x); (void)hipFree(d_out); (void)hipFree(d_scr);
+  const hipError_t e = summary_columns(f->d_draws, f->d_lp, M, n, D, n_cols, cols, out, kSummaryScratchBytes, f->m->stream);
   if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
   return PPCX_OK;
 }
@@ -1958,14 +1925,11 @@ extern "C" int ppcx_testing_psis(int n, int n_cols, const double* lr, const doub
   std::vector<int> ids(n_cols + 1);
   for (int i = 0; i < n_cols; ++i) ids[i] = i;
   ids[n_cols] = -1;
-  double *d_draws = nullptr, *d_r = nullptr;
-  hipError_t e = hipMalloc(&d_draws, sizeof(double) * (size_t)n * D);
-  if (e == hipSuccess) e = hipMalloc(&d_r, sizeof(double) * (size_t)n);
-  if (e == hipSuccess && n_cols > 0) e = hipMemcpy(d_draws, cols, sizeof(double) * (size_t)n * n_cols, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(d_r, lr, sizeof(double) * (size_t)n, hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = psis_columns(d_draws, d_r, n, D, n_cols + 1, ids.data(), khat, psis_scratch_bytes(), nullptr);
-  (void)hipFree(d_draws); (void)hipFree(d_r);
-  if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
+  DeviceBuffer<double> d_draws, d_r;
+  hipError_t e = n_cols > 0 ? d_draws.upload(cols, (size_t)n * n_cols, nullptr) : d_draws.alloc((size_t)n);
+  if (e == hipSuccess) e = d_r.upload(lr, (size_t)n, nullptr);
+  if (e == hipSuccess) e = psis_columns(d_draws.p, d_r.p, n, D, n_cols + 1, ids.data(), khat, psis_scratch_bytes(), nullptr);
+  if ((e = finish(e, nullptr)) != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
   return PPCX_OK;
 }
 #endif
@@ -2012,6 +1976,7 @@ static int loo_check_reff(const double* r_eff, long n) {
     if (!(isfinite(r_eff[i]) && r_eff[i] > 0.0)) return fail(PPCX_ERR_ARG, "r_eff must be finite and > 0");
   return PPCX_OK;
 }
+// the smallest r_eff of a call (1 without r_eff): the longest tail of its cells, for the limit and the selection buffer
 static double loo_reff_min(const double* r_eff, long n) {
   double mn = 1.0;
   for (long i = 0; r_eff && i < n; ++i) mn = i == 0 || r_eff[i] < mn ? r_eff[i] : mn;
@@ -2025,9 +1990,10 @@ extern "C" int ppcx_fit_loo(ppcx_fit* f, int n_genes, const int32_t* genes, cons
   ppcx_model* m = f->m;
   const long n = (long)f->chains * f->n_keep, ncells = (long)n_genes * m->d.S;
   if ((rc = loo_check_reff(r_eff, ncells)) != PPCX_OK) return rc;
-  if (loo_tail_len(n, loo_reff_min(r_eff, ncells)) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "ppcx_fit_loo: the tail exceeds 4095 draws");
-  hipError_t e = loo_fit_cells(f->d_draws, n, m->d, m->d_expo, m->d_X, n_genes, genes, yenc.data(), r_eff, out, loo_scratch_bytes(),
-                               m->stream);
+  const double rmin = loo_reff_min(r_eff, ncells);
+  if (psis_tail_len(n, rmin) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "ppcx_fit_loo: the tail exceeds 4095 draws");
+  hipError_t e = loo_fit_cells(f->d_draws, n, m->d, m->d_expo, m->d_X, n_genes, genes, yenc.data(), r_eff, rmin, out,
+                               loo_scratch_bytes(), m->stream);
   if (e != hipSuccess) return fail(PPCX_ERR_HIP, std::string("ppcx_fit_loo: ") + hipGetErrorString(e));
   return PPCX_OK;
 }
@@ -2037,8 +2003,9 @@ extern "C" int ppcx_testing_loo(int n, int n_cols, const double* ll, const int32
   if (n < 1 || n_cols < 1 || !ll || !out) return fail(PPCX_ERR_ARG, "bad arguments");
   int rc = loo_check_reff(r_eff, n_cols);
   if (rc != PPCX_OK) return rc;
-  if (loo_tail_len(n, loo_reff_min(r_eff, n_cols)) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "too many draws");
-  hipError_t e = loo_columns(ll, n, n_cols, excluded, r_eff, out, loo_scratch_bytes(), nullptr);
+  const double rmin = loo_reff_min(r_eff, n_cols);
+  if (psis_tail_len(n, rmin) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "too many draws");
+  hipError_t e = loo_columns(ll, n, n_cols, excluded, r_eff, rmin, out, loo_scratch_bytes(), nullptr);
   if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
   return PPCX_OK;
 }

@@ -179,6 +179,11 @@ long summary_slice_doubles(int M, int n);
 size_t summary_lds_bytes(int M, int n);       // 0: the columns are too long for the LDS path
 hipError_t launch_summary_gather_kernel(const double* draws, const double* lp, long rows, int D, const int* cols, int n_cols, double* out, hipStream_t st);
 hipError_t launch_summary_kernel(const SummaryArgs& a, int nblocks, hipStream_t st);
+// the summary of the columns `cols` (host; -1: lp) of M chains of n draws [M n][D] (device) into out [n_cols][SUM_FIELDS]
+// (host), through column scratch and slices of at most scratch_bytes together (kSummaryScratchBytes in the product); synchronous
+constexpr size_t kSummaryScratchBytes = (size_t)256 << 20;
+hipError_t summary_columns(const double* draws, const double* lp, int M, int n, int D, int n_cols, const int* cols, double* out,
+                           size_t scratch_bytes, hipStream_t st);
 
 // the Pareto-k diagnostic of an ADVI fit (ppcx_psis.hip, statistic in ppcx_psis.h): the M + 1 largest values of a column are
 // selected and sorted in LDS (kPsisMaxSel of them at most: columns of up to 1.86 million draws); columns of up to kPsisLdsDraws
@@ -227,14 +232,15 @@ struct LooArgs {
 };
 int loo_sel_pad(long n, double r_eff_min);     // power of two >= M + 1 for n draws at the smallest r_eff
 // LOO of the cells of genes[0 .. n_genes) (host) for draws [n][D] (device); yenc, r_eff (null or [cells]) and out host;
-// synchronous
+// r_eff_min: the smallest r_eff (1 without r_eff). Synchronous
 hipError_t loo_fit_cells(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
-                         const int* genes, const int* yenc, const double* r_eff, double* out, size_t scratch_bytes, hipStream_t st);
+                         const int* genes, const int* yenc, const double* r_eff, double r_eff_min, double* out,
+                         size_t scratch_bytes, hipStream_t st);
 // the log-likelihood matrix of those cells, [n][cells] (host out); synchronous
 hipError_t loo_fit_log_lik(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
                            const int* genes, const int* yenc, double* out, size_t scratch_bytes, hipStream_t st);
 // LOO of host-given columns cols [n_cols][n] (testing build); synchronous
-hipError_t loo_columns(const double* cols, long n, int n_cols, const int* excl, const double* r_eff, double* out,
+hipError_t loo_columns(const double* cols, long n, int n_cols, const int* excl, const double* r_eff, double r_eff_min, double* out,
                        size_t scratch_bytes, hipStream_t st);
 hipError_t launch_xchg_abort_kernel(const XchgArgs& x, hipStream_t st);      // tells every peer that this rank has left the fit
 

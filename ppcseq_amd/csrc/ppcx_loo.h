@@ -51,11 +51,6 @@ PPCX_HD double loo_ll(int y, double eta, double sigma_raw) {
   const double lw = loo_log1pexp(eta + sigma_raw);
   return yd * eta - yd - (yd + p.phi) * lw + F - lgamma_int1(yd);
 }
-// tail length M of N draws at relative efficiency r_eff (step 1; for r_eff = 1 the same bits as psis_tail_len)
-PPCX_HD int loo_tail_len(long N, double r_eff) {
-  const double a = 0.2 * (double)N, b = 3.0 * sqrt((double)N / r_eff);
-  return (int)ceil(a < b ? a : b);
-}
 // the smoothed log weight of tail position j = 1 .. M (shifted frame), given k-hat, sigma and exp(cutoff - mx)
 PPCX_HD double loo_smoothed(int j, int M, double khat, double sigma, double ec) {
   PPCX_NO_CONTRACT
@@ -99,28 +94,14 @@ inline void loo_cell_host(const double* ll, long n, double r_eff, bool excluded,
   const double mx = r[N - 1];
   std::vector<double> lw(N);
   for (long i = 0; i < N; ++i) lw[i] = r[i] - mx;
-  const int M = loo_tail_len(N, r_eff);
+  const int M = psis_tail_len(N, r_eff);
   double khat = INFINITY;
   if (M >= 5 && M < N && r[N - M] != mx) {
-    const double c = r[N - M - 1], ec = exp(c - mx);
-    std::vector<double> x(M);
-    for (int i = 0; i < M; ++i) x[i] = exp(r[N - M + i] - mx) - ec;
-    const int m = psis_grid_size(M);
-    const double xstar = x[psis_xstar_index(M) - 1];
-    std::vector<double> th(m), el(m);
-    for (int j = 0; j < m; ++j) {
-      th[j] = psis_theta(j + 1, m, x[M - 1], xstar);
-      double a = 0.0;
-      for (int i = 0; i < M; ++i) a += log1p(-th[j] * x[i]);
-      el[j] = psis_ell(th[j], a / M, M);
-    }
-    const double t = psis_theta_hat(th.data(), el.data(), m);
-    double a = 0.0;
-    for (int i = 0; i < M; ++i) a += log1p(-t * x[i]);
-    const double k = a / M, sigma = -k / t;
-    khat = psis_adjust(k, M);
+    const PsisTailHost t = psis_tail_host(r.data(), N, M);
+    const double sigma = -t.k_mean / t.theta_hat;
+    khat = psis_adjust(t.k_mean, M);
     if (loo_smooth_ok(khat, sigma))
-      for (int j = 1; j <= M; ++j) lw[N - M + j - 1] = loo_smoothed(j, M, khat, sigma, ec);
+      for (int j = 1; j <= M; ++j) lw[N - M + j - 1] = loo_smoothed(j, M, khat, sigma, t.ec);
   }
   std::vector<double> a(N);
   for (long i = 0; i < N; ++i) { lw[i] = lw[i] > 0.0 ? 0.0 : lw[i]; a[i] = lw[i] - r[i]; }

@@ -18,7 +18,7 @@
 #include <algorithm>
 #include "ppcx_psis_dev.h"
 #include "ppcx_loo.h"
-#include "ppcx_kernels.h"
+#include "ppcx_columns.h"
 
 namespace ppcx {
 
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(256) void ppcx_loo_ll_kernel(LooArgs a, long j0, lo
 struct LooTerms { double a, b; };                // running max or sum of the two logsumexps: a over lw + ll, b over lw
 
 template <bool LDS, bool COLS>
-__global__ __launch_bounds__(kPsisThreads) void ppcx_loo_kernel(LooArgs a) {
+__global__ __launch_bounds__(kBlockThreads) void ppcx_loo_kernel(LooArgs a) {
   extern __shared__ uint64_t lds_u[];
   __shared__ PsisShared sh;
   const int tid = threadIdx.x;
@@ -88,55 +88,44 @@ __global__ __launch_bounds__(kPsisThreads) void ppcx_loo_kernel(LooArgs a) {
   double* o = a.out + (long)cell * kLooFields;
   // ---- the ratios; NaN / +Inf; N (the -Inf ratios take no part); the largest ratio and the largest ll
   bool bad = false; double cnt = 0.0, rmax = -INFINITY, lmax = -INFINITY;
-  for (long i = tid; i < n; i += kPsisThreads) {
+  for (long i = tid; i < n; i += kBlockThreads) {
     const double ll = COLS ? a.cols[(long)cell * n + i] : loo_cell_ll(a, gi, s, i, y);
     const double r = -ll;
     bad = bad || isnan(r) || (!excluded && r == INFINITY);
     if (r != -INFINITY) { cnt += 1.0; rmax = fmax(rmax, r); lmax = fmax(lmax, ll); }
     V[i] = r;
   }
-  bad = __syncthreads_or(bad ? 1 : 0) != 0;
+  bad = block_any(bad);
   if (bad) {
     if (tid == 0) o[0] = o[1] = o[2] = o[3] = NAN;
     return;
   }
-  const long N = (long)psis_block_sum(cnt, sh.red);
-  rmax = psis_block_max(rmax, sh.red);
-  lmax = psis_block_max(lmax, sh.red);
+  const long N = (long)block_sum(cnt, sh.red);
+  rmax = block_max(rmax, sh.red);
+  lmax = block_max(lmax, sh.red);
   // ---- lpd = logsumexp(ll) - log N
   double sl = 0.0;
-  for (long i = tid; i < n; i += kPsisThreads) { const double r = V[i]; if (r != -INFINITY) sl += exp(-r - lmax); }
-  sl = psis_block_sum(sl, sh.red);
+  for (long i = tid; i < n; i += kBlockThreads) { const double r = V[i]; if (r != -INFINITY) sl += exp(-r - lmax); }
+  sl = block_sum(sl, sh.red);
   const double lpd = N > 0 ? (lmax == -INFINITY ? -INFINITY : lmax + log(sl)) - log((double)N) : NAN;
   if (excluded) {                                        // already held out: the exact held-out predictive density
     if (tid == 0) { o[0] = lpd; o[1] = 0.0; o[2] = -2.0 * lpd; o[3] = NAN; }
     return;
   }
   // ---- the tail: M + 1 largest, the profile fit, k-hat and sigma
-  const double mx = rmax;
-  const double reff = a.r_eff ? a.r_eff[cell] : 1.0;
-  const int M = loo_tail_len(N, reff);
-  double khat = INFINITY, sigma = 0.0, ec = 0.0;
-  bool smooth = false;
-  uint64_t prefix = 0; int n_extra = 0;
-  if (M >= 5 && (long)M < N) {
-    int want;
-    prefix = psis_select_top(V, n, M, K, a.sel_pad, sh, &want);
-    if (psis_unkey(K[1]) != mx) {
-      const double cut = psis_unkey(K[0]);
-      ec = exp(cut - mx);
-      for (int i = tid; i < M; i += kPsisThreads) X[i] = exp(psis_unkey(K[i + 1]) - mx) - ec;
-      __syncthreads();
-      double theta_hat, k_mean;
-      psis_fit_tail(X, M, sh, &theta_hat, &k_mean);
-      khat = psis_adjust(k_mean, M);
-      sigma = -k_mean / theta_hat;
-      smooth = loo_smooth_ok(khat, sigma);
-      if (smooth) {                                      // copies of the cutoff outside the tail: all of them but want - 1
-        double eq = 0.0;
-        for (long i = tid; i < n; i += kPsisThreads) eq += psis_key(V[i]) == prefix ? 1.0 : 0.0;
-        n_extra = (int)psis_block_sum(eq, sh.red) - (want - 1);
-      }
+  const double mx = rmax;                                // the tail's own mx is this value (it exists only where M >= 5)
+  const int M = psis_tail_len(N, a.r_eff ? a.r_eff[cell] : 1.0);
+  double khat = INFINITY, sigma = 0.0;
+  bool smooth = false; int n_extra = 0;
+  PsisTail tl{};
+  if (psis_tail(V, n, N, M, K, X, a.sel_pad, sh, &tl) == PSIS_TAIL_FITTED) {
+    khat = psis_adjust(tl.k_mean, M);
+    sigma = -tl.k_mean / tl.theta_hat;
+    smooth = loo_smooth_ok(khat, sigma);
+    if (smooth) {                                        // copies of the cutoff outside the tail: all of them but want - 1
+      double eq = 0.0;
+      for (long i = tid; i < n; i += kBlockThreads) eq += psis_key(V[i]) == tl.key ? 1.0 : 0.0;
+      n_extra = (int)block_sum(eq, sh.red) - (tl.want - 1);
     }
   }
   // ---- logsumexp(lw + ll) and logsumexp(lw): a raw draw has lw = r - mx (<= 0), a tail draw the smoothed value truncated at 0
@@ -147,33 +136,32 @@ __global__ __launch_bounds__(kPsisThreads) void ppcx_loo_kernel(LooArgs a) {
       if (sum) { t.a += mult * exp(va - mxv.a); t.b += mult * exp(lw - mxv.b); }
       else { t.a = fmax(t.a, va); t.b = fmax(t.b, lw); }
     };
-    for (long i = tid; i < n; i += kPsisThreads) {
+    for (long i = tid; i < n; i += kBlockThreads) {
       const double r = V[i];
-      if (r == -INFINITY || (smooth && psis_key(r) >= prefix)) continue;
+      if (r == -INFINITY || (smooth && psis_key(r) >= tl.key)) continue;
       add(r - mx, r, 1.0);
     }
     if (smooth) {
-      for (int j = tid; j < M; j += kPsisThreads) {
-        const double sm = loo_smoothed(j + 1, M, khat, sigma, ec);
+      for (int j = tid; j < M; j += kBlockThreads) {
+        const double sm = loo_smoothed(j + 1, M, khat, sigma, tl.ec);
         add(sm > 0.0 ? 0.0 : sm, psis_unkey(K[j + 1]), 1.0);
       }
-      if (tid == 0 && n_extra > 0) { const double c = psis_unkey(prefix); add(c - mx, c, (double)n_extra); }
+      if (tid == 0 && n_extra > 0) { const double c = tl.cut; add(c - mx, c, (double)n_extra); }
     }
     return t;
   };
   LooTerms m0 = terms(false, LooTerms{0.0, 0.0});
-  m0.a = psis_block_max(m0.a, sh.red);
-  m0.b = psis_block_max(m0.b, sh.red);
+  m0.a = block_max(m0.a, sh.red);
+  m0.b = block_max(m0.b, sh.red);
   LooTerms s0 = terms(true, m0);
-  s0.a = psis_block_sum(s0.a, sh.red);
-  s0.b = psis_block_sum(s0.b, sh.red);
+  s0.a = block_sum(s0.a, sh.red);
+  s0.b = block_sum(s0.b, sh.red);
   const double elpd = (m0.a + log(s0.a)) - (m0.b + log(s0.b));
   if (tid == 0) { o[0] = elpd; o[1] = lpd - elpd; o[2] = -2.0 * elpd; o[3] = khat; }
 }
 
 // ---- launch helpers (host)
-static int loo_pow2(long n) { int p = 1; while (p < n) p <<= 1; return p; }
-int loo_sel_pad(long n, double r_eff_min) { return loo_pow2((long)loo_tail_len(n, r_eff_min) + 1); }
+int loo_sel_pad(long n, double r_eff_min) { return pow2_at_least((long)psis_tail_len(n, r_eff_min) + 1); }
 hipError_t launch_loo_table_kernel(const double* draws, long n_draws, const Dims& d, const int* genes, int n_genes, double* T,
                                    hipStream_t st) {
   dim3 grid((unsigned)((n_draws + 31) / 32), (unsigned)((n_genes + 31) / 32));
@@ -188,124 +176,93 @@ hipError_t launch_loo_ll_kernel(const LooArgs& a, long j0, long n_rows, double* 
 hipError_t launch_loo_kernel(const LooArgs& a, int n_blocks, hipStream_t st) {
   const bool lds = a.n <= kPsisLdsDraws, cols = a.cols != nullptr;
   const size_t bytes = sizeof(double) * (2 * (size_t)a.sel_pad + (lds ? (size_t)a.n : 0));
-  const void* fn = lds ? (cols ? (const void*)ppcx_loo_kernel<true, true> : (const void*)ppcx_loo_kernel<true, false>)
-                       : (cols ? (const void*)ppcx_loo_kernel<false, true> : (const void*)ppcx_loo_kernel<false, false>);
-  if (bytes > 64u * 1024u) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return e;
-  }
-  if (lds && cols) hipLaunchKernelGGL((ppcx_loo_kernel<true, true>), dim3(n_blocks), dim3(kPsisThreads), bytes, st, a);
-  else if (lds) hipLaunchKernelGGL((ppcx_loo_kernel<true, false>), dim3(n_blocks), dim3(kPsisThreads), bytes, st, a);
-  else if (cols) hipLaunchKernelGGL((ppcx_loo_kernel<false, true>), dim3(n_blocks), dim3(kPsisThreads), bytes, st, a);
-  else hipLaunchKernelGGL((ppcx_loo_kernel<false, false>), dim3(n_blocks), dim3(kPsisThreads), bytes, st, a);
-  return hipGetLastError();
+  void (*const kernel)(LooArgs) = lds ? (cols ? ppcx_loo_kernel<true, true> : ppcx_loo_kernel<true, false>)
+                                      : (cols ? ppcx_loo_kernel<false, true> : ppcx_loo_kernel<false, false>);
+  return launch_dynamic_lds(kernel, n_blocks, kBlockThreads, bytes, st, a);
 }
 
-// Cells of a launch in batches: all at once where the ratios live in LDS, else as many as the scratch bound holds
-static hipError_t loo_cells(LooArgs a, int n_cells, size_t scratch_bytes, hipStream_t st) {
+// Cells of a launch in batches: all at once where the ratios live in LDS, else as many as the scratch bound holds.
+// Asynchronous: `scratch` belongs to the caller, who synchronises before it goes.
+static hipError_t loo_cells(LooArgs a, int n_cells, size_t scratch_bytes, DeviceBuffer<double>& scratch, hipStream_t st) {
   hipError_t e = hipSuccess;
   int batch = n_cells;
   if (a.n > kPsisLdsDraws) {
-    batch = (int)std::max<size_t>(1, scratch_bytes / (sizeof(double) * (size_t)a.n));
-    if (batch > n_cells) batch = n_cells;
-    e = hipMalloc(&a.scratch, sizeof(double) * (size_t)a.n * batch);
+    batch = column_batch(scratch_bytes, a.n, n_cells);
+    if (!scratch.p) e = scratch.alloc((size_t)a.n * batch);
+    a.scratch = scratch.p;
   }
   for (int c0 = 0; e == hipSuccess && c0 < n_cells; c0 += batch) {
     a.cell0 = c0;
     e = launch_loo_kernel(a, n_cells - c0 < batch ? n_cells - c0 : batch, st);
   }
-  const hipError_t es = hipStreamSynchronize(st);      // nothing is freed under a running kernel
-  if (e == hipSuccess) e = es;
-  (void)hipFree(a.scratch);
   return e;
 }
 
 hipError_t loo_fit_cells(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
-                         const int* genes, const int* yenc, const double* r_eff, double* out, size_t scratch_bytes,
-                         hipStream_t st) {
+                         const int* genes, const int* yenc, const double* r_eff, double r_eff_min, double* out,
+                         size_t scratch_bytes, hipStream_t st) {
   const int S = d.S, ncol = d.C + 1;
-  double rmin = 1.0;
-  for (long i = 0; r_eff && i < (long)n_genes * S; ++i) rmin = std::min(rmin, r_eff[i]);
-  int gb = (int)std::max<size_t>(1, scratch_bytes / (sizeof(double) * (size_t)ncol * (size_t)n));
-  if (gb > n_genes) gb = n_genes;
-  int *d_genes = nullptr, *d_y = nullptr; double *d_T = nullptr, *d_reff = nullptr, *d_out = nullptr;
   const size_t ncells = (size_t)n_genes * S;
-  hipError_t e = hipMalloc(&d_genes, sizeof(int) * (size_t)n_genes);
-  if (e == hipSuccess) e = hipMalloc(&d_y, sizeof(int) * ncells);
-  if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(double) * kLooFields * ncells);
-  if (e == hipSuccess) e = hipMalloc(&d_T, sizeof(double) * (size_t)ncol * (size_t)n * gb);
-  if (e == hipSuccess && r_eff) e = hipMalloc(&d_reff, sizeof(double) * ncells);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_genes, genes, sizeof(int) * (size_t)n_genes, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_y, yenc, sizeof(int) * ncells, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && r_eff) e = hipMemcpyAsync(d_reff, r_eff, sizeof(double) * ncells, hipMemcpyHostToDevice, st);
+  const int gb = column_batch(scratch_bytes, (long)ncol * n, n_genes);
+  DeviceBuffer<int> d_genes, d_y; DeviceBuffer<double> d_T, d_reff, d_out, d_scr;
+  hipError_t e = d_genes.upload(genes, (size_t)n_genes, st);
+  if (e == hipSuccess) e = d_y.upload(yenc, ncells, st);
+  if (e == hipSuccess && r_eff) e = d_reff.upload(r_eff, ncells, st);
+  if (e == hipSuccess) e = d_out.alloc(kLooFields * ncells);
+  if (e == hipSuccess) e = d_T.alloc((size_t)ncol * (size_t)n * gb);
   for (int g0 = 0; e == hipSuccess && g0 < n_genes; g0 += gb) {
     const int ng = n_genes - g0 < gb ? n_genes - g0 : gb;
-    e = launch_loo_table_kernel(draws, n, d, d_genes + g0, ng, d_T, st);
+    e = launch_loo_table_kernel(draws, n, d, d_genes.p + g0, ng, d_T.p, st);
     if (e != hipSuccess) break;
     LooArgs a;
-    a.T = d_T; a.y = d_y + (size_t)g0 * S; a.expo = expo; a.X = X; a.S = S; a.C = d.C; a.n = n;
-    a.r_eff = d_reff ? d_reff + (size_t)g0 * S : nullptr; a.out = d_out + (size_t)g0 * S * kLooFields;
-    a.n_cells = ng * S; a.sel_pad = loo_sel_pad(n, rmin);
-    e = loo_cells(a, ng * S, scratch_bytes, st);
+    a.T = d_T.p; a.y = d_y.p + (size_t)g0 * S; a.expo = expo; a.X = X; a.S = S; a.C = d.C; a.n = n;
+    a.r_eff = d_reff.p ? d_reff.p + (size_t)g0 * S : nullptr; a.out = d_out.p + (size_t)g0 * S * kLooFields;
+    a.n_cells = ng * S; a.sel_pad = loo_sel_pad(n, r_eff_min);
+    e = loo_cells(a, ng * S, scratch_bytes, d_scr, st);
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(double) * kLooFields * ncells, hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = es;
-  (void)hipFree(d_genes); (void)hipFree(d_y); (void)hipFree(d_T); (void)hipFree(d_reff); (void)hipFree(d_out);
-  return e;
+  if (e == hipSuccess) e = d_out.download(out, kLooFields * ncells, st);
+  return finish(e, st);
 }
 
 hipError_t loo_fit_log_lik(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
                            const int* genes, const int* yenc, double* out, size_t scratch_bytes, hipStream_t st) {
   const int S = d.S, ncol = d.C + 1;
   const size_t ncells = (size_t)n_genes * S;
-  int *d_genes = nullptr, *d_y = nullptr; double *d_T = nullptr, *d_buf = nullptr;
   // the whole table of the requested genes, then the matrix in row blocks of at most scratch_bytes
   long rows = (long)std::max<size_t>(1, scratch_bytes / (sizeof(double) * ncells));
   if (rows > n) rows = n;
-  hipError_t e = hipMalloc(&d_genes, sizeof(int) * (size_t)n_genes);
-  if (e == hipSuccess) e = hipMalloc(&d_y, sizeof(int) * ncells);
-  if (e == hipSuccess) e = hipMalloc(&d_T, sizeof(double) * (size_t)ncol * (size_t)n * n_genes);
-  if (e == hipSuccess) e = hipMalloc(&d_buf, sizeof(double) * ncells * (size_t)rows);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_genes, genes, sizeof(int) * (size_t)n_genes, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_y, yenc, sizeof(int) * ncells, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = launch_loo_table_kernel(draws, n, d, d_genes, n_genes, d_T, st);
+  DeviceBuffer<int> d_genes, d_y; DeviceBuffer<double> d_T, d_buf;
+  hipError_t e = d_genes.upload(genes, (size_t)n_genes, st);
+  if (e == hipSuccess) e = d_y.upload(yenc, ncells, st);
+  if (e == hipSuccess) e = d_T.alloc((size_t)ncol * (size_t)n * n_genes);
+  if (e == hipSuccess) e = d_buf.alloc(ncells * (size_t)rows);
+  if (e == hipSuccess) e = launch_loo_table_kernel(draws, n, d, d_genes.p, n_genes, d_T.p, st);
   LooArgs a;
-  a.T = d_T; a.y = d_y; a.expo = expo; a.X = X; a.S = S; a.C = d.C; a.n = n; a.n_cells = (int)ncells;
+  a.T = d_T.p; a.y = d_y.p; a.expo = expo; a.X = X; a.S = S; a.C = d.C; a.n = n; a.n_cells = (int)ncells;
   for (long j0 = 0; e == hipSuccess && j0 < n; j0 += rows) {
     const long nr = n - j0 < rows ? n - j0 : rows;
-    e = launch_loo_ll_kernel(a, j0, nr, d_buf, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(out + (size_t)j0 * ncells, d_buf, sizeof(double) * ncells * (size_t)nr, hipMemcpyDeviceToHost, st);
-    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    e = launch_loo_ll_kernel(a, j0, nr, d_buf.p, st);
+    if (e == hipSuccess) e = d_buf.download(out + (size_t)j0 * ncells, ncells * (size_t)nr, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);   // d_buf is rewritten by the next block
   }
-  const hipError_t es = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = es;
-  (void)hipFree(d_genes); (void)hipFree(d_y); (void)hipFree(d_T); (void)hipFree(d_buf);
-  return e;
+  return finish(e, st);
 }
 
-hipError_t loo_columns(const double* cols, long n, int n_cols, const int* excl, const double* r_eff, double* out,
+hipError_t loo_columns(const double* cols, long n, int n_cols, const int* excl, const double* r_eff, double r_eff_min, double* out,
                        size_t scratch_bytes, hipStream_t st) {
-  double rmin = 1.0;
-  for (int i = 0; r_eff && i < n_cols; ++i) rmin = std::min(rmin, r_eff[i]);
-  double *d_cols = nullptr, *d_reff = nullptr, *d_out = nullptr; int* d_excl = nullptr;
-  hipError_t e = hipMalloc(&d_cols, sizeof(double) * (size_t)n * n_cols);
-  if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(double) * kLooFields * (size_t)n_cols);
-  if (e == hipSuccess && excl) e = hipMalloc(&d_excl, sizeof(int) * (size_t)n_cols);
-  if (e == hipSuccess && r_eff) e = hipMalloc(&d_reff, sizeof(double) * (size_t)n_cols);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_cols, cols, sizeof(double) * (size_t)n * n_cols, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && excl) e = hipMemcpyAsync(d_excl, excl, sizeof(int) * (size_t)n_cols, hipMemcpyHostToDevice, st);
-  if (e == hipSuccess && r_eff) e = hipMemcpyAsync(d_reff, r_eff, sizeof(double) * (size_t)n_cols, hipMemcpyHostToDevice, st);
+  DeviceBuffer<double> d_cols, d_reff, d_out, d_scr; DeviceBuffer<int> d_excl;
+  hipError_t e = d_cols.upload(cols, (size_t)n * n_cols, st);
+  if (e == hipSuccess && excl) e = d_excl.upload(excl, (size_t)n_cols, st);
+  if (e == hipSuccess && r_eff) e = d_reff.upload(r_eff, (size_t)n_cols, st);
+  if (e == hipSuccess) e = d_out.alloc(kLooFields * (size_t)n_cols);
   if (e == hipSuccess) {
     LooArgs a;
-    a.cols = d_cols; a.excl = d_excl; a.r_eff = d_reff; a.n = n; a.n_cells = n_cols; a.out = d_out; a.sel_pad = loo_sel_pad(n, rmin);
-    e = loo_cells(a, n_cols, scratch_bytes, st);
+    a.cols = d_cols.p; a.excl = d_excl.p; a.r_eff = d_reff.p; a.n = n; a.n_cells = n_cols; a.out = d_out.p;
+    a.sel_pad = loo_sel_pad(n, r_eff_min);
+    e = loo_cells(a, n_cols, scratch_bytes, d_scr, st);
   }
-  if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, sizeof(double) * kLooFields * (size_t)n_cols, hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);
-  if (e == hipSuccess) e = es;
-  (void)hipFree(d_cols); (void)hipFree(d_reff); (void)hipFree(d_out); (void)hipFree(d_excl);
-  return e;
+  if (e == hipSuccess) e = d_out.download(out, kLooFields * (size_t)n_cols, st);
+  return finish(e, st);
 }
 
 }  // namespace ppcx

@@ -36,9 +36,10 @@ namespace ppcx {
 constexpr double kPsisPrior = 3.0;
 constexpr double kPsisMinWeight = 10.0 * 2.220446049250313e-16;   // 10 DBL_EPSILON
 
-// tail length M of N finite values (step 1)
-PPCX_HD int psis_tail_len(long N) {
-  const double a = 0.2 * (double)N, b = 3.0 * sqrt((double)N);
+// tail length M of N finite values (step 1); PSIS-LOO divides N by the relative efficiency r_eff of the cell's draws
+// (ppcx_loo.h step 1; N / 1.0 is N: the same bits)
+PPCX_HD int psis_tail_len(long N, double r_eff = 1.0) {
+  const double a = 0.2 * (double)N, b = 3.0 * sqrt((double)N / r_eff);
   return (int)ceil(a < b ? a : b);
 }
 // grid size m of the profile fit (step 3)
@@ -102,20 +103,11 @@ PPCX_HD double psis_value(double theta, double r, int col) {
 #include <algorithm>
 #include <vector>
 namespace ppcx {
-// the whole spec, sequentially, for the CPU check
-inline double psis_khat_host(const double* v, long n) {
-  std::vector<double> s;
-  s.reserve((size_t)n);
-  for (long i = 0; i < n; ++i) {
-    if (isnan(v[i]) || v[i] == INFINITY) return NAN;
-    if (v[i] != -INFINITY) s.push_back(v[i]);
-  }
-  const long N = (long)s.size();
-  const int M = psis_tail_len(N);
-  if (M < 5 || M >= N) return INFINITY;
-  std::sort(s.begin(), s.end());
+// steps 2 and 3 for the CPU checks, sequentially: the ascending s[0 .. N) (no NaN, all finite) with M (5 <= M < N) of them
+// in a tail that is not all equal -> the mean k before the prior adjustment, theta^ and exp(cutoff - largest)
+struct PsisTailHost { double k_mean, theta_hat, ec; };
+inline PsisTailHost psis_tail_host(const double* s, long N, int M) {
   const double mx = s[N - 1], c = s[N - M - 1];
-  if (s[N - M] == mx) return INFINITY;
   std::vector<double> x(M);
   const double ec = exp(c - mx);
   for (int i = 0; i < M; ++i) x[i] = exp(s[N - M + i] - mx) - ec;
@@ -131,7 +123,22 @@ inline double psis_khat_host(const double* v, long n) {
   const double t = psis_theta_hat(th.data(), ll.data(), m);
   double a = 0.0;
   for (int i = 0; i < M; ++i) a += log1p(-t * x[i]);
-  return psis_adjust(a / M, M);
+  return PsisTailHost{a / M, t, ec};
+}
+// the whole spec, sequentially, for the CPU check
+inline double psis_khat_host(const double* v, long n) {
+  std::vector<double> s;
+  s.reserve((size_t)n);
+  for (long i = 0; i < n; ++i) {
+    if (isnan(v[i]) || v[i] == INFINITY) return NAN;
+    if (v[i] != -INFINITY) s.push_back(v[i]);
+  }
+  const long N = (long)s.size();
+  const int M = psis_tail_len(N);
+  if (M < 5 || M >= N) return INFINITY;
+  std::sort(s.begin(), s.end());
+  if (s[N - M] == s[N - 1]) return INFINITY;
+  return psis_adjust(psis_tail_host(s.data(), N, M).k_mean, M);
 }
 }  // namespace ppcx
 #endif

@@ -21,7 +21,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "ppcx_psis_dev.h"
-#include "ppcx_kernels.h"
+#include "ppcx_columns.h"
 
 namespace ppcx {
 
@@ -61,18 +61,18 @@ __global__ void ppcx_psis_record_kernel(Dims d, const Cmd* cmds, const double* r
   log_p[c] = hyper_close(d, cm.hy, cm.hyp_q, r[PT_LP], r + PT_H0, g6);
 }
 
-__global__ __launch_bounds__(kPsisThreads) void ppcx_psis_log_g_kernel(const double* draws, int D, const double* mu,
+__global__ __launch_bounds__(kBlockThreads) void ppcx_psis_log_g_kernel(const double* draws, int D, const double* mu,
                                                                        const double* omega, const double* log_p, double* log_g,
                                                                        double* r) {
-  __shared__ double red[kPsisWaves];
+  __shared__ double red[kBlockWaves];
   const long row = blockIdx.x;
   const double* x = draws + row * D;
   double s = 0.0;
-  for (int i = threadIdx.x; i < D; i += kPsisThreads) {
+  for (int i = threadIdx.x; i < D; i += kBlockThreads) {
     const double z = (x[i] - mu[i]) * exp(-omega[i]);
     s += z * z;
   }
-  const double lg = -0.5 * psis_block_sum(s, red);
+  const double lg = -0.5 * block_sum(s, red);
   if (threadIdx.x == 0) {
     const double lp = log_p[row];
     log_g[row] = lg;
@@ -81,7 +81,7 @@ __global__ __launch_bounds__(kPsisThreads) void ppcx_psis_log_g_kernel(const dou
 }
 
 template <bool LDS>
-__global__ __launch_bounds__(kPsisThreads) void ppcx_psis_kernel(PsisArgs a) {
+__global__ __launch_bounds__(kBlockThreads) void ppcx_psis_kernel(PsisArgs a) {
   extern __shared__ uint64_t lds_u[];
   __shared__ PsisShared sh;
   const int tid = threadIdx.x;
@@ -93,42 +93,25 @@ __global__ __launch_bounds__(kPsisThreads) void ppcx_psis_kernel(PsisArgs a) {
     double* V = LDS ? X + a.sel_pad : a.x + (long)c * n;  // the column's values
     // ---- the values, their count N (the -Inf entries take no part), a NaN / +Inf entry
     bool bad = false; double cnt = 0.0;
-    for (long i = tid; i < n; i += kPsisThreads) {
+    for (long i = tid; i < n; i += kBlockThreads) {
       const double v = psis_value(a.x[(long)c * n + i], a.r[i], col);
       bad = bad || isnan(v) || v == INFINITY;
       cnt += v != -INFINITY ? 1.0 : 0.0;
       V[i] = v;
     }
-    bad = __syncthreads_or(bad ? 1 : 0) != 0;
-    const long N = (long)psis_block_sum(cnt, sh.red);
+    bad = block_any(bad);
+    const long N = (long)block_sum(cnt, sh.red);
+    // ---- the tail: the M + 1 largest, the profile fit (one wavefront per grid point), k-hat
     const int M = psis_tail_len(N);
-    if (bad || M < 5 || (long)M >= N) {
-      if (tid == 0) a.out[c] = bad ? NAN : INFINITY;
-      __syncthreads();
-      continue;
-    }
-    int want;
-    (void)psis_select_top(V, n, M, K, a.sel_pad, sh, &want);
-    const double cut = psis_unkey(K[0]), mx = psis_unkey(K[M]);
-    if (psis_unkey(K[1]) == mx) {                        // the M tail values are all equal
-      if (tid == 0) a.out[c] = INFINITY;
-      __syncthreads();
-      continue;
-    }
-    const double ec = exp(cut - mx);
-    for (int i = tid; i < M; i += kPsisThreads) X[i] = exp(psis_unkey(K[i + 1]) - mx) - ec;
-    __syncthreads();
-    // ---- the profile fit: one wavefront per grid point
-    double theta_hat, k_mean;
-    psis_fit_tail(X, M, sh, &theta_hat, &k_mean);
-    if (tid == 0) a.out[c] = psis_adjust(k_mean, M);
+    PsisTail t;
+    const PsisTailStatus ts = bad ? PSIS_TAIL_SHORT : psis_tail(V, n, N, M, K, X, a.sel_pad, sh, &t);
+    if (tid == 0) a.out[c] = bad ? NAN : (ts == PSIS_TAIL_FITTED ? psis_adjust(t.k_mean, M) : INFINITY);
     __syncthreads();                                     // K, X, V and the shared block are reused by the next column
   }
 }
 
 // ---- launch helpers (host)
-static int psis_pow2(long n) { int p = 1; while (p < n) p <<= 1; return p; }
-int psis_sel_pad(long n) { return psis_pow2((long)psis_tail_len(n) + 1); }
+int psis_sel_pad(long n) { return pow2_at_least((long)psis_tail_len(n) + 1); }
 hipError_t launch_psis_approx_kernel(const Dims& d, const double* sq, const double* sg, const double* hyper, double* mu, double* omega,
                                      hipStream_t st) {
   hipLaunchKernelGGL(ppcx_psis_approx_kernel, dim3((unsigned)((d.D + 255) / 256)), dim3(256), 0, st, d, sq, sg, hyper, mu, omega);
@@ -146,46 +129,25 @@ hipError_t launch_psis_record_kernel(const Dims& d, const Cmd* cmds, const doubl
 }
 hipError_t launch_psis_log_g_kernel(const double* draws, long rows, int D, const double* mu, const double* omega, const double* log_p,
                                     double* log_g, double* r, hipStream_t st) {
-  hipLaunchKernelGGL(ppcx_psis_log_g_kernel, dim3((unsigned)rows), dim3(kPsisThreads), 0, st, draws, D, mu, omega, log_p, log_g, r);
+  hipLaunchKernelGGL(ppcx_psis_log_g_kernel, dim3((unsigned)rows), dim3(kBlockThreads), 0, st, draws, D, mu, omega, log_p, log_g, r);
   return hipGetLastError();
 }
 hipError_t launch_psis_kernel(const PsisArgs& a, hipStream_t st) {
   const bool lds = a.n <= kPsisLdsDraws;
   const size_t bytes = sizeof(double) * (2 * (size_t)a.sel_pad + (lds ? (size_t)a.n : 0));
-  const void* fn = lds ? (const void*)ppcx_psis_kernel<true> : (const void*)ppcx_psis_kernel<false>;
-  if (bytes > 64u * 1024u) {
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return e;
-  }
-  if (lds) hipLaunchKernelGGL(ppcx_psis_kernel<true>, dim3(a.n_cols), dim3(kPsisThreads), bytes, st, a);
-  else hipLaunchKernelGGL(ppcx_psis_kernel<false>, dim3(a.n_cols), dim3(kPsisThreads), bytes, st, a);
-  return hipGetLastError();
+  return launch_dynamic_lds(lds ? ppcx_psis_kernel<true> : ppcx_psis_kernel<false>, a.n_cols, kBlockThreads, bytes, st, a);
 }
 
 // k-hat of the columns `cols` (host array; -1: r) of the draws [n][D] (device), r [n] (device): the columns go through
 // column-major scratch in batches of at most scratch_bytes (never a second copy of all the draws). Synchronous.
 hipError_t psis_columns(const double* draws, const double* r, long n, int D, int n_cols, const int* cols, double* khat,
                         size_t scratch_bytes, hipStream_t st) {
-  int batch = (int)std::max<size_t>(1, scratch_bytes / (sizeof(double) * (size_t)n));
-  if (batch > n_cols) batch = n_cols;
-  int* d_cols = nullptr; double *d_x = nullptr, *d_out = nullptr;
-  hipError_t e = hipMalloc(&d_cols, sizeof(int) * (size_t)n_cols);
-  if (e == hipSuccess) e = hipMalloc(&d_out, sizeof(double) * (size_t)n_cols);
-  if (e == hipSuccess) e = hipMalloc(&d_x, sizeof(double) * (size_t)n * batch);
-  if (e == hipSuccess) e = hipMemcpyAsync(d_cols, cols, sizeof(int) * (size_t)n_cols, hipMemcpyHostToDevice, st);
-  for (int b0 = 0; e == hipSuccess && b0 < n_cols; b0 += batch) {
-    const int nb = n_cols - b0 < batch ? n_cols - b0 : batch;
-    e = launch_summary_gather_kernel(draws, r, n, D, d_cols + b0, nb, d_x, st);
-    if (e != hipSuccess) break;
+  return for_column_batches(draws, r, n, D, n_cols, cols, scratch_bytes, 1, khat, st,
+                            [&](double* x, const int* d_cols, int nb, double* d_out) {
     PsisArgs a;
-    a.x = d_x; a.r = r; a.cols = d_cols + b0; a.n_cols = nb; a.n = n; a.sel_pad = psis_sel_pad(n); a.out = d_out + b0;
-    e = launch_psis_kernel(a, st);
-  }
-  if (e == hipSuccess) e = hipMemcpyAsync(khat, d_out, sizeof(double) * (size_t)n_cols, hipMemcpyDeviceToHost, st);
-  const hipError_t es = hipStreamSynchronize(st);    // also after a failed launch: nothing is freed under a running kernel
-  if (e == hipSuccess) e = es;
-  (void)hipFree(d_cols); (void)hipFree(d_x); (void)hipFree(d_out);
-  return e;
+    a.x = x; a.r = r; a.cols = d_cols; a.n_cols = nb; a.n = n; a.sel_pad = psis_sel_pad(n); a.out = d_out;
+    return launch_psis_kernel(a, st);
+  });
 }
 
 }  // namespace ppcx

@@ -12,13 +12,12 @@
 //                               its waves after the barrier, as in the posterior-predictive kernel's global path).
 // A column's result depends on its draws only (fixed reduction orders): the same bits on every call and in both paths.
 #include <hip/hip_runtime.h>
+#include "ppcx_block.h"
 #include "ppcx_summary.h"
-#include "ppcx_kernels.h"
+#include "ppcx_columns.h"
 
 namespace ppcx {
 
-constexpr int kSummaryThreads = 256;
-constexpr int kSummaryWaves = kSummaryThreads / 64;
 constexpr int kSummaryLags = 16;              // autocovariance lags per chunk (even: a chunk holds whole Geyer pairs)
 
 __global__ __launch_bounds__(256) void ppcx_summary_gather_kernel(const double* draws, const double* lp, long rows, int D,
@@ -39,44 +38,10 @@ __global__ __launch_bounds__(256) void ppcx_summary_gather_kernel(const double* 
   }
 }
 
-__device__ __forceinline__ double summary_wave_sum(double v) {
-#pragma unroll
-  for (int msk = 1; msk < 64; msk <<= 1) v += __shfl_xor(v, msk, 64);
-  return v;                                    // the same bits in every lane
-}
-// sum over the workgroup in a fixed order; every thread gets it. red: kSummaryWaves doubles of LDS
-__device__ double summary_block_sum(double v, double* red) {
-  v = summary_wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  double s = 0.0;
-  for (int w = 0; w < kSummaryWaves; ++w) s += red[w];
-  return s;
-}
-__device__ bool summary_block_any(bool b) { return __syncthreads_or(b ? 1 : 0) != 0; }
-
-// ascending bitonic sort of s[0 .. npad) (npad a power of two; the caller pads with +inf)
-__device__ void summary_sort(double* s, int npad) {
-  for (int k = 2; k <= npad; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = threadIdx.x; i < (npad >> 1); i += kSummaryThreads) {
-        const int lo = 2 * j * (i / j) + (i % j), hi = lo + j;
-        const bool up = (lo & k) == 0;
-        const double a = s[lo], b = s[hi];
-        if ((a > b) == up) { s[lo] = b; s[hi] = a; }
-      }
-      __syncthreads();
-    }
-  }
-}
-__device__ __forceinline__ int summary_pow2(long n) { int p = 1; while (p < n) p <<= 1; return p; }
-
 struct SummaryShared {
-  double red[kSummaryWaves];
+  double red[kBlockWaves];
   double rho[kSummaryLags];
-  double part[kSummaryWaves][kSummaryLags];
+  double part[kBlockWaves][kSummaryLags];
   double seq_mean[2 * kSummaryMaxChains];
   double seq_var[2 * kSummaryMaxChains];
 };
@@ -85,14 +50,14 @@ struct SummaryShared {
 // sequence for the means and variances; the autocovariances summed over all sequences in chunks of kSummaryLags lags.
 __device__ double summary_sequences(double* z, int m, int nh, bool want_ess, double* ess, SummaryShared& sh) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  for (int j = wave; j < m; j += kSummaryWaves) {
+  for (int j = wave; j < m; j += kBlockWaves) {
     const double* q = z + (long)j * nh;
     double s = 0.0;
     for (int i = lane; i < nh; i += 64) s += q[i];
-    const double mu = summary_wave_sum(s) / nh;
+    const double mu = block_wave_sum(s) / nh;
     double v = 0.0;
     for (int i = lane; i < nh; i += 64) { const double d = q[i] - mu; v += d * d; }
-    v = summary_wave_sum(v) / (nh - 1.0);
+    v = block_wave_sum(v) / (nh - 1.0);
     if (lane == 0) { sh.seq_mean[j] = mu; sh.seq_var[j] = v; }
   }
   __syncthreads();
@@ -107,7 +72,7 @@ __device__ double summary_sequences(double* z, int m, int nh, bool want_ess, dou
   const double vp = var_plus_of(vm, mv, nh);
   if (!(vp > 0.0)) { *ess = NAN; __syncthreads(); return rh; }
   const long N = (long)m * nh;
-  for (long k = threadIdx.x; k < N; k += kSummaryThreads) z[k] -= sh.seq_mean[k / nh];
+  for (long k = threadIdx.x; k < N; k += kBlockThreads) z[k] -= sh.seq_mean[k / nh];
   __syncthreads();
   Geyer g;                                      // every thread runs the same scalar recurrence on the same values
   bool started = false;
@@ -115,7 +80,7 @@ __device__ double summary_sequences(double* z, int m, int nh, bool want_ess, dou
     double acc[kSummaryLags];
 #pragma unroll
     for (int l = 0; l < kSummaryLags; ++l) acc[l] = 0.0;
-    for (long k = threadIdx.x; k < N; k += kSummaryThreads) {
+    for (long k = threadIdx.x; k < N; k += kBlockThreads) {
       const int i = (int)(k % nh);
       const double c = z[k];
 #pragma unroll
@@ -123,13 +88,13 @@ __device__ double summary_sequences(double* z, int m, int nh, bool want_ess, dou
     }
 #pragma unroll
     for (int l = 0; l < kSummaryLags; ++l) {
-      const double v = summary_wave_sum(acc[l]);
+      const double v = block_wave_sum(acc[l]);
       if (lane == 0) sh.part[wave][l] = v;
     }
     __syncthreads();
     if (threadIdx.x < kSummaryLags) {
       double s = 0.0;
-      for (int w = 0; w < kSummaryWaves; ++w) s += sh.part[w][threadIdx.x];
+      for (int w = 0; w < kBlockWaves; ++w) s += sh.part[w][threadIdx.x];
       sh.rho[threadIdx.x] = rho_of(s / (double)N, mv, vp);
     }
     __syncthreads();
@@ -144,7 +109,7 @@ __device__ double summary_sequences(double* z, int m, int nh, bool want_ess, dou
 }
 
 template <bool LDS>
-__global__ __launch_bounds__(kSummaryThreads) void ppcx_summary_kernel(SummaryArgs a) {
+__global__ __launch_bounds__(kBlockThreads) void ppcx_summary_kernel(SummaryArgs a) {
   extern __shared__ double lds[];
   __shared__ SummaryShared sh;
   const long Mn = (long)a.M * a.n;
@@ -157,52 +122,52 @@ __global__ __launch_bounds__(kSummaryThreads) void ppcx_summary_kernel(SummaryAr
     double* out = a.out + (long)c * SUM_FIELDS;
     // ---- plain summary over all M n draws
     double s = 0.0; bool bad = false;
-    for (long i = threadIdx.x; i < Mn; i += kSummaryThreads) { const double v = x[i]; bad = bad || !isfinite(v); s += v; }
-    bad = summary_block_any(bad);
-    const double mean = summary_block_sum(s, sh.red) / (double)Mn;
+    for (long i = threadIdx.x; i < Mn; i += kBlockThreads) { const double v = x[i]; bad = bad || !isfinite(v); s += v; }
+    bad = block_any(bad);
+    const double mean = block_sum(s, sh.red) / (double)Mn;
     if (bad) {
       if (threadIdx.x < SUM_FIELDS) out[threadIdx.x] = NAN;
       continue;
     }
     double ss = 0.0;
-    for (long i = threadIdx.x; i < Mn; i += kSummaryThreads) { const double d = x[i] - mean; ss += d * d; }
-    ss = summary_block_sum(ss, sh.red);
+    for (long i = threadIdx.x; i < Mn; i += kBlockThreads) { const double d = x[i] - mean; ss += d * d; }
+    ss = block_sum(ss, sh.red);
     double q05 = 0.0, q50 = 0.0, q95 = 0.0;
     if (N != Mn || nh < 2) {                    // odd n (the split values drop the middle draws) or nothing to split
-      const int np = summary_pow2(Mn);
-      for (long i = threadIdx.x; i < np; i += kSummaryThreads) S[i] = i < Mn ? x[i] : INFINITY;
+      const int np = pow2_at_least(Mn);
+      for (long i = threadIdx.x; i < np; i += kBlockThreads) S[i] = i < Mn ? x[i] : INFINITY;
       __syncthreads();
-      summary_sort(S, np);
+      block_sort(S, np);
       q05 = quantile7_sorted(S, Mn, 0.05); q50 = quantile7_sorted(S, Mn, 0.5); q95 = quantile7_sorted(S, Mn, 0.95);
       __syncthreads();
     }
     double rhat = NAN, ess_bulk = NAN, ess_tail = NAN;
     if (nh >= 2) {
-      const int np = summary_pow2(N);
-      for (long k = threadIdx.x; k < np; k += kSummaryThreads) S[k] = k < N ? x[split_source(k, nh, a.n)] : INFINITY;
+      const int np = pow2_at_least(N);
+      for (long k = threadIdx.x; k < np; k += kBlockThreads) S[k] = k < N ? x[split_source(k, nh, a.n)] : INFINITY;
       __syncthreads();
-      summary_sort(S, np);
+      block_sort(S, np);
       const double sq05 = quantile7_sorted(S, N, 0.05), med = quantile7_sorted(S, N, 0.5), sq95 = quantile7_sorted(S, N, 0.95);
       if (N == Mn) { q05 = sq05; q50 = med; q95 = sq95; }
       if (S[0] < S[N - 1]) {
-        for (long k = threadIdx.x; k < N; k += kSummaryThreads) Z[k] = blom_z(average_rank(S, N, x[split_source(k, nh, a.n)]), N);
+        for (long k = threadIdx.x; k < N; k += kBlockThreads) Z[k] = blom_z(average_rank(S, N, x[split_source(k, nh, a.n)]), N);
         __syncthreads();
         const double rb = summary_sequences(Z, m, nh, true, &ess_bulk, sh);
         __syncthreads();                        // S and Z are rewritten below
-        for (long k = threadIdx.x; k < np; k += kSummaryThreads) S[k] = k < N ? fabs(x[split_source(k, nh, a.n)] - med) : INFINITY;
+        for (long k = threadIdx.x; k < np; k += kBlockThreads) S[k] = k < N ? fabs(x[split_source(k, nh, a.n)] - med) : INFINITY;
         __syncthreads();
-        summary_sort(S, np);
-        for (long k = threadIdx.x; k < N; k += kSummaryThreads) Z[k] = blom_z(average_rank(S, N, fabs(x[split_source(k, nh, a.n)] - med)), N);
+        block_sort(S, np);
+        for (long k = threadIdx.x; k < N; k += kBlockThreads) Z[k] = blom_z(average_rank(S, N, fabs(x[split_source(k, nh, a.n)] - med)), N);
         __syncthreads();
         const double rf = summary_sequences(Z, m, nh, false, nullptr, sh);
         rhat = fmax(rb, rf);
         __syncthreads();
         double e05 = NAN, e95 = NAN;
-        for (long k = threadIdx.x; k < N; k += kSummaryThreads) Z[k] = x[split_source(k, nh, a.n)] <= sq05 ? 1.0 : 0.0;
+        for (long k = threadIdx.x; k < N; k += kBlockThreads) Z[k] = x[split_source(k, nh, a.n)] <= sq05 ? 1.0 : 0.0;
         __syncthreads();
         summary_sequences(Z, m, nh, true, &e05, sh);
         __syncthreads();
-        for (long k = threadIdx.x; k < N; k += kSummaryThreads) Z[k] = x[split_source(k, nh, a.n)] <= sq95 ? 1.0 : 0.0;
+        for (long k = threadIdx.x; k < N; k += kBlockThreads) Z[k] = x[split_source(k, nh, a.n)] <= sq95 ? 1.0 : 0.0;
         __syncthreads();
         summary_sequences(Z, m, nh, true, &e95, sh);
         ess_tail = isnan(e05) ? e95 : (isnan(e95) ? e05 : (e05 < e95 ? e05 : e95));
@@ -218,8 +183,7 @@ __global__ __launch_bounds__(kSummaryThreads) void ppcx_summary_kernel(SummaryAr
 }
 
 // ---- launch helpers (host)
-static int summary_pow2_host(long n) { int p = 1; while (p < n) p <<= 1; return p; }
-int summary_npad(int M, int n) { return summary_pow2_host((long)M * n); }
+int summary_npad(int M, int n) { return pow2_at_least((long)M * n); }
 long summary_slice_doubles(int M, int n) { return (long)summary_npad(M, n) + 2L * M * (n / 2) + 1; }
 size_t summary_lds_bytes(int M, int n) { return (long)M * n <= kSummaryLdsDraws ? sizeof(double) * (size_t)summary_slice_doubles(M, n) : 0; }
 hipError_t launch_summary_gather_kernel(const double* draws, const double* lp, long rows, int D, const int* cols, int n_cols, double* out, hipStream_t st) {
@@ -228,17 +192,30 @@ hipError_t launch_summary_gather_kernel(const double* draws, const double* lp, l
   return hipGetLastError();
 }
 hipError_t launch_summary_kernel(const SummaryArgs& a, int nblocks, hipStream_t st) {
-  if (a.scratch) {
-    hipLaunchKernelGGL(ppcx_summary_kernel<false>, dim3(nblocks), dim3(kSummaryThreads), 0, st, a);
-    return hipGetLastError();
-  }
-  const size_t lds = summary_lds_bytes(a.M, a.n);
-  if (lds > 64u * 1024u) {
-    hipError_t e = hipFuncSetAttribute((const void*)ppcx_summary_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(ppcx_summary_kernel<true>, dim3(nblocks), dim3(kSummaryThreads), lds, st, a);
-  return hipGetLastError();
+  if (a.scratch) return launch_dynamic_lds(ppcx_summary_kernel<false>, nblocks, kBlockThreads, 0, st, a);
+  return launch_dynamic_lds(ppcx_summary_kernel<true>, nblocks, kBlockThreads, summary_lds_bytes(a.M, a.n), st, a);
+}
+
+// The summary of the columns `cols` (host; -1: lp) of M chains of n draws [M n][D] (device) into out [n_cols][SUM_FIELDS] (host).
+// Half of scratch_bytes bounds a batch's columns ([batch][M n]), the other half the global path's slices, one per workgroup
+// (at most 2048 of them). Synchronous.
+hipError_t summary_columns(const double* draws, const double* lp, int M, int n, int D, int n_cols, const int* cols, double* out,
+                           size_t scratch_bytes, hipStream_t st) {
+  const long rows = (long)M * n;
+  const bool lds = summary_lds_bytes(M, n) > 0;
+  const long slice = summary_slice_doubles(M, n);
+  int nslices = lds ? 0 : column_batch(scratch_bytes / 2, slice, column_batch(scratch_bytes / 2, rows, n_cols));
+  if (nslices > 2048) nslices = 2048;
+  DeviceBuffer<double> d_scr;
+  hipError_t e = lds ? hipSuccess : d_scr.alloc((size_t)slice * nslices);
+  if (e != hipSuccess) return e;
+  return for_column_batches(draws, lp, rows, D, n_cols, cols, scratch_bytes / 2, SUM_FIELDS, out, st,
+                            [&](const double* x, const int*, int nb, double* d_out) {
+    SummaryArgs a;
+    a.x = x; a.n_cols = nb; a.M = M; a.n = n; a.npad = summary_npad(M, n);
+    a.out = d_out; a.scratch = d_scr.p; a.slice = slice;
+    return launch_summary_kernel(a, lds ? nb : nslices, st);
+  });
 }
 
 }  // namespace ppcx
