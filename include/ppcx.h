@@ -163,6 +163,28 @@ PPCX_API int ppcx_fit_psis(ppcx_fit* f, int n_cols, const int32_t* cols, double*
 #define PPCX_LOO_FIELDS 4       /* elpd_loo, p_loo, looic, khat */
 PPCX_API int ppcx_fit_get_log_lik(ppcx_fit* f, int n_genes, const int32_t* genes, double* out);
 PPCX_API int ppcx_fit_loo(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double* out);
+/* The leave-one-out predictive interval and LOO-PIT per observed cell of a NUTS fit, from that ONE fit: for cell (g, s) the
+ * distribution of its count under the posterior that has not seen the cell (what loo::E_loo(yrep, psis, type = "quantile" /
+ * "mean") and bayesplot's ppc_loo_intervals / ppc_loo_pit give; ppcseq's question -- is the observed count inside the interval? --
+ * without the second fit). Fits, genes, r_eff and refusals as ppcx_fit_loo; besides PPCX_ERR_ARG unless 0 <= p_lo < p_hi <= 1
+ * and truncation_compensation is finite and > 0. Synchronous on the model's stream.
+ *   out [n_genes][S][PPCX_LOO_PREDICT_FIELDS]: mean, lower, upper, pit_lt, pit_le, khat.
+ *   The predictive count of kept draw i (all chains, the fit's order) is neg_binomial_2_log_rng(exposure_s + X_s alpha_g(i),
+ *   truncation_compensation exp(-sigma_raw_g(i))) on the Philox address (seed, g S + s, i): for g < K the integers of
+ *   ppcx_fit_ppc's counts_rng with n_gen = 0, resample = 0. Draw i carries the PSIS weight w_i of ppcx_fit_loo's cell (the tail
+ *   smoothed in the order of a stable sort of the ratios: tied draws take the tail's positions in draw order); the compensation
+ *   scales the predictive draw only, never the likelihood behind the weights. With F(v) = sum w_i 1[x_i <= v]:
+ *   mean = sum w_i x_i; pit_lt = sum w_i 1[x_i < y], pit_le = F(y) (the two ends of the randomised LOO-PIT of the observed count
+ *   y); lower, upper = Q(p_lo), Q(p_hi), loo's weighted quantile: v* the smallest drawn value with F(v*) >= p, Q = v* if no drawn
+ *   value is below it, else Q = v- + (v* - v-) (p - F(v-)) / (F(v*) - F(v-)) with v- the largest drawn value below v*;
+ *   khat as ppcx_fit_loo (above 0.7 the weights are not to be trusted).
+ *   A cell excluded by the model at the time of the call is already held out: uniform weights, khat = NaN, mean, lower and upper
+ *   equal ppcx_fit_ppc's mean, .lower and .upper (type-7 quantiles) bit for bit at the same seed, probabilities and compensation
+ *   (g < K). A NaN log_lik, one of -Inf, or an invalid predictive draw: the cell is NaN. Neither the log-likelihood nor the
+ *   counts matrix is materialised; the same bits on every call, for any gene subset. Tail limit as ppcx_fit_loo.              */
+#define PPCX_LOO_PREDICT_FIELDS 6   /* mean, lower, upper, pit_lt, pit_le, khat */
+PPCX_API int ppcx_fit_loo_predict(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double truncation_compensation,
+                                  double p_lo, double p_hi, unsigned long long seed, double* out);
 /* lp: [chains][n_keep]; the rest [chains][iter] (warmup included); any pointer may be NULL */
 PPCX_API int ppcx_fit_get_diagnostics(ppcx_fit* f, double* lp, double* stepsize, int32_t* treedepth,
                              int32_t* n_leapfrog, int32_t* divergent, double* accept);

@@ -25,10 +25,12 @@ EXPORTS = [
     "ppcx_xchg_create", "ppcx_xchg_handle", "ppcx_xchg_connect", "ppcx_xchg_connect_local", "ppcx_xchg_set_timeout", "ppcx_xchg_destroy",
     "ppcx_fit_nuts_xchg", "ppcx_fit_get_xchg_timing", "ppcx_fit_get_inv_metric", "ppcx_fit_summary",
     "ppcx_fit_get_approximation", "ppcx_fit_get_log_ratios", "ppcx_fit_psis", "ppcx_fit_get_log_lik", "ppcx_fit_loo",
+    "ppcx_fit_loo_predict",
 ]
 ABI_VERSION = 400           # include/ppcx.h PPCX_VERSION this binding was written for
 SUMMARY_FIELDS = ("mean", "sd", "q05", "q50", "q95", "rhat", "ess_bulk", "ess_tail")   # PPCX_SUMMARY_FIELDS, in order
 LOO_FIELDS = ("elpd_loo", "p_loo", "looic", "khat")                                      # PPCX_LOO_FIELDS, in order
+LOO_PREDICT_FIELDS = ("mean", "lower", "upper", "pit_lt", "pit_le", "khat")              # PPCX_LOO_PREDICT_FIELDS, in order
 
 
 class PpcxError(RuntimeError):
@@ -101,6 +103,7 @@ def load() -> C.CDLL:
     lib.ppcx_fit_psis.argtypes = [C.c_void_p, C.c_int, ip, dp]
     lib.ppcx_fit_get_log_lik.argtypes = [C.c_void_p, C.c_int, ip, dp]
     lib.ppcx_fit_loo.argtypes = [C.c_void_p, C.c_int, ip, dp, dp]
+    lib.ppcx_fit_loo_predict.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_double, C.c_double, C.c_double, C.c_ulonglong, dp]
     lib.ppcx_fit_get_diagnostics.argtypes = [C.c_void_p, dp, dp, ip, ip, ip, dp]
     lib.ppcx_fit_get_timing.argtypes = [C.c_void_p, dp, C.POINTER(C.c_longlong), dp, C.POINTER(C.c_longlong), dp]
     lib.ppcx_fit_get_kernel_times.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(C.c_longlong)]
@@ -133,6 +136,8 @@ def load() -> C.CDLL:
         lib.ppcx_testing_psis.argtypes = [C.c_int, C.c_int, dp, dp, dp]
     if hasattr(lib, "ppcx_testing_loo"):
         lib.ppcx_testing_loo.argtypes = [C.c_int, C.c_int, dp, ip, dp, dp]
+    if hasattr(lib, "ppcx_testing_loo_predict"):
+        lib.ppcx_testing_loo_predict.argtypes = [dp, ip, C.c_int, C.c_int, ip, ip, dp, C.c_double, C.c_double, dp]
     lib.ppcx_fit_free.restype = None
     lib.ppcx_advi_config_default.argtypes = [C.POINTER(AdviConfig)]
     lib.ppcx_advi_config_default.restype = None
@@ -234,6 +239,30 @@ def testing_loo(ll, excluded=None, r_eff=None):
     return out
 
 
+def testing_loo_predict(ll, x, y, excluded=None, r_eff=None, p_lo=0.025, p_hi=0.975):
+    """The kernel of ppcx_fit_loo_predict on host-given columns (testing build only; csrc/ppcx_testing.h
+    ppcx_testing_loo_predict): ll [n_draws, n_cells] log-likelihoods, x [n_draws, n_cells] predictive counts, y [n_cells] observed
+    counts, excluded / r_eff None or [n_cells]. Returns [n_cells, 6]: mean, lower, upper, pit_lt, pit_le, khat."""
+    lib = load()
+    if not hasattr(lib, "ppcx_testing_loo_predict"):
+        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before ppcx_testing_loo_predict existed: rebuild it "
+                        "(`python -m ppcseq_amd.build --testing --force`)")
+    ll = np.asarray(ll, dtype=np.float64)
+    ll = ll.reshape(ll.shape[0], -1)
+    n, nc = ll.shape
+    cols = np.ascontiguousarray(ll.T)
+    xs = np.ascontiguousarray(np.asarray(x).reshape(n, nc).T, dtype=np.int32)
+    ys = np.ascontiguousarray(np.broadcast_to(np.asarray(y), (nc,)), dtype=np.int32)
+    ex = None if excluded is None else np.ascontiguousarray(excluded, dtype=np.int32).ravel()
+    re = None if r_eff is None else np.ascontiguousarray(r_eff, dtype=np.float64).ravel()
+    out = np.zeros((nc, len(LOO_PREDICT_FIELDS)))
+    _check(lib.ppcx_testing_loo_predict(_p(cols, C.c_double), _p(xs, C.c_int32), n, nc, _p(ys, C.c_int32),
+                                        _p(ex, C.c_int32) if ex is not None else None,
+                                        _p(re, C.c_double) if re is not None else None, float(p_lo), float(p_hi),
+                                        _p(out, C.c_double)))
+    return out
+
+
 def loo_estimates(pointwise, excluded):
     """loo's `estimates` for elpd_loo, p_loo and looic over the non-excluded cells: {name: (sum, sqrt(n var))}, var of ddof 1"""
     keep = ~np.asarray(excluded, bool)
@@ -283,6 +312,7 @@ class Model:
         excl = np.ascontiguousarray(excl if excl is not None else np.zeros(0), dtype=np.int32)
         self.X, self.exposure_rate = X, exposure_rate
         self.excl = excl.copy()                  # the cells excluded now (Fit.loo holds them out)
+        self.counts = counts                     # the observed counts (Fit.loo_predict reports them beside the intervals)
         h = C.c_void_p()
         self.shard = shard
         if shard is None:
@@ -608,6 +638,34 @@ class Fit:
         res["genes"] = g.astype(np.int64)
         res["n_draws"] = self.chains * self.n_keep
         res["estimates"] = loo_estimates(res, res["excluded"])
+        return res
+
+    def loo_predict(self, genes=None, r_eff=None, p_lo=0.025, p_hi=0.975, seed=1, truncation_compensation=1.0):
+        """The leave-one-out predictive interval and LOO-PIT per observed cell on the device (ppcx_fit_loo_predict; loo::E_loo,
+        bayesplot::ppc_loo_intervals / ppc_loo_pit): a dict of mean, lower, upper (the p_lo / p_hi quantiles of the cell's count
+        under the posterior that has not seen the cell), pit_lt, pit_le (P(x < y), P(x <= y)) and khat, [n_genes, S] each;
+        `excluded` (cells the model holds out now: uniform weights, Fit.ppc's interval, khat NaN), `y` (the observed counts),
+        `outside` = (y < lower) | (y > upper), `genes`, `n_draws`. genes=None: all G genes; r_eff None (all 1) or [n_genes, S].
+        seed and truncation_compensation as Fit.ppc: the predictive counts of a checked gene are its counts_rng."""
+        g = self._genes(genes)
+        S = self.model.S
+        out = np.zeros((g.size, S, len(LOO_PREDICT_FIELDS)))
+        re = None
+        if r_eff is not None:
+            re = np.ascontiguousarray(np.broadcast_to(np.asarray(r_eff, dtype=np.float64), (g.size, S)))
+        if g.size:
+            _check(load().ppcx_fit_loo_predict(self._h, int(g.size), _p(g, C.c_int32),
+                                               _p(re, C.c_double) if re is not None else None, float(truncation_compensation),
+                                               float(p_lo), float(p_hi), int(seed), _p(out, C.c_double)))
+        res = {k: out[:, :, i].copy() for i, k in enumerate(LOO_PREDICT_FIELDS)}
+        excl = np.zeros(self.model.G * S, bool)
+        excl[np.asarray(self.model.excl, dtype=np.int64)] = True
+        res["excluded"] = excl.reshape(self.model.G, S)[g]
+        res["y"] = np.asarray(self.model.counts).reshape(self.model.G, S)[g].astype(np.int64)
+        with np.errstate(invalid="ignore"):
+            res["outside"] = (res["y"] < res["lower"]) | (res["y"] > res["upper"])
+        res["genes"] = g.astype(np.int64)
+        res["n_draws"] = self.chains * self.n_keep
         return res
 
     def diagnostics(self):

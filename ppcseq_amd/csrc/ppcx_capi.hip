@@ -1997,6 +1997,30 @@ extern "C" int ppcx_fit_loo(ppcx_fit* f, int n_genes, const int32_t* genes, cons
   if (e != hipSuccess) return fail(PPCX_ERR_HIP, std::string("ppcx_fit_loo: ") + hipGetErrorString(e));
   return PPCX_OK;
 }
+// ---- the leave-one-out predictive interval and LOO-PIT of the same cells (loo::E_loo / bayesplot::ppc_loo_intervals, ppc_loo_pit)
+static int loo_predict_check_probs(double p_lo, double p_hi) {
+  if (!(p_lo >= 0.0 && p_lo < p_hi && p_hi <= 1.0)) return fail(PPCX_ERR_ARG, "need 0 <= p_lo < p_hi <= 1");
+  return PPCX_OK;
+}
+extern "C" int ppcx_fit_loo_predict(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double truncation_compensation,
+                                    double p_lo, double p_hi, unsigned long long seed, double* out) {
+  std::vector<int> yenc;
+  int rc = loo_prepare(f, n_genes, genes, yenc);
+  if (rc != PPCX_OK) return rc;
+  if (!out) return fail(PPCX_ERR_ARG, "bad arguments");
+  ppcx_model* m = f->m;
+  const long n = (long)f->chains * f->n_keep, ncells = (long)n_genes * m->d.S;
+  if ((rc = loo_check_reff(r_eff, ncells)) != PPCX_OK) return rc;
+  if ((rc = loo_predict_check_probs(p_lo, p_hi)) != PPCX_OK) return rc;
+  if (!(isfinite(truncation_compensation) && truncation_compensation > 0.0))
+    return fail(PPCX_ERR_ARG, "truncation_compensation must be finite and > 0");
+  const double rmin = loo_reff_min(r_eff, ncells);
+  if (psis_tail_len(n, rmin) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "ppcx_fit_loo_predict: the tail exceeds 4095 draws");
+  hipError_t e = loo_predict_fit_cells(f->d_draws, n, m->d, m->d_expo, m->d_X, n_genes, genes, yenc.data(), r_eff, rmin,
+                                       truncation_compensation, p_lo, p_hi, seed32(seed), out, loo_scratch_bytes(), m->stream);
+  if (e != hipSuccess) return fail(PPCX_ERR_HIP, std::string("ppcx_fit_loo_predict: ") + hipGetErrorString(e));
+  return PPCX_OK;
+}
 #ifdef PPCX_TESTING
 // testing build only (ppcx_testing.h): the LOO kernel on host-given columns, on the current device
 extern "C" int ppcx_testing_loo(int n, int n_cols, const double* ll, const int32_t* excluded, const double* r_eff, double* out) {
@@ -2006,6 +2030,22 @@ extern "C" int ppcx_testing_loo(int n, int n_cols, const double* ll, const int32
   const double rmin = loo_reff_min(r_eff, n_cols);
   if (psis_tail_len(n, rmin) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "too many draws");
   hipError_t e = loo_columns(ll, n, n_cols, excluded, r_eff, rmin, out, loo_scratch_bytes(), nullptr);
+  if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
+  return PPCX_OK;
+}
+#endif
+#ifdef PPCX_TESTING
+// testing build only (ppcx_testing.h): the LOO predictive kernel on host-given columns, on the current device
+extern "C" int ppcx_testing_loo_predict(const double* ll, const int32_t* x, int n, int n_cols, const int32_t* y, const int32_t* excluded,
+                                        const double* r_eff, double p_lo, double p_hi, double* out) {
+  if (n < 1 || n_cols < 1 || !ll || !x || !y || !out) return fail(PPCX_ERR_ARG, "bad arguments");
+  for (size_t i = 0; i < (size_t)n * n_cols; ++i) if (x[i] < 0) return fail(PPCX_ERR_ARG, "predictive counts must be >= 0");
+  int rc = loo_check_reff(r_eff, n_cols);
+  if (rc != PPCX_OK) return rc;
+  if ((rc = loo_predict_check_probs(p_lo, p_hi)) != PPCX_OK) return rc;
+  const double rmin = loo_reff_min(r_eff, n_cols);
+  if (psis_tail_len(n, rmin) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "too many draws");
+  hipError_t e = loo_predict_columns(ll, x, n, n_cols, y, excluded, r_eff, rmin, p_lo, p_hi, out, loo_scratch_bytes(), nullptr);
   if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
   return PPCX_OK;
 }

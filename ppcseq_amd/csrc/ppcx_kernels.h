@@ -242,6 +242,19 @@ hipError_t loo_fit_log_lik(const double* draws, long n, const Dims& d, const dou
 // LOO of host-given columns cols [n_cols][n] (testing build); synchronous
 hipError_t loo_columns(const double* cols, long n, int n_cols, const int* excl, const double* r_eff, double r_eff_min, double* out,
                        size_t scratch_bytes, hipStream_t st);
+// The leave-one-out predictive interval and LOO-PIT of the same cells (ppcx_loo_predict.hip, statistic in ppcx_loo_predict.h): one
+// workgroup per cell; ratios, weights and predictive counts (20 bytes per draw) in LDS up to kPsisLdsDraws draws, beyond that in
+// the scratch, bounded like the gene table. tc: truncation compensation of the predictive draws; k0 = seed32(seed). out (host)
+// [cells][kLooPredictFields]. Synchronous
+hipError_t launch_loo_table_kernel(const double* draws, long n_draws, const Dims& d, const int* genes, int n_genes, double* T,
+                                   hipStream_t st);    // T[g][c][draw] of the genes (device ids), ppcx_loo.hip
+hipError_t loo_predict_fit_cells(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
+                                 const int* genes, const int* yenc, const double* r_eff, double r_eff_min, double tc, double p_lo,
+                                 double p_hi, uint32_t k0, double* out, size_t scratch_bytes, hipStream_t st);
+// ... of host-given columns cols [n_cols][n] with predictive counts x [n_cols][n] and observed counts y [n_cols] (testing build)
+hipError_t loo_predict_columns(const double* cols, const int* x, long n, int n_cols, const int* y, const int* excl,
+                               const double* r_eff, double r_eff_min, double p_lo, double p_hi, double* out, size_t scratch_bytes,
+                               hipStream_t st);
 hipError_t launch_xchg_abort_kernel(const XchgArgs& x, hipStream_t st);      // tells every peer that this rank has left the fit
 
 }  // namespace ppcx

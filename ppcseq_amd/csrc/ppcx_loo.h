@@ -22,7 +22,8 @@
 //   3. every log weight lw is truncated at 0 (the largest raw one); the weights are normalised by logsumexp(lw).
 //   4. elpd_loo = logsumexp(lw + ll) - logsumexp(lw); lpd = logsumexp(ll) - log N; p_loo = lpd - elpd_loo;
 //      looic = -2 elpd_loo; khat = k-hat.
-//   Tied ratios have equal ll, so which of them receives which smoothed weight does not change any sum.
+//   Tied ratios have equal ll, so which of them receives which smoothed weight does not change any sum here. It does where a
+//   draw carries more than its ll: ppcx_loo_predict.h step 2 fixes the order (a stable sort: tied draws in draw order).
 // An excluded cell (not in the likelihood at the time of the call) is already held out: elpd_loo = lpd, p_loo = 0,
 // looic = -2 lpd, khat = NaN (a NaN ll: all NaN; ll = +Inf takes no part).
 // Every reduction runs in a fixed order: a cell's fields depend on its own column only.

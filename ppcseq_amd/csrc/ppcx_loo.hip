@@ -16,9 +16,7 @@
 // requested and however the work is batched. The G S x n matrix is never materialised for LOO.
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include "ppcx_psis_dev.h"
-#include "ppcx_loo.h"
-#include "ppcx_columns.h"
+#include "ppcx_loo_dev.h"
 
 namespace ppcx {
 
@@ -50,14 +48,6 @@ __global__ __launch_bounds__(256) void ppcx_loo_table_kernel(const double* draws
   }
 }
 
-// log-likelihood of cell (gene gi of the table, sample s) at draw j, count y >= 0
-__device__ __forceinline__ double loo_cell_ll(const LooArgs& a, int gi, int s, long j, int y) {
-  const double* Tg = a.T + (long)gi * (a.C + 1) * a.n;
-  double eta = a.expo[s] + a.X[s] * Tg[j];
-  for (int cc = 1; cc < a.C; ++cc) eta += a.X[(long)cc * a.S + s] * Tg[(long)cc * a.n + j];
-  return loo_ll(y, eta, Tg[(long)a.C * a.n + j]);
-}
-
 __global__ __launch_bounds__(256) void ppcx_loo_ll_kernel(LooArgs a, long j0, long n_rows, double* out) {
   const long n_cells = (long)a.n_cells;
   const long t = (long)blockIdx.x * 256 + threadIdx.x;
@@ -87,22 +77,11 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_kernel(LooArgs a) {
   const int gi = COLS ? 0 : cell / a.S, s = COLS ? 0 : cell - gi * a.S;
   double* o = a.out + (long)cell * kLooFields;
   // ---- the ratios; NaN / +Inf; N (the -Inf ratios take no part); the largest ratio and the largest ll
-  bool bad = false; double cnt = 0.0, rmax = -INFINITY, lmax = -INFINITY;
-  for (long i = tid; i < n; i += kBlockThreads) {
-    const double ll = COLS ? a.cols[(long)cell * n + i] : loo_cell_ll(a, gi, s, i, y);
-    const double r = -ll;
-    bad = bad || isnan(r) || (!excluded && r == INFINITY);
-    if (r != -INFINITY) { cnt += 1.0; rmax = fmax(rmax, r); lmax = fmax(lmax, ll); }
-    V[i] = r;
-  }
-  bad = block_any(bad);
-  if (bad) {
+  long N; double rmax, lmax;
+  if (loo_cell_ratios<COLS>(a, cell, gi, s, y, excluded, V, sh, &N, &rmax, &lmax)) {
     if (tid == 0) o[0] = o[1] = o[2] = o[3] = NAN;
     return;
   }
-  const long N = (long)block_sum(cnt, sh.red);
-  rmax = block_max(rmax, sh.red);
-  lmax = block_max(lmax, sh.red);
   // ---- lpd = logsumexp(ll) - log N
   double sl = 0.0;
   for (long i = tid; i < n; i += kBlockThreads) { const double r = V[i]; if (r != -INFINITY) sl += exp(-r - lmax); }
@@ -115,19 +94,11 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_kernel(LooArgs a) {
   // ---- the tail: M + 1 largest, the profile fit, k-hat and sigma
   const double mx = rmax;                                // the tail's own mx is this value (it exists only where M >= 5)
   const int M = psis_tail_len(N, a.r_eff ? a.r_eff[cell] : 1.0);
-  double khat = INFINITY, sigma = 0.0;
-  bool smooth = false; int n_extra = 0;
-  PsisTail tl{};
-  if (psis_tail(V, n, N, M, K, X, a.sel_pad, sh, &tl) == PSIS_TAIL_FITTED) {
-    khat = psis_adjust(tl.k_mean, M);
-    sigma = -tl.k_mean / tl.theta_hat;
-    smooth = loo_smooth_ok(khat, sigma);
-    if (smooth) {                                        // copies of the cutoff outside the tail: all of them but want - 1
-      double eq = 0.0;
-      for (long i = tid; i < n; i += kBlockThreads) eq += psis_key(V[i]) == tl.key ? 1.0 : 0.0;
-      n_extra = (int)block_sum(eq, sh.red) - (tl.want - 1);
-    }
-  }
+  const LooTail lt = loo_cell_tail(V, n, N, M, K, X, a.sel_pad, sh);
+  const double khat = lt.khat, sigma = lt.sigma;
+  const bool smooth = lt.smooth;
+  const PsisTail& tl = lt.tl;
+  const int n_extra = smooth ? lt.n_eq - (tl.want - 1) : 0;   // copies of the cutoff outside the tail: all of them but want - 1
   // ---- logsumexp(lw + ll) and logsumexp(lw): a raw draw has lw = r - mx (<= 0), a tail draw the smoothed value truncated at 0
   auto terms = [&](bool sum, LooTerms mxv) {
     LooTerms t{sum ? 0.0 : -INFINITY, sum ? 0.0 : -INFINITY};
@@ -182,20 +153,11 @@ hipError_t launch_loo_kernel(const LooArgs& a, int n_blocks, hipStream_t st) {
 }
 
 // Cells of a launch in batches: all at once where the ratios live in LDS, else as many as the scratch bound holds.
-// Asynchronous: `scratch` belongs to the caller, who synchronises before it goes.
 static hipError_t loo_cells(LooArgs a, int n_cells, size_t scratch_bytes, DeviceBuffer<double>& scratch, hipStream_t st) {
-  hipError_t e = hipSuccess;
-  int batch = n_cells;
-  if (a.n > kPsisLdsDraws) {
-    batch = column_batch(scratch_bytes, a.n, n_cells);
-    if (!scratch.p) e = scratch.alloc((size_t)a.n * batch);
-    a.scratch = scratch.p;
-  }
-  for (int c0 = 0; e == hipSuccess && c0 < n_cells; c0 += batch) {
-    a.cell0 = c0;
-    e = launch_loo_kernel(a, n_cells - c0 < batch ? n_cells - c0 : batch, st);
-  }
-  return e;
+  return loo_cell_batches(n_cells, a.n > kPsisLdsDraws ? a.n : 0, scratch_bytes, scratch, [&](int c0, int nc, double* scr) {
+    a.cell0 = c0; a.scratch = scr;
+    return launch_loo_kernel(a, nc, st);
+  });
 }
 
 hipError_t loo_fit_cells(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,

@@ -1,0 +1,218 @@
+// ppcx_loo_predict.hip -- gfx950 kernel of the leave-one-out predictive interval and LOO-PIT per observed cell
+// (ppcx_fit_loo_predict, include/ppcx.h; the statistic: ppcx_loo_predict.h).
+//
+//   ppcx_loo_predict_kernel  one workgroup of kBlockThreads per cell. The cell's n ratios r = -ll from the transposed table T
+//                            (ppcx_loo_table_kernel) and its tail as in ppcx_loo_kernel (ppcx_loo_dev.h); then per draw its
+//                            predictive count x_i (nb2_log_rng on the address of ppcx_fit_ppc) and its weight w_i: the tail
+//                            position of a draw by binary search in the sorted keys of the M + 1 largest ratios, and for keys
+//                            that occur more than once a scan of the earlier draws (the tie rule of ppcx_loo_predict.h). Sums of
+//                            weights give the mean and the two ends of the LOO-PIT; each quantile is a bisection on the integer
+//                            value with one fixed-order sum of weights per step.
+//                            Per draw 20 bytes: r (8), w (8), x (4) -- in LDS up to kPsisLdsDraws draws (80 KB, beside the two
+//                            selection arrays), in the workgroup's slice of a bounded global scratch beyond.
+// Every reduction runs in a fixed order and a cell reads nothing of another cell: its fields are the same bits whatever else is
+// requested and however the work is batched. Neither the log-likelihood nor the counts matrix is materialised.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include "ppcx_loo_dev.h"
+#include "ppcx_loo_predict.h"
+
+namespace ppcx {
+
+struct LooPredictArgs {
+  LooArgs l;                       // the table or the columns, y, r_eff, n, the cells, sel_pad (l.out and l.scratch unused)
+  const int* genes = nullptr;      // [table's genes] their ids in the model: the Philox address is genes[gi] S + s
+  const int* xcols = nullptr;      // [cells][n] predictive counts of the given columns (testing build)
+  const int* ycols = nullptr;      // [cells] observed counts of the given columns
+  double tc = 1.0, p_lo = 0.025, p_hi = 0.975;
+  uint32_t k0 = 0;
+  double* scratch = nullptr; long slice = 0;   // [launch's cells][slice] doubles: the long path's r, w, x
+  double* out = nullptr;           // [cells][kLooPredictFields]
+};
+
+// doubles of scratch per cell on the long path: r [n], w [n], x [n] as integers
+static long loo_predict_slice(long n) { return 2 * n + (n + 1) / 2; }
+
+// sum over the cell's draws i of f(i); every thread gets it (fixed order)
+template <class F>
+__device__ __forceinline__ double draws_sum(long n, double* red, F f) {
+  double s = 0.0;
+  for (long i = threadIdx.x; i < n; i += kBlockThreads) s += f(i);
+  return block_sum(s, red);
+}
+template <class F>
+__device__ __forceinline__ double draws_max(long n, double* red, F f) {
+  double m = -INFINITY;
+  for (long i = threadIdx.x; i < n; i += kBlockThreads) m = fmax(m, f(i));
+  return block_max(m, red);
+}
+
+template <bool LDS, bool COLS>
+__global__ __launch_bounds__(kBlockThreads) void ppcx_loo_predict_kernel(LooPredictArgs p) {
+#pragma clang fp contract(off)
+  extern __shared__ uint64_t lds_u[];
+  __shared__ PsisShared sh;
+  const LooArgs& a = p.l;
+  const int tid = threadIdx.x;
+  const long n = a.n;
+  uint64_t* K = lds_u;                                   // [sel_pad] keys of the M + 1 largest ratios
+  double* X = reinterpret_cast<double*>(lds_u + a.sel_pad);            // [sel_pad] the tail's exceedances
+  double* V = LDS ? X + a.sel_pad : p.scratch + (long)blockIdx.x * p.slice;   // [n] the ratios r = -ll
+  double* W = V + n;                                     // [n] log weights, then weights
+  int* XI = reinterpret_cast<int*>(W + n);               // [n] predictive counts
+  const int cell = a.cell0 + blockIdx.x;
+  int y; bool excluded;
+  if (COLS) { excluded = a.excl && a.excl[cell] != 0; y = p.ycols[cell]; }
+  else { const int ye = a.y[cell]; excluded = ye < 0; y = excluded ? -ye - 1 : ye; }
+  const int gi = COLS ? 0 : cell / a.S, s = COLS ? 0 : cell - gi * a.S;
+  double* o = p.out + (long)cell * kLooPredictFields;
+  auto all_nan = [&]() { if (tid == 0) for (int f = 0; f < kLooPredictFields; ++f) o[f] = NAN; };
+  // ---- the ratios
+  long N; double rmax, lmax;
+  if (loo_cell_ratios<COLS>(a, cell, gi, s, y, excluded, V, sh, &N, &rmax, &lmax)) { all_nan(); return; }
+  // ---- the predictive count of every draw
+  bool inval = false;
+  if (COLS) {
+    for (long i = tid; i < n; i += kBlockThreads) { const int v = p.xcols[(long)cell * n + i]; XI[i] = v; inval = inval || v == kLooPredictInvalid; }
+  } else {
+    const double* Tg = a.T + (long)gi * (a.C + 1) * n;
+    const uint32_t addr = (uint32_t)(p.genes[gi] * a.S + s);
+    for (long i = tid; i < n; i += kBlockThreads) {
+      const int v = nb2_log_rng(loo_cell_eta(a, Tg, s, i), loo_predict_phi(Tg[(long)a.C * n + i], p.tc), p.k0, addr, (uint32_t)i);
+      XI[i] = v; inval = inval || v == kLooPredictInvalid;
+    }
+  }
+  if (block_any(inval) || (!excluded && N == 0)) { all_nan(); return; }   // block_any: XI is visible to every thread
+  const double pr[2] = {p.p_lo, p.p_hi};
+  double q[2];
+  if (excluded) {
+    // ---- already held out: uniform weights over all n draws, the type-7 quantiles of the posterior-predictive kernels
+    const double sum = draws_sum(n, sh.red, [&](long i) { return (double)XI[i]; });
+    const int vmax = (int)draws_max(n, sh.red, [&](long i) { return (double)XI[i]; });
+    auto count_le = [&](int v) { return (long)draws_sum(n, sh.red, [&](long i) { return XI[i] <= v ? 1.0 : 0.0; }); };
+    for (int k = 0; k < 2; ++k) {
+      double h; long r;
+      loo_predict_type7_rank(n, pr[k], &h, &r);
+      int lo = 0, hi = vmax;                              // order statistic r: the smallest v with #{x <= v} >= r + 1
+      while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (count_le(mid) >= r + 1) hi = mid; else lo = mid + 1; }
+      int nxt = lo;                                       // order statistic r + 1: lo again, or the smallest draw above it
+      if (r + 1 < n && count_le(lo) < r + 2) nxt = (int)-draws_max(n, sh.red, [&](long i) { return XI[i] > lo ? -(double)XI[i] : -INFINITY; });
+      q[k] = loo_predict_type7(h, r, n, (double)lo, (double)nxt);
+    }
+    const double lt = draws_sum(n, sh.red, [&](long i) { return XI[i] < y ? 1.0 : 0.0; });
+    const double le = draws_sum(n, sh.red, [&](long i) { return XI[i] <= y ? 1.0 : 0.0; });
+    if (tid == 0) { o[0] = sum / (double)n; o[1] = q[0]; o[2] = q[1]; o[3] = lt / (double)n; o[4] = le / (double)n; o[5] = NAN; }
+    return;
+  }
+  // ---- the tail, and the log weight of every draw
+  const double mx = rmax;
+  const int M = psis_tail_len(N, a.r_eff ? a.r_eff[cell] : 1.0);
+  const LooTail lt = loo_cell_tail(V, n, N, M, K, X, a.sel_pad, sh);
+  const PsisTail& tl = lt.tl;
+  double mxw = -INFINITY;
+  for (long i = tid; i < n; i += kBlockThreads) {
+    const double r = V[i];
+    int j = 0;
+    if (lt.smooth && r != -INFINITY) {
+      const uint64_t k = psis_key(r);
+      if (k >= tl.key) {
+        // the earlier draws with this key count only where the key occurs more than once in the tail (ties are rare)
+        const bool scan = k == tl.key ? tl.want > 1 : loo_predict_tied(K, M, loo_predict_lower_bound(K, M, k));
+        long before = 0;
+        if (scan) for (long i2 = 0; i2 < i; ++i2) before += psis_key(V[i2]) == k ? 1 : 0;
+        j = loo_predict_tail_pos(k, K, M, tl.key, tl.want, lt.n_eq, before);
+      }
+    }
+    const double lw = loo_predict_lw(r, mx, j, M, lt.khat, lt.sigma, tl.ec);
+    W[i] = lw; mxw = fmax(mxw, lw);
+  }
+  mxw = block_max(mxw, sh.red);
+  double sw = 0.0;
+  for (long i = tid; i < n; i += kBlockThreads) { const double e = exp(W[i] - mxw); W[i] = e; sw += e; }
+  sw = block_sum(sw, sh.red);
+  for (long i = tid; i < n; i += kBlockThreads) W[i] = W[i] / sw;
+  __syncthreads();
+  // ---- sums of weights: the mean, the LOO-PIT, and F for the quantiles (a draw that takes no part has weight 0)
+  const double mean = draws_sum(n, sh.red, [&](long i) { return W[i] * (double)XI[i]; });
+  const double plt = draws_sum(n, sh.red, [&](long i) { return XI[i] < y ? W[i] : 0.0; });
+  const double ple = draws_sum(n, sh.red, [&](long i) { return XI[i] <= y ? W[i] : 0.0; });
+  auto F = [&](int v) { return draws_sum(n, sh.red, [&](long i) { return XI[i] <= v ? W[i] : 0.0; }); };
+  const int vmax = (int)draws_max(n, sh.red, [&](long i) { return V[i] != -INFINITY ? (double)XI[i] : -INFINITY; });
+  const int vmin = (int)-draws_max(n, sh.red, [&](long i) { return V[i] != -INFINITY ? -(double)XI[i] : -INFINITY; });
+  for (int k = 0; k < 2; ++k) {
+    int lo = vmin, hi = vmax;                              // v*: the smallest drawn value with F(v*) >= p, else the largest
+    while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (F(mid) >= pr[k]) hi = mid; else lo = mid + 1; }
+    const double vm = draws_max(n, sh.red, [&](long i) { return V[i] != -INFINITY && XI[i] < lo ? (double)XI[i] : -INFINITY; });
+    q[k] = vm == -INFINITY ? (double)lo : loo_predict_interp(vm, (double)lo, F((int)vm), F(lo), pr[k]);
+  }
+  if (tid == 0) { o[0] = mean; o[1] = q[0]; o[2] = q[1]; o[3] = plt; o[4] = ple; o[5] = lt.khat; }
+}
+
+// ---- launch helpers (host)
+static hipError_t launch_loo_predict_kernel(const LooPredictArgs& p, int n_blocks, hipStream_t st) {
+  const bool lds = p.l.n <= kPsisLdsDraws, cols = p.l.cols != nullptr;
+  const size_t bytes = sizeof(double) * (2 * (size_t)p.l.sel_pad + (lds ? (size_t)loo_predict_slice(p.l.n) : 0));
+  void (*const kernel)(LooPredictArgs) = lds ? (cols ? ppcx_loo_predict_kernel<true, true> : ppcx_loo_predict_kernel<true, false>)
+                                             : (cols ? ppcx_loo_predict_kernel<false, true> : ppcx_loo_predict_kernel<false, false>);
+  return launch_dynamic_lds(kernel, n_blocks, kBlockThreads, bytes, st, p);
+}
+static hipError_t loo_predict_cells(LooPredictArgs p, int n_cells, size_t scratch_bytes, DeviceBuffer<double>& scratch, hipStream_t st) {
+  p.slice = p.l.n > kPsisLdsDraws ? loo_predict_slice(p.l.n) : 0;
+  return loo_cell_batches(n_cells, p.slice, scratch_bytes, scratch, [&](int c0, int nc, double* scr) {
+    p.l.cell0 = c0; p.scratch = scr;
+    return launch_loo_predict_kernel(p, nc, st);
+  });
+}
+
+hipError_t loo_predict_fit_cells(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
+                                 const int* genes, const int* yenc, const double* r_eff, double r_eff_min, double tc, double p_lo,
+                                 double p_hi, uint32_t k0, double* out, size_t scratch_bytes, hipStream_t st) {
+  const int S = d.S, ncol = d.C + 1;
+  const size_t ncells = (size_t)n_genes * S;
+  const int gb = column_batch(scratch_bytes, (long)ncol * n, n_genes);
+  DeviceBuffer<int> d_genes, d_y; DeviceBuffer<double> d_T, d_reff, d_out, d_scr;
+  hipError_t e = d_genes.upload(genes, (size_t)n_genes, st);
+  if (e == hipSuccess) e = d_y.upload(yenc, ncells, st);
+  if (e == hipSuccess && r_eff) e = d_reff.upload(r_eff, ncells, st);
+  if (e == hipSuccess) e = d_out.alloc(kLooPredictFields * ncells);
+  if (e == hipSuccess) e = d_T.alloc((size_t)ncol * (size_t)n * gb);
+  for (int g0 = 0; e == hipSuccess && g0 < n_genes; g0 += gb) {
+    const int ng = n_genes - g0 < gb ? n_genes - g0 : gb;
+    e = launch_loo_table_kernel(draws, n, d, d_genes.p + g0, ng, d_T.p, st);
+    if (e != hipSuccess) break;
+    LooPredictArgs p;
+    LooArgs& a = p.l;
+    a.T = d_T.p; a.y = d_y.p + (size_t)g0 * S; a.expo = expo; a.X = X; a.S = S; a.C = d.C; a.n = n;
+    a.r_eff = d_reff.p ? d_reff.p + (size_t)g0 * S : nullptr;
+    a.n_cells = ng * S; a.sel_pad = loo_sel_pad(n, r_eff_min);
+    p.genes = d_genes.p + g0; p.tc = tc; p.p_lo = p_lo; p.p_hi = p_hi; p.k0 = k0;
+    p.out = d_out.p + (size_t)g0 * S * kLooPredictFields;
+    e = loo_predict_cells(p, ng * S, scratch_bytes, d_scr, st);
+  }
+  if (e == hipSuccess) e = d_out.download(out, kLooPredictFields * ncells, st);
+  return finish(e, st);
+}
+
+hipError_t loo_predict_columns(const double* cols, const int* x, long n, int n_cols, const int* y, const int* excl,
+                               const double* r_eff, double r_eff_min, double p_lo, double p_hi, double* out, size_t scratch_bytes,
+                               hipStream_t st) {
+  DeviceBuffer<double> d_cols, d_reff, d_out, d_scr; DeviceBuffer<int> d_x, d_y, d_excl;
+  hipError_t e = d_cols.upload(cols, (size_t)n * n_cols, st);
+  if (e == hipSuccess) e = d_x.upload(x, (size_t)n * n_cols, st);
+  if (e == hipSuccess) e = d_y.upload(y, (size_t)n_cols, st);
+  if (e == hipSuccess && excl) e = d_excl.upload(excl, (size_t)n_cols, st);
+  if (e == hipSuccess && r_eff) e = d_reff.upload(r_eff, (size_t)n_cols, st);
+  if (e == hipSuccess) e = d_out.alloc(kLooPredictFields * (size_t)n_cols);
+  if (e == hipSuccess) {
+    LooPredictArgs p;
+    LooArgs& a = p.l;
+    a.cols = d_cols.p; a.excl = d_excl.p; a.r_eff = d_reff.p; a.n = n; a.n_cells = n_cols;
+    a.sel_pad = loo_sel_pad(n, r_eff_min);
+    p.xcols = d_x.p; p.ycols = d_y.p; p.p_lo = p_lo; p.p_hi = p_hi; p.out = d_out.p;
+    e = loo_predict_cells(p, n_cols, scratch_bytes, d_scr, st);
+  }
+  if (e == hipSuccess) e = d_out.download(out, kLooPredictFields * (size_t)n_cols, st);
+  return finish(e, st);
+}
+
+}  // namespace ppcx

@@ -64,6 +64,7 @@ class InferenceResult:
     convergence: dict | None = None   # check_convergence: Fit.summary of alpha_sub_1 (and lp__ where the fit holds it)
     approximation: dict | None = None  # check_approximation: Fit.psis of alpha_sub_1 and the overall k-hat (column -1, last)
     loo: dict | None = None            # check_loo: Fit.loo of the checked genes' cells ([K, S] arrays and loo's estimates)
+    loo_intervals: dict | None = None  # check_loo_intervals: Fit.loo_predict of the checked genes' cells ([K, S] arrays)
 
     def to_frame(self):
         import pandas as pd
@@ -193,7 +194,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                  launch=None,
                  check_convergence=False,
                  check_approximation=False,
-                 check_loo=False):
+                 check_loo=False,
+                 check_loo_intervals=False):
     """One inference pass (discovery or test) of ppcseq on the GPU.
 
     counts            G x S integer matrix, genes ordered with the `how_many_to_check` checked genes first
@@ -220,6 +222,11 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                       estimates over the cells not excluded) on the device (Fit.loo), kept as `res.loo` and reported as
                       RuntimeWarning when a k-hat is too high (loo_warnings). An excluded cell holds its exact held-out
                       density. devices=[...]: over the pooled chains. Not for an ADVI pass.
+    check_loo_intervals  the leave-one-out predictive interval and LOO-PIT of every checked cell from this pass's own fit
+                      (loo::E_loo / bayesplot::ppc_loo_intervals, ppc_loo_pit) on the device (Fit.loo_predict), at the pass's
+                      interval probabilities, seed and truncation compensation, kept as `res.loo_intervals`. It raises no
+                      warning (the k-hat warnings are check_loo's) and changes no flag. devices=[...]: over the pooled chains.
+                      Not for an ADVI pass.
     Returns an InferenceResult.
     """
     counts = np.asarray(counts)
@@ -249,6 +256,9 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                          "diagnostic judges the variational approximation")
     if check_loo and approximate_posterior_inference:
         raise ValueError("check_loo needs a NUTS pass: PSIS-LOO of an ADVI fit (loo_approximate_posterior) is not available")
+    if check_loo_intervals and approximate_posterior_inference:
+        raise ValueError("check_loo_intervals needs a NUTS pass: PSIS-LOO of an ADVI fit (loo_approximate_posterior) is not "
+                         "available")
     if devices is not None and len(devices) > 1 and (save_generated_quantities or pass_fit or model is not None or approximate_posterior_inference):
         raise ValueError("devices=[...] splits the chains of a NUTS fit over several devices and pools their draws: it cannot "
                          "be combined with save_generated_quantities, pass_fit, a caller's model or approximate_posterior_inference")
@@ -256,7 +266,7 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
         return _do_inference_devices(counts, X, exposure_rate, K, list(devices), chains, n_iter, warmup, excl,
                                      lambda_mu_mu, approximate_posterior_analysis, adj_prob_theshold,
                                      how_many_posterior_draws, truncation_compensation, seed, launch, check_convergence,
-                                     check_loo)
+                                     check_loo, check_loo_intervals)
     if devices is not None and len(devices) >= 1 and model is None:
         device = devices[0]
     own_model = model is None
@@ -306,6 +316,9 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
             if check_loo:
                 res.loo = fit.loo(np.arange(K))
                 _warn_loo(res.loo, fit.chains * fit.n_keep)
+            if check_loo_intervals:
+                res.loo_intervals = fit.loo_predict(np.arange(K), p_lo=p, p_hi=1 - p, seed=seed,
+                                                    truncation_compensation=truncation_compensation)
         res.counts_rng = rng
         if pass_fit:
             res.fit = fit
@@ -358,18 +371,19 @@ def checked_columns(G, C, K):
 
 def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, approximate_posterior_analysis,
                    adj_prob_theshold, how_many_posterior_draws, truncation_compensation, seed, device=0, convergence=False,
-                   loo=False, excl=None):
+                   loo=False, excl=None, loo_intervals=False):
     """Credible intervals, slopes and flags from the pooled draws of all chains (rstan::summary over merged chains,
     R/utilities.R:685-703): `draws_checked` is [chains, n_keep, len(checked_columns)] in global chain order. The
     posterior-predictive kernel runs on a model that holds the K checked genes only -- cell ids g*S+s and draw indices are
     those of the full model, so the result is what a single fit of all the chains gives, bit for bit. convergence: also the
     summary of alpha_sub_1 over the pooled chains (res.convergence; Fit.summary). loo: also PSIS-LOO of the checked cells over
     the pooled chains (res.loo; Fit.loo); the small model then carries the checked genes' cells of `excl` (0-based cell ids of
-    the full model), so that the cells excluded from the fit are held out."""
+    the full model), so that the cells excluded from the fit are held out. loo_intervals: also their leave-one-out predictive
+    intervals (res.loo_intervals; Fit.loo_predict), likewise."""
     counts = np.asarray(counts)
     X = np.asarray(X, dtype=np.float64).reshape(counts.shape[1], -1)
     small_excl = None
-    if loo and excl is not None:
+    if (loo or loo_intervals) and excl is not None:
         e = np.asarray(excl, dtype=np.int64).ravel()
         small_excl = e[e < K * counts.shape[1]].astype(np.int32)
     small = _lib.Model(counts[:K], X, exposure_rate, K, lambda_mu_mu=lambda_mu_mu, device=device, excl=small_excl)
@@ -384,6 +398,10 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
             slope = fit.columns(np.arange(3 + K, 3 + 2 * K)).reshape(-1, K).mean(axis=0) if K else np.zeros(0)
             conv = fit.summary(np.arange(3 + K, 3 + 2 * K), lp=False) if convergence else None
             loo_res = fit.loo(np.arange(K)) if loo and K else None
+            loo_int = None
+            if loo_intervals and K:
+                loo_int = fit.loo_predict(np.arange(K), p_lo=p, p_hi=1 - p, seed=seed,
+                                          truncation_compensation=truncation_compensation)
         finally:
             fit.close()
     finally:
@@ -392,12 +410,14 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
     res.total_draws = counts.shape[1] * K * int(how_many_posterior_draws)
     res.convergence = conv
     res.loo = loo_res
+    res.loo_intervals = loo_int
     return res
 
 
 def _do_inference_devices(counts, X, exposure_rate, K, devices, chains, n_iter, warmup, excl, lambda_mu_mu,
                           approximate_posterior_analysis, adj_prob_theshold, how_many_posterior_draws,
-                          truncation_compensation, seed, launch=None, check_convergence=False, check_loo=False):
+                          truncation_compensation, seed, launch=None, check_convergence=False, check_loo=False,
+                          check_loo_intervals=False):
     """Chains split over several devices of this process (one host thread per device; the C ABI allows different handles
     on different threads), pooled summary on the first device."""
     import threading
@@ -438,7 +458,8 @@ def _do_inference_devices(counts, X, exposure_rate, K, devices, chains, n_iter, 
     res = pooled_summary(counts, X, exposure_rate, K, pooled, lambda_mu_mu=lambda_mu_mu,
                          approximate_posterior_analysis=approximate_posterior_analysis, adj_prob_theshold=adj_prob_theshold,
                          how_many_posterior_draws=how_many_posterior_draws, truncation_compensation=truncation_compensation,
-                         seed=seed, device=devices[0], convergence=check_convergence, loo=check_loo, excl=excl)
+                         seed=seed, device=devices[0], convergence=check_convergence, loo=check_loo, excl=excl,
+                         loo_intervals=check_loo_intervals)
     res.chains, res.iter = chains, n_iter
     if check_convergence:
         _warn_convergence(res.convergence, chains)

@@ -117,7 +117,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                       draws_after_tail=10, save_generated_quantities=False, additional_parameters_to_save=(),
                       cores=None, pass_fit=False, do_check_only_on_detrimental=None, tol_rel_obj=0.01,
                       just_discovery=False, seed=None, adj_prob_theshold_2=None, device=0, devices=None, launch=None, _pass=None,
-                      check_convergence=False, check_approximation=False, check_loo=False):
+                      check_convergence=False, check_approximation=False, check_loo=False,
+                      check_loo_intervals=False):
     """Mirror of ppcseq::identify_outliers (R/methods.R:74-367): same arguments, same defaults.
 
     data is a tidy pandas DataFrame (one row per transcript x sample); column arguments are strings. As in the
@@ -142,6 +143,10 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
     `check_loo` = True (NUTS only): both passes compute PSIS-LOO of the checked cells, as rstan::loo(fit) would
     (inference.do_inference; pass 2 holds its excluded cells out); the results (Fit.loo: [K, S] elpd_loo, p_loo, looic, khat and
     loo's estimates) go to out.attrs["loo_discovery"] and ["loo_test"], loo's k-hat warning is a RuntimeWarning.
+    `check_loo_intervals` = True (NUTS only): both passes also keep the leave-one-out predictive interval and LOO-PIT of the
+    checked cells from their own fit (Fit.loo_predict: [K, S] mean, lower, upper, pit_lt, pit_le, khat, y, outside, excluded) at
+    the pass's interval probabilities, seed and truncation compensation, in out.attrs["loo_intervals_discovery"] and
+    ["loo_intervals_test"]. They are reported only: the cells flagged stay those of the reference's rule, no warning is raised.
     """
     import os
     import pandas as pd
@@ -170,6 +175,11 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
         raise ValueError("check_loo needs NUTS (approximate_posterior_inference = False): PSIS-LOO of an ADVI fit is not available")
     if check_loo and _pass is not None:
         raise ValueError("check_loo is not available for passes over several ranks")
+    if check_loo_intervals and approximate_posterior_inference:
+        raise ValueError("check_loo_intervals needs NUTS (approximate_posterior_inference = False): PSIS-LOO of an ADVI fit is "
+                         "not available")
+    if check_loo_intervals and _pass is not None:
+        raise ValueError("check_loo_intervals is not available for passes over several ranks")
     if check_convergence and _pass is not None:
         raise ValueError("check_convergence is not available for passes over several ranks")
     if approximate_posterior_inference and save_generated_quantities:
@@ -255,6 +265,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
             where.update(check_approximation=True)
         if check_loo:
             where.update(check_loo=True)
+        if check_loo_intervals:
+            where.update(check_loo_intervals=True)
     try:
         # ---- pass 1: discovery (R/methods.R:268-286); always the full posterior analysis
         res1 = run_pass(counts, X, exposure_rate, K,
@@ -269,6 +281,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                 out1.attrs["approximation_discovery"] = res1.approximation
             if check_loo:
                 out1.attrs["loo_discovery"] = res1.loo
+            if check_loo_intervals:
+                out1.attrs["loo_intervals_discovery"] = res1.loo_intervals
             return out1
         # ---- cells to exclude (R/methods.R:292-300)
         flag = res1.deleterious_outliers if (do_check_only_on_detrimental and res1.deleterious_outliers is not None) else ~res1.ppc
@@ -316,6 +330,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
         out.attrs["approximation_discovery"], out.attrs["approximation_test"] = res1.approximation, res2.approximation
     if check_loo:
         out.attrs["loo_discovery"], out.attrs["loo_test"] = res1.loo, res2.loo
+    if check_loo_intervals:
+        out.attrs["loo_intervals_discovery"], out.attrs["loo_intervals_test"] = res1.loo_intervals, res2.loo_intervals
     if pass_fit:                                                           # R/methods.R:353-357: attrs "fit 1" / "fit 2"
         out.attrs["fit 1"], out.attrs["fit 2"] = res1.fit, res2.fit        # device-resident; the library keeps the model
     return out                                                             # alive until both fits are closed
