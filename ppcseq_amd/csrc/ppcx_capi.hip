@@ -26,11 +26,12 @@ using namespace ppcx;
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) { g_err = msg; return code; }
+// a HIP error as a status: `what` is the failed expression (HIPCHK) or the name of the step
+static int hip_fail(hipError_t e, const char* what) { return fail(PPCX_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
 #define HIPCHK(expr)                                                                       \
   do {                                                                                     \
     hipError_t e_ = (expr);                                                                \
-    if (e_ != hipSuccess)                                                                  \
-      return fail(PPCX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_));       \
+    if (e_ != hipSuccess) return hip_fail(e_, #expr);                                      \
   } while (0)
 
 // Test hooks exist only in the testing build (-DPPCX_TESTING: tests/libppcx_testing.so, built by __graft_entry__.build()
@@ -93,9 +94,10 @@ struct ppcx_fit {
   ppcx_model* m;
   NutsConfig cfg;
   int chains, n_keep, iter;
-  double* d_draws = nullptr;                   // [chains][n_keep][D]
-  double *d_lp = nullptr, *d_stepsize = nullptr, *d_accept = nullptr;
-  int *d_treedepth = nullptr, *d_nleap = nullptr, *d_div = nullptr;
+  // the fit owns its device buffers: they go with it (ppcx_fit_free, on the model's device); .p stays null where a fit has none
+  DeviceBuffer<double> d_draws;                // [chains][n_keep][D] (none without kept draws)
+  DeviceBuffer<double> d_lp, d_stepsize, d_accept;   // lp [chains][n_keep] (none without kept draws, none over draws made elsewhere)
+  DeviceBuffer<int> d_treedepth, d_nleap, d_div;     // the diagnostics [chains][iter] each
   double seconds = 0; long long grad_evals = 0;
   double kA_ms_mean = 0; long long kA_samples = 0; double kA_chain_launches_mean = 0;
   double kC_ms_mean = 0, kU_ms_mean = 0; long long launch_triples = 0;
@@ -104,8 +106,8 @@ struct ppcx_fit {
   long long xchg_ticks = 0, xchg_count = 0;    // direct exchange: 100 MHz ticks the chains' state machines waited for peers, exchanges
   std::vector<double> inv_metric;              // [chains][D] diagonal of the adapted inverse metric (host; ppcx_fit_get_inv_metric)
   bool advi = false;                           // draws of an ADVI approximation (independent: ppcx_fit_summary refuses them)
-  double *d_mu = nullptr, *d_omega = nullptr;  // ADVI: the fitted approximation [D] each (ppcx_fit_get_approximation)
-  double *d_log_p = nullptr, *d_log_g = nullptr, *d_r = nullptr;   // ADVI: log densities and log ratios at the kept draws
+  DeviceBuffer<double> d_mu, d_omega;          // ADVI: the fitted approximation [D] each (ppcx_fit_get_approximation)
+  DeviceBuffer<double> d_log_p, d_log_g, d_r;  // ADVI: log densities and log ratios at the kept draws
                                                // [n_keep] each, made by the first ppcx_fit_get_log_ratios / ppcx_fit_psis
 };
 
@@ -1166,10 +1168,7 @@ static void fit_attach(ppcx_fit* f, ppcx_model* m) { f->m = m; m->live_fits++; }
 extern "C" void ppcx_fit_free(ppcx_fit* f) {
   if (!f) return;
   ppcx_model* m = f->m;
-  (void)hipSetDevice(m->device);
-  (void)hipFree(f->d_draws); (void)hipFree(f->d_lp); (void)hipFree(f->d_stepsize); (void)hipFree(f->d_accept);
-  (void)hipFree(f->d_treedepth); (void)hipFree(f->d_nleap); (void)hipFree(f->d_div);
-  (void)hipFree(f->d_mu); (void)hipFree(f->d_omega); (void)hipFree(f->d_log_p); (void)hipFree(f->d_log_g); (void)hipFree(f->d_r);
+  (void)hipSetDevice(m->device);                 // the fit's buffers are freed on the current device
   delete f;
   if (--m->live_fits == 0 && m->destroy_requested) ppcx_model_destroy(m);
 }
@@ -1268,6 +1267,72 @@ static void xchg_fill(const ppcx_xchg* x, XchgArgs* a) {
   }
 }
 
+// ---- what the NUTS entry points share (fit_nuts_impl: ppcx_fit_nuts, ppcx_fit_nuts_xchg; fit_sharded: ppcx_fit_nuts_shards,
+// ---- ppcx_fit_nuts_comm) -------------------------------------------------------------------------------------------------
+static int nuts_config_check(const ppcx_nuts_config* cfg) {
+  if (cfg->chains < 1 || cfg->chains > 1024 || cfg->iter < 1 || cfg->warmup < 0 || cfg->warmup > cfg->iter)
+    return fail(PPCX_ERR_ARG, "need 1<=chains<=1024, iter>=1, 0<=warmup<=iter");
+  if (cfg->max_treedepth < 1 || cfg->max_treedepth > kMaxDepth) return fail(PPCX_ERR_LIMIT, "max_treedepth must be in 1..10");
+  return PPCX_OK;
+}
+static NutsConfig nuts_config(const ppcx_nuts_config* cfg) {
+  NutsConfig nc;
+  nc.chains = cfg->chains; nc.iter = cfg->iter; nc.warmup = cfg->warmup; nc.seed = cfg->seed; nc.adapt_delta = cfg->adapt_delta;
+  nc.max_treedepth = cfg->max_treedepth; nc.init_radius = cfg->init_radius; nc.stepsize0 = cfg->stepsize0;
+  nc.init_buffer = cfg->init_buffer; nc.term_buffer = cfg->term_buffer; nc.window = cfg->window;
+  nc.chain_id_offset = cfg->chain_id_offset;
+  return nc;
+}
+// A fit of `m` for the run `nc`, its buffers zero-filled on `st`, which is idle again on return: the chain groups of a fit run on
+// streams of their own that nothing else orders against this one. A failure leaves nothing behind.
+static int fit_create(ppcx_model* m, const NutsConfig& nc, hipStream_t st, ppcx_fit** out) {
+  ppcx_fit* f = new ppcx_fit();
+  fit_attach(f, m); f->chains = nc.chains; f->n_keep = nc.iter - nc.warmup; f->iter = nc.iter; f->cfg = nc;
+  const size_t ni = (size_t)nc.chains * nc.iter, nk = (size_t)nc.chains * f->n_keep;
+  hipError_t e = hipSuccess;
+  if (nk > 0) e = f->d_draws.alloc_zeroed(nk * m->d.D, st);
+  if (nk > 0 && e == hipSuccess) e = f->d_lp.alloc_zeroed(nk, st);
+  if (e == hipSuccess) e = f->d_stepsize.alloc_zeroed(ni, st);
+  if (e == hipSuccess) e = f->d_accept.alloc_zeroed(ni, st);
+  if (e == hipSuccess) e = f->d_treedepth.alloc_zeroed(ni, st);
+  if (e == hipSuccess) e = f->d_nleap.alloc_zeroed(ni, st);
+  if (e == hipSuccess) e = f->d_div.alloc_zeroed(ni, st);
+  if ((e = finish(e, st)) != hipSuccess) { ppcx_fit_free(f); return hip_fail(e, "the fit's buffers"); }
+  *out = f;
+  return PPCX_OK;
+}
+// where a run of the fit's chains from c0 on writes
+static RunIO fit_io(const ppcx_fit* f, int c0) {
+  const size_t k0 = (size_t)c0 * f->n_keep, i0 = (size_t)c0 * f->iter;
+  const long D = f->m->d.D;
+  RunIO io;
+  io.draws = f->d_draws.p ? f->d_draws.p + k0 * D : nullptr; io.draws_stride = (long)f->n_keep * D;
+  io.n_keep = f->n_keep; io.iter = f->iter;
+  io.lp = f->d_lp.p ? f->d_lp.p + k0 : nullptr;
+  io.stepsize = f->d_stepsize.p + i0; io.accept = f->d_accept.p + i0;
+  io.treedepth = f->d_treedepth.p + i0; io.nleap = f->d_nleap.p + i0; io.div = f->d_div.p + i0;
+  return io;
+}
+// the initial states of the chains c0 .. c0 + n - 1 of the run `nc` into w, a Work of n chains
+static int upload_initial_states(Work& w, const NutsConfig& nc, int c0, int n) {
+  std::vector<ChainState> states(n);
+  NutsConfig ncg = nc; ncg.chain_id_offset = nc.chain_id_offset + c0;
+  for (int c = 0; c < n; ++c) state_init(states[c], ncg, c, 0);
+  HIPCHK(hipMemcpyAsync(w.states[0], states.data(), sizeof(ChainState) * n, hipMemcpyHostToDevice, w.stream));
+  HIPCHK(hipStreamSynchronize(w.stream));       // `states` is a host temporary
+  return PPCX_OK;
+}
+static void fit_record(ppcx_fit* f, const PumpStats& ps, double seconds, long long leapfrogs) {
+  f->seconds = seconds;
+  f->grad_evals = leapfrogs;
+  f->kA_samples = ps.kA_samples;
+  f->kA_ms_mean = ps.kA_samples ? ps.kA_ms_sum / (double)ps.kA_samples : 0.0;
+  f->kA_chain_launches_mean = ps.kA_samples ? ps.chain_launches / (double)ps.kA_samples : 0.0;
+  f->kC_ms_mean = ps.kA_samples ? ps.kC_ms_sum / (double)ps.kA_samples : 0.0;
+  f->kU_ms_mean = ps.kA_samples ? ps.kU_ms_sum / (double)ps.kA_samples : 0.0;
+  f->launch_triples = ps.pairs;
+}
+
 static int fit_nuts_impl(ppcx_model* m, const ppcx_nuts_config* cfg, ppcx_xchg* xg, ppcx_fit** out);
 extern "C" int ppcx_fit_nuts(ppcx_model* m, const ppcx_nuts_config* cfg, ppcx_fit** out) { return fit_nuts_impl(m, cfg, nullptr, out); }
 // One gene shard per rank, the ranks' sums added by the state machines themselves (direct exchange): the pipelined round of
@@ -1279,11 +1344,10 @@ extern "C" int ppcx_fit_nuts_xchg(ppcx_model* shard, const ppcx_nuts_config* cfg
 static int fit_nuts_impl(ppcx_model* m, const ppcx_nuts_config* cfg, ppcx_xchg* xg, ppcx_fit** out) {
   if (!m || !cfg || !out) return fail(PPCX_ERR_ARG, "NULL argument");
   *out = nullptr;
-  if (cfg->chains < 1 || cfg->chains > 1024 || cfg->iter < 1 || cfg->warmup < 0 || cfg->warmup > cfg->iter)
-    return fail(PPCX_ERR_ARG, "need 1<=chains<=1024, iter>=1, 0<=warmup<=iter");
-  if (cfg->max_treedepth < 1 || cfg->max_treedepth > kMaxDepth) return fail(PPCX_ERR_LIMIT, "max_treedepth must be in 1..10");
+  int rc = nuts_config_check(cfg);
+  if (rc != PPCX_OK) return rc;
   HIPCHK(hipSetDevice(m->device));
-  const int nch = cfg->chains, D = m->d.D, iter = cfg->iter, n_keep = cfg->iter - cfg->warmup;
+  const int nch = cfg->chains, D = m->d.D, iter = cfg->iter;
   choose_launch(m, (xg && xg->nranks > 1) ? nch : fit_launch_chains(m, nch));   // (between ranks: one group, below)
   // Round structure. Pipelined (default where it applies): two launches per leapfrog, the state machine beside the
   // log-likelihood workgroups (ppcx_kernels.hip, "Pipelined rounds"). It needs a model whose cells read the anticipated
@@ -1316,31 +1380,9 @@ static int fit_nuts_impl(ppcx_model* m, const ppcx_nuts_config* cfg, ppcx_xchg* 
     g_err = msg;
     return rc;
   };
-  f = new ppcx_fit();
-  fit_attach(f, m); f->chains = nch; f->n_keep = n_keep; f->iter = iter;
+  const NutsConfig nc = nuts_config(cfg);
+  if ((rc = fit_create(m, nc, m->stream, &f)) != PPCX_OK) return leave(rc);
   f->inv_metric.assign((size_t)nch * D, 1.0);
-  NutsConfig nc;
-  nc.chains = nch; nc.iter = iter; nc.warmup = cfg->warmup; nc.seed = cfg->seed; nc.adapt_delta = cfg->adapt_delta;
-  nc.max_treedepth = cfg->max_treedepth; nc.init_radius = cfg->init_radius; nc.stepsize0 = cfg->stepsize0;
-  nc.init_buffer = cfg->init_buffer; nc.term_buffer = cfg->term_buffer; nc.window = cfg->window;
-  nc.chain_id_offset = cfg->chain_id_offset;
-  f->cfg = nc;
-#define FHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return leave(fail(PPCX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_))); } while (0)
-  if (n_keep > 0) FHIP(hipMalloc(&f->d_draws, sizeof(double) * (size_t)nch * n_keep * D));
-  if (n_keep > 0) FHIP(hipMalloc(&f->d_lp, sizeof(double) * (size_t)nch * n_keep));
-  FHIP(hipMalloc(&f->d_stepsize, sizeof(double) * (size_t)nch * iter));
-  FHIP(hipMalloc(&f->d_accept, sizeof(double) * (size_t)nch * iter));
-  FHIP(hipMalloc(&f->d_treedepth, sizeof(int) * (size_t)nch * iter));
-  FHIP(hipMalloc(&f->d_nleap, sizeof(int) * (size_t)nch * iter));
-  FHIP(hipMalloc(&f->d_div, sizeof(int) * (size_t)nch * iter));
-  if (n_keep > 0) FHIP(hipMemsetAsync(f->d_draws, 0, sizeof(double) * (size_t)nch * n_keep * D, m->stream));
-  if (n_keep > 0) FHIP(hipMemsetAsync(f->d_lp, 0, sizeof(double) * (size_t)nch * n_keep, m->stream));
-  FHIP(hipMemsetAsync(f->d_stepsize, 0, sizeof(double) * (size_t)nch * iter, m->stream));
-  FHIP(hipMemsetAsync(f->d_accept, 0, sizeof(double) * (size_t)nch * iter, m->stream));
-  FHIP(hipMemsetAsync(f->d_treedepth, 0, sizeof(int) * (size_t)nch * iter, m->stream));
-  FHIP(hipMemsetAsync(f->d_nleap, 0, sizeof(int) * (size_t)nch * iter, m->stream));
-  FHIP(hipMemsetAsync(f->d_div, 0, sizeof(int) * (size_t)nch * iter, m->stream));
-  FHIP(hipStreamSynchronize(m->stream));
   // Chains can also be split into groups that run on their own streams from their own host threads
   // (ppcx_model_set_rounds): while one group sits in its memory-bound gene kernel another group's log-likelihood
   // workgroups have the CUs: measured at cfg3 / 8 chains, pipelined rounds (final kernels of round 3, mean of two fits):
@@ -1368,21 +1410,14 @@ static int fit_nuts_impl(ppcx_model* m, const ppcx_nuts_config* cfg, ppcx_xchg* 
     G.w.stop = &stop;
     G.w.shared_chip = ngrp > 1;
     if (xg && xg->nranks > 1) G.w.xchg = &xa;
-    if (g > 0) { FHIP(hipStreamCreateWithFlags(&G.w.stream, hipStreamNonBlocking)); G.w.own_stream = true; }
-    int rc = work_alloc(G.w, m, G.n);
-    if (rc != PPCX_OK) return leave(rc);
-    std::vector<ChainState> states(G.n);
-    NutsConfig ncg = nc; ncg.chain_id_offset = nc.chain_id_offset + G.c0;
-    for (int c = 0; c < G.n; ++c) state_init(states[c], ncg, c, 0);
-    FHIP(hipMemcpyAsync(G.w.states[0], states.data(), sizeof(ChainState) * G.n, hipMemcpyHostToDevice, G.w.stream));
-    FHIP(hipStreamSynchronize(G.w.stream));     // `states` is a host temporary
-    const size_t c0 = (size_t)G.c0;
-    G.io.draws = f->d_draws ? f->d_draws + c0 * n_keep * D : nullptr; G.io.draws_stride = (long)n_keep * D;
-    G.io.n_keep = n_keep; G.io.iter = iter;
-    G.io.lp = f->d_lp ? f->d_lp + c0 * n_keep : nullptr;
-    G.io.stepsize = f->d_stepsize + c0 * iter; G.io.accept = f->d_accept + c0 * iter;
-    G.io.treedepth = f->d_treedepth + c0 * iter; G.io.nleap = f->d_nleap + c0 * iter; G.io.div = f->d_div + c0 * iter;
-    FHIP(hipStreamSynchronize(G.w.stream));
+    if (g > 0) {
+      const hipError_t e = hipStreamCreateWithFlags(&G.w.stream, hipStreamNonBlocking);
+      if (e != hipSuccess) return leave(hip_fail(e, "hipStreamCreateWithFlags (chain group)"));
+      G.w.own_stream = true;
+    }
+    if ((rc = work_alloc(G.w, m, G.n)) != PPCX_OK) return leave(rc);
+    if ((rc = upload_initial_states(G.w, nc, G.c0, G.n)) != PPCX_OK) return leave(rc);
+    G.io = fit_io(f, G.c0);
   }
   const auto t0 = std::chrono::steady_clock::now();
   auto run_group = [&](Group* G) {
@@ -1418,20 +1453,14 @@ static int fit_nuts_impl(ppcx_model* m, const ppcx_nuts_config* cfg, ppcx_xchg* 
     const int rc = grp[g].rc; const std::string e = grp[g].err;
     return leave(fail(rc, e));                   // (the peers' state machines wait for this rank: leave() tells them it has left)
   }
-  f->seconds = std::chrono::duration<double>(t1 - t0).count();
-  f->grad_evals = 0;
   PumpStats ps;
+  long long leap = 0;
   for (int g = 0; g < ngrp; ++g) {
-    f->grad_evals += grp[g].leap; f->xchg_ticks += grp[g].xticks; f->xchg_count += grp[g].xcount;
+    leap += grp[g].leap; f->xchg_ticks += grp[g].xticks; f->xchg_count += grp[g].xcount;
     ps.kA_ms_sum += grp[g].ps.kA_ms_sum; ps.kC_ms_sum += grp[g].ps.kC_ms_sum; ps.kU_ms_sum += grp[g].ps.kU_ms_sum;
     ps.kA_samples += grp[g].ps.kA_samples; ps.chain_launches += grp[g].ps.chain_launches; ps.pairs += grp[g].ps.pairs;
   }
-  f->kA_samples = ps.kA_samples;
-  f->kA_ms_mean = ps.kA_samples ? ps.kA_ms_sum / (double)ps.kA_samples : 0.0;
-  f->kA_chain_launches_mean = ps.kA_samples ? ps.chain_launches / (double)ps.kA_samples : 0.0;
-  f->kC_ms_mean = ps.kA_samples ? ps.kC_ms_sum / (double)ps.kA_samples : 0.0;
-  f->kU_ms_mean = ps.kA_samples ? ps.kU_ms_sum / (double)ps.kA_samples : 0.0;
-  f->launch_triples = ps.pairs;
+  fit_record(f, ps, std::chrono::duration<double>(t1 - t0).count(), leap);
   *out = f;
   return PPCX_OK;
 }
@@ -1522,9 +1551,9 @@ extern "C" int ppcx_fit_advi(ppcx_model* m, const ppcx_advi_config* cfg, ppcx_fi
   const int n2 = d.C > 2 ? d.C - 2 : 0;
   r.lp_const = -(6.0 + 2.0 * d.G + (double)n2 * d.K) * HL2PI - 5.0 * log(2.0) - (d.C >= 2 ? d.K * log(2.0) : 0.0) - (double)n2 * d.K * log(2.5);
   r.ent_const = 0.5 * (double)D * (1.0 + 2.0 * HL2PI);
-  struct Guard { double* a = nullptr; double* b = nullptr; ~Guard() { (void)hipFree(a); (void)hipFree(b); } } guard;
-  HIPCHK(hipMalloc(&guard.a, sizeof(double) * 4)); r.d_acc = guard.a;
-  HIPCHK(hipMalloc(&guard.b, sizeof(double) * r.nb_advi)); r.d_omega = guard.b;
+  DeviceBuffer<double> acc, omega_part;          // (declared after `w`: released before it)
+  HIPCHK(acc.alloc(4)); r.d_acc = acc.p;
+  HIPCHK(omega_part.alloc((size_t)r.nb_advi)); r.d_omega = omega_part.p;
   hipStream_t st = w.stream;
   // ---- initial point: init = "random" U(-R, R), retried until the density and gradient are finite
   std::vector<double> q0(D), red(PT_COUNT);
@@ -1598,22 +1627,24 @@ extern "C" int ppcx_fit_advi(ppcx_model* m, const ppcx_advi_config* cfg, ppcx_fi
   ppcx_fit* f = new ppcx_fit();
   fit_attach(f, m); f->chains = 1; f->n_keep = cfg->output_samples; f->iter = iters_done; f->advi = true;
   memset(&f->cfg, 0, sizeof f->cfg);
-#define AHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { ppcx_fit_free(f); return fail(PPCX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
-  AHIP(hipMalloc(&f->d_draws, sizeof(double) * (size_t)cfg->output_samples * D));
-  AHIP(hipMalloc(&f->d_lp, sizeof(double) * (size_t)cfg->output_samples));
-  AHIP(hipMemset(f->d_lp, 0, sizeof(double) * (size_t)cfg->output_samples));
-  AHIP(hipMalloc(&f->d_stepsize, sizeof(double) * (size_t)(iters_done > 0 ? iters_done : 1)));
-  AHIP(hipMemset(f->d_stepsize, 0, sizeof(double) * (size_t)(iters_done > 0 ? iters_done : 1)));
-  for (int row = 0; row < cfg->output_samples; row += 64) {
+  hipError_t e = f->d_draws.alloc((size_t)cfg->output_samples * D);
+  if (e == hipSuccess) e = f->d_lp.alloc_zeroed((size_t)cfg->output_samples, st);
+  if (e == hipSuccess) e = f->d_stepsize.alloc_zeroed((size_t)(iters_done > 0 ? iters_done : 1), st);
+  for (int row = 0; e == hipSuccess && rc == PPCX_OK && row < cfg->output_samples; row += 64) {
     const int nb = cfg->output_samples - row < 64 ? cfg->output_samples - row : 64;
-    if ((rc = advi_launch(r, ADVI_DRAW, nb, 0.0, 0, 0, r.draw_id, f->d_draws, row)) != PPCX_OK) { ppcx_fit_free(f); return rc; }
+    rc = advi_launch(r, ADVI_DRAW, nb, 0.0, 0, 0, r.draw_id, f->d_draws.p, row);
     r.draw_id += nb;
   }
   // the approximation itself (mu, omega of every coordinate), for the Pareto-k diagnostic (ppcx_fit_psis)
-  AHIP(hipMalloc(&f->d_mu, sizeof(double) * (size_t)D));
-  AHIP(hipMalloc(&f->d_omega, sizeof(double) * (size_t)D));
-  AHIP(launch_psis_approx_kernel(d, w.vecs + (size_t)V_SQ * w.Dpad, w.vecs + (size_t)V_SG * w.Dpad, w.hyper_vecs[0], f->d_mu, f->d_omega, st));
-  AHIP(hipStreamSynchronize(st));
+  if (e == hipSuccess) e = f->d_mu.alloc((size_t)D);
+  if (e == hipSuccess) e = f->d_omega.alloc((size_t)D);
+  if (e == hipSuccess && rc == PPCX_OK)
+    e = launch_psis_approx_kernel(d, w.vecs + (size_t)V_SQ * w.Dpad, w.vecs + (size_t)V_SG * w.Dpad, w.hyper_vecs[0], f->d_mu.p, f->d_omega.p, st);
+  e = finish(e, st);                             // nothing of the fit is freed under a running kernel
+  if (e != hipSuccess || rc != PPCX_OK) {
+    ppcx_fit_free(f);
+    return rc != PPCX_OK ? rc : hip_fail(e, "the ADVI fit's draws");
+  }
   f->grad_evals = (long long)r.draw_id; f->seconds = 0; f->advi_elbo = elbo; f->advi_eta = eta_best; f->advi_converged = converged ? 1 : 0;
   *out = f;
   return PPCX_OK;
@@ -1652,78 +1683,39 @@ extern "C" int ppcx_model_create_shard(int device, int G_total, int S, int C, in
 static int fit_sharded(ppcx_model** models, int ns, const ppcx_nuts_config* cfg, ppcx_comm* comm, ppcx_fit** fits) {
   if (!models || !cfg || !fits || ns < 1 || ns > kMaxShards) return fail(PPCX_ERR_ARG, "bad shard arguments");
   for (int k = 0; k < ns; ++k) { fits[k] = nullptr; if (!models[k]) return fail(PPCX_ERR_ARG, "NULL shard model"); }
-  if (cfg->chains < 1 || cfg->chains > 1024 || cfg->iter < 1 || cfg->warmup < 0 || cfg->warmup > cfg->iter)
-    return fail(PPCX_ERR_ARG, "need 1<=chains<=1024, iter>=1, 0<=warmup<=iter");
-  if (cfg->max_treedepth < 1 || cfg->max_treedepth > kMaxDepth) return fail(PPCX_ERR_LIMIT, "max_treedepth must be in 1..10");
+  int rc = nuts_config_check(cfg);
+  if (rc != PPCX_OK) return rc;
   const int dev = models[0]->device;
   for (int k = 0; k < ns; ++k) if (models[k]->device != dev) return fail(PPCX_ERR_ARG, "in-process shards must share a device");
   HIPCHK(hipSetDevice(dev));
-  const int nch = cfg->chains, iter = cfg->iter, n_keep = cfg->iter - cfg->warmup;
-  NutsConfig nc;
-  nc.chains = nch; nc.iter = iter; nc.warmup = cfg->warmup; nc.seed = cfg->seed; nc.adapt_delta = cfg->adapt_delta;
-  nc.max_treedepth = cfg->max_treedepth; nc.init_radius = cfg->init_radius; nc.stepsize0 = cfg->stepsize0;
-  nc.init_buffer = cfg->init_buffer; nc.term_buffer = cfg->term_buffer; nc.window = cfg->window;
-  nc.chain_id_offset = cfg->chain_id_offset;
+  const int nch = cfg->chains;
+  const NutsConfig nc = nuts_config(cfg);
+  hipStream_t st = models[0]->stream;           // all in-process shards are ordered on one stream
   std::vector<Work> works(ns);
   std::vector<Shard> sh(ns);
-  int rc = PPCX_OK;
-  auto cleanup = [&]() { for (int k = 0; k < ns; ++k) { ppcx_fit_free(fits[k]); fits[k] = nullptr; } };
-#define SHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return fail(PPCX_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
+  auto drop = [&](int code) { for (int k = 0; k < ns; ++k) { ppcx_fit_free(fits[k]); fits[k] = nullptr; } return code; };   // (g_err stays)
   for (int k = 0; k < ns; ++k) {
     ppcx_model* m = models[k];
-    const int D = m->d.D;
     choose_launch(m, nch);
-    ppcx_fit* f = new ppcx_fit();
-    fits[k] = f;
-    fit_attach(f, m); f->chains = nch; f->n_keep = n_keep; f->iter = iter; f->cfg = nc;
-    if (n_keep > 0) SHIP(hipMalloc(&f->d_draws, sizeof(double) * (size_t)nch * n_keep * D));
-    if (n_keep > 0) SHIP(hipMalloc(&f->d_lp, sizeof(double) * (size_t)nch * n_keep));
-    SHIP(hipMalloc(&f->d_stepsize, sizeof(double) * (size_t)nch * iter));
-    SHIP(hipMalloc(&f->d_accept, sizeof(double) * (size_t)nch * iter));
-    SHIP(hipMalloc(&f->d_treedepth, sizeof(int) * (size_t)nch * iter));
-    SHIP(hipMalloc(&f->d_nleap, sizeof(int) * (size_t)nch * iter));
-    SHIP(hipMalloc(&f->d_div, sizeof(int) * (size_t)nch * iter));
-    if (n_keep > 0) SHIP(hipMemset(f->d_draws, 0, sizeof(double) * (size_t)nch * n_keep * D));
-    if (n_keep > 0) SHIP(hipMemset(f->d_lp, 0, sizeof(double) * (size_t)nch * n_keep));
-    SHIP(hipMemset(f->d_stepsize, 0, sizeof(double) * (size_t)nch * iter));
-    SHIP(hipMemset(f->d_accept, 0, sizeof(double) * (size_t)nch * iter));
-    SHIP(hipMemset(f->d_treedepth, 0, sizeof(int) * (size_t)nch * iter));
-    SHIP(hipMemset(f->d_nleap, 0, sizeof(int) * (size_t)nch * iter));
-    SHIP(hipMemset(f->d_div, 0, sizeof(int) * (size_t)nch * iter));
-    works[k].stream = models[0]->stream;        // all in-process shards are ordered on one stream
-    if ((rc = work_alloc(works[k], m, nch)) != PPCX_OK) { cleanup(); return rc; }
-    std::vector<ChainState> states(nch);
-    for (int c = 0; c < nch; ++c) state_init(states[c], nc, c, 0);   // every shard replicates the same chains
-    SHIP(hipMemcpyAsync(works[k].states[0], states.data(), sizeof(ChainState) * nch, hipMemcpyHostToDevice, works[k].stream));
-    SHIP(hipStreamSynchronize(works[k].stream));   // `states` is a host temporary
-    sh[k].m = m; sh[k].w = &works[k];
-    RunIO& io = sh[k].io;
-    io.draws = f->d_draws; io.draws_stride = (long)n_keep * D; io.n_keep = n_keep; io.iter = iter;
-    io.lp = f->d_lp; io.stepsize = f->d_stepsize; io.accept = f->d_accept; io.treedepth = f->d_treedepth;
-    io.nleap = f->d_nleap; io.div = f->d_div;
+    if ((rc = fit_create(m, nc, st, &fits[k])) != PPCX_OK) return drop(rc);
+    works[k].stream = st;
+    if ((rc = work_alloc(works[k], m, nch)) != PPCX_OK) return drop(rc);
+    if ((rc = upload_initial_states(works[k], nc, 0, nch)) != PPCX_OK) return drop(rc);   // every shard replicates the same chains
+    sh[k].m = m; sh[k].w = &works[k]; sh[k].io = fit_io(fits[k], 0);
   }
-  SHIP(hipStreamSynchronize(models[0]->stream));
-  const long long max_pairs = (long long)iter * ((1LL << cfg->max_treedepth) + 8) + 100000;
+  const long long max_pairs = (long long)nc.iter * ((1LL << cfg->max_treedepth) + 8) + 100000;
   PumpStats ps;
   const auto t0 = std::chrono::steady_clock::now();
   rc = pump(sh, nch, comm, max_pairs, true, &ps);
   const auto t1 = std::chrono::steady_clock::now();
-  if (rc != PPCX_OK) { cleanup(); return rc; }
+  if (rc != PPCX_OK) return drop(rc);
   std::vector<ChainState> states(nch);
-  SHIP(hipMemcpy(states.data(), current_states(works[0]), sizeof(ChainState) * nch, hipMemcpyDeviceToHost));
+  const hipError_t e = hipMemcpy(states.data(), current_states(works[0]), sizeof(ChainState) * nch, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return drop(hip_fail(e, "reading back the chain states"));
   long long leap = 0;
   for (int c = 0; c < nch; ++c) leap += states[c].sc.total_leapfrogs;
-  for (int k = 0; k < ns; ++k) {
-    ppcx_fit* f = fits[k];
-    f->seconds = std::chrono::duration<double>(t1 - t0).count();
-    f->grad_evals = leap;
-    f->kA_samples = ps.kA_samples;
-    f->kA_ms_mean = ps.kA_samples ? ps.kA_ms_sum / (double)ps.kA_samples : 0.0;
-    f->kA_chain_launches_mean = ps.kA_samples ? ps.chain_launches / (double)ps.kA_samples : 0.0;
-    f->kC_ms_mean = ps.kA_samples ? ps.kC_ms_sum / (double)ps.kA_samples : 0.0;
-    f->kU_ms_mean = ps.kA_samples ? ps.kU_ms_sum / (double)ps.kA_samples : 0.0;
-    f->launch_triples = ps.pairs;
-  }
+  // (no adapted metric and no exchange timing on these fits: ppcx_fit_get_inv_metric refuses them)
+  for (int k = 0; k < ns; ++k) fit_record(fits[k], ps, std::chrono::duration<double>(t1 - t0).count(), leap);
   return PPCX_OK;
 }
 extern "C" int ppcx_fit_nuts_shards(ppcx_model** models, int n_shards, const ppcx_nuts_config* cfg, ppcx_fit** fits) {
@@ -1779,8 +1771,8 @@ extern "C" int ppcx_fit_from_draws(ppcx_model* m, int chains, int n_keep, const 
   fit_attach(f, m); f->chains = chains; f->n_keep = n_keep; f->iter = n_keep;
   memset(&f->cfg, 0, sizeof f->cfg);
   const size_t n = (size_t)chains * n_keep * m->d.D;
-  hipError_t e = hipMalloc(&f->d_draws, sizeof(double) * n);
-  if (e == hipSuccess) e = hipMemcpy(f->d_draws, draws, sizeof(double) * n, hipMemcpyHostToDevice);
+  hipError_t e = f->d_draws.alloc(n);
+  if (e == hipSuccess) e = hipMemcpy(f->d_draws.p, draws, sizeof(double) * n, hipMemcpyHostToDevice);
   if (e != hipSuccess) { ppcx_fit_free(f); return fail(PPCX_ERR_HIP, hipGetErrorString(e)); }
   *out = f;
   return PPCX_OK;
@@ -1797,7 +1789,7 @@ extern "C" int ppcx_fit_info(const ppcx_fit* f, int* chains, int* n_keep, int* D
 extern "C" int ppcx_fit_get_draws(ppcx_fit* f, double* out) {
   if (!f || !out) return fail(PPCX_ERR_ARG, "NULL argument");
   HIPCHK(hipSetDevice(f->m->device));
-  if (f->n_keep > 0) HIPCHK(hipMemcpy(out, f->d_draws, sizeof(double) * (size_t)f->chains * f->n_keep * f->m->d.D, hipMemcpyDeviceToHost));
+  if (f->n_keep > 0) HIPCHK(hipMemcpy(out, f->d_draws.p, sizeof(double) * (size_t)f->chains * f->n_keep * f->m->d.D, hipMemcpyDeviceToHost));
   return PPCX_OK;
 }
 extern "C" int ppcx_fit_get_columns(ppcx_fit* f, int n_cols, const int32_t* cols, double* out) {
@@ -1811,7 +1803,7 @@ extern "C" int ppcx_fit_get_columns(ppcx_fit* f, int n_cols, const int32_t* cols
   DeviceBuffer<int> d_cols; DeviceBuffer<double> d_out;
   hipError_t e = d_cols.upload(cols, (size_t)n_cols, st);
   if (e == hipSuccess) e = d_out.alloc((size_t)rows * n_cols);
-  if (e == hipSuccess) e = launch_gather_kernel(f->d_draws, rows, D, d_cols.p, n_cols, d_out.p, st);
+  if (e == hipSuccess) e = launch_gather_kernel(f->d_draws.p, rows, D, d_cols.p, n_cols, d_out.p, st);
   if (e == hipSuccess) e = d_out.download(out, (size_t)rows * n_cols, st);
   if ((e = finish(e, st)) != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
   return PPCX_OK;
@@ -1824,19 +1816,19 @@ extern "C" int ppcx_fit_summary(ppcx_fit* f, int n_cols, const int32_t* cols, do
   const int D = f->m->d.D, M = f->chains, n = f->n_keep;
   for (int i = 0; i < n_cols; ++i) {
     if (cols[i] < -1 || cols[i] >= D) return fail(PPCX_ERR_ARG, "column out of range");
-    if (cols[i] == -1 && !f->d_lp) return fail(PPCX_ERR_ARG, "this fit holds no lp__ (a fit over draws produced elsewhere)");
+    if (cols[i] == -1 && !f->d_lp.p) return fail(PPCX_ERR_ARG, "this fit holds no lp__ (a fit over draws produced elsewhere)");
   }
   if (M < 1 || n < 1) return fail(PPCX_ERR_ARG, "fit holds no kept draws");
   if (M > kSummaryMaxChains) return fail(PPCX_ERR_LIMIT, "ppcx_fit_summary takes at most 128 chains");
   HIPCHK(hipSetDevice(f->m->device));
-  const hipError_t e = summary_columns(f->d_draws, f->d_lp, M, n, D, n_cols, cols, out, kSummaryScratchBytes, f->m->stream);
+  const hipError_t e = summary_columns(f->d_draws.p, f->d_lp.p, M, n, D, n_cols, cols, out, kSummaryScratchBytes, f->m->stream);
   if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
   return PPCX_OK;
 }
 // ---- the Pareto-k diagnostic of an ADVI fit (rstan::vb, rstan >= 2.21: PSIS on log_p - log_g of the output draws)
 static int psis_fit_check(ppcx_fit* f) {
   if (!f) return fail(PPCX_ERR_ARG, "fit is NULL");
-  if (!f->advi || !f->d_mu) return fail(PPCX_ERR_ARG, "the Pareto-k diagnostic needs an ADVI fit (a NUTS fit, or one over draws "
+  if (!f->advi || !f->d_mu.p) return fail(PPCX_ERR_ARG, "the Pareto-k diagnostic needs an ADVI fit (a NUTS fit, or one over draws "
                                                       "produced elsewhere, holds no approximation)");
   HIPCHK(hipSetDevice(f->m->device));            // every allocation and launch below belongs to the fit's device
   return PPCX_OK;
@@ -1859,7 +1851,7 @@ static size_t psis_scratch_bytes() {
 static int psis_ratios(ppcx_fit* f) {
   ppcx_model* m = f->m;
   HIPCHK(hipSetDevice(m->device));
-  if (f->d_r) return PPCX_OK;
+  if (f->d_r.p) return PPCX_OK;
   const int n = f->n_keep, D = m->d.D;
   const int slots = psis_slots();
   const int nslot = n < slots ? n : slots;
@@ -1867,32 +1859,29 @@ static int psis_ratios(ppcx_fit* f) {
   Work w;
   int rc = work_alloc(w, m, nslot);
   if (rc != PPCX_OK) return rc;
-  double *lp = nullptr, *lg = nullptr, *rr = nullptr;
-  hipError_t e = hipMalloc(&lp, sizeof(double) * (size_t)n);
-  if (e == hipSuccess) e = hipMalloc(&lg, sizeof(double) * (size_t)n);
-  if (e == hipSuccess) e = hipMalloc(&rr, sizeof(double) * (size_t)n);
+  DeviceBuffer<double> lp, lg, rr;               // (declared after `w`: released before it; the fit takes them on success)
+  hipError_t e = lp.alloc((size_t)n);
+  if (e == hipSuccess) e = lg.alloc((size_t)n);
+  if (e == hipSuccess) e = rr.alloc((size_t)n);
   AdviRun r; r.m = m; r.w = &w;
   for (int row0 = 0; e == hipSuccess && rc == PPCX_OK && row0 < n; row0 += nslot) {
     const int nb = n - row0 < nslot ? n - row0 : nslot;
-    e = launch_psis_stage_kernel(m->d, f->d_draws, row0, nb, w.vecs, w.Dpad, w.cmds[0], w.stream);
-    if (e == hipSuccess && (rc = advi_eval(r, nb)) == PPCX_OK) e = launch_psis_record_kernel(m->d, w.cmds[0], w.red, nb, lp + row0, w.stream);
+    e = launch_psis_stage_kernel(m->d, f->d_draws.p, row0, nb, w.vecs, w.Dpad, w.cmds[0], w.stream);
+    if (e == hipSuccess && (rc = advi_eval(r, nb)) == PPCX_OK) e = launch_psis_record_kernel(m->d, w.cmds[0], w.red, nb, lp.p + row0, w.stream);
   }
-  if (e == hipSuccess && rc == PPCX_OK) e = launch_psis_log_g_kernel(f->d_draws, n, D, f->d_mu, f->d_omega, lp, lg, rr, w.stream);
-  const hipError_t es = hipStreamSynchronize(w.stream);
-  if (e == hipSuccess) e = es;
-  if (e != hipSuccess || rc != PPCX_OK) {
-    (void)hipFree(lp); (void)hipFree(lg); (void)hipFree(rr);
-    return rc != PPCX_OK ? rc : fail(PPCX_ERR_HIP, std::string("log ratios: ") + hipGetErrorString(e));
-  }
-  f->d_log_p = lp; f->d_log_g = lg; f->d_r = rr;
+  if (e == hipSuccess && rc == PPCX_OK) e = launch_psis_log_g_kernel(f->d_draws.p, n, D, f->d_mu.p, f->d_omega.p, lp.p, lg.p, rr.p, w.stream);
+  e = finish(e, w.stream);
+  if (rc != PPCX_OK) return rc;
+  if (e != hipSuccess) return hip_fail(e, "log ratios");
+  std::swap(f->d_log_p.p, lp.p); std::swap(f->d_log_g.p, lg.p); std::swap(f->d_r.p, rr.p);
   return PPCX_OK;
 }
 extern "C" int ppcx_fit_get_approximation(ppcx_fit* f, double* mu, double* omega) {
   int rc = psis_fit_check(f);
   if (rc != PPCX_OK) return rc;
   const size_t bytes = sizeof(double) * (size_t)f->m->d.D;
-  if (mu) HIPCHK(hipMemcpy(mu, f->d_mu, bytes, hipMemcpyDeviceToHost));
-  if (omega) HIPCHK(hipMemcpy(omega, f->d_omega, bytes, hipMemcpyDeviceToHost));
+  if (mu) HIPCHK(hipMemcpy(mu, f->d_mu.p, bytes, hipMemcpyDeviceToHost));
+  if (omega) HIPCHK(hipMemcpy(omega, f->d_omega.p, bytes, hipMemcpyDeviceToHost));
   return PPCX_OK;
 }
 extern "C" int ppcx_fit_get_log_ratios(ppcx_fit* f, double* log_p, double* log_g) {
@@ -1900,8 +1889,8 @@ extern "C" int ppcx_fit_get_log_ratios(ppcx_fit* f, double* log_p, double* log_g
   if (rc == PPCX_OK) rc = psis_ratios(f);
   if (rc != PPCX_OK) return rc;
   const size_t bytes = sizeof(double) * (size_t)f->n_keep;
-  if (log_p) HIPCHK(hipMemcpy(log_p, f->d_log_p, bytes, hipMemcpyDeviceToHost));
-  if (log_g) HIPCHK(hipMemcpy(log_g, f->d_log_g, bytes, hipMemcpyDeviceToHost));
+  if (log_p) HIPCHK(hipMemcpy(log_p, f->d_log_p.p, bytes, hipMemcpyDeviceToHost));
+  if (log_g) HIPCHK(hipMemcpy(log_g, f->d_log_g.p, bytes, hipMemcpyDeviceToHost));
   return PPCX_OK;
 }
 extern "C" int ppcx_fit_psis(ppcx_fit* f, int n_cols, const int32_t* cols, double* khat) {
@@ -1912,7 +1901,7 @@ extern "C" int ppcx_fit_psis(ppcx_fit* f, int n_cols, const int32_t* cols, doubl
   for (int i = 0; i < n_cols; ++i) if (cols[i] < -1 || cols[i] >= D) return fail(PPCX_ERR_ARG, "column out of range");
   if (psis_tail_len(f->n_keep) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "ppcx_fit_psis takes at most 1.86 million draws");
   if ((rc = psis_ratios(f)) != PPCX_OK) return rc;
-  hipError_t e = psis_columns(f->d_draws, f->d_r, f->n_keep, D, n_cols, cols, khat, psis_scratch_bytes(), f->m->stream);
+  hipError_t e = psis_columns(f->d_draws.p, f->d_r.p, f->n_keep, D, n_cols, cols, khat, psis_scratch_bytes(), f->m->stream);
   if (e != hipSuccess) return fail(PPCX_ERR_HIP, std::string("ppcx_fit_psis: ") + hipGetErrorString(e));
   return PPCX_OK;
 }
@@ -1966,7 +1955,7 @@ extern "C" int ppcx_fit_get_log_lik(ppcx_fit* f, int n_genes, const int32_t* gen
   if (rc != PPCX_OK) return rc;
   if (!out) return fail(PPCX_ERR_ARG, "bad arguments");
   ppcx_model* m = f->m;
-  hipError_t e = loo_fit_log_lik(f->d_draws, (long)f->chains * f->n_keep, m->d, m->d_expo, m->d_X, n_genes, genes, yenc.data(), out,
+  hipError_t e = loo_fit_log_lik(f->d_draws.p, (long)f->chains * f->n_keep, m->d, m->d_expo, m->d_X, n_genes, genes, yenc.data(), out,
                                  loo_scratch_bytes(), m->stream);
   if (e != hipSuccess) return fail(PPCX_ERR_HIP, std::string("ppcx_fit_get_log_lik: ") + hipGetErrorString(e));
   return PPCX_OK;
@@ -1992,7 +1981,7 @@ extern "C" int ppcx_fit_loo(ppcx_fit* f, int n_genes, const int32_t* genes, cons
   if ((rc = loo_check_reff(r_eff, ncells)) != PPCX_OK) return rc;
   const double rmin = loo_reff_min(r_eff, ncells);
   if (psis_tail_len(n, rmin) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "ppcx_fit_loo: the tail exceeds 4095 draws");
-  hipError_t e = loo_fit_cells(f->d_draws, n, m->d, m->d_expo, m->d_X, n_genes, genes, yenc.data(), r_eff, rmin, out,
+  hipError_t e = loo_fit_cells(f->d_draws.p, n, m->d, m->d_expo, m->d_X, n_genes, genes, yenc.data(), r_eff, rmin, out,
                                loo_scratch_bytes(), m->stream);
   if (e != hipSuccess) return fail(PPCX_ERR_HIP, std::string("ppcx_fit_loo: ") + hipGetErrorString(e));
   return PPCX_OK;
@@ -2016,7 +2005,7 @@ extern "C" int ppcx_fit_loo_predict(ppcx_fit* f, int n_genes, const int32_t* gen
     return fail(PPCX_ERR_ARG, "truncation_compensation must be finite and > 0");
   const double rmin = loo_reff_min(r_eff, ncells);
   if (psis_tail_len(n, rmin) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "ppcx_fit_loo_predict: the tail exceeds 4095 draws");
-  hipError_t e = loo_predict_fit_cells(f->d_draws, n, m->d, m->d_expo, m->d_X, n_genes, genes, yenc.data(), r_eff, rmin,
+  hipError_t e = loo_predict_fit_cells(f->d_draws.p, n, m->d, m->d_expo, m->d_X, n_genes, genes, yenc.data(), r_eff, rmin,
                                        truncation_compensation, p_lo, p_hi, seed32(seed), out, loo_scratch_bytes(), m->stream);
   if (e != hipSuccess) return fail(PPCX_ERR_HIP, std::string("ppcx_fit_loo_predict: ") + hipGetErrorString(e));
   return PPCX_OK;
@@ -2055,12 +2044,12 @@ extern "C" int ppcx_fit_get_diagnostics(ppcx_fit* f, double* lp, double* stepsiz
   if (!f) return fail(PPCX_ERR_ARG, "fit is NULL");
   HIPCHK(hipSetDevice(f->m->device));
   const size_t ni = (size_t)f->chains * f->iter, nk = (size_t)f->chains * f->n_keep;
-  if (lp && nk && f->d_lp) HIPCHK(hipMemcpy(lp, f->d_lp, sizeof(double) * nk, hipMemcpyDeviceToHost));
-  if (stepsize && f->d_stepsize) HIPCHK(hipMemcpy(stepsize, f->d_stepsize, sizeof(double) * ni, hipMemcpyDeviceToHost));
-  if (treedepth && f->d_treedepth) HIPCHK(hipMemcpy(treedepth, f->d_treedepth, sizeof(int) * ni, hipMemcpyDeviceToHost));
-  if (n_leapfrog && f->d_nleap) HIPCHK(hipMemcpy(n_leapfrog, f->d_nleap, sizeof(int) * ni, hipMemcpyDeviceToHost));
-  if (divergent && f->d_div) HIPCHK(hipMemcpy(divergent, f->d_div, sizeof(int) * ni, hipMemcpyDeviceToHost));
-  if (accept && f->d_accept) HIPCHK(hipMemcpy(accept, f->d_accept, sizeof(double) * ni, hipMemcpyDeviceToHost));
+  if (lp && nk && f->d_lp.p) HIPCHK(hipMemcpy(lp, f->d_lp.p, sizeof(double) * nk, hipMemcpyDeviceToHost));
+  if (stepsize && f->d_stepsize.p) HIPCHK(hipMemcpy(stepsize, f->d_stepsize.p, sizeof(double) * ni, hipMemcpyDeviceToHost));
+  if (treedepth && f->d_treedepth.p) HIPCHK(hipMemcpy(treedepth, f->d_treedepth.p, sizeof(int) * ni, hipMemcpyDeviceToHost));
+  if (n_leapfrog && f->d_nleap.p) HIPCHK(hipMemcpy(n_leapfrog, f->d_nleap.p, sizeof(int) * ni, hipMemcpyDeviceToHost));
+  if (divergent && f->d_div.p) HIPCHK(hipMemcpy(divergent, f->d_div.p, sizeof(int) * ni, hipMemcpyDeviceToHost));
+  if (accept && f->d_accept.p) HIPCHK(hipMemcpy(accept, f->d_accept.p, sizeof(double) * ni, hipMemcpyDeviceToHost));
   return PPCX_OK;
 }
 extern "C" int ppcx_fit_get_inv_metric(ppcx_fit* f, double* out) {
@@ -2113,47 +2102,36 @@ extern "C" int ppcx_fit_ppc(ppcx_fit* f, double truncation_compensation, double 
   if (!(p_lo >= 0.0 && p_hi <= 1.0 && p_lo <= p_hi)) return fail(PPCX_ERR_ARG, "need 0 <= p_lo <= p_hi <= 1");
   HIPCHK(hipSetDevice(m->device));
   const int n_cells = m->d.K * m->d.S;
-  double* d_ci = nullptr; int* d_rng = nullptr; int* d_scratch = nullptr;
-  HIPCHK(hipMalloc(&d_ci, sizeof(double) * (size_t)n_cells * 4));
+  DeviceBuffer<double> d_ci, d_T;                // d_T: the checked genes' parameters, transposed: [K][C + 1][draws]
+  DeviceBuffer<int> d_rng, d_scratch;
   // a cell's draws live in LDS (160 KB per CU; 4 KB of it is the kernel's static scratch) when they fit; beyond that
   // 1024 workgroups share the cells and keep the current cell's draws in their slice of a global scratch buffer
   const int kLdsDraws = 39680;
   int nblocks = n_cells;
   const bool wave_kernel = n_gen <= ppc_wave_max_draws();      // one wavefront per cell (else one workgroup per cell)
-  double* d_T = nullptr;                                       // the checked genes' parameters, transposed: [K][C + 1][draws]
-  {
-    hipError_t e = hipMalloc(&d_T, sizeof(double) * (size_t)m->d.K * (m->d.C + 1) * (size_t)n_draws);
-    if (e != hipSuccess) { (void)hipFree(d_ci); return fail(PPCX_ERR_HIP, hipGetErrorString(e)); }
-  }
-  if (wave_kernel) {
-    nblocks = (n_cells + 3) / 4; if (nblocks > 4096) nblocks = 4096;
-  } else if (n_gen > kLdsDraws) {
-    nblocks = n_cells < 1024 ? n_cells : 1024;
-    hipError_t e = hipMalloc(&d_scratch, sizeof(int) * (size_t)nblocks * n_gen);
-    if (e != hipSuccess) { (void)hipFree(d_ci); (void)hipFree(d_T); return fail(PPCX_ERR_HIP, hipGetErrorString(e)); }
-  }
-  if (counts_rng) {
-    hipError_t e = hipMalloc(&d_rng, sizeof(int) * (size_t)n_gen * n_cells);
-    if (e != hipSuccess) { (void)hipFree(d_ci); (void)hipFree(d_scratch); (void)hipFree(d_T); return fail(PPCX_ERR_HIP, hipGetErrorString(e)); }
-  }
+  if (wave_kernel) { nblocks = (n_cells + 3) / 4; if (nblocks > 4096) nblocks = 4096; }
+  else if (n_gen > kLdsDraws) nblocks = n_cells < 1024 ? n_cells : 1024;
+  hipError_t e = d_ci.alloc((size_t)n_cells * 4);
+  if (e == hipSuccess) e = d_T.alloc((size_t)m->d.K * (m->d.C + 1) * (size_t)n_draws);
+  if (e == hipSuccess && !wave_kernel && n_gen > kLdsDraws) e = d_scratch.alloc((size_t)nblocks * n_gen);
+  if (e == hipSuccess && counts_rng) e = d_rng.alloc((size_t)n_gen * n_cells);
+  if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
   PpcArgs pa;
-  pa.d = m->d; pa.draws = f->d_draws; pa.n_draws = n_draws; pa.exposure = m->d_expo; pa.X = m->d_X;
+  pa.d = m->d; pa.draws = f->d_draws.p; pa.n_draws = n_draws; pa.exposure = m->d_expo; pa.X = m->d_X;
   pa.truncation_compensation = truncation_compensation; pa.p_lo = p_lo; pa.p_hi = p_hi; pa.k0 = seed32(seed);
-  pa.n_gen = n_gen; pa.resample = resample ? 1 : 0; pa.n_cells = n_cells; pa.ci = d_ci; pa.counts_rng = d_rng; pa.scratch = d_scratch;
+  pa.n_gen = n_gen; pa.resample = resample ? 1 : 0; pa.n_cells = n_cells; pa.ci = d_ci.p; pa.counts_rng = d_rng.p; pa.scratch = d_scratch.p;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   (void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1);
   if (ev0) (void)hipEventRecord(ev0, m->stream);
-  hipError_t e = hipSuccess;
-  e = launch_ppc_table_kernel(f->d_draws, n_draws, m->d, truncation_compensation, d_T, m->stream);
-  if (e == hipSuccess) e = wave_kernel ? launch_ppc_wave_kernel(pa, d_T, nblocks, m->stream) : launch_ppc_kernel(pa, d_T, nblocks, m->stream);
+  e = launch_ppc_table_kernel(f->d_draws.p, n_draws, m->d, truncation_compensation, d_T.p, m->stream);
+  if (e == hipSuccess) e = wave_kernel ? launch_ppc_wave_kernel(pa, d_T.p, nblocks, m->stream) : launch_ppc_kernel(pa, d_T.p, nblocks, m->stream);
   if (ev1) (void)hipEventRecord(ev1, m->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(m->stream);
+  e = finish(e, m->stream);                      // drained whatever happened: the buffers go out of scope below
   if (e == hipSuccess && ev0 && ev1) { float ms = 0; if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) { f->ppc_ms = ms; f->ppc_draws = (long long)n_gen * n_cells; } }
   if (ev0) (void)hipEventDestroy(ev0);
   if (ev1) (void)hipEventDestroy(ev1);
-  if (e == hipSuccess) e = hipMemcpy(ci, d_ci, sizeof(double) * (size_t)n_cells * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && counts_rng) e = hipMemcpy(counts_rng, d_rng, sizeof(int) * (size_t)n_gen * n_cells, hipMemcpyDeviceToHost);
-  (void)hipFree(d_ci); (void)hipFree(d_rng); (void)hipFree(d_scratch); (void)hipFree(d_T);
+  if (e == hipSuccess) e = hipMemcpy(ci, d_ci.p, sizeof(double) * (size_t)n_cells * 4, hipMemcpyDeviceToHost);
+  if (e == hipSuccess && counts_rng) e = hipMemcpy(counts_rng, d_rng.p, sizeof(int) * (size_t)n_gen * n_cells, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
   return PPCX_OK;
 }

@@ -1,5 +1,6 @@
 // ppcx_columns.h -- the host side that the fit diagnostics share (ppcx_summary.hip, ppcx_psis.hip, ppcx_loo.hip and their entry
-// points in ppcx_capi.hip): an owning device buffer, the column-batch driver and the launch of a kernel with dynamic LDS.
+// points in ppcx_capi.hip): an owning device buffer -- also what a fit holds its draws and diagnostics in, and the scratch of a
+// call (ppcx_capi.hip) --, the column-batch driver and the launch of a kernel with dynamic LDS.
 // Every driver built from these synchronises its stream before a buffer goes out of scope (finish() below), also after a
 // failed launch: nothing is freed under a running kernel.
 #pragma once
@@ -18,6 +19,10 @@ struct DeviceBuffer {
   DeviceBuffer& operator=(const DeviceBuffer&) = delete;
   ~DeviceBuffer() { (void)hipFree(p); }
   hipError_t alloc(size_t n) { return hipMalloc(&p, sizeof(T) * n); }
+  hipError_t alloc_zeroed(size_t n, hipStream_t st) {                   // allocates; the zero fill is ordered on st
+    const hipError_t e = alloc(n);
+    return e == hipSuccess ? hipMemsetAsync(p, 0, sizeof(T) * n, st) : e;
+  }
   hipError_t upload(const T* host, size_t n, hipStream_t st) {          // allocates; the copy is ordered on st
     const hipError_t e = alloc(n);
     return e == hipSuccess ? hipMemcpyAsync(p, host, sizeof(T) * n, hipMemcpyHostToDevice, st) : e;

@@ -544,6 +544,87 @@ def test_a_refused_exchange_fit_leaves_nothing_on_the_device():
     assert abs(free2 - free0) < 16 << 20, "Model.close() was deferred by a fit that was never handed out"
 
 
+def _make_and_close_every_kind_of_fit(L, d, n_keep, output_samples):
+    """A NUTS fit with two chain groups and the calls that read it, a pair of in-process shard fits, an ADVI fit with its cached
+    log ratios, a fit over draws made elsewhere: all of them and their models closed on return."""
+    kw = dict(chains=4, iter=30 + n_keep, warmup=30, seed=1, max_treedepth=4)   # (short trees: what counts here is the memory)
+    m = L.Model(d["counts"], d["X"], d["exposure"], 20)
+    shards = [L.Model(d["counts"][g0:g1], d["X"], d["exposure"], 0, shard=(300, 20, g0, g1)) for g0, g1 in ((0, 150), (150, 300))]
+    try:
+        m.set_rounds(stream_groups=2)
+        f = m.fit_nuts(**kw)
+        ci, rng = f.ppc(0.7352941, 0.05, 0.95, seed=3, return_counts_rng=True)
+        assert rng.shape == (4 * n_keep, 20, 40) and np.isfinite(ci).all()
+        assert f.summary(cols=[0, 1, 2])["rhat"].shape == (4,)
+        assert f.loo(genes=[0, 1])["elpd_loo"].shape == (2, 40)
+        assert f.diagnostics()["n_leapfrog"].min() >= 1
+        draws = f.draws()
+        f.close()
+        fits = L.fit_nuts_shards(shards, **kw)
+        assert np.array_equal(fits[0].diagnostics()["n_leapfrog"], fits[1].diagnostics()["n_leapfrog"])
+        for fs in fits:
+            fs.close()
+        a = m.fit_advi(output_samples=output_samples, iter=200, seed=1)
+        assert a.psis(cols=[0, 1])["khat"].shape == (3,)
+        a.close()
+        fd = m.fit_from_draws(draws)
+        assert np.array_equal(fd.draws(), draws)
+        fd.close()
+    finally:
+        for x in shards + [m]:
+            x.close()
+
+
+def test_every_way_of_making_a_fit_gives_its_memory_back():
+    """A fit owns its device buffers, whichever entry point made it, and the calls that read it keep nothing: with every fit and
+    model closed the device is back where it was, within the margin the refused-fit test above allows for a released model.
+    The HIP runtime itself keeps what a process uses for the first time -- code objects, the queue of a second stream, kernel
+    scratch: 270 MB over this sequence from a fresh process, 0 bytes over the same sequence run again (measured) -- so the
+    sequence runs once, with short fits, before the memory is read, and the test does not depend on what ran before it. The
+    fits of the measured pass are long enough for the margin to see them: 900 kept draws of 4 chains are 18 MB in the
+    unsharded fit and in the fit over its draws, 9 MB in each shard's, and 4000 draws of the approximation 20 MB."""
+    from ppcseq_amd import _lib as L
+    if L.device_count() < 1:
+        pytest.fail("no HIP device visible: the product has no CPU fallback")
+    d = ind.synth(300, 40, K=20, seed=31, C=2)
+    _make_and_close_every_kind_of_fit(L, d, 30, 100)
+    free0, _ = L.device_memory(0)
+    _make_and_close_every_kind_of_fit(L, d, 900, 4000)
+    free1, _ = L.device_memory(0)
+    print("device memory not given back: %d bytes" % (free0 - free1))
+    assert abs(free1 - free0) < 16 << 20, "a closed fit or a finished call left device memory behind"
+
+
+def test_a_fit_without_kept_draws_holds_its_diagnostics_and_nothing_else():
+    """warmup == iter: ppcx_fit_nuts and ppcx_fit_nuts_shards both return [chains][iter] diagnostics and an empty draws array,
+    the replicated state machines of the shards take the unsharded run's decisions, and what needs kept draws says so."""
+    from ppcseq_amd import _lib as L
+    d = ind.synth(XG, XS, K=XK, seed=4)
+    kw = dict(chains=2, iter=12, warmup=12, seed=6)
+    whole = L.Model(d["counts"], d["X"], d["exposure"], XK)
+    shards = [L.Model(d["counts"][g0:g1], d["X"], d["exposure"], 0, shard=(XG, XK, g0, g1)) for g0, g1 in ((0, 40), (40, 80))]
+    try:
+        fits = [whole.fit_nuts(**kw)] + L.fit_nuts_shards(shards, **kw)
+        dgs = [f.diagnostics() for f in fits]
+        for f, dg in zip(fits, dgs):
+            assert (f.chains, f.n_keep, f.iter) == (2, 0, 12)
+            assert f.draws().shape == (2, 0, f.D) and dg["lp"].shape == (2, 0)
+            assert all(dg[k].shape == (2, 12) for k in ("stepsize", "accept", "treedepth", "n_leapfrog", "divergent"))
+            assert dg["n_leapfrog"].min() >= 1 and dg["stepsize"].min() > 0
+            assert np.array_equal(dg["n_leapfrog"], dgs[0]["n_leapfrog"]) and np.array_equal(dg["treedepth"], dgs[0]["treedepth"])
+            with pytest.raises(L.PpcxError, match="fit holds no kept draws"):
+                f.summary(cols=[0], lp=False)
+            with pytest.raises(L.PpcxError, match="ppcx error -1"):       # lp__ of such a fit: there is none (PPCX_ERR_ARG)
+                f.summary(cols=[0])
+            with pytest.raises(L.PpcxError, match="fit holds no kept draws"):
+                f.ppc(0.7352941, 0.05, 0.95, seed=3)
+        for f in fits:
+            f.close()
+    finally:
+        for m in shards + [whole]:
+            m.close()
+
+
 # ---- identify_outliers() -- both passes -- over several devices and over several ranks (R/methods.R:268-342 with the reference's
 # ---- chains spread over `cores`, R/utilities.R:1500-1501) -------------------------------------------------------------------
 def _two_pass_frame():
