@@ -163,6 +163,18 @@ PPCX_API int ppcx_fit_psis(ppcx_fit* f, int n_cols, const int32_t* cols, double*
 #define PPCX_LOO_FIELDS 4       /* elpd_loo, p_loo, looic, khat */
 PPCX_API int ppcx_fit_get_log_lik(ppcx_fit* f, int n_genes, const int32_t* genes, double* out);
 PPCX_API int ppcx_fit_loo(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double* out);
+/* The relative efficiency of the importance ratios per observed cell of a NUTS fit: what rstan::loo(fit) passes to loo::loo as
+ * r_eff, loo::relative_eff(exp(log_lik), chain_id), so that ppcx_fit_loo / ppcx_fit_loo_predict with it report what rstan::loo(fit)
+ * does without the log-likelihood matrix ever leaving the device. Fits, genes and refusals as ppcx_fit_loo; more than 128 chains:
+ * PPCX_ERR_LIMIT (ppcx_fit_summary's bound). Synchronous on the model's stream; the same bits on every call, for any gene subset.
+ *   out [n_genes][S]: ESS / N of v = exp(log_lik - max log_lik) over the split chains (each chain's first and last
+ *   floor(n_keep / 2) draws; N values in 2 chains sequences), ESS the Geyer estimator of ppcx_fit_summary on v itself (no rank
+ *   normalisation, no folding: posterior::ess_mean). The shift by the maximum does not change the ESS and keeps it defined where
+ *   exp(log_lik) underflows. Values above 1 (antithetic chains) are kept. NaN: a NaN or +Inf log_lik, n_keep < 4, or all
+ *   values equal; log_lik = -Inf is an ordinary value (v = 0). A cell excluded by the model gets a value like any other
+ *   (ppcx_fit_loo does not use it). The caller replaces NaN (by 1, the default tail) before handing the array to ppcx_fit_loo,
+ *   which refuses a non-finite r_eff.                                                                                          */
+PPCX_API int ppcx_fit_relative_eff(ppcx_fit* f, int n_genes, const int32_t* genes, double* out);
 /* The leave-one-out predictive interval and LOO-PIT per observed cell of a NUTS fit, from that ONE fit: for cell (g, s) the
  * distribution of its count under the posterior that has not seen the cell (what loo::E_loo(yrep, psis, type = "quantile" /
  * "mean") and bayesplot's ppc_loo_intervals / ppc_loo_pit give; ppcseq's question -- is the observed count inside the interval? --

@@ -25,7 +25,7 @@ EXPORTS = [
     "ppcx_xchg_create", "ppcx_xchg_handle", "ppcx_xchg_connect", "ppcx_xchg_connect_local", "ppcx_xchg_set_timeout", "ppcx_xchg_destroy",
     "ppcx_fit_nuts_xchg", "ppcx_fit_get_xchg_timing", "ppcx_fit_get_inv_metric", "ppcx_fit_summary",
     "ppcx_fit_get_approximation", "ppcx_fit_get_log_ratios", "ppcx_fit_psis", "ppcx_fit_get_log_lik", "ppcx_fit_loo",
-    "ppcx_fit_loo_predict",
+    "ppcx_fit_loo_predict", "ppcx_fit_relative_eff",
 ]
 ABI_VERSION = 400           # include/ppcx.h PPCX_VERSION this binding was written for
 SUMMARY_FIELDS = ("mean", "sd", "q05", "q50", "q95", "rhat", "ess_bulk", "ess_tail")   # PPCX_SUMMARY_FIELDS, in order
@@ -104,6 +104,7 @@ def load() -> C.CDLL:
     lib.ppcx_fit_get_log_lik.argtypes = [C.c_void_p, C.c_int, ip, dp]
     lib.ppcx_fit_loo.argtypes = [C.c_void_p, C.c_int, ip, dp, dp]
     lib.ppcx_fit_loo_predict.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_double, C.c_double, C.c_double, C.c_ulonglong, dp]
+    lib.ppcx_fit_relative_eff.argtypes = [C.c_void_p, C.c_int, ip, dp]
     lib.ppcx_fit_get_diagnostics.argtypes = [C.c_void_p, dp, dp, ip, ip, ip, dp]
     lib.ppcx_fit_get_timing.argtypes = [C.c_void_p, dp, C.POINTER(C.c_longlong), dp, C.POINTER(C.c_longlong), dp]
     lib.ppcx_fit_get_kernel_times.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(C.c_longlong)]
@@ -138,6 +139,8 @@ def load() -> C.CDLL:
         lib.ppcx_testing_loo.argtypes = [C.c_int, C.c_int, dp, ip, dp, dp]
     if hasattr(lib, "ppcx_testing_loo_predict"):
         lib.ppcx_testing_loo_predict.argtypes = [dp, ip, C.c_int, C.c_int, ip, ip, dp, C.c_double, C.c_double, dp]
+    if hasattr(lib, "ppcx_testing_relative_eff"):
+        lib.ppcx_testing_relative_eff.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp]
     lib.ppcx_fit_free.restype = None
     lib.ppcx_advi_config_default.argtypes = [C.POINTER(AdviConfig)]
     lib.ppcx_advi_config_default.restype = None
@@ -260,6 +263,25 @@ def testing_loo_predict(ll, x, y, excluded=None, r_eff=None, p_lo=0.025, p_hi=0.
                                         _p(ex, C.c_int32) if ex is not None else None,
                                         _p(re, C.c_double) if re is not None else None, float(p_lo), float(p_hi),
                                         _p(out, C.c_double)))
+    return out
+
+
+def testing_relative_eff(ll, chains):
+    """The kernel of ppcx_fit_relative_eff on host-given log-likelihood columns (testing build only; csrc/ppcx_testing.h
+    ppcx_testing_relative_eff): ll [chains * n, n_cells], the draws chain-major. Returns [n_cells]."""
+    lib = load()
+    if not hasattr(lib, "ppcx_testing_relative_eff"):
+        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before ppcx_testing_relative_eff existed: rebuild it "
+                        "(`python -m ppcseq_amd.build --testing --force`)")
+    ll = np.asarray(ll, dtype=np.float64)
+    ll = ll.reshape(ll.shape[0], -1)
+    rows, nc = ll.shape
+    chains = int(chains)
+    if chains < 1 or rows % chains:
+        raise ValueError("ll must hold chains * n rows")
+    cols = np.ascontiguousarray(ll.T)
+    out = np.zeros(nc)
+    _check(lib.ppcx_testing_relative_eff(chains, rows // chains, nc, _p(cols, C.c_double), _p(out, C.c_double)))
     return out
 
 
@@ -617,17 +639,38 @@ class Fit:
             _check(load().ppcx_fit_get_log_lik(self._h, int(g.size), _p(g, C.c_int32), _p(out, C.c_double)))
         return out
 
+    def relative_eff(self, genes=None):
+        """The relative efficiency of the importance ratios per observed cell on the device (ppcx_fit_relative_eff;
+        loo::relative_eff(exp(log_lik), chain_id), what rstan::loo(fit) passes to loo::loo): [n_genes, S]. NaN where it is not
+        defined (a NaN or +Inf log-likelihood, fewer than 4 kept draws per chain, no variance). genes=None: all G genes."""
+        g = self._genes(genes)
+        out = np.zeros((g.size, self.model.S))
+        if g.size:
+            _check(load().ppcx_fit_relative_eff(self._h, int(g.size), _p(g, C.c_int32), _p(out, C.c_double)))
+        return out
+
+    def _r_eff(self, g, r_eff):
+        """The r_eff argument of loo / loo_predict as a contiguous [n_genes, S] array or None; "auto": relative_eff of the same
+        genes with 1 where it is not defined (the default tail)."""
+        if r_eff is None:
+            return None
+        if isinstance(r_eff, str):
+            if r_eff != "auto":
+                raise ValueError(f'r_eff must be None, "auto" or an array, not {r_eff!r}')
+            re = self.relative_eff(g)
+            return np.ascontiguousarray(np.where(np.isnan(re), 1.0, re))
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(r_eff, dtype=np.float64), (g.size, self.model.S)))
+
     def loo(self, genes=None, r_eff=None):
         """PSIS-LOO per observed cell on the device (ppcx_fit_loo; rstan::loo / loo::loo(log_lik, r_eff)): a dict of the
         pointwise elpd_loo, p_loo, looic and khat, [n_genes, S] each, `excluded` (the cells the model holds out now: elpd_loo is
         their exact held-out density, p_loo 0, khat NaN), `genes`, `n_draws`, and `estimates`: {elpd_loo, p_loo, looic: (sum, se)} over the
-        non-excluded cells as loo reports them. genes=None: all G genes; r_eff None (all 1) or [n_genes, S]."""
+        non-excluded cells as loo reports them. genes=None: all G genes; r_eff None (all 1), [n_genes, S], or "auto": relative_eff
+        of the same cells (1 where it is NaN), as rstan::loo(fit) does; the result then carries it as `r_eff`."""
         g = self._genes(genes)
         S = self.model.S
         out = np.zeros((g.size, S, len(LOO_FIELDS)))
-        re = None
-        if r_eff is not None:
-            re = np.ascontiguousarray(np.broadcast_to(np.asarray(r_eff, dtype=np.float64), (g.size, S)))
+        re = self._r_eff(g, r_eff)
         if g.size:
             _check(load().ppcx_fit_loo(self._h, int(g.size), _p(g, C.c_int32), _p(re, C.c_double) if re is not None else None,
                                        _p(out, C.c_double)))
@@ -637,6 +680,8 @@ class Fit:
         res["excluded"] = excl.reshape(self.model.G, S)[g]
         res["genes"] = g.astype(np.int64)
         res["n_draws"] = self.chains * self.n_keep
+        if isinstance(r_eff, str):
+            res["r_eff"] = re
         res["estimates"] = loo_estimates(res, res["excluded"])
         return res
 
@@ -645,14 +690,12 @@ class Fit:
         bayesplot::ppc_loo_intervals / ppc_loo_pit): a dict of mean, lower, upper (the p_lo / p_hi quantiles of the cell's count
         under the posterior that has not seen the cell), pit_lt, pit_le (P(x < y), P(x <= y)) and khat, [n_genes, S] each;
         `excluded` (cells the model holds out now: uniform weights, Fit.ppc's interval, khat NaN), `y` (the observed counts),
-        `outside` = (y < lower) | (y > upper), `genes`, `n_draws`. genes=None: all G genes; r_eff None (all 1) or [n_genes, S].
+        `outside` = (y < lower) | (y > upper), `genes`, `n_draws`. genes=None: all G genes; r_eff as Fit.loo ("auto" adds `r_eff`).
         seed and truncation_compensation as Fit.ppc: the predictive counts of a checked gene are its counts_rng."""
         g = self._genes(genes)
         S = self.model.S
         out = np.zeros((g.size, S, len(LOO_PREDICT_FIELDS)))
-        re = None
-        if r_eff is not None:
-            re = np.ascontiguousarray(np.broadcast_to(np.asarray(r_eff, dtype=np.float64), (g.size, S)))
+        re = self._r_eff(g, r_eff)
         if g.size:
             _check(load().ppcx_fit_loo_predict(self._h, int(g.size), _p(g, C.c_int32),
                                                _p(re, C.c_double) if re is not None else None, float(truncation_compensation),
@@ -666,6 +709,8 @@ class Fit:
             res["outside"] = (res["y"] < res["lower"]) | (res["y"] > res["upper"])
         res["genes"] = g.astype(np.int64)
         res["n_draws"] = self.chains * self.n_keep
+        if isinstance(r_eff, str):
+            res["r_eff"] = re
         return res
 
     def diagnostics(self):

@@ -2039,6 +2039,29 @@ extern "C" int ppcx_testing_loo_predict(const double* ll, const int32_t* x, int 
   return PPCX_OK;
 }
 #endif
+// ---- the relative efficiency of the same cells (loo::relative_eff(exp(log_lik), chain_id): what rstan::loo(fit) passes as r_eff)
+extern "C" int ppcx_fit_relative_eff(ppcx_fit* f, int n_genes, const int32_t* genes, double* out) {
+  std::vector<int> yenc;
+  int rc = loo_prepare(f, n_genes, genes, yenc);
+  if (rc != PPCX_OK) return rc;
+  if (!out) return fail(PPCX_ERR_ARG, "bad arguments");
+  if (f->chains > kSummaryMaxChains) return fail(PPCX_ERR_LIMIT, "ppcx_fit_relative_eff takes at most 128 chains");
+  ppcx_model* m = f->m;
+  hipError_t e = reff_fit_cells(f->d_draws.p, f->chains, f->n_keep, m->d, m->d_expo, m->d_X, n_genes, genes, yenc.data(), out,
+                                loo_scratch_bytes(), m->stream);
+  if (e != hipSuccess) return fail(PPCX_ERR_HIP, std::string("ppcx_fit_relative_eff: ") + hipGetErrorString(e));
+  return PPCX_OK;
+}
+#ifdef PPCX_TESTING
+// testing build only (ppcx_testing.h): the relative-efficiency kernel on host-given columns, on the current device
+extern "C" int ppcx_testing_relative_eff(int chains, int n, int n_cols, const double* ll, double* out) {
+  if (chains < 1 || n < 1 || n_cols < 1 || !ll || !out) return fail(PPCX_ERR_ARG, "bad arguments");
+  if (chains > kSummaryMaxChains) return fail(PPCX_ERR_LIMIT, "too many chains");
+  hipError_t e = reff_columns(ll, chains, n, n_cols, out, loo_scratch_bytes(), nullptr);
+  if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
+  return PPCX_OK;
+}
+#endif
 extern "C" int ppcx_fit_get_diagnostics(ppcx_fit* f, double* lp, double* stepsize, int32_t* treedepth,
                                         int32_t* n_leapfrog, int32_t* divergent, double* accept) {
   if (!f) return fail(PPCX_ERR_ARG, "fit is NULL");

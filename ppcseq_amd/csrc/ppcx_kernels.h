@@ -255,6 +255,16 @@ hipError_t loo_predict_fit_cells(const double* draws, long n, const Dims& d, con
 hipError_t loo_predict_columns(const double* cols, const int* x, long n, int n_cols, const int* y, const int* excl,
                                const double* r_eff, double r_eff_min, double p_lo, double p_hi, double* out, size_t scratch_bytes,
                                hipStream_t st);
+// The relative efficiency of the same cells (ppcx_reff.hip, statistic in ppcx_reff.h): one workgroup per cell; the split values
+// (8 bytes each) in LDS for fits of up to kPsisLdsDraws draws, beyond that in the scratch, bounded like the gene table. Of `l` it
+// uses T / y / expo / X / S / C or cols, n = chains n_keep, cell0, n_cells, scratch ([launch's cells][2 chains (n_keep / 2)]) and
+// out ([cells], one value each). At most kSummaryMaxChains chains.
+struct ReffArgs { LooArgs l; int chains = 0, n_keep = 0; };
+// r_eff of the cells of genes[0 .. n_genes) (host) for draws [chains n_keep][D] (device); yenc and out ([cells]) host. Synchronous
+hipError_t reff_fit_cells(const double* draws, int chains, int n_keep, const Dims& d, const double* expo, const double* X, int n_genes,
+                          const int* genes, const int* yenc, double* out, size_t scratch_bytes, hipStream_t st);
+// ... of host-given columns cols [n_cols][chains n_keep] (testing build); synchronous
+hipError_t reff_columns(const double* cols, int chains, int n_keep, int n_cols, double* out, size_t scratch_bytes, hipStream_t st);
 hipError_t launch_xchg_abort_kernel(const XchgArgs& x, hipStream_t st);      // tells every peer that this rank has left the fit
 
 }  // namespace ppcx

@@ -58,6 +58,9 @@ PPCX_API int ppcx_testing_loo(int n, int n_cols, const double* ll, const int32_t
  * NULL or [n_cols] flags, r_eff NULL or [n_cols]; out [n_cols][6]: mean, lower, upper, pit_lt, pit_le, khat. */
 PPCX_API int ppcx_testing_loo_predict(const double* ll, const int32_t* x, int n, int n_cols, const int32_t* y, const int32_t* excluded,
                                       const double* r_eff, double p_lo, double p_hi, double* out);
+/* The kernel of ppcx_fit_relative_eff on host-given log-likelihood columns, on the current device (ppcx_reff.hip): ll
+ * [n_cols][chains n] (a cell's draws contiguous, chain-major), out [n_cols]. */
+PPCX_API int ppcx_testing_relative_eff(int chains, int n, int n_cols, const double* ll, double* out);
 #ifdef __cplusplus
 }
 #endif

@@ -195,7 +195,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                  check_convergence=False,
                  check_approximation=False,
                  check_loo=False,
-                 check_loo_intervals=False):
+                 check_loo_intervals=False,
+                 loo_r_eff=None):
     """One inference pass (discovery or test) of ppcseq on the GPU.
 
     counts            G x S integer matrix, genes ordered with the `how_many_to_check` checked genes first
@@ -227,6 +228,10 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                       interval probabilities, seed and truncation compensation, kept as `res.loo_intervals`. It raises no
                       warning (the k-hat warnings are check_loo's) and changes no flag. devices=[...]: over the pooled chains.
                       Not for an ADVI pass.
+    loo_r_eff         None: check_loo and check_loo_intervals take r_eff = 1 (loo::loo(log_lik)). "auto": the relative efficiency
+                      of every checked cell from the fit's own chains on the device (Fit.relative_eff; 1 where it is not
+                      defined), as rstan::loo(fit) does; the results then carry it as `r_eff`. devices=[...]: over the pooled
+                      chains (the split is the same). Needs check_loo or check_loo_intervals.
     Returns an InferenceResult.
     """
     counts = np.asarray(counts)
@@ -259,6 +264,7 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
     if check_loo_intervals and approximate_posterior_inference:
         raise ValueError("check_loo_intervals needs a NUTS pass: PSIS-LOO of an ADVI fit (loo_approximate_posterior) is not "
                          "available")
+    _check_loo_r_eff(loo_r_eff, check_loo, check_loo_intervals)
     if devices is not None and len(devices) > 1 and (save_generated_quantities or pass_fit or model is not None or approximate_posterior_inference):
         raise ValueError("devices=[...] splits the chains of a NUTS fit over several devices and pools their draws: it cannot "
                          "be combined with save_generated_quantities, pass_fit, a caller's model or approximate_posterior_inference")
@@ -266,7 +272,7 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
         return _do_inference_devices(counts, X, exposure_rate, K, list(devices), chains, n_iter, warmup, excl,
                                      lambda_mu_mu, approximate_posterior_analysis, adj_prob_theshold,
                                      how_many_posterior_draws, truncation_compensation, seed, launch, check_convergence,
-                                     check_loo, check_loo_intervals)
+                                     check_loo, check_loo_intervals, loo_r_eff)
     if devices is not None and len(devices) >= 1 and model is None:
         device = devices[0]
     own_model = model is None
@@ -314,10 +320,10 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                 res.convergence = fit.summary(np.arange(off_alpha1, off_alpha1 + K), lp=True)
                 _warn_convergence(res.convergence, chains)
             if check_loo:
-                res.loo = fit.loo(np.arange(K))
+                res.loo = fit.loo(np.arange(K), r_eff=loo_r_eff)
                 _warn_loo(res.loo, fit.chains * fit.n_keep)
             if check_loo_intervals:
-                res.loo_intervals = fit.loo_predict(np.arange(K), p_lo=p, p_hi=1 - p, seed=seed,
+                res.loo_intervals = fit.loo_predict(np.arange(K), r_eff=loo_r_eff, p_lo=p, p_hi=1 - p, seed=seed,
                                                     truncation_compensation=truncation_compensation)
         res.counts_rng = rng
         if pass_fit:
@@ -328,6 +334,15 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
             if own_model:
                 model.close()
     return res
+
+
+def _check_loo_r_eff(loo_r_eff, check_loo, check_loo_intervals):
+    if loo_r_eff is None:
+        return
+    if not (isinstance(loo_r_eff, str) and loo_r_eff == "auto"):
+        raise ValueError(f'loo_r_eff must be None or "auto", not {loo_r_eff!r}')
+    if not (check_loo or check_loo_intervals):
+        raise ValueError("loo_r_eff needs check_loo or check_loo_intervals: it is the r_eff of their PSIS")
 
 
 def _to_cell_ids(to_exclude, S):
@@ -371,7 +386,7 @@ def checked_columns(G, C, K):
 
 def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, approximate_posterior_analysis,
                    adj_prob_theshold, how_many_posterior_draws, truncation_compensation, seed, device=0, convergence=False,
-                   loo=False, excl=None, loo_intervals=False):
+                   loo=False, excl=None, loo_intervals=False, loo_r_eff=None):
     """Credible intervals, slopes and flags from the pooled draws of all chains (rstan::summary over merged chains,
     R/utilities.R:685-703): `draws_checked` is [chains, n_keep, len(checked_columns)] in global chain order. The
     posterior-predictive kernel runs on a model that holds the K checked genes only -- cell ids g*S+s and draw indices are
@@ -379,7 +394,7 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
     summary of alpha_sub_1 over the pooled chains (res.convergence; Fit.summary). loo: also PSIS-LOO of the checked cells over
     the pooled chains (res.loo; Fit.loo); the small model then carries the checked genes' cells of `excl` (0-based cell ids of
     the full model), so that the cells excluded from the fit are held out. loo_intervals: also their leave-one-out predictive
-    intervals (res.loo_intervals; Fit.loo_predict), likewise."""
+    intervals (res.loo_intervals; Fit.loo_predict), likewise. loo_r_eff: their r_eff (None or "auto", do_inference)."""
     counts = np.asarray(counts)
     X = np.asarray(X, dtype=np.float64).reshape(counts.shape[1], -1)
     small_excl = None
@@ -397,10 +412,10 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
                 ci = fit.ppc(truncation_compensation, p, 1 - p, seed=seed, n_gen=0, resample=False)
             slope = fit.columns(np.arange(3 + K, 3 + 2 * K)).reshape(-1, K).mean(axis=0) if K else np.zeros(0)
             conv = fit.summary(np.arange(3 + K, 3 + 2 * K), lp=False) if convergence else None
-            loo_res = fit.loo(np.arange(K)) if loo and K else None
+            loo_res = fit.loo(np.arange(K), r_eff=loo_r_eff) if loo and K else None
             loo_int = None
             if loo_intervals and K:
-                loo_int = fit.loo_predict(np.arange(K), p_lo=p, p_hi=1 - p, seed=seed,
+                loo_int = fit.loo_predict(np.arange(K), r_eff=loo_r_eff, p_lo=p, p_hi=1 - p, seed=seed,
                                           truncation_compensation=truncation_compensation)
         finally:
             fit.close()
@@ -417,7 +432,7 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
 def _do_inference_devices(counts, X, exposure_rate, K, devices, chains, n_iter, warmup, excl, lambda_mu_mu,
                           approximate_posterior_analysis, adj_prob_theshold, how_many_posterior_draws,
                           truncation_compensation, seed, launch=None, check_convergence=False, check_loo=False,
-                          check_loo_intervals=False):
+                          check_loo_intervals=False, loo_r_eff=None):
     """Chains split over several devices of this process (one host thread per device; the C ABI allows different handles
     on different threads), pooled summary on the first device."""
     import threading
@@ -459,7 +474,7 @@ def _do_inference_devices(counts, X, exposure_rate, K, devices, chains, n_iter, 
                          approximate_posterior_analysis=approximate_posterior_analysis, adj_prob_theshold=adj_prob_theshold,
                          how_many_posterior_draws=how_many_posterior_draws, truncation_compensation=truncation_compensation,
                          seed=seed, device=devices[0], convergence=check_convergence, loo=check_loo, excl=excl,
-                         loo_intervals=check_loo_intervals)
+                         loo_intervals=check_loo_intervals, loo_r_eff=loo_r_eff)
     res.chains, res.iter = chains, n_iter
     if check_convergence:
         _warn_convergence(res.convergence, chains)

@@ -15,7 +15,7 @@ import warnings
 
 import numpy as np
 
-from .inference import do_inference
+from .inference import _check_loo_r_eff, do_inference
 
 
 def parse_formula(formula: str):
@@ -118,7 +118,7 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                       cores=None, pass_fit=False, do_check_only_on_detrimental=None, tol_rel_obj=0.01,
                       just_discovery=False, seed=None, adj_prob_theshold_2=None, device=0, devices=None, launch=None, _pass=None,
                       check_convergence=False, check_approximation=False, check_loo=False,
-                      check_loo_intervals=False):
+                      check_loo_intervals=False, loo_r_eff=None):
     """Mirror of ppcseq::identify_outliers (R/methods.R:74-367): same arguments, same defaults.
 
     data is a tidy pandas DataFrame (one row per transcript x sample); column arguments are strings. As in the
@@ -147,6 +147,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
     checked cells from their own fit (Fit.loo_predict: [K, S] mean, lower, upper, pit_lt, pit_le, khat, y, outside, excluded) at
     the pass's interval probabilities, seed and truncation compensation, in out.attrs["loo_intervals_discovery"] and
     ["loo_intervals_test"]. They are reported only: the cells flagged stay those of the reference's rule, no warning is raised.
+    `loo_r_eff` = "auto" (with check_loo or check_loo_intervals): their PSIS takes the relative efficiency of every checked cell
+    from the pass's own chains (Fit.relative_eff), as rstan::loo(fit) does, and the results carry it as `r_eff`; None: r_eff = 1.
     """
     import os
     import pandas as pd
@@ -180,6 +182,7 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                          "not available")
     if check_loo_intervals and _pass is not None:
         raise ValueError("check_loo_intervals is not available for passes over several ranks")
+    _check_loo_r_eff(loo_r_eff, check_loo, check_loo_intervals)
     if check_convergence and _pass is not None:
         raise ValueError("check_convergence is not available for passes over several ranks")
     if approximate_posterior_inference and save_generated_quantities:
@@ -267,6 +270,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
             where.update(check_loo=True)
         if check_loo_intervals:
             where.update(check_loo_intervals=True)
+        if loo_r_eff is not None:
+            where.update(loo_r_eff=loo_r_eff)
     try:
         # ---- pass 1: discovery (R/methods.R:268-286); always the full posterior analysis
         res1 = run_pass(counts, X, exposure_rate, K,
