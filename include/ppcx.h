@@ -147,8 +147,8 @@ PPCX_API int ppcx_fit_summary(ppcx_fit* f, int n_cols, const int32_t* cols, doub
 PPCX_API int ppcx_fit_get_approximation(ppcx_fit* f, double* mu, double* omega);
 PPCX_API int ppcx_fit_get_log_ratios(ppcx_fit* f, double* log_p, double* log_g);
 PPCX_API int ppcx_fit_psis(ppcx_fit* f, int n_cols, const int32_t* cols, double* khat);
-/* PSIS-LOO per observed cell of a NUTS fit (what rstan::loo(fit) / loo::loo(log_lik, r_eff) report per observation, without
- * the MCSE). Every count is one observation: cell (g, s) of a gene g in genes[0 .. n_genes) and a sample s. NUTS fits of every
+/* PSIS-LOO per observed cell of a NUTS fit (what rstan::loo(fit) / loo::loo(log_lik, r_eff) report per observation; the
+ * Monte-Carlo standard error and the effective sample size through ppcx_fit_loo_mcse). Every count is one observation: cell (g, s) of a gene g in genes[0 .. n_genes) and a sample s. NUTS fits of every
  * entry point and ppcx_fit_from_draws fits; an ADVI fit, a gene out of range or a bad r_eff: PPCX_ERR_ARG. Synchronous on the
  * model's stream; the same bits on every call, whatever other genes are requested.
  *   ppcx_fit_get_log_lik  log_lik = neg_binomial_2_log_lpmf(y | exposure_s + X_s alpha_g, exp(-sigma_raw_g)) with every constant
@@ -163,6 +163,17 @@ PPCX_API int ppcx_fit_psis(ppcx_fit* f, int n_cols, const int32_t* cols, double*
 #define PPCX_LOO_FIELDS 4       /* elpd_loo, p_loo, looic, khat */
 PPCX_API int ppcx_fit_get_log_lik(ppcx_fit* f, int n_genes, const int32_t* genes, double* out);
 PPCX_API int ppcx_fit_loo(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double* out);
+/* ppcx_fit_loo with how far each cell's elpd_loo can be trusted once its khat is acceptable: loo::loo's pointwise mcse_elpd_loo
+ * (its deterministic form on 1 000 Blom scores) and psis_n_eff, restated from the published package. Fits, genes, r_eff, refusals
+ * and limits as ppcx_fit_loo. out [n_genes][S][PPCX_LOO_MCSE_FIELDS]: the four fields of ppcx_fit_loo, bit for bit, then
+ *   n_eff         = r_eff / sum w_i^2 over the cell's normalised PSIS weights w (r_eff = 1 where none is given);
+ *   mcse_elpd_loo = sqrt(v / r_eff), v the variance (ddof 1) of log1p(c z_j) over the scores z_j = Phi^-1((j - 3/8) / 1000.25),
+ *                   j = 1 .. 1000, with 1 + c z_j > 0, c = sqrt(sum w_i^2 expm1(log_lik_i - elpd_loo)^2), elpd_loo taken within the
+ *                   range of the cell's log_lik (a constant column: c = 0, mcse_elpd_loo = 0).
+ * A cell excluded by the model has uniform weights: n_eff = N r_eff (khat stays NaN). A cell that is NaN in ppcx_fit_loo is NaN in
+ * both. The same bits on every call, whatever other genes are requested.                                                       */
+#define PPCX_LOO_MCSE_FIELDS 6  /* elpd_loo, p_loo, looic, khat, mcse_elpd_loo, n_eff */
+PPCX_API int ppcx_fit_loo_mcse(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double* out);
 /* The relative efficiency of the importance ratios per observed cell of a NUTS fit: what rstan::loo(fit) passes to loo::loo as
  * r_eff, loo::relative_eff(exp(log_lik), chain_id), so that ppcx_fit_loo / ppcx_fit_loo_predict with it report what rstan::loo(fit)
  * does without the log-likelihood matrix ever leaving the device. Fits, genes and refusals as ppcx_fit_loo; more than 128 chains:

@@ -25,11 +25,12 @@ EXPORTS = [
     "ppcx_xchg_create", "ppcx_xchg_handle", "ppcx_xchg_connect", "ppcx_xchg_connect_local", "ppcx_xchg_set_timeout", "ppcx_xchg_destroy",
     "ppcx_fit_nuts_xchg", "ppcx_fit_get_xchg_timing", "ppcx_fit_get_inv_metric", "ppcx_fit_summary",
     "ppcx_fit_get_approximation", "ppcx_fit_get_log_ratios", "ppcx_fit_psis", "ppcx_fit_get_log_lik", "ppcx_fit_loo",
-    "ppcx_fit_loo_predict", "ppcx_fit_relative_eff",
+    "ppcx_fit_loo_predict", "ppcx_fit_relative_eff", "ppcx_fit_loo_mcse",
 ]
 ABI_VERSION = 400           # include/ppcx.h PPCX_VERSION this binding was written for
 SUMMARY_FIELDS = ("mean", "sd", "q05", "q50", "q95", "rhat", "ess_bulk", "ess_tail")   # PPCX_SUMMARY_FIELDS, in order
 LOO_FIELDS = ("elpd_loo", "p_loo", "looic", "khat")                                      # PPCX_LOO_FIELDS, in order
+LOO_MCSE_FIELDS = LOO_FIELDS + ("mcse_elpd_loo", "n_eff")                                # PPCX_LOO_MCSE_FIELDS, in order
 LOO_PREDICT_FIELDS = ("mean", "lower", "upper", "pit_lt", "pit_le", "khat")              # PPCX_LOO_PREDICT_FIELDS, in order
 
 
@@ -103,6 +104,7 @@ def load() -> C.CDLL:
     lib.ppcx_fit_psis.argtypes = [C.c_void_p, C.c_int, ip, dp]
     lib.ppcx_fit_get_log_lik.argtypes = [C.c_void_p, C.c_int, ip, dp]
     lib.ppcx_fit_loo.argtypes = [C.c_void_p, C.c_int, ip, dp, dp]
+    lib.ppcx_fit_loo_mcse.argtypes = [C.c_void_p, C.c_int, ip, dp, dp]
     lib.ppcx_fit_loo_predict.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_double, C.c_double, C.c_double, C.c_ulonglong, dp]
     lib.ppcx_fit_relative_eff.argtypes = [C.c_void_p, C.c_int, ip, dp]
     lib.ppcx_fit_get_diagnostics.argtypes = [C.c_void_p, dp, dp, ip, ip, ip, dp]
@@ -137,6 +139,8 @@ def load() -> C.CDLL:
         lib.ppcx_testing_psis.argtypes = [C.c_int, C.c_int, dp, dp, dp]
     if hasattr(lib, "ppcx_testing_loo"):
         lib.ppcx_testing_loo.argtypes = [C.c_int, C.c_int, dp, ip, dp, dp]
+    if hasattr(lib, "ppcx_testing_loo_mcse"):
+        lib.ppcx_testing_loo_mcse.argtypes = [C.c_int, C.c_int, dp, ip, dp, dp]
     if hasattr(lib, "ppcx_testing_loo_predict"):
         lib.ppcx_testing_loo_predict.argtypes = [dp, ip, C.c_int, C.c_int, ip, ip, dp, C.c_double, C.c_double, dp]
     if hasattr(lib, "ppcx_testing_relative_eff"):
@@ -226,9 +230,19 @@ def testing_psis(lr, cols=None):
 def testing_loo(ll, excluded=None, r_eff=None):
     """PSIS-LOO kernel on host-given log-likelihood columns (testing build only; csrc/ppcx_testing.h ppcx_testing_loo): ll
     [n_draws, n_cells], excluded / r_eff None or [n_cells]. Returns [n_cells, 4]: elpd_loo, p_loo, looic, khat."""
+    return _testing_loo("ppcx_testing_loo", LOO_FIELDS, ll, excluded, r_eff)
+
+
+def testing_loo_mcse(ll, excluded=None, r_eff=None):
+    """testing_loo as ppcx_fit_loo_mcse runs the kernel (csrc/ppcx_testing.h ppcx_testing_loo_mcse). Returns [n_cells, 6]:
+    elpd_loo, p_loo, looic, khat, mcse_elpd_loo, n_eff."""
+    return _testing_loo("ppcx_testing_loo_mcse", LOO_MCSE_FIELDS, ll, excluded, r_eff)
+
+
+def _testing_loo(entry, fields, ll, excluded, r_eff):
     lib = load()
-    if not hasattr(lib, "ppcx_testing_loo"):
-        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before ppcx_testing_loo existed: rebuild it "
+    if not hasattr(lib, entry):
+        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before {entry} existed: rebuild it "
                         "(`python -m ppcseq_amd.build --testing --force`)")
     ll = np.asarray(ll, dtype=np.float64)
     ll = ll.reshape(ll.shape[0], -1)
@@ -236,9 +250,9 @@ def testing_loo(ll, excluded=None, r_eff=None):
     cols = np.ascontiguousarray(ll.T)
     ex = None if excluded is None else np.ascontiguousarray(excluded, dtype=np.int32).ravel()
     re = None if r_eff is None else np.ascontiguousarray(r_eff, dtype=np.float64).ravel()
-    out = np.zeros((nc, len(LOO_FIELDS)))
-    _check(lib.ppcx_testing_loo(n, nc, _p(cols, C.c_double), _p(ex, C.c_int32) if ex is not None else None,
-                                _p(re, C.c_double) if re is not None else None, _p(out, C.c_double)))
+    out = np.zeros((nc, len(fields)))
+    _check(getattr(lib, entry)(n, nc, _p(cols, C.c_double), _p(ex, C.c_int32) if ex is not None else None,
+                               _p(re, C.c_double) if re is not None else None, _p(out, C.c_double)))
     return out
 
 
@@ -661,20 +675,25 @@ class Fit:
             return np.ascontiguousarray(np.where(np.isnan(re), 1.0, re))
         return np.ascontiguousarray(np.broadcast_to(np.asarray(r_eff, dtype=np.float64), (g.size, self.model.S)))
 
-    def loo(self, genes=None, r_eff=None):
+    def loo(self, genes=None, r_eff=None, mcse=False):
         """PSIS-LOO per observed cell on the device (ppcx_fit_loo; rstan::loo / loo::loo(log_lik, r_eff)): a dict of the
         pointwise elpd_loo, p_loo, looic and khat, [n_genes, S] each, `excluded` (the cells the model holds out now: elpd_loo is
         their exact held-out density, p_loo 0, khat NaN), `genes`, `n_draws`, and `estimates`: {elpd_loo, p_loo, looic: (sum, se)} over the
         non-excluded cells as loo reports them. genes=None: all G genes; r_eff None (all 1), [n_genes, S], or "auto": relative_eff
-        of the same cells (1 where it is NaN), as rstan::loo(fit) does; the result then carries it as `r_eff`."""
+        of the same cells (1 where it is NaN), as rstan::loo(fit) does; the result then carries it as `r_eff`.
+        mcse=True (ppcx_fit_loo_mcse; the fields above are the same bits): also loo's pointwise `mcse_elpd_loo` (the Monte-Carlo
+        standard error of the cell's elpd_loo) and `n_eff` (the effective sample size of its PSIS weights; N r_eff for an
+        excluded cell), [n_genes, S] each, and `mcse_elpd_loo_total` (inference.loo_mcse_total: loo's mcse_loo)."""
         g = self._genes(genes)
         S = self.model.S
-        out = np.zeros((g.size, S, len(LOO_FIELDS)))
+        fields = LOO_MCSE_FIELDS if mcse else LOO_FIELDS
+        out = np.zeros((g.size, S, len(fields)))
         re = self._r_eff(g, r_eff)
         if g.size:
-            _check(load().ppcx_fit_loo(self._h, int(g.size), _p(g, C.c_int32), _p(re, C.c_double) if re is not None else None,
-                                       _p(out, C.c_double)))
-        res = {k: out[:, :, i].copy() for i, k in enumerate(LOO_FIELDS)}
+            entry = load().ppcx_fit_loo_mcse if mcse else load().ppcx_fit_loo
+            _check(entry(self._h, int(g.size), _p(g, C.c_int32), _p(re, C.c_double) if re is not None else None,
+                         _p(out, C.c_double)))
+        res = {k: out[:, :, i].copy() for i, k in enumerate(fields)}
         excl = np.zeros(self.model.G * S, bool)
         excl[np.asarray(self.model.excl, dtype=np.int64)] = True
         res["excluded"] = excl.reshape(self.model.G, S)[g]
@@ -683,6 +702,9 @@ class Fit:
         if isinstance(r_eff, str):
             res["r_eff"] = re
         res["estimates"] = loo_estimates(res, res["excluded"])
+        if mcse:
+            from .inference import loo_mcse_total
+            res["mcse_elpd_loo_total"] = loo_mcse_total(res)
         return res
 
     def loo_predict(self, genes=None, r_eff=None, p_lo=0.025, p_hi=0.975, seed=1, truncation_compensation=1.0):

@@ -1971,7 +1971,8 @@ static double loo_reff_min(const double* r_eff, long n) {
   for (long i = 0; r_eff && i < n; ++i) mn = i == 0 || r_eff[i] < mn ? r_eff[i] : mn;
   return mn;
 }
-extern "C" int ppcx_fit_loo(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double* out) {
+// ppcx_fit_loo (fields = kLooFields) and ppcx_fit_loo_mcse (kLooMcseFields): the same checks, limits and walk
+static int fit_loo(const char* who, ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, int fields, double* out) {
   std::vector<int> yenc;
   int rc = loo_prepare(f, n_genes, genes, yenc);
   if (rc != PPCX_OK) return rc;
@@ -1980,11 +1981,17 @@ extern "C" int ppcx_fit_loo(ppcx_fit* f, int n_genes, const int32_t* genes, cons
   const long n = (long)f->chains * f->n_keep, ncells = (long)n_genes * m->d.S;
   if ((rc = loo_check_reff(r_eff, ncells)) != PPCX_OK) return rc;
   const double rmin = loo_reff_min(r_eff, ncells);
-  if (psis_tail_len(n, rmin) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "ppcx_fit_loo: the tail exceeds 4095 draws");
-  hipError_t e = loo_fit_cells(f->d_draws.p, n, m->d, m->d_expo, m->d_X, n_genes, genes, yenc.data(), r_eff, rmin, out,
+  if (psis_tail_len(n, rmin) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, std::string(who) + ": the tail exceeds 4095 draws");
+  hipError_t e = loo_fit_cells(f->d_draws.p, n, m->d, m->d_expo, m->d_X, n_genes, genes, yenc.data(), r_eff, rmin, fields, out,
                                loo_scratch_bytes(), m->stream);
-  if (e != hipSuccess) return fail(PPCX_ERR_HIP, std::string("ppcx_fit_loo: ") + hipGetErrorString(e));
+  if (e != hipSuccess) return fail(PPCX_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
   return PPCX_OK;
+}
+extern "C" int ppcx_fit_loo(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double* out) {
+  return fit_loo("ppcx_fit_loo", f, n_genes, genes, r_eff, kLooFields, out);
+}
+extern "C" int ppcx_fit_loo_mcse(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double* out) {
+  return fit_loo("ppcx_fit_loo_mcse", f, n_genes, genes, r_eff, kLooMcseFields, out);
 }
 // ---- the leave-one-out predictive interval and LOO-PIT of the same cells (loo::E_loo / bayesplot::ppc_loo_intervals, ppc_loo_pit)
 static int loo_predict_check_probs(double p_lo, double p_hi) {
@@ -2012,15 +2019,22 @@ extern "C" int ppcx_fit_loo_predict(ppcx_fit* f, int n_genes, const int32_t* gen
 }
 #ifdef PPCX_TESTING
 // testing build only (ppcx_testing.h): the LOO kernel on host-given columns, on the current device
-extern "C" int ppcx_testing_loo(int n, int n_cols, const double* ll, const int32_t* excluded, const double* r_eff, double* out) {
+static int testing_loo(int n, int n_cols, const double* ll, const int32_t* excluded, const double* r_eff, int fields, double* out) {
   if (n < 1 || n_cols < 1 || !ll || !out) return fail(PPCX_ERR_ARG, "bad arguments");
   int rc = loo_check_reff(r_eff, n_cols);
   if (rc != PPCX_OK) return rc;
   const double rmin = loo_reff_min(r_eff, n_cols);
   if (psis_tail_len(n, rmin) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "too many draws");
-  hipError_t e = loo_columns(ll, n, n_cols, excluded, r_eff, rmin, out, loo_scratch_bytes(), nullptr);
+  hipError_t e = loo_columns(ll, n, n_cols, excluded, r_eff, rmin, fields, out, loo_scratch_bytes(), nullptr);
   if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
   return PPCX_OK;
+}
+extern "C" int ppcx_testing_loo(int n, int n_cols, const double* ll, const int32_t* excluded, const double* r_eff, double* out) {
+  return testing_loo(n, n_cols, ll, excluded, r_eff, kLooFields, out);
+}
+// ... with mcse_elpd_loo and n_eff (the kernel of ppcx_fit_loo_mcse)
+extern "C" int ppcx_testing_loo_mcse(int n, int n_cols, const double* ll, const int32_t* excluded, const double* r_eff, double* out) {
+  return testing_loo(n, n_cols, ll, excluded, r_eff, kLooMcseFields, out);
 }
 #endif
 #ifdef PPCX_TESTING

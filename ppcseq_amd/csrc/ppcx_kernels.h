@@ -228,20 +228,21 @@ struct LooArgs {
   int cell0 = 0, n_cells = 0;   // first cell of the launch; cells of the table / columns
   double* scratch = nullptr;    // [launch's cells][n] the long path's ratios
   int sel_pad = 0;              // loo_sel_pad: the selection buffer
-  double* out = nullptr;        // [cells][kLooFields]
+  double* out = nullptr;        // [cells][kLooFields], or [cells][kLooMcseFields] (ppcx_fit_loo_mcse)
 };
 int loo_sel_pad(long n, double r_eff_min);     // power of two >= M + 1 for n draws at the smallest r_eff
 // LOO of the cells of genes[0 .. n_genes) (host) for draws [n][D] (device); yenc, r_eff (null or [cells]) and out host;
-// r_eff_min: the smallest r_eff (1 without r_eff). Synchronous
+// r_eff_min: the smallest r_eff (1 without r_eff). fields: kLooFields, or kLooMcseFields for mcse_elpd_loo and n_eff as well
+// (out holds that many per cell; the first four are the same bits). Synchronous
 hipError_t loo_fit_cells(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
-                         const int* genes, const int* yenc, const double* r_eff, double r_eff_min, double* out,
+                         const int* genes, const int* yenc, const double* r_eff, double r_eff_min, int fields, double* out,
                          size_t scratch_bytes, hipStream_t st);
 // the log-likelihood matrix of those cells, [n][cells] (host out); synchronous
 hipError_t loo_fit_log_lik(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
                            const int* genes, const int* yenc, double* out, size_t scratch_bytes, hipStream_t st);
 // LOO of host-given columns cols [n_cols][n] (testing build); synchronous
-hipError_t loo_columns(const double* cols, long n, int n_cols, const int* excl, const double* r_eff, double r_eff_min, double* out,
-                       size_t scratch_bytes, hipStream_t st);
+hipError_t loo_columns(const double* cols, long n, int n_cols, const int* excl, const double* r_eff, double r_eff_min, int fields,
+                       double* out, size_t scratch_bytes, hipStream_t st);
 // The leave-one-out predictive interval and LOO-PIT of the same cells (ppcx_loo_predict.hip, statistic in ppcx_loo_predict.h): one
 // workgroup per cell; ratios, weights and predictive counts (20 bytes per draw) in LDS up to kPsisLdsDraws draws, beyond that in
 // the scratch, bounded like the gene table. tc: truncation compensation of the predictive draws; k0 = seed32(seed). out (host)

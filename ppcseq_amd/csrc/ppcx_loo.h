@@ -26,16 +26,32 @@
 //   draw carries more than its ll: ppcx_loo_predict.h step 2 fixes the order (a stable sort: tied draws in draw order).
 // An excluded cell (not in the likelihood at the time of the call) is already held out: elpd_loo = lpd, p_loo = 0,
 // looic = -2 lpd, khat = NaN (a NaN ll: all NaN; ll = +Inf takes no part).
+//
+// The Monte-Carlo standard error of elpd_loo and the effective sample size of the PSIS weights (ppcx_fit_loo_mcse: as loo::loo
+// reports mcse_elpd_loo -- deterministic Blom-score form, n_samples = 1000 -- and psis_n_eff; restated from the published
+// package, not run against it). For a cell that is not NaN, with w_i its normalised weights (those behind elpd_loo: step 3,
+// raw where khat = +Inf; uniform 1 / N for an excluded cell), sum w_i = 1, and r its r_eff (1 without):
+//   5. n_eff = r / sum w_i^2 (an excluded cell: N r, formed as that product).
+//   6. c = sqrt(sum w_i^2 expm1(ll_i - e)^2), e = elpd_loo: loo's sd_epd / E_epd, in the shifted frame, which stays defined
+//      where exp(ll) underflows. e is elpd_loo brought into [min ll, max ll], where it lies but for the rounding of the two
+//      logsumexps: a constant column then gives c = 0 exactly.
+//   7. z_j = 1 + c blom_z(j, 1000), j = 1 .. 1000 (ppcx_summary.h: Phi^-1((j - 3/8) / (1000 + 1/4)); loo's E + sd z over E);
+//      v = the variance (ddof 1) of log1p(c blom_z(j, 1000)) over the j with z_j > 0 (at least 500 of them).
+//   8. mcse_elpd_loo = sqrt(v / r).
+//   A cell that is NaN above, or without a participating draw, is NaN in both.
 // Every reduction runs in a fixed order: a cell's fields depend on its own column only.
 #pragma once
 #include <stdint.h>
 #include "ppcx_math.h"
 #include "ppcx_disp.h"
 #include "ppcx_psis.h"
+#include "ppcx_summary.h"
 
 namespace ppcx {
 
 constexpr int kLooFields = 4;                  // elpd_loo, p_loo, looic, khat (include/ppcx.h PPCX_LOO_FIELDS)
+constexpr int kLooMcseFields = 6;              // those, mcse_elpd_loo, n_eff (include/ppcx.h PPCX_LOO_MCSE_FIELDS)
+constexpr int kLooMcseScores = 1000;           // loo's n_samples: the Blom scores of step 7
 
 // ln(1 + e^t) for every t
 PPCX_HD double loo_log1pexp(double t) {
@@ -62,6 +78,33 @@ PPCX_HD double loo_smoothed(int j, int M, double khat, double sigma, double ec) 
 // whether the tail is replaced (step 2)
 PPCX_HD bool loo_smooth_ok(double khat, double sigma) { return isfinite(khat) && sigma > 0.0; }
 
+// ---- steps 5 - 8
+// e of step 6: elpd_loo within the range of the participating ll
+PPCX_HD double loo_mcse_frame(double elpd, double ll_min, double ll_max) { return fmin(fmax(elpd, ll_min), ll_max); }
+// one draw's terms (mult copies): w = exp(lw - lse) its normalised weight; *w2 += w^2, *c2 += (w expm1(ll - e))^2
+PPCX_HD void loo_mcse_add(double lw, double ll, double lse, double e, double mult, double* w2, double* c2) {
+  PPCX_NO_CONTRACT
+  const double w = exp(lw - lse);
+  const double d = w * expm1(ll - e);
+  *w2 += mult * (w * w);
+  *c2 += mult * (d * d);
+}
+// one draw's term of an excluded cell before the division by N^2: expm1(ll - e)^2
+PPCX_HD double loo_mcse_uniform_term(double ll, double e) {
+  PPCX_NO_CONTRACT
+  const double d = expm1(ll - e);
+  return d * d;
+}
+PPCX_HD double loo_mcse_uniform_c2(double sum, long N) { return sum / ((double)N * (double)N); }
+// step 7, score j = 1 .. kLooMcseScores: log1p(c blom_z(j)), NaN where z_j <= 0 (the score takes no part)
+PPCX_HD double loo_mcse_score(int j, double c) {
+  PPCX_NO_CONTRACT
+  const double t = c * blom_z((double)j, kLooMcseScores);
+  return 1.0 + t > 0.0 ? log1p(t) : NAN;
+}
+// step 8 from the sum of squared deviations of the cnt scores that take part
+PPCX_HD double loo_mcse_from(double ss, double cnt, double r_eff) { return cnt >= 2.0 ? sqrt(ss / (cnt - 1.0) / r_eff) : NAN; }
+
 }  // namespace ppcx
 
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -76,10 +119,21 @@ inline double loo_logsumexp_host(const std::vector<double>& v) {
   for (double x : v) s += exp(x - mx);
   return mx + log(s);
 }
-// the whole spec for one cell, sequentially, for the CPU check: out[kLooFields]
-inline void loo_cell_host(const double* ll, long n, double r_eff, bool excluded, double* out) {
+// steps 7 - 8, sequentially
+inline double loo_mcse_blom_host(double c, double r_eff) {
+  std::vector<double> x;
+  for (int j = 1; j <= kLooMcseScores; ++j) { const double v = loo_mcse_score(j, c); if (!isnan(v)) x.push_back(v); }
+  double s = 0.0, ss = 0.0;
+  for (double v : x) s += v;
+  const double mean = s / (double)x.size();
+  for (double v : x) ss += (v - mean) * (v - mean);
+  return loo_mcse_from(ss, (double)x.size(), r_eff);
+}
+// the whole spec for one cell, sequentially, for the CPU check: out[kLooFields], or out[kLooMcseFields] with mcse
+inline void loo_cell_host(const double* ll, long n, double r_eff, bool excluded, double* out, bool mcse = false) {
   std::vector<double> l;
   l.reserve((size_t)n);
+  if (mcse) out[4] = out[5] = NAN;
   for (long i = 0; i < n; ++i) {
     const double r = -ll[i];
     if (isnan(r) || (!excluded && r == INFINITY)) { out[0] = out[1] = out[2] = out[3] = NAN; return; }
@@ -87,7 +141,19 @@ inline void loo_cell_host(const double* ll, long n, double r_eff, bool excluded,
   }
   const long N = (long)l.size();
   const double lpd = N > 0 ? loo_logsumexp_host(l) - log((double)N) : NAN;
-  if (excluded) { out[0] = lpd; out[1] = 0.0; out[2] = -2.0 * lpd; out[3] = NAN; return; }
+  double ll_min = INFINITY, ll_max = -INFINITY;
+  for (double x : l) { ll_min = x < ll_min ? x : ll_min; ll_max = x > ll_max ? x : ll_max; }
+  if (excluded) {
+    out[0] = lpd; out[1] = 0.0; out[2] = -2.0 * lpd; out[3] = NAN;
+    if (mcse && N > 0) {
+      const double e = loo_mcse_frame(lpd, ll_min, ll_max);
+      double sum = 0.0;
+      for (double x : l) sum += loo_mcse_uniform_term(x, e);
+      out[4] = loo_mcse_blom_host(sqrt(loo_mcse_uniform_c2(sum, N)), r_eff);
+      out[5] = (double)N * r_eff;
+    }
+    return;
+  }
   // ratios sorted ascending, each with its draw's ll (tied ratios have equal ll)
   std::vector<double> r(N);
   for (long i = 0; i < N; ++i) r[i] = -l[i];
@@ -106,8 +172,16 @@ inline void loo_cell_host(const double* ll, long n, double r_eff, bool excluded,
   }
   std::vector<double> a(N);
   for (long i = 0; i < N; ++i) { lw[i] = lw[i] > 0.0 ? 0.0 : lw[i]; a[i] = lw[i] - r[i]; }
-  const double elpd = loo_logsumexp_host(a) - loo_logsumexp_host(lw);
+  const double lse = loo_logsumexp_host(lw);
+  const double elpd = loo_logsumexp_host(a) - lse;
   out[0] = elpd; out[1] = lpd - elpd; out[2] = -2.0 * elpd; out[3] = khat;
+  if (mcse) {
+    const double e = loo_mcse_frame(elpd, ll_min, ll_max);
+    double w2 = 0.0, c2 = 0.0;
+    for (long i = 0; i < N; ++i) loo_mcse_add(lw[i], -r[i], lse, e, 1.0, &w2, &c2);
+    out[4] = loo_mcse_blom_host(sqrt(c2), r_eff);
+    out[5] = r_eff / w2;
+  }
 }
 }  // namespace ppcx
 #endif

@@ -10,8 +10,10 @@
 //                          of T, through L2), as ratios r = -ll in LDS (up to kPsisLdsDraws draws) or in the workgroup's slice
 //                          of a bounded global scratch; the M + 1 largest selected exactly and sorted (ppcx_psis_dev.h, the
 //                          radix selection of the Pareto-k kernel), the profile fit, the smoothed tail and three logsumexp
-//                          reductions (lpd; the weights; the weights times the likelihood). The testing build runs it on
-//                          host-given columns too.
+//                          reductions (lpd; the weights; the weights times the likelihood). With MCSE (ppcx_fit_loo_mcse) one
+//                          more sweep over the same terms with the known normaliser gives sum w^2 and sum w^2 expm1^2, then
+//                          the 1000 Blom scores, at most four per thread in registers, the Monte-Carlo standard error. The
+//                          testing build runs it on host-given columns too.
 // Every reduction runs in a fixed order and a cell reads nothing of another cell: its fields are the same bits whatever else is
 // requested and however the work is batched. The G S x n matrix is never materialised for LOO.
 #include <hip/hip_runtime.h>
@@ -60,8 +62,32 @@ __global__ __launch_bounds__(256) void ppcx_loo_ll_kernel(LooArgs a, long j0, lo
 }
 
 struct LooTerms { double a, b; };                // running max or sum of the two logsumexps: a over lw + ll, b over lw
+enum LooSweep : int { LOO_MAX = 0, LOO_SUM, LOO_MCSE };   // what a sweep over the terms accumulates
 
-template <bool LDS, bool COLS>
+// ppcx_loo.h steps 7 - 8 by the workgroup: the scores in registers, mean and variance by fixed-order block sums
+__device__ inline double loo_mcse_blom(double c, double r_eff, double* red) {
+  PPCX_NO_CONTRACT
+  constexpr int kPer = (kLooMcseScores + kBlockThreads - 1) / kBlockThreads;
+  double x[kPer];
+  double s = 0.0, cnt = 0.0;
+#pragma unroll
+  for (int q = 0; q < kPer; ++q) {
+    const int j = q * kBlockThreads + (int)threadIdx.x + 1;
+    x[q] = j <= kLooMcseScores ? loo_mcse_score(j, c) : NAN;
+    if (!isnan(x[q])) { s += x[q]; cnt += 1.0; }
+  }
+  s = block_sum(s, red);
+  cnt = block_sum(cnt, red);
+  const double mean = s / cnt;
+  double ss = 0.0;
+#pragma unroll
+  for (int q = 0; q < kPer; ++q)
+    if (!isnan(x[q])) { const double d = x[q] - mean; ss += d * d; }
+  ss = block_sum(ss, red);
+  return loo_mcse_from(ss, cnt, r_eff);
+}
+
+template <bool LDS, bool COLS, bool MCSE>
 __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_kernel(LooArgs a) {
   extern __shared__ uint64_t lds_u[];
   __shared__ PsisShared sh;
@@ -75,11 +101,14 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_kernel(LooArgs a) {
   if (COLS) excluded = a.excl && a.excl[cell] != 0;
   else { const int ye = a.y[cell]; excluded = ye < 0; y = excluded ? -ye - 1 : ye; }
   const int gi = COLS ? 0 : cell / a.S, s = COLS ? 0 : cell - gi * a.S;
-  double* o = a.out + (long)cell * kLooFields;
+  double* o = a.out + (long)cell * (MCSE ? kLooMcseFields : kLooFields);
   // ---- the ratios; NaN / +Inf; N (the -Inf ratios take no part); the largest ratio and the largest ll
   long N; double rmax, lmax;
   if (loo_cell_ratios<COLS>(a, cell, gi, s, y, excluded, V, sh, &N, &rmax, &lmax)) {
-    if (tid == 0) o[0] = o[1] = o[2] = o[3] = NAN;
+    if (tid == 0) {
+      o[0] = o[1] = o[2] = o[3] = NAN;
+      if constexpr (MCSE) o[4] = o[5] = NAN;
+    }
     return;
   }
   // ---- lpd = logsumexp(ll) - log N
@@ -89,6 +118,14 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_kernel(LooArgs a) {
   const double lpd = N > 0 ? (lmax == -INFINITY ? -INFINITY : lmax + log(sl)) - log((double)N) : NAN;
   if (excluded) {                                        // already held out: the exact held-out predictive density
     if (tid == 0) { o[0] = lpd; o[1] = 0.0; o[2] = -2.0 * lpd; o[3] = NAN; }
+    if constexpr (MCSE) {                                // uniform weights 1 / N
+      const double e = loo_mcse_frame(lpd, -rmax, lmax), re = a.r_eff ? a.r_eff[cell] : 1.0;
+      double sd = 0.0;
+      for (long i = tid; i < n; i += kBlockThreads) { const double r = V[i]; if (r != -INFINITY) sd += loo_mcse_uniform_term(-r, e); }
+      sd = block_sum(sd, sh.red);
+      const double mc = N > 0 ? loo_mcse_blom(sqrt(loo_mcse_uniform_c2(sd, N)), re, sh.red) : NAN;
+      if (tid == 0) { o[4] = mc; o[5] = N > 0 ? (double)N * re : NAN; }
+    }
     return;
   }
   // ---- the tail: M + 1 largest, the profile fit, k-hat and sigma
@@ -100,9 +137,12 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_kernel(LooArgs a) {
   const PsisTail& tl = lt.tl;
   const int n_extra = smooth ? lt.n_eq - (tl.want - 1) : 0;   // copies of the cutoff outside the tail: all of them but want - 1
   // ---- logsumexp(lw + ll) and logsumexp(lw): a raw draw has lw = r - mx (<= 0), a tail draw the smoothed value truncated at 0
-  auto terms = [&](bool sum, LooTerms mxv) {
+  // (an MCSE sweep: mxv = {e, logsumexp(lw)}, a the sum of w^2 and b that of w^2 expm1(ll - e)^2)
+  auto terms = [&](LooSweep sweep, LooTerms mxv) {
+    const bool sum = sweep != LOO_MAX;
     LooTerms t{sum ? 0.0 : -INFINITY, sum ? 0.0 : -INFINITY};
     auto add = [&](double lw, double r, double mult) {
+      if constexpr (MCSE) if (sweep == LOO_MCSE) { loo_mcse_add(lw, -r, mxv.b, mxv.a, mult, &t.a, &t.b); return; }
       const double va = lw - r;
       if (sum) { t.a += mult * exp(va - mxv.a); t.b += mult * exp(lw - mxv.b); }
       else { t.a = fmax(t.a, va); t.b = fmax(t.b, lw); }
@@ -121,14 +161,22 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_kernel(LooArgs a) {
     }
     return t;
   };
-  LooTerms m0 = terms(false, LooTerms{0.0, 0.0});
+  LooTerms m0 = terms(LOO_MAX, LooTerms{0.0, 0.0});
   m0.a = block_max(m0.a, sh.red);
   m0.b = block_max(m0.b, sh.red);
-  LooTerms s0 = terms(true, m0);
+  LooTerms s0 = terms(LOO_SUM, m0);
   s0.a = block_sum(s0.a, sh.red);
   s0.b = block_sum(s0.b, sh.red);
   const double elpd = (m0.a + log(s0.a)) - (m0.b + log(s0.b));
   if (tid == 0) { o[0] = elpd; o[1] = lpd - elpd; o[2] = -2.0 * elpd; o[3] = khat; }
+  if constexpr (MCSE) {
+    const double re = a.r_eff ? a.r_eff[cell] : 1.0;
+    LooTerms q = terms(LOO_MCSE, LooTerms{loo_mcse_frame(elpd, -rmax, lmax), m0.b + log(s0.b)});
+    q.a = block_sum(q.a, sh.red);
+    q.b = block_sum(q.b, sh.red);
+    const double mc = loo_mcse_blom(sqrt(q.b), re, sh.red);
+    if (tid == 0) { o[4] = mc; o[5] = re / q.a; }
+  }
 }
 
 // ---- launch helpers (host)
@@ -144,24 +192,29 @@ hipError_t launch_loo_ll_kernel(const LooArgs& a, long j0, long n_rows, double* 
   hipLaunchKernelGGL(ppcx_loo_ll_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a, j0, n_rows, out);
   return hipGetLastError();
 }
-hipError_t launch_loo_kernel(const LooArgs& a, int n_blocks, hipStream_t st) {
+template <bool MCSE>
+static hipError_t launch_loo_kernel_of(const LooArgs& a, int n_blocks, hipStream_t st) {
   const bool lds = a.n <= kPsisLdsDraws, cols = a.cols != nullptr;
   const size_t bytes = sizeof(double) * (2 * (size_t)a.sel_pad + (lds ? (size_t)a.n : 0));
-  void (*const kernel)(LooArgs) = lds ? (cols ? ppcx_loo_kernel<true, true> : ppcx_loo_kernel<true, false>)
-                                      : (cols ? ppcx_loo_kernel<false, true> : ppcx_loo_kernel<false, false>);
+  void (*const kernel)(LooArgs) = lds ? (cols ? ppcx_loo_kernel<true, true, MCSE> : ppcx_loo_kernel<true, false, MCSE>)
+                                      : (cols ? ppcx_loo_kernel<false, true, MCSE> : ppcx_loo_kernel<false, false, MCSE>);
   return launch_dynamic_lds(kernel, n_blocks, kBlockThreads, bytes, st, a);
+}
+// fields: kLooFields, or kLooMcseFields (a.out then holds six per cell)
+hipError_t launch_loo_kernel(const LooArgs& a, int fields, int n_blocks, hipStream_t st) {
+  return fields == kLooMcseFields ? launch_loo_kernel_of<true>(a, n_blocks, st) : launch_loo_kernel_of<false>(a, n_blocks, st);
 }
 
 // Cells of a launch in batches: all at once where the ratios live in LDS, else as many as the scratch bound holds.
-static hipError_t loo_cells(LooArgs a, int n_cells, size_t scratch_bytes, DeviceBuffer<double>& scratch, hipStream_t st) {
+static hipError_t loo_cells(LooArgs a, int fields, int n_cells, size_t scratch_bytes, DeviceBuffer<double>& scratch, hipStream_t st) {
   return loo_cell_batches(n_cells, a.n > kPsisLdsDraws ? a.n : 0, scratch_bytes, scratch, [&](int c0, int nc, double* scr) {
     a.cell0 = c0; a.scratch = scr;
-    return launch_loo_kernel(a, nc, st);
+    return launch_loo_kernel(a, fields, nc, st);
   });
 }
 
 hipError_t loo_fit_cells(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
-                         const int* genes, const int* yenc, const double* r_eff, double r_eff_min, double* out,
+                         const int* genes, const int* yenc, const double* r_eff, double r_eff_min, int fields, double* out,
                          size_t scratch_bytes, hipStream_t st) {
   const int S = d.S, ncol = d.C + 1;
   const size_t ncells = (size_t)n_genes * S;
@@ -170,7 +223,7 @@ hipError_t loo_fit_cells(const double* draws, long n, const Dims& d, const doubl
   hipError_t e = d_genes.upload(genes, (size_t)n_genes, st);
   if (e == hipSuccess) e = d_y.upload(yenc, ncells, st);
   if (e == hipSuccess && r_eff) e = d_reff.upload(r_eff, ncells, st);
-  if (e == hipSuccess) e = d_out.alloc(kLooFields * ncells);
+  if (e == hipSuccess) e = d_out.alloc((size_t)fields * ncells);
   if (e == hipSuccess) e = d_T.alloc((size_t)ncol * (size_t)n * gb);
   for (int g0 = 0; e == hipSuccess && g0 < n_genes; g0 += gb) {
     const int ng = n_genes - g0 < gb ? n_genes - g0 : gb;
@@ -178,11 +231,11 @@ hipError_t loo_fit_cells(const double* draws, long n, const Dims& d, const doubl
     if (e != hipSuccess) break;
     LooArgs a;
     a.T = d_T.p; a.y = d_y.p + (size_t)g0 * S; a.expo = expo; a.X = X; a.S = S; a.C = d.C; a.n = n;
-    a.r_eff = d_reff.p ? d_reff.p + (size_t)g0 * S : nullptr; a.out = d_out.p + (size_t)g0 * S * kLooFields;
+    a.r_eff = d_reff.p ? d_reff.p + (size_t)g0 * S : nullptr; a.out = d_out.p + (size_t)g0 * S * fields;
     a.n_cells = ng * S; a.sel_pad = loo_sel_pad(n, r_eff_min);
-    e = loo_cells(a, ng * S, scratch_bytes, d_scr, st);
+    e = loo_cells(a, fields, ng * S, scratch_bytes, d_scr, st);
   }
-  if (e == hipSuccess) e = d_out.download(out, kLooFields * ncells, st);
+  if (e == hipSuccess) e = d_out.download(out, (size_t)fields * ncells, st);
   return finish(e, st);
 }
 
@@ -210,20 +263,20 @@ hipError_t loo_fit_log_lik(const double* draws, long n, const Dims& d, const dou
   return finish(e, st);
 }
 
-hipError_t loo_columns(const double* cols, long n, int n_cols, const int* excl, const double* r_eff, double r_eff_min, double* out,
-                       size_t scratch_bytes, hipStream_t st) {
+hipError_t loo_columns(const double* cols, long n, int n_cols, const int* excl, const double* r_eff, double r_eff_min, int fields,
+                       double* out, size_t scratch_bytes, hipStream_t st) {
   DeviceBuffer<double> d_cols, d_reff, d_out, d_scr; DeviceBuffer<int> d_excl;
   hipError_t e = d_cols.upload(cols, (size_t)n * n_cols, st);
   if (e == hipSuccess && excl) e = d_excl.upload(excl, (size_t)n_cols, st);
   if (e == hipSuccess && r_eff) e = d_reff.upload(r_eff, (size_t)n_cols, st);
-  if (e == hipSuccess) e = d_out.alloc(kLooFields * (size_t)n_cols);
+  if (e == hipSuccess) e = d_out.alloc((size_t)fields * (size_t)n_cols);
   if (e == hipSuccess) {
     LooArgs a;
     a.cols = d_cols.p; a.excl = d_excl.p; a.r_eff = d_reff.p; a.n = n; a.n_cells = n_cols; a.out = d_out.p;
     a.sel_pad = loo_sel_pad(n, r_eff_min);
-    e = loo_cells(a, n_cols, scratch_bytes, d_scr, st);
+    e = loo_cells(a, fields, n_cols, scratch_bytes, d_scr, st);
   }
-  if (e == hipSuccess) e = d_out.download(out, kLooFields * (size_t)n_cols, st);
+  if (e == hipSuccess) e = d_out.download(out, (size_t)fields * (size_t)n_cols, st);
   return finish(e, st);
 }
 

@@ -53,6 +53,8 @@ PPCX_API int ppcx_testing_psis(int n, int n_cols, const double* lr, const double
 /* The PSIS-LOO kernel of ppcx_fit_loo on host-given log-likelihood columns, on the current device (ppcx_loo.hip): ll [n_cols][n]
  * (column-major: a cell's n draws contiguous), excluded NULL or [n_cols] flags, r_eff NULL or [n_cols]; out [n_cols][4]. */
 PPCX_API int ppcx_testing_loo(int n, int n_cols, const double* ll, const int32_t* excluded, const double* r_eff, double* out);
+/* The same kernel as ppcx_fit_loo_mcse runs it: out [n_cols][6], the four fields above (the same bits), mcse_elpd_loo, n_eff. */
+PPCX_API int ppcx_testing_loo_mcse(int n, int n_cols, const double* ll, const int32_t* excluded, const double* r_eff, double* out);
 /* The kernel of ppcx_fit_loo_predict on host-given columns, on the current device (ppcx_loo_predict.hip): ll [n_cols][n]
  * log-likelihoods and x [n_cols][n] predictive counts (>= 0; a cell's n draws contiguous), y [n_cols] the observed counts, excluded
  * NULL or [n_cols] flags, r_eff NULL or [n_cols]; out [n_cols][6]: mean, lower, upper, pit_lt, pit_le, khat. */

@@ -163,6 +163,39 @@ def loo_warnings(khat, n_draws):
     return []
 
 
+def loo_mcse_total(loo):
+    """loo's mcse_loo from Fit.loo(mcse=True): sqrt(sum mcse_elpd_loo^2) over the non-excluded cells, the Monte-Carlo standard
+    error of their summed elpd_loo; NaN if any of their k-hats exceeds loo_threshold(n_draws) (the sum is then not to be
+    trusted at all), or without such a cell."""
+    keep = ~np.asarray(loo["excluded"], bool)
+    k = np.asarray(loo["khat"], dtype=np.float64)[keep]
+    if k.size == 0 or np.any(k[~np.isnan(k)] > loo_threshold(loo["n_draws"])):
+        return float("nan")
+    m = np.asarray(loo["mcse_elpd_loo"], dtype=np.float64)[keep]
+    return float(np.sqrt(np.sum(m * m)))
+
+
+def pareto_k_table(loo):
+    """loo's pareto_k_table of a Fit.loo result, on the host: the non-excluded cells' k-hats (NaN ones left out) in the bins
+    (-Inf, thr] (good), (thr, 1] (bad) and (1, Inf) (very bad), thr = loo_threshold(n_draws). Returns {"threshold", "bins":
+    [{"label", "lower", "upper", "count", "pct", "min_n_eff"}, ...]}: pct in percent of the cells counted; min_n_eff the smallest
+    n_eff of the bin's cells, NaN for an empty bin or a result without n_eff (Fit.loo(mcse=True) carries it)."""
+    thr = loo_threshold(loo["n_draws"])
+    keep = ~np.asarray(loo["excluded"], bool)
+    k = np.asarray(loo["khat"], dtype=np.float64)[keep]
+    ok = ~np.isnan(k)
+    n_eff = np.asarray(loo["n_eff"], dtype=np.float64)[keep][ok] if "n_eff" in loo else None
+    k = k[ok]
+    bins = []
+    for label, lo, hi in (("good", -np.inf, thr), ("bad", thr, 1.0), ("very bad", 1.0, np.inf)):
+        inside = (k > lo) & (k <= hi) if lo != -np.inf else k <= hi
+        cnt = int(inside.sum())
+        mn = float(np.min(n_eff[inside])) if n_eff is not None and cnt else float("nan")
+        bins.append(dict(label=label, lower=float(lo), upper=float(hi), count=cnt,
+                         pct=100.0 * cnt / k.size if k.size else float("nan"), min_n_eff=mn))
+    return dict(threshold=thr, bins=bins)
+
+
 def _warn_loo(loo, n_draws):
     import warnings
     for msg in loo_warnings(loo["khat"], n_draws):
@@ -196,7 +229,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                  check_approximation=False,
                  check_loo=False,
                  check_loo_intervals=False,
-                 loo_r_eff=None):
+                 loo_r_eff=None,
+                 loo_mcse=False):
     """One inference pass (discovery or test) of ppcseq on the GPU.
 
     counts            G x S integer matrix, genes ordered with the `how_many_to_check` checked genes first
@@ -232,6 +266,9 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                       of every checked cell from the fit's own chains on the device (Fit.relative_eff; 1 where it is not
                       defined), as rstan::loo(fit) does; the results then carry it as `r_eff`. devices=[...]: over the pooled
                       chains (the split is the same). Needs check_loo or check_loo_intervals.
+    loo_mcse          True: `res.loo` also carries loo's pointwise `mcse_elpd_loo` and `n_eff` of every checked cell and
+                      `mcse_elpd_loo_total` (Fit.loo(mcse=True); pareto_k_table reads it). It raises no further warning.
+                      devices=[...]: over the pooled chains. Needs check_loo.
     Returns an InferenceResult.
     """
     counts = np.asarray(counts)
@@ -265,6 +302,7 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
         raise ValueError("check_loo_intervals needs a NUTS pass: PSIS-LOO of an ADVI fit (loo_approximate_posterior) is not "
                          "available")
     _check_loo_r_eff(loo_r_eff, check_loo, check_loo_intervals)
+    _check_loo_mcse(loo_mcse, check_loo)
     if devices is not None and len(devices) > 1 and (save_generated_quantities or pass_fit or model is not None or approximate_posterior_inference):
         raise ValueError("devices=[...] splits the chains of a NUTS fit over several devices and pools their draws: it cannot "
                          "be combined with save_generated_quantities, pass_fit, a caller's model or approximate_posterior_inference")
@@ -272,7 +310,7 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
         return _do_inference_devices(counts, X, exposure_rate, K, list(devices), chains, n_iter, warmup, excl,
                                      lambda_mu_mu, approximate_posterior_analysis, adj_prob_theshold,
                                      how_many_posterior_draws, truncation_compensation, seed, launch, check_convergence,
-                                     check_loo, check_loo_intervals, loo_r_eff)
+                                     check_loo, check_loo_intervals, loo_r_eff, loo_mcse)
     if devices is not None and len(devices) >= 1 and model is None:
         device = devices[0]
     own_model = model is None
@@ -320,7 +358,7 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                 res.convergence = fit.summary(np.arange(off_alpha1, off_alpha1 + K), lp=True)
                 _warn_convergence(res.convergence, chains)
             if check_loo:
-                res.loo = fit.loo(np.arange(K), r_eff=loo_r_eff)
+                res.loo = fit.loo(np.arange(K), r_eff=loo_r_eff, mcse=bool(loo_mcse))
                 _warn_loo(res.loo, fit.chains * fit.n_keep)
             if check_loo_intervals:
                 res.loo_intervals = fit.loo_predict(np.arange(K), r_eff=loo_r_eff, p_lo=p, p_hi=1 - p, seed=seed,
@@ -343,6 +381,11 @@ def _check_loo_r_eff(loo_r_eff, check_loo, check_loo_intervals):
         raise ValueError(f'loo_r_eff must be None or "auto", not {loo_r_eff!r}')
     if not (check_loo or check_loo_intervals):
         raise ValueError("loo_r_eff needs check_loo or check_loo_intervals: it is the r_eff of their PSIS")
+
+
+def _check_loo_mcse(loo_mcse, check_loo):
+    if loo_mcse and not check_loo:
+        raise ValueError("loo_mcse needs check_loo: it adds the Monte-Carlo standard error and n_eff to its PSIS-LOO")
 
 
 def _to_cell_ids(to_exclude, S):
@@ -386,7 +429,7 @@ def checked_columns(G, C, K):
 
 def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, approximate_posterior_analysis,
                    adj_prob_theshold, how_many_posterior_draws, truncation_compensation, seed, device=0, convergence=False,
-                   loo=False, excl=None, loo_intervals=False, loo_r_eff=None):
+                   loo=False, excl=None, loo_intervals=False, loo_r_eff=None, loo_mcse=False):
     """Credible intervals, slopes and flags from the pooled draws of all chains (rstan::summary over merged chains,
     R/utilities.R:685-703): `draws_checked` is [chains, n_keep, len(checked_columns)] in global chain order. The
     posterior-predictive kernel runs on a model that holds the K checked genes only -- cell ids g*S+s and draw indices are
@@ -394,7 +437,8 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
     summary of alpha_sub_1 over the pooled chains (res.convergence; Fit.summary). loo: also PSIS-LOO of the checked cells over
     the pooled chains (res.loo; Fit.loo); the small model then carries the checked genes' cells of `excl` (0-based cell ids of
     the full model), so that the cells excluded from the fit are held out. loo_intervals: also their leave-one-out predictive
-    intervals (res.loo_intervals; Fit.loo_predict), likewise. loo_r_eff: their r_eff (None or "auto", do_inference)."""
+    intervals (res.loo_intervals; Fit.loo_predict), likewise. loo_r_eff: their r_eff (None or "auto", do_inference). loo_mcse:
+    res.loo with mcse_elpd_loo and n_eff (Fit.loo(mcse=True))."""
     counts = np.asarray(counts)
     X = np.asarray(X, dtype=np.float64).reshape(counts.shape[1], -1)
     small_excl = None
@@ -412,7 +456,7 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
                 ci = fit.ppc(truncation_compensation, p, 1 - p, seed=seed, n_gen=0, resample=False)
             slope = fit.columns(np.arange(3 + K, 3 + 2 * K)).reshape(-1, K).mean(axis=0) if K else np.zeros(0)
             conv = fit.summary(np.arange(3 + K, 3 + 2 * K), lp=False) if convergence else None
-            loo_res = fit.loo(np.arange(K), r_eff=loo_r_eff) if loo and K else None
+            loo_res = fit.loo(np.arange(K), r_eff=loo_r_eff, mcse=bool(loo_mcse)) if loo and K else None
             loo_int = None
             if loo_intervals and K:
                 loo_int = fit.loo_predict(np.arange(K), r_eff=loo_r_eff, p_lo=p, p_hi=1 - p, seed=seed,
@@ -432,7 +476,7 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
 def _do_inference_devices(counts, X, exposure_rate, K, devices, chains, n_iter, warmup, excl, lambda_mu_mu,
                           approximate_posterior_analysis, adj_prob_theshold, how_many_posterior_draws,
                           truncation_compensation, seed, launch=None, check_convergence=False, check_loo=False,
-                          check_loo_intervals=False, loo_r_eff=None):
+                          check_loo_intervals=False, loo_r_eff=None, loo_mcse=False):
     """Chains split over several devices of this process (one host thread per device; the C ABI allows different handles
     on different threads), pooled summary on the first device."""
     import threading
@@ -474,7 +518,7 @@ def _do_inference_devices(counts, X, exposure_rate, K, devices, chains, n_iter, 
                          approximate_posterior_analysis=approximate_posterior_analysis, adj_prob_theshold=adj_prob_theshold,
                          how_many_posterior_draws=how_many_posterior_draws, truncation_compensation=truncation_compensation,
                          seed=seed, device=devices[0], convergence=check_convergence, loo=check_loo, excl=excl,
-                         loo_intervals=check_loo_intervals, loo_r_eff=loo_r_eff)
+                         loo_intervals=check_loo_intervals, loo_r_eff=loo_r_eff, loo_mcse=loo_mcse)
     res.chains, res.iter = chains, n_iter
     if check_convergence:
         _warn_convergence(res.convergence, chains)

@@ -15,7 +15,7 @@ import warnings
 
 import numpy as np
 
-from .inference import _check_loo_r_eff, do_inference
+from .inference import _check_loo_mcse, _check_loo_r_eff, do_inference
 
 
 def parse_formula(formula: str):
@@ -118,7 +118,7 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                       cores=None, pass_fit=False, do_check_only_on_detrimental=None, tol_rel_obj=0.01,
                       just_discovery=False, seed=None, adj_prob_theshold_2=None, device=0, devices=None, launch=None, _pass=None,
                       check_convergence=False, check_approximation=False, check_loo=False,
-                      check_loo_intervals=False, loo_r_eff=None):
+                      check_loo_intervals=False, loo_r_eff=None, loo_mcse=False):
     """Mirror of ppcseq::identify_outliers (R/methods.R:74-367): same arguments, same defaults.
 
     data is a tidy pandas DataFrame (one row per transcript x sample); column arguments are strings. As in the
@@ -149,6 +149,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
     ["loo_intervals_test"]. They are reported only: the cells flagged stay those of the reference's rule, no warning is raised.
     `loo_r_eff` = "auto" (with check_loo or check_loo_intervals): their PSIS takes the relative efficiency of every checked cell
     from the pass's own chains (Fit.relative_eff), as rstan::loo(fit) does, and the results carry it as `r_eff`; None: r_eff = 1.
+    `loo_mcse` = True (with check_loo): out.attrs["loo_discovery"] and ["loo_test"] also carry loo's pointwise `mcse_elpd_loo` and
+    `n_eff` of the checked cells and `mcse_elpd_loo_total` (Fit.loo(mcse=True); inference.pareto_k_table tabulates them).
     """
     import os
     import pandas as pd
@@ -183,6 +185,7 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
     if check_loo_intervals and _pass is not None:
         raise ValueError("check_loo_intervals is not available for passes over several ranks")
     _check_loo_r_eff(loo_r_eff, check_loo, check_loo_intervals)
+    _check_loo_mcse(loo_mcse, check_loo)
     if check_convergence and _pass is not None:
         raise ValueError("check_convergence is not available for passes over several ranks")
     if approximate_posterior_inference and save_generated_quantities:
@@ -272,6 +275,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
             where.update(check_loo_intervals=True)
         if loo_r_eff is not None:
             where.update(loo_r_eff=loo_r_eff)
+        if loo_mcse:
+            where.update(loo_mcse=True)
     try:
         # ---- pass 1: discovery (R/methods.R:268-286); always the full posterior analysis
         res1 = run_pass(counts, X, exposure_rate, K,
