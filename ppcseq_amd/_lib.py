@@ -675,6 +675,25 @@ class Fit:
             return np.ascontiguousarray(np.where(np.isnan(re), 1.0, re))
         return np.ascontiguousarray(np.broadcast_to(np.asarray(r_eff, dtype=np.float64), (g.size, self.model.S)))
 
+    def _loo_cells(self, genes, r_eff, fields, call):
+        """What loo and loo_predict share: call(n_genes, genes, r_eff or None, out) fills [n_genes, S, fields]. Returns the
+        genes, the dict of the fields and `excluded`, and what closes the dict after the caller's own keys: `genes`, `n_draws`
+        and, for r_eff="auto", the `r_eff` that was used."""
+        g = self._genes(genes)
+        S = self.model.S
+        out = np.zeros((g.size, S, len(fields)))
+        re = self._r_eff(g, r_eff)
+        if g.size:
+            _check(call(int(g.size), _p(g, C.c_int32), _p(re, C.c_double) if re is not None else None, _p(out, C.c_double)))
+        res = {k: out[:, :, i].copy() for i, k in enumerate(fields)}
+        excl = np.zeros(self.model.G * S, bool)
+        excl[np.asarray(self.model.excl, dtype=np.int64)] = True
+        res["excluded"] = excl.reshape(self.model.G, S)[g]
+        last = {"genes": g.astype(np.int64), "n_draws": self.chains * self.n_keep}
+        if isinstance(r_eff, str):
+            last["r_eff"] = re
+        return g, res, last
+
     def loo(self, genes=None, r_eff=None, mcse=False):
         """PSIS-LOO per observed cell on the device (ppcx_fit_loo; rstan::loo / loo::loo(log_lik, r_eff)): a dict of the
         pointwise elpd_loo, p_loo, looic and khat, [n_genes, S] each, `excluded` (the cells the model holds out now: elpd_loo is
@@ -684,23 +703,10 @@ class Fit:
         mcse=True (ppcx_fit_loo_mcse; the fields above are the same bits): also loo's pointwise `mcse_elpd_loo` (the Monte-Carlo
         standard error of the cell's elpd_loo) and `n_eff` (the effective sample size of its PSIS weights; N r_eff for an
         excluded cell), [n_genes, S] each, and `mcse_elpd_loo_total` (inference.loo_mcse_total: loo's mcse_loo)."""
-        g = self._genes(genes)
-        S = self.model.S
-        fields = LOO_MCSE_FIELDS if mcse else LOO_FIELDS
-        out = np.zeros((g.size, S, len(fields)))
-        re = self._r_eff(g, r_eff)
-        if g.size:
-            entry = load().ppcx_fit_loo_mcse if mcse else load().ppcx_fit_loo
-            _check(entry(self._h, int(g.size), _p(g, C.c_int32), _p(re, C.c_double) if re is not None else None,
-                         _p(out, C.c_double)))
-        res = {k: out[:, :, i].copy() for i, k in enumerate(fields)}
-        excl = np.zeros(self.model.G * S, bool)
-        excl[np.asarray(self.model.excl, dtype=np.int64)] = True
-        res["excluded"] = excl.reshape(self.model.G, S)[g]
-        res["genes"] = g.astype(np.int64)
-        res["n_draws"] = self.chains * self.n_keep
-        if isinstance(r_eff, str):
-            res["r_eff"] = re
+        entry = load().ppcx_fit_loo_mcse if mcse else load().ppcx_fit_loo
+        _, res, last = self._loo_cells(genes, r_eff, LOO_MCSE_FIELDS if mcse else LOO_FIELDS,
+                                       lambda n, g, re, out: entry(self._h, n, g, re, out))
+        res.update(last)
         res["estimates"] = loo_estimates(res, res["excluded"])
         if mcse:
             from .inference import loo_mcse_total
@@ -714,25 +720,12 @@ class Fit:
         `excluded` (cells the model holds out now: uniform weights, Fit.ppc's interval, khat NaN), `y` (the observed counts),
         `outside` = (y < lower) | (y > upper), `genes`, `n_draws`. genes=None: all G genes; r_eff as Fit.loo ("auto" adds `r_eff`).
         seed and truncation_compensation as Fit.ppc: the predictive counts of a checked gene are its counts_rng."""
-        g = self._genes(genes)
-        S = self.model.S
-        out = np.zeros((g.size, S, len(LOO_PREDICT_FIELDS)))
-        re = self._r_eff(g, r_eff)
-        if g.size:
-            _check(load().ppcx_fit_loo_predict(self._h, int(g.size), _p(g, C.c_int32),
-                                               _p(re, C.c_double) if re is not None else None, float(truncation_compensation),
-                                               float(p_lo), float(p_hi), int(seed), _p(out, C.c_double)))
-        res = {k: out[:, :, i].copy() for i, k in enumerate(LOO_PREDICT_FIELDS)}
-        excl = np.zeros(self.model.G * S, bool)
-        excl[np.asarray(self.model.excl, dtype=np.int64)] = True
-        res["excluded"] = excl.reshape(self.model.G, S)[g]
-        res["y"] = np.asarray(self.model.counts).reshape(self.model.G, S)[g].astype(np.int64)
+        g, res, last = self._loo_cells(genes, r_eff, LOO_PREDICT_FIELDS, lambda n, g, re, out: load().ppcx_fit_loo_predict(
+            self._h, n, g, re, float(truncation_compensation), float(p_lo), float(p_hi), int(seed), out))
+        res["y"] = np.asarray(self.model.counts).reshape(self.model.G, self.model.S)[g].astype(np.int64)
         with np.errstate(invalid="ignore"):
             res["outside"] = (res["y"] < res["lower"]) | (res["y"] > res["upper"])
-        res["genes"] = g.astype(np.int64)
-        res["n_draws"] = self.chains * self.n_keep
-        if isinstance(r_eff, str):
-            res["r_eff"] = re
+        res.update(last)
         return res
 
     def diagnostics(self):

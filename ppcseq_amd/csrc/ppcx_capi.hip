@@ -1929,8 +1929,13 @@ static size_t loo_scratch_bytes() {
 #endif
   return kPsisScratchBytes;
 }
-// the fit, the genes and the cells' counts (an excluded cell as -(y + 1)); sets the fit's device
-static int loo_prepare(ppcx_fit* f, int n_genes, const int32_t* genes, std::vector<int>& yenc) {
+// the end of an entry point: the driver's error as PPCX_ERR_HIP under the entry's name (null: the bare text)
+static int loo_done(const char* who, hipError_t e) {
+  return e == hipSuccess ? PPCX_OK : who ? hip_fail(e, who) : fail(PPCX_ERR_HIP, hipGetErrorString(e));
+}
+// the fit, the genes, the cells' counts (an excluded cell as -(y + 1), kept in yenc) and the output as the record of these
+// cells; sets the fit's device
+static int loo_prepare(ppcx_fit* f, int n_genes, const int32_t* genes, const void* out, std::vector<int>& yenc, FitCells& fc) {
   if (!f) return fail(PPCX_ERR_ARG, "fit is NULL");
   if (f->advi) return fail(PPCX_ERR_ARG, "PSIS-LOO needs the draws of a NUTS fit (loo_approximate_posterior for ADVI fits is "
                                          "not available)");
@@ -1947,45 +1952,42 @@ static int loo_prepare(ppcx_fit* f, int n_genes, const int32_t* genes, std::vect
       yenc[(size_t)i * S + s] = m->excluded_host[c] ? -y - 1 : y;
     }
   HIPCHK(hipSetDevice(m->device));
+  if (!out) return fail(PPCX_ERR_ARG, "bad arguments");
+  fc.draws = f->d_draws.p; fc.n = (long)f->chains * f->n_keep; fc.chains = f->chains; fc.n_keep = f->n_keep;
+  fc.d = m->d; fc.expo = m->d_expo; fc.X = m->d_X;
+  fc.n_genes = n_genes; fc.genes = genes; fc.yenc = yenc.data();
   return PPCX_OK;
 }
 extern "C" int ppcx_fit_get_log_lik(ppcx_fit* f, int n_genes, const int32_t* genes, double* out) {
-  std::vector<int> yenc;
-  int rc = loo_prepare(f, n_genes, genes, yenc);
+  std::vector<int> yenc; FitCells fc;
+  const int rc = loo_prepare(f, n_genes, genes, out, yenc, fc);
   if (rc != PPCX_OK) return rc;
-  if (!out) return fail(PPCX_ERR_ARG, "bad arguments");
-  ppcx_model* m = f->m;
-  hipError_t e = loo_fit_log_lik(f->d_draws.p, (long)f->chains * f->n_keep, m->d, m->d_expo, m->d_X, n_genes, genes, yenc.data(), out,
-                                 loo_scratch_bytes(), m->stream);
-  if (e != hipSuccess) return fail(PPCX_ERR_HIP, std::string("ppcx_fit_get_log_lik: ") + hipGetErrorString(e));
-  return PPCX_OK;
+  return loo_done("ppcx_fit_get_log_lik", loo_fit_log_lik(fc, out, loo_scratch_bytes(), f->m->stream));
 }
-static int loo_check_reff(const double* r_eff, long n) {
-  for (long i = 0; r_eff && i < n; ++i)
-    if (!(isfinite(r_eff[i]) && r_eff[i] > 0.0)) return fail(PPCX_ERR_ARG, "r_eff must be finite and > 0");
-  return PPCX_OK;
-}
-// the smallest r_eff of a call (1 without r_eff): the longest tail of its cells, for the limit and the selection buffer
-static double loo_reff_min(const double* r_eff, long n) {
+// r_eff of `cells` cells of n draws (null: all 1): every value finite and > 0; *r_eff_min the smallest (the longest tail of the
+// cells, for the selection buffer), whose tail has to fit that buffer. who: the entry point, null in the testing build
+static int loo_reff_limits(const char* who, const double* r_eff, long cells, long n, double* r_eff_min) {
   double mn = 1.0;
-  for (long i = 0; r_eff && i < n; ++i) mn = i == 0 || r_eff[i] < mn ? r_eff[i] : mn;
-  return mn;
+  for (long i = 0; r_eff && i < cells; ++i) {
+    if (!(isfinite(r_eff[i]) && r_eff[i] > 0.0)) return fail(PPCX_ERR_ARG, "r_eff must be finite and > 0");
+    mn = i == 0 || r_eff[i] < mn ? r_eff[i] : mn;
+  }
+  if (psis_tail_len(n, mn) + 1 > kPsisMaxSel)
+    return fail(PPCX_ERR_LIMIT, who ? std::string(who) + ": the tail exceeds 4095 draws" : std::string("too many draws"));
+  *r_eff_min = mn;
+  return PPCX_OK;
+}
+static int loo_fit_reff(const char* who, FitCells& fc, const double* r_eff) {
+  fc.r_eff = r_eff;
+  return loo_reff_limits(who, r_eff, (long)fc.n_genes * fc.d.S, fc.n, &fc.r_eff_min);
 }
 // ppcx_fit_loo (fields = kLooFields) and ppcx_fit_loo_mcse (kLooMcseFields): the same checks, limits and walk
 static int fit_loo(const char* who, ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, int fields, double* out) {
-  std::vector<int> yenc;
-  int rc = loo_prepare(f, n_genes, genes, yenc);
+  std::vector<int> yenc; FitCells fc;
+  int rc = loo_prepare(f, n_genes, genes, out, yenc, fc);
+  if (rc == PPCX_OK) rc = loo_fit_reff(who, fc, r_eff);
   if (rc != PPCX_OK) return rc;
-  if (!out) return fail(PPCX_ERR_ARG, "bad arguments");
-  ppcx_model* m = f->m;
-  const long n = (long)f->chains * f->n_keep, ncells = (long)n_genes * m->d.S;
-  if ((rc = loo_check_reff(r_eff, ncells)) != PPCX_OK) return rc;
-  const double rmin = loo_reff_min(r_eff, ncells);
-  if (psis_tail_len(n, rmin) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, std::string(who) + ": the tail exceeds 4095 draws");
-  hipError_t e = loo_fit_cells(f->d_draws.p, n, m->d, m->d_expo, m->d_X, n_genes, genes, yenc.data(), r_eff, rmin, fields, out,
-                               loo_scratch_bytes(), m->stream);
-  if (e != hipSuccess) return fail(PPCX_ERR_HIP, std::string(who) + ": " + hipGetErrorString(e));
-  return PPCX_OK;
+  return loo_done(who, loo_fit_cells(fc, fields, out, loo_scratch_bytes(), f->m->stream));
 }
 extern "C" int ppcx_fit_loo(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double* out) {
   return fit_loo("ppcx_fit_loo", f, n_genes, genes, r_eff, kLooFields, out);
@@ -2000,34 +2002,26 @@ static int loo_predict_check_probs(double p_lo, double p_hi) {
 }
 extern "C" int ppcx_fit_loo_predict(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double truncation_compensation,
                                     double p_lo, double p_hi, unsigned long long seed, double* out) {
-  std::vector<int> yenc;
-  int rc = loo_prepare(f, n_genes, genes, yenc);
+  const char* who = "ppcx_fit_loo_predict";
+  std::vector<int> yenc; FitCells fc;
+  int rc = loo_prepare(f, n_genes, genes, out, yenc, fc);
+  if (rc == PPCX_OK) rc = loo_predict_check_probs(p_lo, p_hi);
   if (rc != PPCX_OK) return rc;
-  if (!out) return fail(PPCX_ERR_ARG, "bad arguments");
-  ppcx_model* m = f->m;
-  const long n = (long)f->chains * f->n_keep, ncells = (long)n_genes * m->d.S;
-  if ((rc = loo_check_reff(r_eff, ncells)) != PPCX_OK) return rc;
-  if ((rc = loo_predict_check_probs(p_lo, p_hi)) != PPCX_OK) return rc;
   if (!(isfinite(truncation_compensation) && truncation_compensation > 0.0))
     return fail(PPCX_ERR_ARG, "truncation_compensation must be finite and > 0");
-  const double rmin = loo_reff_min(r_eff, ncells);
-  if (psis_tail_len(n, rmin) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "ppcx_fit_loo_predict: the tail exceeds 4095 draws");
-  hipError_t e = loo_predict_fit_cells(f->d_draws.p, n, m->d, m->d_expo, m->d_X, n_genes, genes, yenc.data(), r_eff, rmin,
-                                       truncation_compensation, p_lo, p_hi, seed32(seed), out, loo_scratch_bytes(), m->stream);
-  if (e != hipSuccess) return fail(PPCX_ERR_HIP, std::string("ppcx_fit_loo_predict: ") + hipGetErrorString(e));
-  return PPCX_OK;
+  if ((rc = loo_fit_reff(who, fc, r_eff)) != PPCX_OK) return rc;
+  return loo_done(who, loo_predict_fit_cells(fc, truncation_compensation, p_lo, p_hi, seed32(seed), out, loo_scratch_bytes(),
+                                             f->m->stream));
 }
 #ifdef PPCX_TESTING
 // testing build only (ppcx_testing.h): the LOO kernel on host-given columns, on the current device
 static int testing_loo(int n, int n_cols, const double* ll, const int32_t* excluded, const double* r_eff, int fields, double* out) {
   if (n < 1 || n_cols < 1 || !ll || !out) return fail(PPCX_ERR_ARG, "bad arguments");
-  int rc = loo_check_reff(r_eff, n_cols);
+  GivenCells gc;
+  gc.cols = ll; gc.n = n; gc.n_cols = n_cols; gc.excl = excluded; gc.r_eff = r_eff;
+  const int rc = loo_reff_limits(nullptr, r_eff, n_cols, n, &gc.r_eff_min);
   if (rc != PPCX_OK) return rc;
-  const double rmin = loo_reff_min(r_eff, n_cols);
-  if (psis_tail_len(n, rmin) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "too many draws");
-  hipError_t e = loo_columns(ll, n, n_cols, excluded, r_eff, rmin, fields, out, loo_scratch_bytes(), nullptr);
-  if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
-  return PPCX_OK;
+  return loo_done(nullptr, loo_columns(gc, fields, out, loo_scratch_bytes(), nullptr));
 }
 extern "C" int ppcx_testing_loo(int n, int n_cols, const double* ll, const int32_t* excluded, const double* r_eff, double* out) {
   return testing_loo(n, n_cols, ll, excluded, r_eff, kLooFields, out);
@@ -2036,44 +2030,35 @@ extern "C" int ppcx_testing_loo(int n, int n_cols, const double* ll, const int32
 extern "C" int ppcx_testing_loo_mcse(int n, int n_cols, const double* ll, const int32_t* excluded, const double* r_eff, double* out) {
   return testing_loo(n, n_cols, ll, excluded, r_eff, kLooMcseFields, out);
 }
-#endif
-#ifdef PPCX_TESTING
-// testing build only (ppcx_testing.h): the LOO predictive kernel on host-given columns, on the current device
+// ... the LOO predictive kernel on host-given columns
 extern "C" int ppcx_testing_loo_predict(const double* ll, const int32_t* x, int n, int n_cols, const int32_t* y, const int32_t* excluded,
                                         const double* r_eff, double p_lo, double p_hi, double* out) {
   if (n < 1 || n_cols < 1 || !ll || !x || !y || !out) return fail(PPCX_ERR_ARG, "bad arguments");
   for (size_t i = 0; i < (size_t)n * n_cols; ++i) if (x[i] < 0) return fail(PPCX_ERR_ARG, "predictive counts must be >= 0");
-  int rc = loo_check_reff(r_eff, n_cols);
+  GivenCells gc;
+  gc.cols = ll; gc.n = n; gc.n_cols = n_cols; gc.excl = excluded; gc.r_eff = r_eff;
+  int rc = loo_predict_check_probs(p_lo, p_hi);
+  if (rc == PPCX_OK) rc = loo_reff_limits(nullptr, r_eff, n_cols, n, &gc.r_eff_min);
   if (rc != PPCX_OK) return rc;
-  if ((rc = loo_predict_check_probs(p_lo, p_hi)) != PPCX_OK) return rc;
-  const double rmin = loo_reff_min(r_eff, n_cols);
-  if (psis_tail_len(n, rmin) + 1 > kPsisMaxSel) return fail(PPCX_ERR_LIMIT, "too many draws");
-  hipError_t e = loo_predict_columns(ll, x, n, n_cols, y, excluded, r_eff, rmin, p_lo, p_hi, out, loo_scratch_bytes(), nullptr);
-  if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
-  return PPCX_OK;
+  return loo_done(nullptr, loo_predict_columns(gc, x, y, p_lo, p_hi, out, loo_scratch_bytes(), nullptr));
 }
 #endif
 // ---- the relative efficiency of the same cells (loo::relative_eff(exp(log_lik), chain_id): what rstan::loo(fit) passes as r_eff)
 extern "C" int ppcx_fit_relative_eff(ppcx_fit* f, int n_genes, const int32_t* genes, double* out) {
-  std::vector<int> yenc;
-  int rc = loo_prepare(f, n_genes, genes, yenc);
+  std::vector<int> yenc; FitCells fc;
+  const int rc = loo_prepare(f, n_genes, genes, out, yenc, fc);
   if (rc != PPCX_OK) return rc;
-  if (!out) return fail(PPCX_ERR_ARG, "bad arguments");
   if (f->chains > kSummaryMaxChains) return fail(PPCX_ERR_LIMIT, "ppcx_fit_relative_eff takes at most 128 chains");
-  ppcx_model* m = f->m;
-  hipError_t e = reff_fit_cells(f->d_draws.p, f->chains, f->n_keep, m->d, m->d_expo, m->d_X, n_genes, genes, yenc.data(), out,
-                                loo_scratch_bytes(), m->stream);
-  if (e != hipSuccess) return fail(PPCX_ERR_HIP, std::string("ppcx_fit_relative_eff: ") + hipGetErrorString(e));
-  return PPCX_OK;
+  return loo_done("ppcx_fit_relative_eff", reff_fit_cells(fc, out, loo_scratch_bytes(), f->m->stream));
 }
 #ifdef PPCX_TESTING
 // testing build only (ppcx_testing.h): the relative-efficiency kernel on host-given columns, on the current device
 extern "C" int ppcx_testing_relative_eff(int chains, int n, int n_cols, const double* ll, double* out) {
   if (chains < 1 || n < 1 || n_cols < 1 || !ll || !out) return fail(PPCX_ERR_ARG, "bad arguments");
   if (chains > kSummaryMaxChains) return fail(PPCX_ERR_LIMIT, "too many chains");
-  hipError_t e = reff_columns(ll, chains, n, n_cols, out, loo_scratch_bytes(), nullptr);
-  if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
-  return PPCX_OK;
+  GivenCells gc;
+  gc.cols = ll; gc.n = (long)chains * n; gc.n_cols = n_cols; gc.chains = chains; gc.n_keep = n;
+  return loo_done(nullptr, reff_columns(gc, out, loo_scratch_bytes(), nullptr));
 }
 #endif
 extern "C" int ppcx_fit_get_diagnostics(ppcx_fit* f, double* lp, double* stepsize, int32_t* treedepth,

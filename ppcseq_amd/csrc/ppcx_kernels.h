@@ -231,41 +231,54 @@ struct LooArgs {
   double* out = nullptr;        // [cells][kLooFields], or [cells][kLooMcseFields] (ppcx_fit_loo_mcse)
 };
 int loo_sel_pad(long n, double r_eff_min);     // power of two >= M + 1 for n draws at the smallest r_eff
-// LOO of the cells of genes[0 .. n_genes) (host) for draws [n][D] (device); yenc, r_eff (null or [cells]) and out host;
-// r_eff_min: the smallest r_eff (1 without r_eff). fields: kLooFields, or kLooMcseFields for mcse_elpd_loo and n_eff as well
-// (out holds that many per cell; the first four are the same bits). Synchronous
-hipError_t loo_fit_cells(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
-                         const int* genes, const int* yenc, const double* r_eff, double r_eff_min, int fields, double* out,
-                         size_t scratch_bytes, hipStream_t st);
-// the log-likelihood matrix of those cells, [n][cells] (host out); synchronous
-hipError_t loo_fit_log_lik(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
-                           const int* genes, const int* yenc, double* out, size_t scratch_bytes, hipStream_t st);
-// LOO of host-given columns cols [n_cols][n] (testing build); synchronous
-hipError_t loo_columns(const double* cols, long n, int n_cols, const int* excl, const double* r_eff, double r_eff_min, int fields,
-                       double* out, size_t scratch_bytes, hipStream_t st);
-// The leave-one-out predictive interval and LOO-PIT of the same cells (ppcx_loo_predict.hip, statistic in ppcx_loo_predict.h): one
-// workgroup per cell; ratios, weights and predictive counts (20 bytes per draw) in LDS up to kPsisLdsDraws draws, beyond that in
-// the scratch, bounded like the gene table. tc: truncation compensation of the predictive draws; k0 = seed32(seed). out (host)
-// [cells][kLooPredictFields]. Synchronous
 hipError_t launch_loo_table_kernel(const double* draws, long n_draws, const Dims& d, const int* genes, int n_genes, double* T,
                                    hipStream_t st);    // T[g][c][draw] of the genes (device ids), ppcx_loo.hip
-hipError_t loo_predict_fit_cells(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
-                                 const int* genes, const int* yenc, const double* r_eff, double r_eff_min, double tc, double p_lo,
-                                 double p_hi, uint32_t k0, double* out, size_t scratch_bytes, hipStream_t st);
-// ... of host-given columns cols [n_cols][n] with predictive counts x [n_cols][n] and observed counts y [n_cols] (testing build)
-hipError_t loo_predict_columns(const double* cols, const int* x, long n, int n_cols, const int* y, const int* excl,
-                               const double* r_eff, double r_eff_min, double p_lo, double p_hi, double* out, size_t scratch_bytes,
-                               hipStream_t st);
+// These cells of this fit: what every per-cell driver below receives (ppcx_capi.hip loo_prepare fills it). The cells are those
+// of genes[0 .. n_genes), S each, gene-major.
+struct FitCells {
+  const double* draws = nullptr;   // [n][D] (device)
+  long n = 0;                      // draws = chains n_keep
+  int chains = 0, n_keep = 0;
+  Dims d{};
+  const double* expo = nullptr;    // [S] (device)
+  const double* X = nullptr;       // [C][S] (device)
+  int n_genes = 0;
+  const int* genes = nullptr;      // [n_genes] (host)
+  const int* yenc = nullptr;       // [cells] the counts, an excluded cell as -(y + 1) (host)
+  const double* r_eff = nullptr;   // [cells] (host) or null: all 1
+  double r_eff_min = 1.0;          // the smallest r_eff (1 without r_eff)
+};
+// Host-given log-likelihood columns in place of a fit's cells (testing build): cols [n_cols][n], n = chains n_keep where the
+// statistic needs chains
+struct GivenCells {
+  const double* cols = nullptr; long n = 0; int n_cols = 0;
+  int chains = 0, n_keep = 0;
+  const int* excl = nullptr;       // [n_cols] excluded flags or null
+  const double* r_eff = nullptr; double r_eff_min = 1.0;
+};
+// The drivers below walk the cells through for_gene_batches / for_given_columns (ppcx_loo_dev.h); out is host, scratch_bytes
+// bounds the gene table of a batch and the cells' scratch of a launch alike (kPsisScratchBytes in the product). Synchronous.
+// LOO: fields = kLooFields, or kLooMcseFields for mcse_elpd_loo and n_eff as well (out holds that many per cell; the first four
+// are the same bits)
+hipError_t loo_fit_cells(const FitCells& fc, int fields, double* out, size_t scratch_bytes, hipStream_t st);
+hipError_t loo_columns(const GivenCells& gc, int fields, double* out, size_t scratch_bytes, hipStream_t st);
+// the log-likelihood matrix of the cells, [n][cells]
+hipError_t loo_fit_log_lik(const FitCells& fc, double* out, size_t scratch_bytes, hipStream_t st);
+// The leave-one-out predictive interval and LOO-PIT of the same cells (ppcx_loo_predict.hip, statistic in ppcx_loo_predict.h): one
+// workgroup per cell; ratios, weights and predictive counts (20 bytes per draw) in LDS up to kPsisLdsDraws draws, beyond that in
+// the scratch. tc: truncation compensation of the predictive draws; k0 = seed32(seed). out [cells][kLooPredictFields]
+hipError_t loo_predict_fit_cells(const FitCells& fc, double tc, double p_lo, double p_hi, uint32_t k0, double* out,
+                                 size_t scratch_bytes, hipStream_t st);
+// ... of given columns with predictive counts x [n_cols][n] and observed counts y [n_cols]
+hipError_t loo_predict_columns(const GivenCells& gc, const int* x, const int* y, double p_lo, double p_hi, double* out,
+                               size_t scratch_bytes, hipStream_t st);
 // The relative efficiency of the same cells (ppcx_reff.hip, statistic in ppcx_reff.h): one workgroup per cell; the split values
-// (8 bytes each) in LDS for fits of up to kPsisLdsDraws draws, beyond that in the scratch, bounded like the gene table. Of `l` it
-// uses T / y / expo / X / S / C or cols, n = chains n_keep, cell0, n_cells, scratch ([launch's cells][2 chains (n_keep / 2)]) and
-// out ([cells], one value each). At most kSummaryMaxChains chains.
+// (8 bytes each) in LDS for fits of up to kPsisLdsDraws draws, beyond that in the scratch. Of `l` it uses T / y / expo / X / S / C
+// or cols, n = chains n_keep, cell0, n_cells, scratch ([launch's cells][2 chains (n_keep / 2)]) and out ([cells], one value
+// each). At most kSummaryMaxChains chains.
 struct ReffArgs { LooArgs l; int chains = 0, n_keep = 0; };
-// r_eff of the cells of genes[0 .. n_genes) (host) for draws [chains n_keep][D] (device); yenc and out ([cells]) host. Synchronous
-hipError_t reff_fit_cells(const double* draws, int chains, int n_keep, const Dims& d, const double* expo, const double* X, int n_genes,
-                          const int* genes, const int* yenc, double* out, size_t scratch_bytes, hipStream_t st);
-// ... of host-given columns cols [n_cols][chains n_keep] (testing build); synchronous
-hipError_t reff_columns(const double* cols, int chains, int n_keep, int n_cols, double* out, size_t scratch_bytes, hipStream_t st);
+hipError_t reff_fit_cells(const FitCells& fc, double* out, size_t scratch_bytes, hipStream_t st);
+hipError_t reff_columns(const GivenCells& gc, double* out, size_t scratch_bytes, hipStream_t st);
 hipError_t launch_xchg_abort_kernel(const XchgArgs& x, hipStream_t st);      // tells every peer that this rank has left the fit
 
 }  // namespace ppcx

@@ -1,5 +1,6 @@
 // ppcx_loo.hip -- gfx950 kernels of PSIS-LOO per observed cell (ppcx_fit_loo, ppcx_fit_get_log_lik, include/ppcx.h; the
-// statistic: ppcx_loo.h).
+// statistic: ppcx_loo.h). The walk over a fit's cells in gene batches is ppcx_loo_dev.h's (for_gene_batches); the drivers at
+// the end of this file add the kernel to it.
 //
 //   ppcx_loo_table_kernel  the per-draw parameters of the requested genes, transposed: T[g][c][draw], c = 0 intercept,
 //                          1 .. C - 1 slopes (0 for a gene without slopes), C sigma_raw. One thread per (draw, gene), 32 x 32
@@ -96,11 +97,9 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_kernel(LooArgs a) {
   uint64_t* K = lds_u;                                   // [sel_pad] keys of the M + 1 largest ratios
   double* X = reinterpret_cast<double*>(lds_u + a.sel_pad);            // [sel_pad] the tail's exceedances
   double* V = LDS ? X + a.sel_pad : a.scratch + (long)blockIdx.x * n;  // the cell's ratios r = -ll
-  const int cell = a.cell0 + blockIdx.x;                 // of this launch's cells (the table's genes, or the given columns)
-  int y = 0; bool excluded;
-  if (COLS) excluded = a.excl && a.excl[cell] != 0;
-  else { const int ye = a.y[cell]; excluded = ye < 0; y = excluded ? -ye - 1 : ye; }
-  const int gi = COLS ? 0 : cell / a.S, s = COLS ? 0 : cell - gi * a.S;
+  const LooCell c = loo_cell<COLS>(a);                   // of this launch's cells (the table's genes, or the given columns)
+  const int cell = c.cell, gi = c.gi, s = c.s, y = c.y;
+  const bool excluded = c.excluded;
   double* o = a.out + (long)cell * (MCSE ? kLooMcseFields : kLooFields);
   // ---- the ratios; NaN / +Inf; N (the -Inf ratios take no part); the largest ratio and the largest ll
   long N; double rmax, lmax;
@@ -213,70 +212,37 @@ static hipError_t loo_cells(LooArgs a, int fields, int n_cells, size_t scratch_b
   });
 }
 
-hipError_t loo_fit_cells(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
-                         const int* genes, const int* yenc, const double* r_eff, double r_eff_min, int fields, double* out,
-                         size_t scratch_bytes, hipStream_t st) {
-  const int S = d.S, ncol = d.C + 1;
-  const size_t ncells = (size_t)n_genes * S;
-  const int gb = column_batch(scratch_bytes, (long)ncol * n, n_genes);
-  DeviceBuffer<int> d_genes, d_y; DeviceBuffer<double> d_T, d_reff, d_out, d_scr;
-  hipError_t e = d_genes.upload(genes, (size_t)n_genes, st);
-  if (e == hipSuccess) e = d_y.upload(yenc, ncells, st);
-  if (e == hipSuccess && r_eff) e = d_reff.upload(r_eff, ncells, st);
-  if (e == hipSuccess) e = d_out.alloc((size_t)fields * ncells);
-  if (e == hipSuccess) e = d_T.alloc((size_t)ncol * (size_t)n * gb);
-  for (int g0 = 0; e == hipSuccess && g0 < n_genes; g0 += gb) {
-    const int ng = n_genes - g0 < gb ? n_genes - g0 : gb;
-    e = launch_loo_table_kernel(draws, n, d, d_genes.p + g0, ng, d_T.p, st);
-    if (e != hipSuccess) break;
-    LooArgs a;
-    a.T = d_T.p; a.y = d_y.p + (size_t)g0 * S; a.expo = expo; a.X = X; a.S = S; a.C = d.C; a.n = n;
-    a.r_eff = d_reff.p ? d_reff.p + (size_t)g0 * S : nullptr; a.out = d_out.p + (size_t)g0 * S * fields;
-    a.n_cells = ng * S; a.sel_pad = loo_sel_pad(n, r_eff_min);
-    e = loo_cells(a, fields, ng * S, scratch_bytes, d_scr, st);
-  }
-  if (e == hipSuccess) e = d_out.download(out, (size_t)fields * ncells, st);
-  return finish(e, st);
+// what both walks run per batch: the LOO kernel over the batch's cells
+static auto loo_body(int fields, size_t scratch_bytes, hipStream_t st) {
+  return [=](const LooArgs& a, const int*, int n_cells, DeviceBuffer<double>& scratch) {
+    return loo_cells(a, fields, n_cells, scratch_bytes, scratch, st);
+  };
+}
+hipError_t loo_fit_cells(const FitCells& fc, int fields, double* out, size_t scratch_bytes, hipStream_t st) {
+  return for_gene_batches(fc, fields, out, scratch_bytes, st, loo_body(fields, scratch_bytes, st));
+}
+hipError_t loo_columns(const GivenCells& gc, int fields, double* out, size_t scratch_bytes, hipStream_t st) {
+  return for_given_columns(gc, fields, out, st, loo_body(fields, scratch_bytes, st));
 }
 
-hipError_t loo_fit_log_lik(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
-                           const int* genes, const int* yenc, double* out, size_t scratch_bytes, hipStream_t st) {
-  const int S = d.S, ncol = d.C + 1;
-  const size_t ncells = (size_t)n_genes * S;
+hipError_t loo_fit_log_lik(const FitCells& fc, double* out, size_t scratch_bytes, hipStream_t st) {
+  const size_t ncells = (size_t)fc.n_genes * fc.d.S;
+  const long n = fc.n;
   // the whole table of the requested genes, then the matrix in row blocks of at most scratch_bytes
   long rows = (long)std::max<size_t>(1, scratch_bytes / (sizeof(double) * ncells));
   if (rows > n) rows = n;
-  DeviceBuffer<int> d_genes, d_y; DeviceBuffer<double> d_T, d_buf;
-  hipError_t e = d_genes.upload(genes, (size_t)n_genes, st);
-  if (e == hipSuccess) e = d_y.upload(yenc, ncells, st);
-  if (e == hipSuccess) e = d_T.alloc((size_t)ncol * (size_t)n * n_genes);
+  FitCellsDev dev; DeviceBuffer<double> d_T, d_buf;
+  hipError_t e = dev.upload(fc, st);
+  if (e == hipSuccess) e = d_T.alloc((size_t)(fc.d.C + 1) * (size_t)n * fc.n_genes);
   if (e == hipSuccess) e = d_buf.alloc(ncells * (size_t)rows);
-  if (e == hipSuccess) e = launch_loo_table_kernel(draws, n, d, d_genes.p, n_genes, d_T.p, st);
-  LooArgs a;
-  a.T = d_T.p; a.y = d_y.p; a.expo = expo; a.X = X; a.S = S; a.C = d.C; a.n = n; a.n_cells = (int)ncells;
+  if (e == hipSuccess) e = launch_loo_table_kernel(fc.draws, n, fc.d, dev.genes.p, fc.n_genes, d_T.p, st);
+  const LooArgs a = dev.args(fc, d_T.p, 0, fc.n_genes);
   for (long j0 = 0; e == hipSuccess && j0 < n; j0 += rows) {
     const long nr = n - j0 < rows ? n - j0 : rows;
     e = launch_loo_ll_kernel(a, j0, nr, d_buf.p, st);
     if (e == hipSuccess) e = d_buf.download(out + (size_t)j0 * ncells, ncells * (size_t)nr, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);   // d_buf is rewritten by the next block
   }
-  return finish(e, st);
-}
-
-hipError_t loo_columns(const double* cols, long n, int n_cols, const int* excl, const double* r_eff, double r_eff_min, int fields,
-                       double* out, size_t scratch_bytes, hipStream_t st) {
-  DeviceBuffer<double> d_cols, d_reff, d_out, d_scr; DeviceBuffer<int> d_excl;
-  hipError_t e = d_cols.upload(cols, (size_t)n * n_cols, st);
-  if (e == hipSuccess && excl) e = d_excl.upload(excl, (size_t)n_cols, st);
-  if (e == hipSuccess && r_eff) e = d_reff.upload(r_eff, (size_t)n_cols, st);
-  if (e == hipSuccess) e = d_out.alloc((size_t)fields * (size_t)n_cols);
-  if (e == hipSuccess) {
-    LooArgs a;
-    a.cols = d_cols.p; a.excl = d_excl.p; a.r_eff = d_reff.p; a.n = n; a.n_cells = n_cols; a.out = d_out.p;
-    a.sel_pad = loo_sel_pad(n, r_eff_min);
-    e = loo_cells(a, fields, n_cols, scratch_bytes, d_scr, st);
-  }
-  if (e == hipSuccess) e = d_out.download(out, (size_t)fields * (size_t)n_cols, st);
   return finish(e, st);
 }
 

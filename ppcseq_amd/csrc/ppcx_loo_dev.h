@@ -1,7 +1,10 @@
-// ppcx_loo_dev.h -- what the two leave-one-out kernels share on the device (ppcx_loo.hip: PSIS-LOO per cell; ppcx_loo_predict.hip:
-// the leave-one-out predictive interval per cell) and in their drivers: the cell's linear predictor and log-likelihood from the
-// transposed table, its ratios r = -ll, the fitted tail with the copies of the cutoff, and the batches of cells under the scratch
-// bound. The statistic is ppcx_loo.h; the workgroup pieces are ppcx_block.h and ppcx_psis_dev.h.
+// ppcx_loo_dev.h -- what the per-cell leave-one-out kernels share (ppcx_loo.hip: PSIS-LOO per cell; ppcx_loo_predict.hip: the
+// leave-one-out predictive interval per cell; ppcx_reff.hip: the relative efficiency per cell). On the device: which cell a
+// workgroup has, the cell's linear predictor and log-likelihood from the transposed table, its ratios r = -ll, the fitted tail
+// with the copies of the cutoff. On the host: the one walk over a fit's cells in gene batches (for_gene_batches), its
+// counterpart for host-given columns (for_given_columns) and the batches of cells under the scratch bound
+// (loo_cell_batches); a statistic's drivers add their argument block and their kernel. The statistic is ppcx_loo.h; the
+// workgroup pieces are ppcx_block.h and ppcx_psis_dev.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ppcx_psis_dev.h"
@@ -9,6 +12,18 @@
 #include "ppcx_columns.h"
 
 namespace ppcx {
+
+// The cell of this workgroup among the launch's cells: of the table's genes (gene gi of the table, sample s, its count y and
+// whether the model holds it out) or of the given columns (their excluded flag; y = ycols[cell] where counts are given)
+struct LooCell { int cell, gi, s, y; bool excluded; };
+template <bool COLS>
+__device__ __forceinline__ LooCell loo_cell(const LooArgs& a, const int* ycols = nullptr) {
+  LooCell c{(int)(a.cell0 + blockIdx.x), 0, 0, 0, false};
+  if (COLS) { c.excluded = a.excl && a.excl[c.cell] != 0; if (ycols) c.y = ycols[c.cell]; }
+  else { const int ye = a.y[c.cell]; c.excluded = ye < 0; c.y = c.excluded ? -ye - 1 : ye; }
+  c.gi = COLS ? 0 : c.cell / a.S; c.s = COLS ? 0 : c.cell - c.gi * a.S;
+  return c;
+}
 
 // linear predictor of cell (gene gi of the table, sample s) at draw j: the expression of the posterior-predictive kernels
 __device__ __forceinline__ double loo_cell_eta(const LooArgs& a, const double* Tg, int s, long j) {
@@ -77,6 +92,72 @@ hipError_t loo_cell_batches(int n_cells, long slice, size_t scratch_bytes, Devic
   for (int c0 = 0; e == hipSuccess && c0 < n_cells; c0 += batch)
     e = launch(c0, n_cells - c0 < batch ? n_cells - c0 : batch, scratch.p);
   return e;
+}
+
+// What a walk over a fit's cells keeps on the device for all of its batches: the gene ids, the encoded counts and r_eff
+// (where given), and from them the LooArgs of genes g0 .. g0 + ng of a table T that holds those genes from its start.
+struct FitCellsDev {
+  DeviceBuffer<int> genes, y; DeviceBuffer<double> r_eff;
+  hipError_t upload(const FitCells& fc, hipStream_t st) {
+    const size_t ncells = (size_t)fc.n_genes * fc.d.S;
+    hipError_t e = genes.upload(fc.genes, (size_t)fc.n_genes, st);
+    if (e == hipSuccess) e = y.upload(fc.yenc, ncells, st);
+    if (e == hipSuccess && fc.r_eff) e = r_eff.upload(fc.r_eff, ncells, st);
+    return e;
+  }
+  LooArgs args(const FitCells& fc, const double* T, int g0, int ng) const {
+    const size_t c0 = (size_t)g0 * fc.d.S;
+    LooArgs a;
+    a.T = T; a.y = y.p + c0; a.expo = fc.expo; a.X = fc.X; a.S = fc.d.S; a.C = fc.d.C; a.n = fc.n;
+    a.r_eff = r_eff.p ? r_eff.p + c0 : nullptr;
+    a.n_cells = ng * fc.d.S; a.sel_pad = loo_sel_pad(fc.n, fc.r_eff_min);
+    return a;
+  }
+};
+
+// The cells of a fit in batches of column_batch(scratch_bytes, ..) genes: each batch's transposed table T (never the table of
+// all the genes), then body(the batch's LooArgs with `out` at its part of the device output [cells][fields], its gene ids
+// (device), its cells, the scratch) launches the statistic over loo_cell_batches. The scratch is allocated by the first batch
+// that needs it and serves the later ones; every buffer lives until the stream has drained. The output is copied to out (host)
+// at the end. Synchronous.
+template <class Body>
+hipError_t for_gene_batches(const FitCells& fc, int fields, double* out, size_t scratch_bytes, hipStream_t st, Body body) {
+  const int S = fc.d.S, ncol = fc.d.C + 1;
+  const size_t ncells = (size_t)fc.n_genes * S;
+  const int gb = column_batch(scratch_bytes, (long)ncol * fc.n, fc.n_genes);
+  FitCellsDev dev; DeviceBuffer<double> d_T, d_out, d_scr;
+  hipError_t e = dev.upload(fc, st);
+  if (e == hipSuccess) e = d_out.alloc((size_t)fields * ncells);
+  if (e == hipSuccess) e = d_T.alloc((size_t)ncol * (size_t)fc.n * gb);
+  for (int g0 = 0; e == hipSuccess && g0 < fc.n_genes; g0 += gb) {
+    const int ng = fc.n_genes - g0 < gb ? fc.n_genes - g0 : gb;
+    e = launch_loo_table_kernel(fc.draws, fc.n, fc.d, dev.genes.p + g0, ng, d_T.p, st);
+    if (e != hipSuccess) break;
+    LooArgs a = dev.args(fc, d_T.p, g0, ng);
+    a.out = d_out.p + (size_t)g0 * S * fields;
+    e = body(a, dev.genes.p + g0, ng * S, d_scr);
+  }
+  if (e == hipSuccess) e = d_out.download(out, (size_t)fields * ncells, st);
+  return finish(e, st);
+}
+
+// The same for host-given columns (testing build): body(the LooArgs of all the columns, null, n_cols, the scratch).
+template <class Body>
+hipError_t for_given_columns(const GivenCells& gc, int fields, double* out, hipStream_t st, Body body) {
+  const size_t n_cols = (size_t)gc.n_cols;
+  DeviceBuffer<double> d_cols, d_reff, d_out, d_scr; DeviceBuffer<int> d_excl;
+  hipError_t e = d_cols.upload(gc.cols, (size_t)gc.n * n_cols, st);
+  if (e == hipSuccess && gc.excl) e = d_excl.upload(gc.excl, n_cols, st);
+  if (e == hipSuccess && gc.r_eff) e = d_reff.upload(gc.r_eff, n_cols, st);
+  if (e == hipSuccess) e = d_out.alloc((size_t)fields * n_cols);
+  if (e == hipSuccess) {
+    LooArgs a;
+    a.cols = d_cols.p; a.excl = d_excl.p; a.r_eff = d_reff.p; a.n = gc.n; a.n_cells = gc.n_cols; a.out = d_out.p;
+    a.sel_pad = loo_sel_pad(gc.n, gc.r_eff_min);
+    e = body(a, (const int*)nullptr, gc.n_cols, d_scr);
+  }
+  if (e == hipSuccess) e = d_out.download(out, (size_t)fields * n_cols, st);
+  return finish(e, st);
 }
 
 }  // namespace ppcx

@@ -1,5 +1,6 @@
 // ppcx_loo_predict.hip -- gfx950 kernel of the leave-one-out predictive interval and LOO-PIT per observed cell
-// (ppcx_fit_loo_predict, include/ppcx.h; the statistic: ppcx_loo_predict.h).
+// (ppcx_fit_loo_predict, include/ppcx.h; the statistic: ppcx_loo_predict.h). The walk over the cells is ppcx_loo_dev.h's
+// (for_gene_batches, for_given_columns); the drivers at the end of this file add the argument block and the kernel.
 //
 //   ppcx_loo_predict_kernel  one workgroup of kBlockThreads per cell. The cell's n ratios r = -ll from the transposed table T
 //                            (ppcx_loo_table_kernel) and its tail as in ppcx_loo_kernel (ppcx_loo_dev.h); then per draw its
@@ -20,14 +21,14 @@
 namespace ppcx {
 
 struct LooPredictArgs {
-  LooArgs l;                       // the table or the columns, y, r_eff, n, the cells, sel_pad (l.out and l.scratch unused)
+  LooArgs l;                       // the table or the columns, y, r_eff, n, the cells, sel_pad (l.scratch unused)
   const int* genes = nullptr;      // [table's genes] their ids in the model: the Philox address is genes[gi] S + s
   const int* xcols = nullptr;      // [cells][n] predictive counts of the given columns (testing build)
   const int* ycols = nullptr;      // [cells] observed counts of the given columns
   double tc = 1.0, p_lo = 0.025, p_hi = 0.975;
   uint32_t k0 = 0;
   double* scratch = nullptr; long slice = 0;   // [launch's cells][slice] doubles: the long path's r, w, x
-  double* out = nullptr;           // [cells][kLooPredictFields]
+  double* out = nullptr;           // [cells][kLooPredictFields] (= l.out)
 };
 
 // doubles of scratch per cell on the long path: r [n], w [n], x [n] as integers
@@ -60,11 +61,9 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_predict_kernel(LooPred
   double* V = LDS ? X + a.sel_pad : p.scratch + (long)blockIdx.x * p.slice;   // [n] the ratios r = -ll
   double* W = V + n;                                     // [n] log weights, then weights
   int* XI = reinterpret_cast<int*>(W + n);               // [n] predictive counts
-  const int cell = a.cell0 + blockIdx.x;
-  int y; bool excluded;
-  if (COLS) { excluded = a.excl && a.excl[cell] != 0; y = p.ycols[cell]; }
-  else { const int ye = a.y[cell]; excluded = ye < 0; y = excluded ? -ye - 1 : ye; }
-  const int gi = COLS ? 0 : cell / a.S, s = COLS ? 0 : cell - gi * a.S;
+  const LooCell c = loo_cell<COLS>(a, p.ycols);
+  const int cell = c.cell, gi = c.gi, s = c.s, y = c.y;
+  const bool excluded = c.excluded;
   double* o = p.out + (long)cell * kLooPredictFields;
   auto all_nan = [&]() { if (tid == 0) for (int f = 0; f < kLooPredictFields; ++f) o[f] = NAN; };
   // ---- the ratios
@@ -164,55 +163,28 @@ static hipError_t loo_predict_cells(LooPredictArgs p, int n_cells, size_t scratc
   });
 }
 
-hipError_t loo_predict_fit_cells(const double* draws, long n, const Dims& d, const double* expo, const double* X, int n_genes,
-                                 const int* genes, const int* yenc, const double* r_eff, double r_eff_min, double tc, double p_lo,
-                                 double p_hi, uint32_t k0, double* out, size_t scratch_bytes, hipStream_t st) {
-  const int S = d.S, ncol = d.C + 1;
-  const size_t ncells = (size_t)n_genes * S;
-  const int gb = column_batch(scratch_bytes, (long)ncol * n, n_genes);
-  DeviceBuffer<int> d_genes, d_y; DeviceBuffer<double> d_T, d_reff, d_out, d_scr;
-  hipError_t e = d_genes.upload(genes, (size_t)n_genes, st);
-  if (e == hipSuccess) e = d_y.upload(yenc, ncells, st);
-  if (e == hipSuccess && r_eff) e = d_reff.upload(r_eff, ncells, st);
-  if (e == hipSuccess) e = d_out.alloc(kLooPredictFields * ncells);
-  if (e == hipSuccess) e = d_T.alloc((size_t)ncol * (size_t)n * gb);
-  for (int g0 = 0; e == hipSuccess && g0 < n_genes; g0 += gb) {
-    const int ng = n_genes - g0 < gb ? n_genes - g0 : gb;
-    e = launch_loo_table_kernel(draws, n, d, d_genes.p + g0, ng, d_T.p, st);
-    if (e != hipSuccess) break;
+hipError_t loo_predict_fit_cells(const FitCells& fc, double tc, double p_lo, double p_hi, uint32_t k0, double* out,
+                                 size_t scratch_bytes, hipStream_t st) {
+  return for_gene_batches(fc, kLooPredictFields, out, scratch_bytes, st,
+                          [&](const LooArgs& a, const int* genes, int n_cells, DeviceBuffer<double>& scratch) {
     LooPredictArgs p;
-    LooArgs& a = p.l;
-    a.T = d_T.p; a.y = d_y.p + (size_t)g0 * S; a.expo = expo; a.X = X; a.S = S; a.C = d.C; a.n = n;
-    a.r_eff = d_reff.p ? d_reff.p + (size_t)g0 * S : nullptr;
-    a.n_cells = ng * S; a.sel_pad = loo_sel_pad(n, r_eff_min);
-    p.genes = d_genes.p + g0; p.tc = tc; p.p_lo = p_lo; p.p_hi = p_hi; p.k0 = k0;
-    p.out = d_out.p + (size_t)g0 * S * kLooPredictFields;
-    e = loo_predict_cells(p, ng * S, scratch_bytes, d_scr, st);
-  }
-  if (e == hipSuccess) e = d_out.download(out, kLooPredictFields * ncells, st);
-  return finish(e, st);
+    p.l = a; p.genes = genes; p.tc = tc; p.p_lo = p_lo; p.p_hi = p_hi; p.k0 = k0; p.out = a.out;
+    return loo_predict_cells(p, n_cells, scratch_bytes, scratch, st);
+  });
 }
 
-hipError_t loo_predict_columns(const double* cols, const int* x, long n, int n_cols, const int* y, const int* excl,
-                               const double* r_eff, double r_eff_min, double p_lo, double p_hi, double* out, size_t scratch_bytes,
-                               hipStream_t st) {
-  DeviceBuffer<double> d_cols, d_reff, d_out, d_scr; DeviceBuffer<int> d_x, d_y, d_excl;
-  hipError_t e = d_cols.upload(cols, (size_t)n * n_cols, st);
-  if (e == hipSuccess) e = d_x.upload(x, (size_t)n * n_cols, st);
-  if (e == hipSuccess) e = d_y.upload(y, (size_t)n_cols, st);
-  if (e == hipSuccess && excl) e = d_excl.upload(excl, (size_t)n_cols, st);
-  if (e == hipSuccess && r_eff) e = d_reff.upload(r_eff, (size_t)n_cols, st);
-  if (e == hipSuccess) e = d_out.alloc(kLooPredictFields * (size_t)n_cols);
-  if (e == hipSuccess) {
+hipError_t loo_predict_columns(const GivenCells& gc, const int* x, const int* y, double p_lo, double p_hi, double* out,
+                               size_t scratch_bytes, hipStream_t st) {
+  const size_t n_cols = (size_t)gc.n_cols;
+  DeviceBuffer<int> d_x, d_y;                            // outlive the walk, which drains the stream before it returns
+  hipError_t e = d_x.upload(x, (size_t)gc.n * n_cols, st);
+  if (e == hipSuccess) e = d_y.upload(y, n_cols, st);
+  if (e != hipSuccess) return finish(e, st);
+  return for_given_columns(gc, kLooPredictFields, out, st, [&](const LooArgs& a, const int*, int n_cells, DeviceBuffer<double>& scratch) {
     LooPredictArgs p;
-    LooArgs& a = p.l;
-    a.cols = d_cols.p; a.excl = d_excl.p; a.r_eff = d_reff.p; a.n = n; a.n_cells = n_cols;
-    a.sel_pad = loo_sel_pad(n, r_eff_min);
-    p.xcols = d_x.p; p.ycols = d_y.p; p.p_lo = p_lo; p.p_hi = p_hi; p.out = d_out.p;
-    e = loo_predict_cells(p, n_cols, scratch_bytes, d_scr, st);
-  }
-  if (e == hipSuccess) e = d_out.download(out, kLooPredictFields * (size_t)n_cols, st);
-  return finish(e, st);
+    p.l = a; p.xcols = d_x.p; p.ycols = d_y.p; p.p_lo = p_lo; p.p_hi = p_hi; p.out = a.out;
+    return loo_predict_cells(p, n_cells, scratch_bytes, scratch, st);
+  });
 }
 
 }  // namespace ppcx

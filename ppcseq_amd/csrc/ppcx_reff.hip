@@ -1,5 +1,6 @@
 // ppcx_reff.hip -- gfx950 kernel of the relative efficiency per observed cell (ppcx_fit_relative_eff, include/ppcx.h; the
-// statistic: ppcx_reff.h).
+// statistic: ppcx_reff.h). The walk over the cells is ppcx_loo_dev.h's (for_gene_batches, for_given_columns); the drivers at the
+// end of this file add the argument block and the kernel.
 //
 //   ppcx_reff_kernel<LDS, COLS>  one workgroup per cell: the cell's log-likelihoods from the transposed gene table
 //                                (ppcx_loo_table_kernel, loo_cell_ll) or, in the testing build, from host-given columns, written
@@ -23,13 +24,11 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_reff_kernel(ReffArgs a) {
   const int tid = threadIdx.x;
   const int nh = a.n_keep / 2, m = 2 * a.chains;
   const long N = (long)m * nh;
-  const int cell = a.l.cell0 + blockIdx.x;              // of this launch's cells (the table's genes, or the given columns)
+  const LooCell c = loo_cell<COLS>(a.l);                // an excluded cell's log-likelihood is defined too
+  const int cell = c.cell, gi = c.gi, s = c.s, y = c.y;
   double* out = a.l.out + cell;
   if (nh < 2) { if (tid == 0) *out = NAN; return; }
   double* Z = LDS ? lds_z : a.l.scratch + (long)blockIdx.x * N;   // [N] the split values
-  int y = 0;
-  if (!COLS) { const int ye = a.l.y[cell]; y = ye < 0 ? -ye - 1 : ye; }   // an excluded cell's log-likelihood is defined too
-  const int gi = COLS ? 0 : cell / a.l.S, s = COLS ? 0 : cell - gi * a.l.S;
   bool bad = false; double lmax = -INFINITY;
   for (long k = tid; k < N; k += kBlockThreads) {
     const long j = split_source(k, nh, a.n_keep);
@@ -67,44 +66,19 @@ static hipError_t reff_cells(ReffArgs a, int n_cells, size_t scratch_bytes, Devi
   });
 }
 
-hipError_t reff_fit_cells(const double* draws, int chains, int n_keep, const Dims& d, const double* expo, const double* X, int n_genes,
-                          const int* genes, const int* yenc, double* out, size_t scratch_bytes, hipStream_t st) {
-  const int S = d.S, ncol = d.C + 1;
-  const long n = (long)chains * n_keep;
-  const size_t ncells = (size_t)n_genes * S;
-  const int gb = column_batch(scratch_bytes, (long)ncol * n, n_genes);
-  DeviceBuffer<int> d_genes, d_y; DeviceBuffer<double> d_T, d_out, d_scr;
-  hipError_t e = d_genes.upload(genes, (size_t)n_genes, st);
-  if (e == hipSuccess) e = d_y.upload(yenc, ncells, st);
-  if (e == hipSuccess) e = d_out.alloc(ncells);
-  if (e == hipSuccess) e = d_T.alloc((size_t)ncol * (size_t)n * gb);
-  for (int g0 = 0; e == hipSuccess && g0 < n_genes; g0 += gb) {
-    const int ng = n_genes - g0 < gb ? n_genes - g0 : gb;
-    e = launch_loo_table_kernel(draws, n, d, d_genes.p + g0, ng, d_T.p, st);
-    if (e != hipSuccess) break;
+// what both walks run per batch: the kernel over the batch's cells
+static auto reff_body(int chains, int n_keep, size_t scratch_bytes, hipStream_t st) {
+  return [=](const LooArgs& l, const int*, int n_cells, DeviceBuffer<double>& scratch) {
     ReffArgs a;
-    a.chains = chains; a.n_keep = n_keep;
-    a.l.T = d_T.p; a.l.y = d_y.p + (size_t)g0 * S; a.l.expo = expo; a.l.X = X; a.l.S = S; a.l.C = d.C; a.l.n = n;
-    a.l.out = d_out.p + (size_t)g0 * S; a.l.n_cells = ng * S;
-    e = reff_cells(a, ng * S, scratch_bytes, d_scr, st);
-  }
-  if (e == hipSuccess) e = d_out.download(out, ncells, st);
-  return finish(e, st);
+    a.l = l; a.chains = chains; a.n_keep = n_keep;
+    return reff_cells(a, n_cells, scratch_bytes, scratch, st);
+  };
 }
-
-hipError_t reff_columns(const double* cols, int chains, int n_keep, int n_cols, double* out, size_t scratch_bytes, hipStream_t st) {
-  const long n = (long)chains * n_keep;
-  DeviceBuffer<double> d_cols, d_out, d_scr;
-  hipError_t e = d_cols.upload(cols, (size_t)n * n_cols, st);
-  if (e == hipSuccess) e = d_out.alloc((size_t)n_cols);
-  if (e == hipSuccess) {
-    ReffArgs a;
-    a.chains = chains; a.n_keep = n_keep;
-    a.l.cols = d_cols.p; a.l.n = n; a.l.n_cells = n_cols; a.l.out = d_out.p;
-    e = reff_cells(a, n_cols, scratch_bytes, d_scr, st);
-  }
-  if (e == hipSuccess) e = d_out.download(out, (size_t)n_cols, st);
-  return finish(e, st);
+hipError_t reff_fit_cells(const FitCells& fc, double* out, size_t scratch_bytes, hipStream_t st) {
+  return for_gene_batches(fc, 1, out, scratch_bytes, st, reff_body(fc.chains, fc.n_keep, scratch_bytes, st));
+}
+hipError_t reff_columns(const GivenCells& gc, double* out, size_t scratch_bytes, hipStream_t st) {
+  return for_given_columns(gc, 1, out, st, reff_body(gc.chains, gc.n_keep, scratch_bytes, st));
 }
 
 }  // namespace ppcx

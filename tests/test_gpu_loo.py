@@ -202,6 +202,52 @@ def test_batches_of_the_fit_give_the_same_bits(small_fit):
     assert np.array_equal(gll, ll)
 
 
+def test_gene_batches_over_scratch_batches_give_the_same_bits(small_fit):
+    """The one walk of the per-cell statistics (for_gene_batches) where both of its bounds bind at once: a fit beyond the LDS
+    path (4 x 1300 = 5200 draws: small_fit's draws repeated along the draw axis, with a jitter of 1e-3 so that no column is an
+    exact copy), the gene table in fifteen batches of two genes and each batch's 20 cells in several scratch launches that
+    reuse one allocation. Every statistic gives the bits of the unbounded call, and the unbounded LOO is the restatement's on
+    the fit's own log-likelihood, at the bound of test_loo_matches_restatement."""
+    from ppcseq_amd import _lib, build
+    m, f, d = small_fit
+    own = L.loo_columns(f.log_lik().reshape(-1, m.G * m.S), None, np.isin(np.arange(m.G * m.S), [3, 17]))
+    dr = np.tile(f.draws(), (1, 6, 1))[:, :1300]
+    dr = dr + 1e-3 * np.sin(np.arange(dr.size, dtype=np.float64)).reshape(dr.shape)
+    n, C = 4 * 1300, np.asarray(d["X"]).reshape(m.S, -1).shape[1]
+
+    def calls(ft):
+        return dict(loo=ft.loo(), mcse=ft.loo(mcse=True), predict=ft.loo_predict(), reff=dict(r_eff=ft.relative_eff()))
+
+    _lib.use_library(build.build_testing())
+    try:
+        mt = _lib.Model(d["counts"], d["X"], d["exposure"], 4, excl=np.array([3, 17], np.int32), device=0)
+        try:
+            ft = mt.fit_from_draws(dr)
+            try:
+                one, ll = calls(ft), ft.log_lik().reshape(n, m.G * m.S)
+                _lib.testing_set("loo_scratch_bytes", 2 * 8 * (C + 1) * n + 8)   # two genes per table batch
+                try:
+                    got = calls(ft)
+                finally:
+                    _lib.testing_set("loo_scratch_bytes", 0)
+            finally:
+                ft.close()
+        finally:
+            mt.close()
+    finally:
+        _lib.use_library(None)
+    for what, res in one.items():
+        for k, v in res.items():
+            if isinstance(v, np.ndarray):
+                assert np.array_equal(got[what][k], v, equal_nan=True), (what, k)
+    ref = L.loo_columns(ll, None, one["loo"]["excluded"].ravel())
+    for i, k in enumerate(L.FIELDS):
+        _compare(one["loo"][k].ravel(), ref[:, i], 1e-12, k)
+    nan_here, nan_own = np.isnan(ref[:, 0]).mean(), np.isnan(own[:, 0]).mean()
+    print("NaN share of elpd_loo: jittered fit", nan_here, "small_fit", nan_own)
+    assert nan_here <= nan_own
+
+
 def test_determinism(small_fit):
     m, f, d = small_fit
     a, b = f.loo(), f.loo()
