@@ -208,6 +208,24 @@ PPCX_API int ppcx_fit_relative_eff(ppcx_fit* f, int n_genes, const int32_t* gene
 #define PPCX_LOO_PREDICT_FIELDS 6   /* mean, lower, upper, pit_lt, pit_le, khat */
 PPCX_API int ppcx_fit_loo_predict(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double truncation_compensation,
                                   double p_lo, double p_hi, unsigned long long seed, double* out);
+/* PSIS-LOO per observed cell of an ADVI fit: what loo::loo_approximate_posterior(log_lik, log_p, log_g) reports per observation
+ * (Magnusson, Andersen, Jonasson, Vehtari 2019; restated from the published package, not run against R). The draws come from the
+ * approximation g, so the log ratio of draw i for a cell is (log_p_i - log_g_i) - log_lik_i -- the first term is the array behind
+ * ppcx_fit_get_log_ratios / ppcx_fit_psis, made on first use -- and PSIS runs on it with r_eff = 1 (the draws are independent).
+ * Genes, cells, limits and layout as ppcx_fit_loo: out [n_genes][S][PPCX_LOO_FIELDS], elpd_loo = logsumexp(lw + log_lik) -
+ * logsumexp(lw), p_loo = lpd - elpd_loo with lpd = logsumexp(log_lik) - log N unweighted, looic, khat. Tied ratios take the tail's
+ * positions in draw order. A NaN log_lik or log ratio, or a ratio of +Inf: the cell is NaN; a ratio of -Inf (a draw whose log_p is
+ * not finite) takes no part. A cell excluded by the model is already held out of p, but the draws are still g's: its ratios are
+ * log_p - log_g alone, elpd_loo the same formula, p_loo = 0 and khat the overall k-hat of ppcx_fit_psis (column -1).
+ * A NUTS fit, or one made by ppcx_fit_from_draws: PPCX_ERR_ARG (theirs is ppcx_fit_loo). The same bits on every call, for any gene
+ * subset. The Monte-Carlo standard error and n_eff of ppcx_fit_loo_mcse are not available for these weights.                   */
+PPCX_API int ppcx_fit_loo_approx(ppcx_fit* f, int n_genes, const int32_t* genes, double* out);
+/* ppcx_fit_loo_predict for an ADVI fit: the same predictive counts, quantiles, mean and LOO-PIT under the normalised weights of
+ * ppcx_fit_loo_approx. A cell excluded by the model is weighted too (by log_p - log_g; it has no uniform path, and its khat is
+ * the overall k-hat). out [n_genes][S][PPCX_LOO_PREDICT_FIELDS]; fits and refusals as ppcx_fit_loo_approx, probabilities and
+ * truncation compensation as ppcx_fit_loo_predict.                                                                              */
+PPCX_API int ppcx_fit_loo_predict_approx(ppcx_fit* f, int n_genes, const int32_t* genes, double truncation_compensation, double p_lo,
+                                         double p_hi, unsigned long long seed, double* out);
 /* lp: [chains][n_keep]; the rest [chains][iter] (warmup included); any pointer may be NULL */
 PPCX_API int ppcx_fit_get_diagnostics(ppcx_fit* f, double* lp, double* stepsize, int32_t* treedepth,
                              int32_t* n_leapfrog, int32_t* divergent, double* accept);

@@ -25,7 +25,7 @@ EXPORTS = [
     "ppcx_xchg_create", "ppcx_xchg_handle", "ppcx_xchg_connect", "ppcx_xchg_connect_local", "ppcx_xchg_set_timeout", "ppcx_xchg_destroy",
     "ppcx_fit_nuts_xchg", "ppcx_fit_get_xchg_timing", "ppcx_fit_get_inv_metric", "ppcx_fit_summary",
     "ppcx_fit_get_approximation", "ppcx_fit_get_log_ratios", "ppcx_fit_psis", "ppcx_fit_get_log_lik", "ppcx_fit_loo",
-    "ppcx_fit_loo_predict", "ppcx_fit_relative_eff", "ppcx_fit_loo_mcse",
+    "ppcx_fit_loo_predict", "ppcx_fit_relative_eff", "ppcx_fit_loo_mcse", "ppcx_fit_loo_approx", "ppcx_fit_loo_predict_approx",
 ]
 ABI_VERSION = 400           # include/ppcx.h PPCX_VERSION this binding was written for
 SUMMARY_FIELDS = ("mean", "sd", "q05", "q50", "q95", "rhat", "ess_bulk", "ess_tail")   # PPCX_SUMMARY_FIELDS, in order
@@ -107,6 +107,8 @@ def load() -> C.CDLL:
     lib.ppcx_fit_loo_mcse.argtypes = [C.c_void_p, C.c_int, ip, dp, dp]
     lib.ppcx_fit_loo_predict.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_double, C.c_double, C.c_double, C.c_ulonglong, dp]
     lib.ppcx_fit_relative_eff.argtypes = [C.c_void_p, C.c_int, ip, dp]
+    lib.ppcx_fit_loo_approx.argtypes = [C.c_void_p, C.c_int, ip, dp]
+    lib.ppcx_fit_loo_predict_approx.argtypes = [C.c_void_p, C.c_int, ip, C.c_double, C.c_double, C.c_double, C.c_ulonglong, dp]
     lib.ppcx_fit_get_diagnostics.argtypes = [C.c_void_p, dp, dp, ip, ip, ip, dp]
     lib.ppcx_fit_get_timing.argtypes = [C.c_void_p, dp, C.POINTER(C.c_longlong), dp, C.POINTER(C.c_longlong), dp]
     lib.ppcx_fit_get_kernel_times.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(C.c_longlong)]
@@ -143,6 +145,9 @@ def load() -> C.CDLL:
         lib.ppcx_testing_loo_mcse.argtypes = [C.c_int, C.c_int, dp, ip, dp, dp]
     if hasattr(lib, "ppcx_testing_loo_predict"):
         lib.ppcx_testing_loo_predict.argtypes = [dp, ip, C.c_int, C.c_int, ip, ip, dp, C.c_double, C.c_double, dp]
+    if hasattr(lib, "ppcx_testing_loo_approx"):
+        lib.ppcx_testing_loo_approx.argtypes = [C.c_int, C.c_int, dp, dp, ip, dp]
+        lib.ppcx_testing_loo_predict_approx.argtypes = [dp, dp, ip, C.c_int, C.c_int, ip, ip, C.c_double, C.c_double, dp]
     if hasattr(lib, "ppcx_testing_relative_eff"):
         lib.ppcx_testing_relative_eff.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp]
     lib.ppcx_fit_free.restype = None
@@ -277,6 +282,47 @@ def testing_loo_predict(ll, x, y, excluded=None, r_eff=None, p_lo=0.025, p_hi=0.
                                         _p(ex, C.c_int32) if ex is not None else None,
                                         _p(re, C.c_double) if re is not None else None, float(p_lo), float(p_hi),
                                         _p(out, C.c_double)))
+    return out
+
+
+def _testing_approx_columns(entry, ll, log_ratio, excluded):
+    """What the two approximate-posterior test entries share: the library, ll as [n_cells][n], log_ratio [n], the flags"""
+    lib = load()
+    if not hasattr(lib, entry):
+        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before {entry} existed: rebuild it "
+                        "(`python -m ppcseq_amd.build --testing --force`)")
+    ll = np.asarray(ll, dtype=np.float64)
+    ll = ll.reshape(ll.shape[0], -1)
+    lr = np.ascontiguousarray(log_ratio, dtype=np.float64).ravel()
+    if lr.size != ll.shape[0]:
+        raise ValueError("log_ratio must hold one value per draw")
+    ex = None if excluded is None else np.ascontiguousarray(excluded, dtype=np.int32).ravel()
+    return lib, np.ascontiguousarray(ll.T), lr, ex
+
+
+def testing_loo_approx(ll, log_ratio, excluded=None):
+    """The kernel of ppcx_fit_loo_approx on host-given columns (testing build only; csrc/ppcx_testing.h ppcx_testing_loo_approx):
+    ll [n_draws, n_cells], log_ratio [n_draws] (log_p - log_g of the draws), excluded None or [n_cells]. Returns [n_cells, 4]:
+    elpd_loo, p_loo, looic, khat."""
+    lib, cols, lr, ex = _testing_approx_columns("ppcx_testing_loo_approx", ll, log_ratio, excluded)
+    nc, n = cols.shape
+    out = np.zeros((nc, len(LOO_FIELDS)))
+    _check(lib.ppcx_testing_loo_approx(n, nc, _p(cols, C.c_double), _p(lr, C.c_double),
+                                       _p(ex, C.c_int32) if ex is not None else None, _p(out, C.c_double)))
+    return out
+
+
+def testing_loo_predict_approx(ll, log_ratio, x, y, excluded=None, p_lo=0.025, p_hi=0.975):
+    """The kernel of ppcx_fit_loo_predict_approx on host-given columns (testing build only; csrc/ppcx_testing.h
+    ppcx_testing_loo_predict_approx): as testing_loo_predict with log_ratio [n_draws] and r_eff = 1. Returns [n_cells, 6]."""
+    lib, cols, lr, ex = _testing_approx_columns("ppcx_testing_loo_predict_approx", ll, log_ratio, excluded)
+    nc, n = cols.shape
+    xs = np.ascontiguousarray(np.asarray(x).reshape(n, nc).T, dtype=np.int32)
+    ys = np.ascontiguousarray(np.broadcast_to(np.asarray(y), (nc,)), dtype=np.int32)
+    out = np.zeros((nc, len(LOO_PREDICT_FIELDS)))
+    _check(lib.ppcx_testing_loo_predict_approx(_p(cols, C.c_double), _p(lr, C.c_double), _p(xs, C.c_int32), n, nc, _p(ys, C.c_int32),
+                                               _p(ex, C.c_int32) if ex is not None else None, float(p_lo), float(p_hi),
+                                               _p(out, C.c_double)))
     return out
 
 
@@ -713,6 +759,14 @@ class Fit:
             res["mcse_elpd_loo_total"] = loo_mcse_total(res)
         return res
 
+    def _loo_predict_result(self, g, res, last):
+        """closes a predictive result: `y`, `outside`, then _loo_cells' last keys"""
+        res["y"] = np.asarray(self.model.counts).reshape(self.model.G, self.model.S)[g].astype(np.int64)
+        with np.errstate(invalid="ignore"):
+            res["outside"] = (res["y"] < res["lower"]) | (res["y"] > res["upper"])
+        res.update(last)
+        return res
+
     def loo_predict(self, genes=None, r_eff=None, p_lo=0.025, p_hi=0.975, seed=1, truncation_compensation=1.0):
         """The leave-one-out predictive interval and LOO-PIT per observed cell on the device (ppcx_fit_loo_predict; loo::E_loo,
         bayesplot::ppc_loo_intervals / ppc_loo_pit): a dict of mean, lower, upper (the p_lo / p_hi quantiles of the cell's count
@@ -722,11 +776,28 @@ class Fit:
         seed and truncation_compensation as Fit.ppc: the predictive counts of a checked gene are its counts_rng."""
         g, res, last = self._loo_cells(genes, r_eff, LOO_PREDICT_FIELDS, lambda n, g, re, out: load().ppcx_fit_loo_predict(
             self._h, n, g, re, float(truncation_compensation), float(p_lo), float(p_hi), int(seed), out))
-        res["y"] = np.asarray(self.model.counts).reshape(self.model.G, self.model.S)[g].astype(np.int64)
-        with np.errstate(invalid="ignore"):
-            res["outside"] = (res["y"] < res["lower"]) | (res["y"] > res["upper"])
+        return self._loo_predict_result(g, res, last)
+
+    def loo_approximate_posterior(self, genes=None):
+        """PSIS-LOO per observed cell of an ADVI fit on the device (ppcx_fit_loo_approx; loo::loo_approximate_posterior(log_lik,
+        log_p, log_g)): Fit.loo's dict -- the pointwise elpd_loo, p_loo, looic and khat, [n_genes, S] each, `excluded`, `genes`,
+        `n_draws`, `estimates` over the non-excluded cells -- and `khat_approximation`, the overall k-hat of the approximation
+        (Fit.psis, column -1). The ratios are (log_p - log_g) - log_lik, r_eff = 1. An excluded cell is held out of p already but
+        still needs the correction for g: elpd_loo under the weights of log_p - log_g, p_loo 0, khat = khat_approximation.
+        genes=None: all G genes. Not for a NUTS fit (Fit.loo); no mcse / n_eff."""
+        _, res, last = self._loo_cells(genes, None, LOO_FIELDS, lambda n, g, re, out: load().ppcx_fit_loo_approx(self._h, n, g, out))
         res.update(last)
+        res["estimates"] = loo_estimates(res, res["excluded"])
+        res["khat_approximation"] = float(self.psis(cols=[], overall=True)["khat"][-1])
         return res
+
+    def loo_predict_approximate_posterior(self, genes=None, p_lo=0.025, p_hi=0.975, seed=1, truncation_compensation=1.0):
+        """The leave-one-out predictive interval and LOO-PIT per observed cell of an ADVI fit on the device
+        (ppcx_fit_loo_predict_approx): Fit.loo_predict's dict (without r_eff) under the weights of loo_approximate_posterior. An
+        excluded cell is weighted too (by log_p - log_g), so its interval is not Fit.ppc's; its khat is the overall k-hat."""
+        g, res, last = self._loo_cells(genes, None, LOO_PREDICT_FIELDS, lambda n, g, re, out: load().ppcx_fit_loo_predict_approx(
+            self._h, n, g, float(truncation_compensation), float(p_lo), float(p_hi), int(seed), out))
+        return self._loo_predict_result(g, res, last)
 
     def diagnostics(self):
         lp = np.zeros((self.chains, self.n_keep))

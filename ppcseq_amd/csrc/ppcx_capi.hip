@@ -1935,10 +1935,15 @@ static int loo_done(const char* who, hipError_t e) {
 }
 // the fit, the genes, the cells' counts (an excluded cell as -(y + 1), kept in yenc) and the output as the record of these
 // cells; sets the fit's device
+static int loo_prepare_cells(ppcx_fit* f, int n_genes, const int32_t* genes, const void* out, std::vector<int>& yenc, FitCells& fc);
 static int loo_prepare(ppcx_fit* f, int n_genes, const int32_t* genes, const void* out, std::vector<int>& yenc, FitCells& fc) {
   if (!f) return fail(PPCX_ERR_ARG, "fit is NULL");
   if (f->advi) return fail(PPCX_ERR_ARG, "PSIS-LOO needs the draws of a NUTS fit (loo_approximate_posterior for ADVI fits is "
                                          "not available)");
+  return loo_prepare_cells(f, n_genes, genes, out, yenc, fc);
+}
+// ... whatever produced the fit's draws
+static int loo_prepare_cells(ppcx_fit* f, int n_genes, const int32_t* genes, const void* out, std::vector<int>& yenc, FitCells& fc) {
   if (!genes || n_genes < 1) return fail(PPCX_ERR_ARG, "bad arguments");
   if ((long)f->chains * f->n_keep < 1) return fail(PPCX_ERR_ARG, "fit holds no kept draws");
   const ppcx_model* m = f->m;
@@ -2013,12 +2018,51 @@ extern "C" int ppcx_fit_loo_predict(ppcx_fit* f, int n_genes, const int32_t* gen
   return loo_done(who, loo_predict_fit_cells(fc, truncation_compensation, p_lo, p_hi, seed32(seed), out, loo_scratch_bytes(),
                                              f->m->stream));
 }
+// ---- the same two for an ADVI fit (loo::loo_approximate_posterior; ppcx_loo_ap.h): the draws come from the approximation, the
+// ratios carry log_p - log_g, cached by the first call (psis_ratios)
+static int loo_approx_prepare(const char* who, ppcx_fit* f, int n_genes, const int32_t* genes, const void* out, std::vector<int>& yenc,
+                              FitCells& fc) {
+  if (!f) return fail(PPCX_ERR_ARG, "fit is NULL");
+  if (!f->advi || !f->d_mu.p)
+    return fail(PPCX_ERR_ARG, std::string(who) + " needs an ADVI fit: a NUTS fit, or one over draws produced elsewhere, holds no "
+                                                 "approximation to correct for (PSIS-LOO of a NUTS fit is ppcx_fit_loo)");
+  const int rc = loo_prepare_cells(f, n_genes, genes, out, yenc, fc);
+  return rc == PPCX_OK ? loo_fit_reff(who, fc, nullptr) : rc;
+}
+// the last step before the walk: log_p - log_g of the draws on the device
+static int loo_approx_ratios(ppcx_fit* f, FitCells& fc) {
+  const int rc = psis_ratios(f);
+  fc.log_ratio = f->d_r.p;
+  return rc;
+}
+extern "C" int ppcx_fit_loo_approx(ppcx_fit* f, int n_genes, const int32_t* genes, double* out) {
+  const char* who = "ppcx_fit_loo_approx";
+  std::vector<int> yenc; FitCells fc;
+  int rc = loo_approx_prepare(who, f, n_genes, genes, out, yenc, fc);
+  if (rc == PPCX_OK) rc = loo_approx_ratios(f, fc);
+  if (rc != PPCX_OK) return rc;
+  return loo_done(who, loo_fit_cells(fc, kLooFields, out, loo_scratch_bytes(), f->m->stream));
+}
+extern "C" int ppcx_fit_loo_predict_approx(ppcx_fit* f, int n_genes, const int32_t* genes, double truncation_compensation, double p_lo,
+                                           double p_hi, unsigned long long seed, double* out) {
+  const char* who = "ppcx_fit_loo_predict_approx";
+  std::vector<int> yenc; FitCells fc;
+  int rc = loo_approx_prepare(who, f, n_genes, genes, out, yenc, fc);
+  if (rc == PPCX_OK) rc = loo_predict_check_probs(p_lo, p_hi);
+  if (rc != PPCX_OK) return rc;
+  if (!(isfinite(truncation_compensation) && truncation_compensation > 0.0))
+    return fail(PPCX_ERR_ARG, "truncation_compensation must be finite and > 0");
+  if ((rc = loo_approx_ratios(f, fc)) != PPCX_OK) return rc;
+  return loo_done(who, loo_predict_fit_cells(fc, truncation_compensation, p_lo, p_hi, seed32(seed), out, loo_scratch_bytes(),
+                                             f->m->stream));
+}
 #ifdef PPCX_TESTING
 // testing build only (ppcx_testing.h): the LOO kernel on host-given columns, on the current device
-static int testing_loo(int n, int n_cols, const double* ll, const int32_t* excluded, const double* r_eff, int fields, double* out) {
+static int testing_loo(int n, int n_cols, const double* ll, const int32_t* excluded, const double* r_eff, int fields, double* out,
+                       const double* log_ratio = nullptr) {
   if (n < 1 || n_cols < 1 || !ll || !out) return fail(PPCX_ERR_ARG, "bad arguments");
   GivenCells gc;
-  gc.cols = ll; gc.n = n; gc.n_cols = n_cols; gc.excl = excluded; gc.r_eff = r_eff;
+  gc.cols = ll; gc.n = n; gc.n_cols = n_cols; gc.excl = excluded; gc.r_eff = r_eff; gc.log_ratio = log_ratio;
   const int rc = loo_reff_limits(nullptr, r_eff, n_cols, n, &gc.r_eff_min);
   if (rc != PPCX_OK) return rc;
   return loo_done(nullptr, loo_columns(gc, fields, out, loo_scratch_bytes(), nullptr));
@@ -2030,17 +2074,31 @@ extern "C" int ppcx_testing_loo(int n, int n_cols, const double* ll, const int32
 extern "C" int ppcx_testing_loo_mcse(int n, int n_cols, const double* ll, const int32_t* excluded, const double* r_eff, double* out) {
   return testing_loo(n, n_cols, ll, excluded, r_eff, kLooMcseFields, out);
 }
-// ... the LOO predictive kernel on host-given columns
-extern "C" int ppcx_testing_loo_predict(const double* ll, const int32_t* x, int n, int n_cols, const int32_t* y, const int32_t* excluded,
-                                        const double* r_eff, double p_lo, double p_hi, double* out) {
+// ... the kernel of ppcx_fit_loo_approx: the columns with the draws' log ratios
+extern "C" int ppcx_testing_loo_approx(int n, int n_cols, const double* ll, const double* log_ratio, const int32_t* excluded, double* out) {
+  if (!log_ratio) return fail(PPCX_ERR_ARG, "bad arguments");
+  return testing_loo(n, n_cols, ll, excluded, nullptr, kLooFields, out, log_ratio);
+}
+// ... the LOO predictive kernel on host-given columns (log_ratio: as ppcx_fit_loo_predict_approx runs it)
+static int testing_loo_predict(const double* ll, const double* log_ratio, const int32_t* x, int n, int n_cols, const int32_t* y,
+                               const int32_t* excluded, const double* r_eff, double p_lo, double p_hi, double* out) {
   if (n < 1 || n_cols < 1 || !ll || !x || !y || !out) return fail(PPCX_ERR_ARG, "bad arguments");
   for (size_t i = 0; i < (size_t)n * n_cols; ++i) if (x[i] < 0) return fail(PPCX_ERR_ARG, "predictive counts must be >= 0");
   GivenCells gc;
-  gc.cols = ll; gc.n = n; gc.n_cols = n_cols; gc.excl = excluded; gc.r_eff = r_eff;
+  gc.cols = ll; gc.n = n; gc.n_cols = n_cols; gc.excl = excluded; gc.r_eff = r_eff; gc.log_ratio = log_ratio;
   int rc = loo_predict_check_probs(p_lo, p_hi);
   if (rc == PPCX_OK) rc = loo_reff_limits(nullptr, r_eff, n_cols, n, &gc.r_eff_min);
   if (rc != PPCX_OK) return rc;
   return loo_done(nullptr, loo_predict_columns(gc, x, y, p_lo, p_hi, out, loo_scratch_bytes(), nullptr));
+}
+extern "C" int ppcx_testing_loo_predict(const double* ll, const int32_t* x, int n, int n_cols, const int32_t* y, const int32_t* excluded,
+                                        const double* r_eff, double p_lo, double p_hi, double* out) {
+  return testing_loo_predict(ll, nullptr, x, n, n_cols, y, excluded, r_eff, p_lo, p_hi, out);
+}
+extern "C" int ppcx_testing_loo_predict_approx(const double* ll, const double* log_ratio, const int32_t* x, int n, int n_cols,
+                                               const int32_t* y, const int32_t* excluded, double p_lo, double p_hi, double* out) {
+  if (!log_ratio) return fail(PPCX_ERR_ARG, "bad arguments");
+  return testing_loo_predict(ll, log_ratio, x, n, n_cols, y, excluded, nullptr, p_lo, p_hi, out);
 }
 #endif
 // ---- the relative efficiency of the same cells (loo::relative_eff(exp(log_lik), chain_id): what rstan::loo(fit) passes as r_eff)

@@ -224,9 +224,10 @@ struct LooArgs {
   const double* cols = nullptr; // [cells][n] log-likelihood columns (testing build), instead of T
   const int* excl = nullptr;    // [cells] excluded flags of the given columns (null: none)
   const double* r_eff = nullptr;   // [cells] relative efficiencies (null: 1)
+  const double* lr = nullptr;   // [n] log_p - log_g of an ADVI fit's draws: the approximate-posterior statistic (ppcx_loo_ap.h)
   long n = 0;                   // draws
   int cell0 = 0, n_cells = 0;   // first cell of the launch; cells of the table / columns
-  double* scratch = nullptr;    // [launch's cells][n] the long path's ratios
+  double* scratch = nullptr;    // [launch's cells][n] the long path's ratios ([..][3 n] with lr: ratios, ll, log weights)
   int sel_pad = 0;              // loo_sel_pad: the selection buffer
   double* out = nullptr;        // [cells][kLooFields], or [cells][kLooMcseFields] (ppcx_fit_loo_mcse)
 };
@@ -247,6 +248,7 @@ struct FitCells {
   const int* yenc = nullptr;       // [cells] the counts, an excluded cell as -(y + 1) (host)
   const double* r_eff = nullptr;   // [cells] (host) or null: all 1
   double r_eff_min = 1.0;          // the smallest r_eff (1 without r_eff)
+  const double* log_ratio = nullptr;   // [n] (device) log_p - log_g of an ADVI fit, or null: the draws are the posterior's
 };
 // Host-given log-likelihood columns in place of a fit's cells (testing build): cols [n_cols][n], n = chains n_keep where the
 // statistic needs chains
@@ -255,18 +257,21 @@ struct GivenCells {
   int chains = 0, n_keep = 0;
   const int* excl = nullptr;       // [n_cols] excluded flags or null
   const double* r_eff = nullptr; double r_eff_min = 1.0;
+  const double* log_ratio = nullptr;   // [n] (host) log ratios of the draws, or null
 };
 // The drivers below walk the cells through for_gene_batches / for_given_columns (ppcx_loo_dev.h); out is host, scratch_bytes
 // bounds the gene table of a batch and the cells' scratch of a launch alike (kPsisScratchBytes in the product). Synchronous.
 // LOO: fields = kLooFields, or kLooMcseFields for mcse_elpd_loo and n_eff as well (out holds that many per cell; the first four
-// are the same bits)
+// are the same bits). With log_ratio (an ADVI fit; kLooFields only) the approximate-posterior statistic of ppcx_loo_ap.h: ratios,
+// log-likelihoods and log weights (24 bytes per draw) in LDS up to kPsisLdsDraws draws, beyond that in the scratch
 hipError_t loo_fit_cells(const FitCells& fc, int fields, double* out, size_t scratch_bytes, hipStream_t st);
 hipError_t loo_columns(const GivenCells& gc, int fields, double* out, size_t scratch_bytes, hipStream_t st);
 // the log-likelihood matrix of the cells, [n][cells]
 hipError_t loo_fit_log_lik(const FitCells& fc, double* out, size_t scratch_bytes, hipStream_t st);
 // The leave-one-out predictive interval and LOO-PIT of the same cells (ppcx_loo_predict.hip, statistic in ppcx_loo_predict.h): one
 // workgroup per cell; ratios, weights and predictive counts (20 bytes per draw) in LDS up to kPsisLdsDraws draws, beyond that in
-// the scratch. tc: truncation compensation of the predictive draws; k0 = seed32(seed). out [cells][kLooPredictFields]
+// the scratch. tc: truncation compensation of the predictive draws; k0 = seed32(seed). out [cells][kLooPredictFields]. With
+// log_ratio the weights are those of ppcx_loo_ap.h
 hipError_t loo_predict_fit_cells(const FitCells& fc, double tc, double p_lo, double p_hi, uint32_t k0, double* out,
                                  size_t scratch_bytes, hipStream_t st);
 // ... of given columns with predictive counts x [n_cols][n] and observed counts y [n_cols]

@@ -15,6 +15,13 @@
 //                          more sweep over the same terms with the known normaliser gives sum w^2 and sum w^2 expm1^2, then
 //                          the 1000 Blom scores, at most four per thread in registers, the Monte-Carlo standard error. The
 //                          testing build runs it on host-given columns too.
+//   ppcx_loo_ap_kernel     the same for an ADVI fit (ppcx_fit_loo_approx; ppcx_loo_ap.h): the ratios r = (log_p - log_g) - ll no
+//                          longer determine ll, so a draw keeps r, ll and its log weight lw -- 24 bytes, in LDS up to
+//                          kPsisLdsDraws draws (96 KB beside the two selection arrays), in the workgroup's slice of the scratch
+//                          beyond. lw of a draw as in the predictive kernel (loo_draw_lw: binary search in the sorted tail keys,
+//                          a scan of the earlier draws only for keys that occur more than once), written once; the logsumexps
+//                          then run over the draws in the fixed strided order. An excluded cell takes the same path with
+//                          r = log_p - log_g.
 // Every reduction runs in a fixed order and a cell reads nothing of another cell: its fields are the same bits whatever else is
 // requested and however the work is batched. The G S x n matrix is never materialised for LOO.
 #include <hip/hip_runtime.h>
@@ -61,6 +68,9 @@ __global__ __launch_bounds__(256) void ppcx_loo_ll_kernel(LooArgs a, long j0, lo
   const int ye = a.y[cell];
   out[t] = loo_cell_ll(a, gi, s, j0 + jr, ye < 0 ? -ye - 1 : ye);
 }
+
+// doubles per cell of the approximate-posterior kernel: r [n], ll [n], lw [n]
+__host__ __device__ inline long loo_ap_slice(long n) { return 3 * n; }
 
 struct LooTerms { double a, b; };                // running max or sum of the two logsumexps: a over lw + ll, b over lw
 enum LooSweep : int { LOO_MAX = 0, LOO_SUM, LOO_MCSE };   // what a sweep over the terms accumulates
@@ -178,6 +188,54 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_kernel(LooArgs a) {
   }
 }
 
+template <bool LDS, bool COLS>
+__global__ __launch_bounds__(kBlockThreads) void ppcx_loo_ap_kernel(LooArgs a) {
+#pragma clang fp contract(off)
+  extern __shared__ uint64_t lds_u[];
+  __shared__ PsisShared sh;
+  const int tid = threadIdx.x;
+  const long n = a.n;
+  uint64_t* K = lds_u;                                   // [sel_pad] keys of the M + 1 largest ratios
+  double* X = reinterpret_cast<double*>(lds_u + a.sel_pad);            // [sel_pad] the tail's exceedances
+  double* V = LDS ? X + a.sel_pad : a.scratch + (long)blockIdx.x * loo_ap_slice(n);   // [n] the ratios
+  double* L = V + n;                                     // [n] the log-likelihoods
+  double* W = L + n;                                     // [n] the log weights
+  const LooCell c = loo_cell<COLS>(a);
+  double* o = a.out + (long)c.cell * kLooFields;
+  long N; double rmax, lmax;
+  if (loo_ap_cell_ratios<COLS>(a, c.cell, c.gi, c.s, c.y, c.excluded, V, L, sh, &N, &rmax, &lmax)) {
+    if (tid == 0) o[0] = o[1] = o[2] = o[3] = NAN;
+    return;
+  }
+  // sum over the draws that take part of f(i), or their maximum; every thread gets it (fixed order)
+  auto part_sum = [&](auto f) {
+    double v = 0.0;
+    for (long i = tid; i < n; i += kBlockThreads) if (V[i] != -INFINITY) v += f(i);
+    return block_sum(v, sh.red);
+  };
+  auto part_max = [&](auto f) {
+    double v = -INFINITY;
+    for (long i = tid; i < n; i += kBlockThreads) if (V[i] != -INFINITY) v = fmax(v, f(i));
+    return block_max(v, sh.red);
+  };
+  // ---- the tail and the log weight of every draw
+  const int M = psis_tail_len(N);
+  const LooTail lt = loo_cell_tail(V, n, N, M, K, X, a.sel_pad, sh);
+  for (long i = tid; i < n; i += kBlockThreads) W[i] = loo_draw_lw(V, i, rmax, lt, M, K);
+  // ---- logsumexp(lw + ll) - logsumexp(lw); lpd = logsumexp(ll) - log N
+  const double ma = part_max([&](long i) { return W[i] + L[i]; });
+  const double mb = part_max([&](long i) { return W[i]; });
+  const double sa = part_sum([&](long i) { return exp(W[i] + L[i] - ma); });
+  const double sb = part_sum([&](long i) { return exp(W[i] - mb); });
+  const double elpd = loo_ap_lse(ma, sa) - loo_ap_lse(mb, sb);
+  double p_loo = 0.0;
+  if (!c.excluded) {
+    const double sl = part_sum([&](long i) { return exp(L[i] - lmax); });
+    p_loo = loo_ap_lse(lmax, sl) - log((double)N) - elpd;
+  }
+  if (tid == 0) { o[0] = elpd; o[1] = p_loo; o[2] = -2.0 * elpd; o[3] = lt.khat; }
+}
+
 // ---- launch helpers (host)
 int loo_sel_pad(long n, double r_eff_min) { return pow2_at_least((long)psis_tail_len(n, r_eff_min) + 1); }
 hipError_t launch_loo_table_kernel(const double* draws, long n_draws, const Dims& d, const int* genes, int n_genes, double* T,
@@ -199,14 +257,22 @@ static hipError_t launch_loo_kernel_of(const LooArgs& a, int n_blocks, hipStream
                                       : (cols ? ppcx_loo_kernel<false, true, MCSE> : ppcx_loo_kernel<false, false, MCSE>);
   return launch_dynamic_lds(kernel, n_blocks, kBlockThreads, bytes, st, a);
 }
-// fields: kLooFields, or kLooMcseFields (a.out then holds six per cell)
+static hipError_t launch_loo_ap_kernel(const LooArgs& a, int n_blocks, hipStream_t st) {
+  const bool lds = a.n <= kPsisLdsDraws, cols = a.cols != nullptr;
+  const size_t bytes = sizeof(double) * (2 * (size_t)a.sel_pad + (lds ? (size_t)loo_ap_slice(a.n) : 0));
+  void (*const kernel)(LooArgs) = lds ? (cols ? ppcx_loo_ap_kernel<true, true> : ppcx_loo_ap_kernel<true, false>)
+                                      : (cols ? ppcx_loo_ap_kernel<false, true> : ppcx_loo_ap_kernel<false, false>);
+  return launch_dynamic_lds(kernel, n_blocks, kBlockThreads, bytes, st, a);
+}
+// fields: kLooFields, or kLooMcseFields (a.out then holds six per cell); with a.lr the approximate-posterior kernel (kLooFields)
 hipError_t launch_loo_kernel(const LooArgs& a, int fields, int n_blocks, hipStream_t st) {
+  if (a.lr) return fields == kLooFields ? launch_loo_ap_kernel(a, n_blocks, st) : hipErrorInvalidValue;
   return fields == kLooMcseFields ? launch_loo_kernel_of<true>(a, n_blocks, st) : launch_loo_kernel_of<false>(a, n_blocks, st);
 }
 
 // Cells of a launch in batches: all at once where the ratios live in LDS, else as many as the scratch bound holds.
 static hipError_t loo_cells(LooArgs a, int fields, int n_cells, size_t scratch_bytes, DeviceBuffer<double>& scratch, hipStream_t st) {
-  return loo_cell_batches(n_cells, a.n > kPsisLdsDraws ? a.n : 0, scratch_bytes, scratch, [&](int c0, int nc, double* scr) {
+  return loo_cell_batches(n_cells, a.n > kPsisLdsDraws ? (a.lr ? loo_ap_slice(a.n) : a.n) : 0, scratch_bytes, scratch, [&](int c0, int nc, double* scr) {
     a.cell0 = c0; a.scratch = scr;
     return launch_loo_kernel(a, fields, nc, st);
   });

@@ -1,7 +1,8 @@
 // ppcx_loo_dev.h -- what the per-cell leave-one-out kernels share (ppcx_loo.hip: PSIS-LOO per cell; ppcx_loo_predict.hip: the
 // leave-one-out predictive interval per cell; ppcx_reff.hip: the relative efficiency per cell). On the device: which cell a
-// workgroup has, the cell's linear predictor and log-likelihood from the transposed table, its ratios r = -ll, the fitted tail
-// with the copies of the cutoff. On the host: the one walk over a fit's cells in gene batches (for_gene_batches), its
+// workgroup has, the cell's linear predictor and log-likelihood from the transposed table, its ratios r = -ll (an ADVI fit:
+// (log_p - log_g) - ll, ppcx_loo_ap.h), the fitted tail with the copies of the cutoff, a draw's log weight under the tie rule.
+// On the host: the one walk over a fit's cells in gene batches (for_gene_batches), its
 // counterpart for host-given columns (for_given_columns) and the batches of cells under the scratch bound
 // (loo_cell_batches); a statistic's drivers add their argument block and their kernel. The statistic is ppcx_loo.h; the
 // workgroup pieces are ppcx_block.h and ppcx_psis_dev.h.
@@ -9,6 +10,7 @@
 #include <hip/hip_runtime.h>
 #include "ppcx_psis_dev.h"
 #include "ppcx_loo.h"
+#include "ppcx_loo_ap.h"
 #include "ppcx_columns.h"
 
 namespace ppcx {
@@ -60,6 +62,31 @@ __device__ inline bool loo_cell_ratios(const LooArgs& a, int cell, int gi, int s
   return false;
 }
 
+// The same for the approximate-posterior statistic (ppcx_loo_ap.h step 0): r = a.lr - ll (an excluded cell: a.lr alone) into
+// V[0 .. n) and, where L is given, ll into L[0 .. n). Also NaN: a cell without a participating draw.
+template <bool COLS>
+__device__ inline bool loo_ap_cell_ratios(const LooArgs& a, int cell, int gi, int s, int y, bool excluded, double* V, double* L,
+                                          PsisShared& sh, long* N, double* rmax_out, double* lmax_out) {
+  const int tid = threadIdx.x;
+  const long n = a.n;
+  bool bad = false; double cnt = 0.0, rmax = -INFINITY, lmax = -INFINITY;
+  for (long i = tid; i < n; i += kBlockThreads) {
+    const double ll = COLS ? a.cols[(long)cell * n + i] : loo_cell_ll(a, gi, s, i, y);
+    const double lr = a.lr[i];
+    const double r = loo_ap_ratio(lr, ll, excluded);
+    bad = bad || loo_ap_bad(lr, ll, r, excluded);
+    if (r != -INFINITY) { cnt += 1.0; rmax = fmax(rmax, r); lmax = fmax(lmax, ll); }
+    V[i] = r;
+    if (L) L[i] = ll;
+  }
+  bad = block_any(bad);
+  if (bad) return true;
+  *N = (long)block_sum(cnt, sh.red);
+  *rmax_out = block_max(rmax, sh.red);
+  *lmax_out = block_max(lmax, sh.red);
+  return *N == 0;
+}
+
 // The tail of the ratios V (ppcx_loo.h step 2): k-hat, sigma, whether the tail is smoothed, and where it is, n_eq = the copies
 // of the cutoff among all the draws (tl.want of them are among the M + 1 largest, one of those the cutoff itself).
 struct LooTail { double khat = INFINITY, sigma = 0.0; bool smooth = false; int n_eq = 0; PsisTail tl{}; };
@@ -76,6 +103,24 @@ __device__ inline LooTail loo_cell_tail(const double* V, long n, long N, int M, 
     }
   }
   return t;
+}
+
+// The log weight of draw i (ppcx_loo_predict.h step 2) from the ratios V, their fitted tail and the sorted keys K[0 .. M]: the
+// tail position of a draw by binary search, and for a key that occurs more than once among the M + 1 largest a scan of the
+// earlier draws (ties are rare)
+__device__ __forceinline__ int loo_draw_tail_pos(const double* V, long i, double r, const LooTail& lt, int M, const uint64_t* K) {
+  if (!lt.smooth || r == -INFINITY) return 0;
+  const PsisTail& tl = lt.tl;
+  const uint64_t k = psis_key(r);
+  if (k < tl.key) return 0;
+  const bool scan = k == tl.key ? tl.want > 1 : loo_predict_tied(K, M, loo_predict_lower_bound(K, M, k));
+  long before = 0;
+  if (scan) for (long i2 = 0; i2 < i; ++i2) before += psis_key(V[i2]) == k ? 1 : 0;
+  return loo_predict_tail_pos(k, K, M, tl.key, tl.want, lt.n_eq, before);
+}
+__device__ __forceinline__ double loo_draw_lw(const double* V, long i, double mx, const LooTail& lt, int M, const uint64_t* K) {
+  const double r = V[i];
+  return loo_predict_lw(r, mx, loo_draw_tail_pos(V, i, r, lt, M, K), M, lt.khat, lt.sigma, lt.tl.ec);
 }
 
 // Cells of a launch in batches: all at once where a cell's arrays live in LDS (slice = 0), else as many as the scratch bound
@@ -109,7 +154,7 @@ struct FitCellsDev {
     const size_t c0 = (size_t)g0 * fc.d.S;
     LooArgs a;
     a.T = T; a.y = y.p + c0; a.expo = fc.expo; a.X = fc.X; a.S = fc.d.S; a.C = fc.d.C; a.n = fc.n;
-    a.r_eff = r_eff.p ? r_eff.p + c0 : nullptr;
+    a.r_eff = r_eff.p ? r_eff.p + c0 : nullptr; a.lr = fc.log_ratio;
     a.n_cells = ng * fc.d.S; a.sel_pad = loo_sel_pad(fc.n, fc.r_eff_min);
     return a;
   }
@@ -145,14 +190,15 @@ hipError_t for_gene_batches(const FitCells& fc, int fields, double* out, size_t 
 template <class Body>
 hipError_t for_given_columns(const GivenCells& gc, int fields, double* out, hipStream_t st, Body body) {
   const size_t n_cols = (size_t)gc.n_cols;
-  DeviceBuffer<double> d_cols, d_reff, d_out, d_scr; DeviceBuffer<int> d_excl;
+  DeviceBuffer<double> d_cols, d_reff, d_lr, d_out, d_scr; DeviceBuffer<int> d_excl;
   hipError_t e = d_cols.upload(gc.cols, (size_t)gc.n * n_cols, st);
   if (e == hipSuccess && gc.excl) e = d_excl.upload(gc.excl, n_cols, st);
   if (e == hipSuccess && gc.r_eff) e = d_reff.upload(gc.r_eff, n_cols, st);
+  if (e == hipSuccess && gc.log_ratio) e = d_lr.upload(gc.log_ratio, (size_t)gc.n, st);
   if (e == hipSuccess) e = d_out.alloc((size_t)fields * n_cols);
   if (e == hipSuccess) {
     LooArgs a;
-    a.cols = d_cols.p; a.excl = d_excl.p; a.r_eff = d_reff.p; a.n = gc.n; a.n_cells = gc.n_cols; a.out = d_out.p;
+    a.cols = d_cols.p; a.excl = d_excl.p; a.r_eff = d_reff.p; a.lr = d_lr.p; a.n = gc.n; a.n_cells = gc.n_cols; a.out = d_out.p;
     a.sel_pad = loo_sel_pad(gc.n, gc.r_eff_min);
     e = body(a, (const int*)nullptr, gc.n_cols, d_scr);
   }

@@ -11,6 +11,8 @@
 //                            value with one fixed-order sum of weights per step.
 //                            Per draw 20 bytes: r (8), w (8), x (4) -- in LDS up to kPsisLdsDraws draws (80 KB, beside the two
 //                            selection arrays), in the workgroup's slice of a bounded global scratch beyond.
+//                            AP (ppcx_fit_loo_predict_approx): the ratios of an ADVI fit, (log_p - log_g) - ll, and an excluded
+//                            cell down the weighted path with log_p - log_g (ppcx_loo_ap.h); the rest is the same code.
 // Every reduction runs in a fixed order and a cell reads nothing of another cell: its fields are the same bits whatever else is
 // requested and however the work is batched. Neither the log-likelihood nor the counts matrix is materialised.
 #include <hip/hip_runtime.h>
@@ -48,7 +50,8 @@ __device__ __forceinline__ double draws_max(long n, double* red, F f) {
   return block_max(m, red);
 }
 
-template <bool LDS, bool COLS>
+// AP: the weights of an ADVI fit (ppcx_loo_ap.h: ratios (log_p - log_g) - ll; an excluded cell is weighted too, by log_p - log_g)
+template <bool LDS, bool COLS, bool AP>
 __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_predict_kernel(LooPredictArgs p) {
 #pragma clang fp contract(off)
   extern __shared__ uint64_t lds_u[];
@@ -68,7 +71,11 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_predict_kernel(LooPred
   auto all_nan = [&]() { if (tid == 0) for (int f = 0; f < kLooPredictFields; ++f) o[f] = NAN; };
   // ---- the ratios
   long N; double rmax, lmax;
-  if (loo_cell_ratios<COLS>(a, cell, gi, s, y, excluded, V, sh, &N, &rmax, &lmax)) { all_nan(); return; }
+  if constexpr (AP) {
+    if (loo_ap_cell_ratios<COLS>(a, cell, gi, s, y, excluded, V, nullptr, sh, &N, &rmax, &lmax)) { all_nan(); return; }
+  } else {
+    if (loo_cell_ratios<COLS>(a, cell, gi, s, y, excluded, V, sh, &N, &rmax, &lmax)) { all_nan(); return; }
+  }
   // ---- the predictive count of every draw
   bool inval = false;
   if (COLS) {
@@ -84,7 +91,7 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_predict_kernel(LooPred
   if (block_any(inval) || (!excluded && N == 0)) { all_nan(); return; }   // block_any: XI is visible to every thread
   const double pr[2] = {p.p_lo, p.p_hi};
   double q[2];
-  if (excluded) {
+  if (!AP && excluded) {
     // ---- already held out: uniform weights over all n draws, the type-7 quantiles of the posterior-predictive kernels
     const double sum = draws_sum(n, sh.red, [&](long i) { return (double)XI[i]; });
     const int vmax = (int)draws_max(n, sh.red, [&](long i) { return (double)XI[i]; });
@@ -107,22 +114,9 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_predict_kernel(LooPred
   const double mx = rmax;
   const int M = psis_tail_len(N, a.r_eff ? a.r_eff[cell] : 1.0);
   const LooTail lt = loo_cell_tail(V, n, N, M, K, X, a.sel_pad, sh);
-  const PsisTail& tl = lt.tl;
   double mxw = -INFINITY;
   for (long i = tid; i < n; i += kBlockThreads) {
-    const double r = V[i];
-    int j = 0;
-    if (lt.smooth && r != -INFINITY) {
-      const uint64_t k = psis_key(r);
-      if (k >= tl.key) {
-        // the earlier draws with this key count only where the key occurs more than once in the tail (ties are rare)
-        const bool scan = k == tl.key ? tl.want > 1 : loo_predict_tied(K, M, loo_predict_lower_bound(K, M, k));
-        long before = 0;
-        if (scan) for (long i2 = 0; i2 < i; ++i2) before += psis_key(V[i2]) == k ? 1 : 0;
-        j = loo_predict_tail_pos(k, K, M, tl.key, tl.want, lt.n_eq, before);
-      }
-    }
-    const double lw = loo_predict_lw(r, mx, j, M, lt.khat, lt.sigma, tl.ec);
+    const double lw = loo_draw_lw(V, i, mx, lt, M, K);
     W[i] = lw; mxw = fmax(mxw, lw);
   }
   mxw = block_max(mxw, sh.red);
@@ -151,8 +145,11 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_predict_kernel(LooPred
 static hipError_t launch_loo_predict_kernel(const LooPredictArgs& p, int n_blocks, hipStream_t st) {
   const bool lds = p.l.n <= kPsisLdsDraws, cols = p.l.cols != nullptr;
   const size_t bytes = sizeof(double) * (2 * (size_t)p.l.sel_pad + (lds ? (size_t)loo_predict_slice(p.l.n) : 0));
-  void (*const kernel)(LooPredictArgs) = lds ? (cols ? ppcx_loo_predict_kernel<true, true> : ppcx_loo_predict_kernel<true, false>)
-                                             : (cols ? ppcx_loo_predict_kernel<false, true> : ppcx_loo_predict_kernel<false, false>);
+  void (*kernel)(LooPredictArgs);
+  if (p.l.lr) kernel = lds ? (cols ? ppcx_loo_predict_kernel<true, true, true> : ppcx_loo_predict_kernel<true, false, true>)
+                           : (cols ? ppcx_loo_predict_kernel<false, true, true> : ppcx_loo_predict_kernel<false, false, true>);
+  else kernel = lds ? (cols ? ppcx_loo_predict_kernel<true, true, false> : ppcx_loo_predict_kernel<true, false, false>)
+                    : (cols ? ppcx_loo_predict_kernel<false, true, false> : ppcx_loo_predict_kernel<false, false, false>);
   return launch_dynamic_lds(kernel, n_blocks, kBlockThreads, bytes, st, p);
 }
 static hipError_t loo_predict_cells(LooPredictArgs p, int n_cells, size_t scratch_bytes, DeviceBuffer<double>& scratch, hipStream_t st) {

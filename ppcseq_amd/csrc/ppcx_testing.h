@@ -60,6 +60,11 @@ PPCX_API int ppcx_testing_loo_mcse(int n, int n_cols, const double* ll, const in
  * NULL or [n_cols] flags, r_eff NULL or [n_cols]; out [n_cols][6]: mean, lower, upper, pit_lt, pit_le, khat. */
 PPCX_API int ppcx_testing_loo_predict(const double* ll, const int32_t* x, int n, int n_cols, const int32_t* y, const int32_t* excluded,
                                       const double* r_eff, double p_lo, double p_hi, double* out);
+/* The kernels of ppcx_fit_loo_approx and ppcx_fit_loo_predict_approx on host-given columns (ppcx_loo_ap.h): as the two above
+ * with log_ratio [n], the draws' log_p - log_g, and r_eff = 1. */
+PPCX_API int ppcx_testing_loo_approx(int n, int n_cols, const double* ll, const double* log_ratio, const int32_t* excluded, double* out);
+PPCX_API int ppcx_testing_loo_predict_approx(const double* ll, const double* log_ratio, const int32_t* x, int n, int n_cols,
+                                             const int32_t* y, const int32_t* excluded, double p_lo, double p_hi, double* out);
 /* The kernel of ppcx_fit_relative_eff on host-given log-likelihood columns, on the current device (ppcx_reff.hip): ll
  * [n_cols][chains n] (a cell's draws contiguous, chain-major), out [n_cols]. */
 PPCX_API int ppcx_testing_relative_eff(int chains, int n, int n_cols, const double* ll, double* out);

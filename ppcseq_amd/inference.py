@@ -65,6 +65,8 @@ class InferenceResult:
     approximation: dict | None = None  # check_approximation: Fit.psis of alpha_sub_1 and the overall k-hat (column -1, last)
     loo: dict | None = None            # check_loo: Fit.loo of the checked genes' cells ([K, S] arrays and loo's estimates)
     loo_intervals: dict | None = None  # check_loo_intervals: Fit.loo_predict of the checked genes' cells ([K, S] arrays)
+    approximation_loo: dict | None = None            # check_approximation_loo: Fit.loo_approximate_posterior of those cells
+    approximation_loo_intervals: dict | None = None  # check_approximation_loo_intervals: Fit.loo_predict_approximate_posterior
 
     def to_frame(self):
         import pandas as pd
@@ -230,7 +232,9 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                  check_loo=False,
                  check_loo_intervals=False,
                  loo_r_eff=None,
-                 loo_mcse=False):
+                 loo_mcse=False,
+                 check_approximation_loo=False,
+                 check_approximation_loo_intervals=False):
     """One inference pass (discovery or test) of ppcseq on the GPU.
 
     counts            G x S integer matrix, genes ordered with the `how_many_to_check` checked genes first
@@ -269,6 +273,13 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
     loo_mcse          True: `res.loo` also carries loo's pointwise `mcse_elpd_loo` and `n_eff` of every checked cell and
                       `mcse_elpd_loo_total` (Fit.loo(mcse=True); pareto_k_table reads it). It raises no further warning.
                       devices=[...]: over the pooled chains. Needs check_loo.
+    check_approximation_loo  check_loo for an ADVI pass: PSIS-LOO of every checked cell with the correction for the approximation
+                      (loo::loo_approximate_posterior; ratios (log_p - log_g) - log_lik, r_eff = 1) on the device
+                      (Fit.loo_approximate_posterior), kept as `res.approximation_loo` and reported as RuntimeWarning when a k-hat
+                      is too high (loo_warnings). No mcse / n_eff. Not for a NUTS pass.
+    check_approximation_loo_intervals  check_loo_intervals for an ADVI pass, under the same weights
+                      (Fit.loo_predict_approximate_posterior) at the pass's interval probabilities, seed and truncation
+                      compensation, kept as `res.approximation_loo_intervals`. No warning, no flag changes. Not for a NUTS pass.
     Returns an InferenceResult.
     """
     counts = np.asarray(counts)
@@ -297,10 +308,12 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
         raise ValueError("check_approximation needs an ADVI pass (approximate_posterior_inference = True): the Pareto k "
                          "diagnostic judges the variational approximation")
     if check_loo and approximate_posterior_inference:
-        raise ValueError("check_loo needs a NUTS pass: PSIS-LOO of an ADVI fit (loo_approximate_posterior) is not available")
+        raise ValueError("check_loo needs a NUTS pass: PSIS-LOO of an ADVI fit (loo_approximate_posterior) is "
+                         "check_approximation_loo")
     if check_loo_intervals and approximate_posterior_inference:
-        raise ValueError("check_loo_intervals needs a NUTS pass: PSIS-LOO of an ADVI fit (loo_approximate_posterior) is not "
-                         "available")
+        raise ValueError("check_loo_intervals needs a NUTS pass: the leave-one-out intervals of an ADVI fit "
+                         "(loo_approximate_posterior) are check_approximation_loo_intervals")
+    _check_approximation_loo(approximate_posterior_inference, check_approximation_loo, check_approximation_loo_intervals)
     _check_loo_r_eff(loo_r_eff, check_loo, check_loo_intervals)
     _check_loo_mcse(loo_mcse, check_loo)
     if devices is not None and len(devices) > 1 and (save_generated_quantities or pass_fit or model is not None or approximate_posterior_inference):
@@ -350,6 +363,12 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
             res.approximation = fit.psis(np.arange(off_alpha1, off_alpha1 + K), overall=True)
             for msg in approximation_warnings(res.approximation["khat"][-1]):
                 warnings.warn(msg, RuntimeWarning, stacklevel=2)
+        if check_approximation_loo:
+            res.approximation_loo = fit.loo_approximate_posterior(np.arange(K))
+            _warn_loo(res.approximation_loo, fit.chains * fit.n_keep)
+        if check_approximation_loo_intervals:
+            res.approximation_loo_intervals = fit.loo_predict_approximate_posterior(
+                np.arange(K), p_lo=p, p_hi=1 - p, seed=seed, truncation_compensation=truncation_compensation)
         if not approximate_posterior_inference:
             import warnings
             for msg in hmc_warnings(res.diagnostics, warmup):
@@ -381,6 +400,17 @@ def _check_loo_r_eff(loo_r_eff, check_loo, check_loo_intervals):
         raise ValueError(f'loo_r_eff must be None or "auto", not {loo_r_eff!r}')
     if not (check_loo or check_loo_intervals):
         raise ValueError("loo_r_eff needs check_loo or check_loo_intervals: it is the r_eff of their PSIS")
+
+
+def _check_approximation_loo(approximate_posterior_inference, check_approximation_loo, check_approximation_loo_intervals):
+    if approximate_posterior_inference:
+        return
+    if check_approximation_loo:
+        raise ValueError("check_approximation_loo needs an ADVI pass (approximate_posterior_inference = True): it corrects "
+                         "PSIS-LOO for the variational approximation; PSIS-LOO of a NUTS pass is check_loo")
+    if check_approximation_loo_intervals:
+        raise ValueError("check_approximation_loo_intervals needs an ADVI pass (approximate_posterior_inference = True): the "
+                         "leave-one-out intervals of a NUTS pass are check_loo_intervals")
 
 
 def _check_loo_mcse(loo_mcse, check_loo):

@@ -15,7 +15,7 @@ import warnings
 
 import numpy as np
 
-from .inference import _check_loo_mcse, _check_loo_r_eff, do_inference
+from .inference import _check_approximation_loo, _check_loo_mcse, _check_loo_r_eff, do_inference
 
 
 def parse_formula(formula: str):
@@ -118,7 +118,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                       cores=None, pass_fit=False, do_check_only_on_detrimental=None, tol_rel_obj=0.01,
                       just_discovery=False, seed=None, adj_prob_theshold_2=None, device=0, devices=None, launch=None, _pass=None,
                       check_convergence=False, check_approximation=False, check_loo=False,
-                      check_loo_intervals=False, loo_r_eff=None, loo_mcse=False):
+                      check_loo_intervals=False, loo_r_eff=None, loo_mcse=False,
+                      check_approximation_loo=False, check_approximation_loo_intervals=False):
     """Mirror of ppcseq::identify_outliers (R/methods.R:74-367): same arguments, same defaults.
 
     data is a tidy pandas DataFrame (one row per transcript x sample); column arguments are strings. As in the
@@ -151,6 +152,13 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
     from the pass's own chains (Fit.relative_eff), as rstan::loo(fit) does, and the results carry it as `r_eff`; None: r_eff = 1.
     `loo_mcse` = True (with check_loo): out.attrs["loo_discovery"] and ["loo_test"] also carry loo's pointwise `mcse_elpd_loo` and
     `n_eff` of the checked cells and `mcse_elpd_loo_total` (Fit.loo(mcse=True); inference.pareto_k_table tabulates them).
+    `check_approximation_loo` = True (ADVI only): both passes compute PSIS-LOO of the checked cells with the correction for the
+    variational approximation, as loo::loo_approximate_posterior would (Fit.loo_approximate_posterior; pass 2 holds its
+    excluded cells out); the results go to out.attrs["approximation_loo_discovery"] and ["approximation_loo_test"], loo's k-hat
+    warning is a RuntimeWarning. `check_approximation_loo_intervals` = True (ADVI only): both passes also keep the leave-one-out
+    predictive interval and LOO-PIT of the checked cells under those weights (Fit.loo_predict_approximate_posterior) at the
+    pass's interval probabilities, seed and truncation compensation, in out.attrs["approximation_loo_intervals_discovery"] and
+    ["approximation_loo_intervals_test"]; reported only.
     """
     import os
     import pandas as pd
@@ -176,16 +184,18 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
         raise ValueError("check_approximation needs ADVI (approximate_posterior_inference = True): it judges the variational "
                          "approximation")
     if check_loo and approximate_posterior_inference:
-        raise ValueError("check_loo needs NUTS (approximate_posterior_inference = False): PSIS-LOO of an ADVI fit is not available")
+        raise ValueError("check_loo needs NUTS (approximate_posterior_inference = False): PSIS-LOO of an ADVI fit is "
+                         "check_approximation_loo")
     if check_loo and _pass is not None:
         raise ValueError("check_loo is not available for passes over several ranks")
     if check_loo_intervals and approximate_posterior_inference:
-        raise ValueError("check_loo_intervals needs NUTS (approximate_posterior_inference = False): PSIS-LOO of an ADVI fit is "
-                         "not available")
+        raise ValueError("check_loo_intervals needs NUTS (approximate_posterior_inference = False): the leave-one-out "
+                         "intervals of an ADVI fit are check_approximation_loo_intervals")
     if check_loo_intervals and _pass is not None:
         raise ValueError("check_loo_intervals is not available for passes over several ranks")
     _check_loo_r_eff(loo_r_eff, check_loo, check_loo_intervals)
     _check_loo_mcse(loo_mcse, check_loo)
+    _check_approximation_loo(approximate_posterior_inference, check_approximation_loo, check_approximation_loo_intervals)
     if check_convergence and _pass is not None:
         raise ValueError("check_convergence is not available for passes over several ranks")
     if approximate_posterior_inference and save_generated_quantities:
@@ -277,6 +287,10 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
             where.update(loo_r_eff=loo_r_eff)
         if loo_mcse:
             where.update(loo_mcse=True)
+        if check_approximation_loo:
+            where.update(check_approximation_loo=True)
+        if check_approximation_loo_intervals:
+            where.update(check_approximation_loo_intervals=True)
     try:
         # ---- pass 1: discovery (R/methods.R:268-286); always the full posterior analysis
         res1 = run_pass(counts, X, exposure_rate, K,
@@ -293,6 +307,10 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                 out1.attrs["loo_discovery"] = res1.loo
             if check_loo_intervals:
                 out1.attrs["loo_intervals_discovery"] = res1.loo_intervals
+            if check_approximation_loo:
+                out1.attrs["approximation_loo_discovery"] = res1.approximation_loo
+            if check_approximation_loo_intervals:
+                out1.attrs["approximation_loo_intervals_discovery"] = res1.approximation_loo_intervals
             return out1
         # ---- cells to exclude (R/methods.R:292-300)
         flag = res1.deleterious_outliers if (do_check_only_on_detrimental and res1.deleterious_outliers is not None) else ~res1.ppc
@@ -342,6 +360,11 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
         out.attrs["loo_discovery"], out.attrs["loo_test"] = res1.loo, res2.loo
     if check_loo_intervals:
         out.attrs["loo_intervals_discovery"], out.attrs["loo_intervals_test"] = res1.loo_intervals, res2.loo_intervals
+    if check_approximation_loo:
+        out.attrs["approximation_loo_discovery"], out.attrs["approximation_loo_test"] = res1.approximation_loo, res2.approximation_loo
+    if check_approximation_loo_intervals:
+        out.attrs["approximation_loo_intervals_discovery"] = res1.approximation_loo_intervals
+        out.attrs["approximation_loo_intervals_test"] = res2.approximation_loo_intervals
     if pass_fit:                                                           # R/methods.R:353-357: attrs "fit 1" / "fit 2"
         out.attrs["fit 1"], out.attrs["fit 2"] = res1.fit, res2.fit        # device-resident; the library keeps the model
     return out                                                             # alive until both fits are closed
