@@ -194,7 +194,7 @@ def testing_set_nccl_provider(path: str):
 
 # function ids of ppcx_testing_eval_math (csrc/ppcx_testing.h PPCX_MATH_*)
 TESTING_MATH = ("fast_rcp", "fast_log", "fast_exp", "table_log", "window_log", "stirling_tails", "stirling_excess",
-                "log_erfc_ratio", "cell", "cell_win", "cell_y", "cell_win_y")
+                "log_erfc_ratio", "cell", "cell_win", "cell_y", "cell_win_y", "sincos_2pi", "lgamma_int1", "rng_exp", "rng_div")
 
 
 def testing_eval_math(fn: str, a, b=None, y=None):

@@ -332,7 +332,14 @@ struct Stream {
 #if defined(__HIP_DEVICE_COMPILE__)
 PPCX_HD double rng_log(double x) { return fast_log(x); }
 PPCX_HD double rng_exp(double x) { return (x > -700.0 && x < 700.0) ? fast_exp(x) : exp(x); }
-PPCX_HD double rng_div(double a, double b) { return a * fast_rcp(b); }      // v_rcp_f64 + Newton instead of the ~30-instruction division
+// a / b without the ~30-instruction division: q = a fast_rcp(b) carries fast_rcp's error (2.2e-15 relative at most, ten units in the
+// last place), so the residual a - b q, exact in one multiply-add, corrects it once: within one unit in the last place of a / b
+// (tests/math_edges.py check_rng_div holds it to two). A non-finite q (exp(eta) overflowed) stays as it is.
+PPCX_HD double rng_div(double a, double b) {
+  const double r = fast_rcp(b), q = a * r;
+  const double c = fma(fma(-b, q, a), r, q);
+  return isfinite(q) ? c : q;
+}
 // sin(2 pi u), cos(2 pi u), u in (0, 1): the quadrant and the reduced argument are exact in u; kernel polynomials of
 // Sun's fdlibm k_sin.c / k_cos.c (public domain algorithm) on [0, pi/4]
 PPCX_HD void sincos_2pi(double u, double* sn, double* cs) {

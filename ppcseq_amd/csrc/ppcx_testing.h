@@ -39,10 +39,14 @@ PPCX_API int ppcx_testing_sm_trace(double* out6);
  *   STIRLING_TAILS: out0, out1 = lg_tail, dg_tail of r = a          STIRLING_EXCESS: dlt, dps of phi = a, ln phi = b, any_small = y
  *   LOG_ERFC_RATIO: log erfc(a), exp(-a^2)/erfc(a)
  *   CELL / CELL_WIN (ppcx_model.h cell_eval / cell_eval_win with one = 1): ln w, 1/w of w = fma(a, b, 1), count y
- *   CELL_Y / CELL_WIN_Y: the same cells' y ln w and y / w accumulations */
+ *   CELL_Y / CELL_WIN_Y: the same cells' y ln w and y / w accumulations
+ *   the posterior-predictive sampler's own functions (ppcx_math.h, the __HIP_DEVICE_COMPILE__ branch):
+ *   SINCOS_2PI: out0, out1 = sin, cos of 2 pi a         LGAMMA_INT1: out0 = lgamma_int1(a)
+ *   RNG_EXP: out0 = rng_exp(a)                          RNG_DIV: out0 = rng_div(a, b) */
 enum { PPCX_MATH_FAST_RCP = 0, PPCX_MATH_FAST_LOG = 1, PPCX_MATH_FAST_EXP = 2, PPCX_MATH_TABLE_LOG = 3, PPCX_MATH_WINDOW_LOG = 4,
        PPCX_MATH_STIRLING_TAILS = 5, PPCX_MATH_STIRLING_EXCESS = 6, PPCX_MATH_LOG_ERFC_RATIO = 7, PPCX_MATH_CELL = 8,
-       PPCX_MATH_CELL_WIN = 9, PPCX_MATH_CELL_Y = 10, PPCX_MATH_CELL_WIN_Y = 11, PPCX_MATH_COUNT = 12 };
+       PPCX_MATH_CELL_WIN = 9, PPCX_MATH_CELL_Y = 10, PPCX_MATH_CELL_WIN_Y = 11, PPCX_MATH_SINCOS_2PI = 12, PPCX_MATH_LGAMMA_INT1 = 13,
+       PPCX_MATH_RNG_EXP = 14, PPCX_MATH_RNG_DIV = 15, PPCX_MATH_COUNT = 16 };
 PPCX_API int ppcx_testing_eval_math(int fn, int n, const double* a, const double* b, const int* y, double* out0, double* out1);
 /* the model's dispersion tables as the device built them: G x 768 doubles (ppcx_disp.h layout) */
 PPCX_API int ppcx_testing_get_disp_table(ppcx_model* m, double* out);

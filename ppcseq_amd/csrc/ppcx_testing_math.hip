@@ -40,6 +40,10 @@ __global__ __launch_bounds__(kMathThreads) void ppcx_testing_math_kernel(int fn,
     case PPCX_MATH_CELL_WIN: (void)cell_eval_win<2, false>(y[i], x, x2, 1.0, gp, s_win, acc); r0 = acc.SL; r1 = acc.Sq; break;
     case PPCX_MATH_CELL_Y: (void)cell_eval<2, false>(y[i], x, x2, gp, s_tab, acc); r0 = acc.SA; r1 = acc.SYq; break;
     case PPCX_MATH_CELL_WIN_Y: (void)cell_eval_win<2, false>(y[i], x, x2, 1.0, gp, s_win, acc); r0 = acc.SA; r1 = acc.SYq; break;
+    case PPCX_MATH_SINCOS_2PI: sincos_2pi(x, &r0, &r1); break;
+    case PPCX_MATH_LGAMMA_INT1: r0 = lgamma_int1(x); break;
+    case PPCX_MATH_RNG_EXP: r0 = rng_exp(x); break;
+    case PPCX_MATH_RNG_DIV: r0 = rng_div(x, x2); break;
     default: r0 = r1 = 0.0; break;
   }
   out0[i] = r0; out1[i] = r1;

@@ -275,6 +275,13 @@ int emul_nb2_log_rng(double eta, double phi, unsigned long long seed, unsigned c
   return nb2_log_rng(eta, phi, seed32(seed), cell, draw);
 }
 
+// draws 0 .. n - 1 of one cell's stream (tests/test_nb_rng_distribution.py: 20 000 draws per designed point)
+extern "C" __attribute__((visibility("default")))
+int emul_nb2_log_rng_draws(double eta, double phi, unsigned long long seed, unsigned cell, int n, int32_t* out) {
+  for (int j = 0; j < n; ++j) out[j] = nb2_log_rng(eta, phi, seed32(seed), cell, (unsigned)j);
+  return 0;
+}
+
 // the host twin of the testing build's ppcx_testing_eval_math (ppcseq_amd/csrc/ppcx_testing_math.hip): the same functions and
 // function ids (ppcx_testing.h PPCX_MATH_*), here their #else branches
 extern "C" __attribute__((visibility("default")))
@@ -298,6 +305,10 @@ int emul_eval_math(int fn, int n, const double* a, const double* b, const int32_
       case 9: (void)cell_eval_win<2, false>(y[i], x, x2, 1.0, gp, window_table(), acc); r0 = acc.SL; r1 = acc.Sq; break;
       case 10: (void)cell_eval<2, false>(y[i], x, x2, gp, log_table(), acc); r0 = acc.SA; r1 = acc.SYq; break;
       case 11: (void)cell_eval_win<2, false>(y[i], x, x2, 1.0, gp, window_table(), acc); r0 = acc.SA; r1 = acc.SYq; break;
+      case 12: sincos_2pi(x, &r0, &r1); break;
+      case 13: r0 = lgamma_int1(x); break;
+      case 14: r0 = rng_exp(x); break;
+      case 15: r0 = rng_div(x, x2); break;
       default: return -1;
     }
     out0[i] = r0; out1[i] = r1;

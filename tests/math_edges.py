@@ -1,4 +1,4 @@
-"""The scalar building blocks of the log density (ppcseq_amd/csrc/ppcx_math.h, the cells of ppcx_model.h) at their edges --
+"""The scalar building blocks of the log density and of the predictive sampler (ppcseq_amd/csrc/ppcx_math.h, the cells of ppcx_model.h) at their edges --
 binade and bin boundaries, the ends of the tables, rint ties, underflow -- against mpmath at 40 digits. Shared by the device
 run (tests/test_gpu_math_edges.py: the testing build's ppcx_testing_eval_math, the gfx950 branches and the LDS tables) and its
 host twin (tests/test_emul_math_edges.py: the #else branches through tests/emul).
@@ -277,9 +277,118 @@ def check_log_erfc_ratio(ev):
             tr = (1e-13 + sub) * float(rref) + 2 * TINY
             assert abs(ra[i] - float(rref)) <= tr, ("ratio", v, ra[i], float(rref), float(e))
 
+# ---- the predictive sampler's own functions (ppcx_math.h: sincos_2pi, lgamma_int1, rng_exp, rng_div) ------------------------------
+# On the device these are hand-written (a quadrant reduction on u with the fdlibm kernels, a table and Stirling, fast_exp inside
+# a guard, a multiplication by fast_rcp); on the host they are libm. An evaluator of the host branch says so with an attribute
+# `host_branch`: where the two branches' bounds differ, each is held to the one that follows from its own code.
+WORST = {}                                       # name -> the worst error of the last run, in the unit of its bound
+
+
+def sincos_grid():
+    g = []
+    for k in range(1, 8):                        # k/8 (and with it k/4): where flip and the quadrant change
+        g += _nb(k / 8.0, 2)
+    g += _nb(2.0 ** -54, 2)[0:1] + [np.nextafter(2.0 ** -54, 1.0), 1.0 - 2.0 ** -54, np.nextafter(1.0 - 2.0 ** -54, 0.0)]   # the ends of u01
+    g += list(np.random.default_rng(11).uniform(0.0, 1.0, 10000))
+    return np.array([v for v in g if 0.0 < v < 1.0])
+
+
+def check_sincos_2pi(ev):
+    u = sincos_grid()
+    sn, cs = ev("sincos_2pi", u)
+    with mp.workdps(DPS):
+        ang = [2 * mp.pi * mp.mpf(float(v)) for v in u]
+        rs, rc = [mp.sin(a) for a in ang], [mp.cos(a) for a in ang]
+    es, ec = _abs_err(sn, rs), _abs_err(cs, rc)
+    # device: r = u - q/4 and the flip are exact, t = r 2pi carries one rounding and the constant's error at t <= pi/4
+    # (5.5e-17 + 3.1e-17) and the fdlibm kernels stay below 1 ulp (1.1e-16): below 2^-52 in all; 2^-51 is asserted.
+    # host: t = fl(2pi) u up to 2 pi carries the constant's 2.5e-16 and half an ulp of t (4.4e-16) before libm's sine: 2^-50.
+    tol = 2.0 ** -50 if getattr(ev, "host_branch", False) else 2.0 ** -51
+    WORST["sincos_2pi"] = float(max(es.max(), ec.max()))
+    _report("sincos_2pi sin", u, es, np.full(u.size, tol))
+    _report("sincos_2pi cos", u, ec, np.full(u.size, tol))
+    # the quadrant: signs wherever the exact value is beyond the bound, and at k/4 the unit component exactly
+    for got, ref, nm in ((sn, rs, "sin"), (cs, rc, "cos")):
+        rf = np.array([float(r) for r in ref])
+        big = np.abs(rf) > tol
+        assert np.array_equal(np.sign(got[big]), np.sign(rf[big])), f"sincos_2pi {nm}: wrong sign"
+    for k, (s_, c_) in ((1, (1.0, 0.0)), (2, (0.0, -1.0)), (3, (-1.0, 0.0))):
+        s1, c1 = ev("sincos_2pi", np.array([k / 4.0]))
+        if s_ != 0.0:
+            assert s1[0] == s_ and abs(c1[0]) <= tol, (k, s1[0], c1[0])
+        else:
+            assert c1[0] == c_ and abs(s1[0]) <= tol, (k, s1[0], c1[0])
+        if not getattr(ev, "host_branch", False):
+            assert (c1[0] if s_ != 0.0 else s1[0]) == 0.0, (k, s1[0], c1[0])      # the reduced argument is exactly 0
+
+
+def lgamma_int_grid():
+    g = [8.0, 9.0, 10.0]
+    for j in range(4, 32):                       # up to 2^31: the largest kf a PTRS proposal with lambda < 2^30 can reach
+        g += [2.0 ** j - 1.0, 2.0 ** j, 2.0 ** j + 1.0]
+    g += list(np.floor(np.exp(np.random.default_rng(12).uniform(math.log(8.0), math.log(2.0 ** 31), 2000))))
+    return np.array(g)
+
+
+def check_lgamma_int1(ev):
+    k = np.arange(8.0)                           # the table: ln k! to one unit in the last place
+    got, _ = ev("lgamma_int1", k)
+    ref = _ref(lambda v: mp.loggamma(v + 1), k)
+    err = _abs_err(got, ref)
+    _report("lgamma_int1 table", k, err, np.maximum(_ulp([float(r) for r in ref]), 0.0) * (k >= 2))
+    k = lgamma_int_grid()
+    got, _ = ev("lgamma_int1", k)
+    ref = _ref(lambda v: mp.loggamma(v + 1), k)
+    err = _abs_err(got, ref)
+    x = k + 1.0
+    unit = _ulp(x * np.log(x))                   # (x - 1/2) ln x, its product with x and the sum: three rounded terms of that size
+    WORST["lgamma_int1"] = float(np.max(err / unit))
+    _report("lgamma_int1", k, err, 4 * unit)
+
+
+def rng_exp_grid():
+    g = []
+    for v in (699.999, 700.0):
+        g += _nb(v, 2) + _nb(-v, 2)
+    g += [709.7, -709.7, -745.2, 710.0, -746.0, 705.0, -705.0, -720.0, 0.0, 1.0, -1.0]
+    return np.array(g)
+
+
+def check_rng_exp(ev):
+    x = rng_exp_grid()
+    got, _ = ev("rng_exp", x)
+    assert got[x == 710.0][0] == np.inf and got[x == -746.0][0] == 0.0
+    fin = (x != 710.0) & (x != -746.0)
+    x, got = x[fin], got[fin]
+    ref = _ref(mp.exp, x)
+    rf = np.array([float(r) for r in ref])
+    err = _abs_err(got, ref)
+    # inside the guard fast_exp's bound (check_fast_exp), outside libm's one unit in the last place (of the subnormal spacing
+    # where the result is subnormal)
+    inside = (x > -700.0) & (x < 700.0)
+    tol = np.where(inside, 2 * _ulp(rf), np.maximum(_ulp(rf), TINY))
+    WORST["rng_exp"] = float(np.max(err / np.maximum(_ulp(rf), TINY)))
+    _report("rng_exp", x, err, tol)
+
+
+def check_rng_div(ev):
+    b = rcp_grid()
+    rng = np.random.default_rng(13)
+    a = np.exp(rng.uniform(-20.0, 20.0, b.size)) * rng.choice([-1.0, 1.0], b.size)
+    keep = (np.abs(a / b) > 1e-290) & (np.abs(a / b) < 1e290) & (b < 1e300)          # normal quotients of normal operands
+    a, b = a[keep], b[keep]
+    got, _ = ev("rng_div", a, b)
+    with mp.workdps(DPS):
+        ref = [mp.mpf(float(p)) / mp.mpf(float(q)) for p, q in zip(a, b)]
+    err = _abs_err(got, ref)
+    unit = _ulp([float(r) for r in ref])
+    WORST["rng_div"] = float(np.max(err / unit))
+    _report("rng_div", b, err, 2 * unit)
+
 
 CHECKS = {
     "fast_rcp": check_fast_rcp, "fast_log": check_fast_log, "fast_exp": check_fast_exp, "table_log": check_table_log,
     "window_log": check_window_log, "cell": check_cell, "cell_win": check_cell_win, "stirling_tails": check_stirling_tails,
     "stirling_excess": check_stirling_excess, "log_erfc_ratio": check_log_erfc_ratio,
+    "sincos_2pi": check_sincos_2pi, "lgamma_int1": check_lgamma_int1, "rng_exp": check_rng_exp, "rng_div": check_rng_div,
 }

@@ -10,7 +10,7 @@ from tests.emul_util import P
 from tests.test_disp_table import _exact, _rows
 
 FNS = ("fast_rcp", "fast_log", "fast_exp", "table_log", "window_log", "stirling_tails", "stirling_excess", "log_erfc_ratio",
-       "cell", "cell_win", "cell_y", "cell_win_y")           # ppcx_testing.h PPCX_MATH_* (ppcseq_amd._lib.TESTING_MATH)
+       "cell", "cell_win", "cell_y", "cell_win_y", "sincos_2pi", "lgamma_int1", "rng_exp", "rng_div")   # ppcx_testing.h PPCX_MATH_* (ppcseq_amd._lib.TESTING_MATH)
 
 
 @pytest.fixture(scope="module")
@@ -24,6 +24,7 @@ def ev(emul):
         assert emul.emul_eval_math(FNS.index(fn), n, P(a, C.c_double), P(b, C.c_double), P(y, C.c_int32), P(o0, C.c_double),
                                    P(o1, C.c_double)) == 0
         return o0, o1
+    run.host_branch = True                       # tests/math_edges.py: the libm #else branches
     return run
 
 

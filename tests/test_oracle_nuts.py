@@ -42,6 +42,9 @@ def test_model_posterior_sane(oracle):
 
 
 def test_rng_is_counter_based_and_reproducible(oracle):
+    """The oracle's generator is addressed by (seed, cell, draw) alone, and its first two moments are in place at two points.
+    The moments are a smoke check only: the sampler is held to the negative binomial's exact pmf, regime by regime, in
+    tests/test_nb_rng_distribution.py (oracle and CPU emulation) and tests/test_gpu_nb_rng.py (the device kernels)."""
     a = [oracle.nb2_log_rng(3.0, 2.0, 7, c, d) for c in range(5) for d in range(5)]
     b = [oracle.nb2_log_rng(3.0, 2.0, 7, c, d) for c in range(5) for d in range(5)]
     assert a == b and len(set(a)) > 5
