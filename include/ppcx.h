@@ -226,6 +226,26 @@ PPCX_API int ppcx_fit_loo_approx(ppcx_fit* f, int n_genes, const int32_t* genes,
  * truncation compensation as ppcx_fit_loo_predict.                                                                              */
 PPCX_API int ppcx_fit_loo_predict_approx(ppcx_fit* f, int n_genes, const int32_t* genes, double truncation_compensation, double p_lo,
                                          double p_hi, unsigned long long seed, double* out);
+/* The exact posterior-predictive tail probabilities and interval per cell of the checked genes: the Rao-Blackwellised form of the
+ * model's `generated quantities`. Given kept draw i the count of cell (g, s) is neg_binomial_2_log(eta_i, phi_i), eta_i =
+ * exposure_s + X_s alpha_g(i), phi_i = truncation_compensation exp(-sigma_raw_g(i)) as in ppcx_fit_ppc, so the posterior predictive
+ * cdf of the cell is the plain average over the kept draws of negative-binomial cdfs (regularised incomplete beta functions,
+ * evaluated on the device). Nothing is sampled: what remains is the Monte-Carlo error of the posterior draws themselves.
+ * NUTS fits, ADVI fits and ppcx_fit_from_draws fits alike. genes: n_genes ids of checked genes (0 .. K - 1), or NULL with
+ * n_genes = K for all of them. PPCX_ERR_ARG unless 0 < p_lo < p_hi < 1, truncation_compensation is finite and > 0 and every gene is
+ * a checked one. Synchronous on the model's stream; the same bits on every call, for any gene subset.
+ *   out [n_genes][S][PPCX_PPC_EXACT_FIELDS]:
+ *   mean = mean_i e^{eta_i};  sd = sqrt(mean_i(mu_i + mu_i^2 / phi_i) + var_i(mu_i)) (ddof 0);
+ *   p_le = P(X <= y), p_ge = P(X >= y) of the observed count y under the predictive distribution;
+ *   lower, upper = the smallest integers k with F(k) >= p_lo, p_hi, F the predictive cdf: the inverse-cdf quantiles of the
+ *   distribution. ppcx_fit_ppc reports type-7 SAMPLE quantiles, which interpolate between integers; the two agree in the limit of
+ *   draws;  y;  excluded (0 / 1: reported only -- the predictive does not depend on whether the cell is in the likelihood);
+ *   outside = (y < lower) | (y > upper) as 0 / 1.
+ *   A draw with invalid parameters (a non-finite eta_i or e^{eta_i}, phi_i not finite and > 0) makes every statistic of the cell
+ *   NaN (y and excluded are still reported).                                                                                    */
+#define PPCX_PPC_EXACT_FIELDS 9     /* mean, sd, p_le, p_ge, lower, upper, y, excluded, outside */
+PPCX_API int ppcx_fit_ppc_exact(ppcx_fit* f, int n_genes, const int32_t* genes, double truncation_compensation, double p_lo,
+                                double p_hi, double* out);
 /* lp: [chains][n_keep]; the rest [chains][iter] (warmup included); any pointer may be NULL */
 PPCX_API int ppcx_fit_get_diagnostics(ppcx_fit* f, double* lp, double* stepsize, int32_t* treedepth,
                              int32_t* n_leapfrog, int32_t* divergent, double* accept);

@@ -26,12 +26,14 @@ EXPORTS = [
     "ppcx_fit_nuts_xchg", "ppcx_fit_get_xchg_timing", "ppcx_fit_get_inv_metric", "ppcx_fit_summary",
     "ppcx_fit_get_approximation", "ppcx_fit_get_log_ratios", "ppcx_fit_psis", "ppcx_fit_get_log_lik", "ppcx_fit_loo",
     "ppcx_fit_loo_predict", "ppcx_fit_relative_eff", "ppcx_fit_loo_mcse", "ppcx_fit_loo_approx", "ppcx_fit_loo_predict_approx",
+    "ppcx_fit_ppc_exact",
 ]
 ABI_VERSION = 400           # include/ppcx.h PPCX_VERSION this binding was written for
 SUMMARY_FIELDS = ("mean", "sd", "q05", "q50", "q95", "rhat", "ess_bulk", "ess_tail")   # PPCX_SUMMARY_FIELDS, in order
 LOO_FIELDS = ("elpd_loo", "p_loo", "looic", "khat")                                      # PPCX_LOO_FIELDS, in order
 LOO_MCSE_FIELDS = LOO_FIELDS + ("mcse_elpd_loo", "n_eff")                                # PPCX_LOO_MCSE_FIELDS, in order
 LOO_PREDICT_FIELDS = ("mean", "lower", "upper", "pit_lt", "pit_le", "khat")              # PPCX_LOO_PREDICT_FIELDS, in order
+PPC_EXACT_FIELDS = ("mean", "sd", "p_le", "p_ge", "lower", "upper", "y", "excluded", "outside")   # PPCX_PPC_EXACT_FIELDS, in order
 
 
 class PpcxError(RuntimeError):
@@ -109,6 +111,7 @@ def load() -> C.CDLL:
     lib.ppcx_fit_relative_eff.argtypes = [C.c_void_p, C.c_int, ip, dp]
     lib.ppcx_fit_loo_approx.argtypes = [C.c_void_p, C.c_int, ip, dp]
     lib.ppcx_fit_loo_predict_approx.argtypes = [C.c_void_p, C.c_int, ip, C.c_double, C.c_double, C.c_double, C.c_ulonglong, dp]
+    lib.ppcx_fit_ppc_exact.argtypes = [C.c_void_p, C.c_int, ip, C.c_double, C.c_double, C.c_double, dp]
     lib.ppcx_fit_get_diagnostics.argtypes = [C.c_void_p, dp, dp, ip, ip, ip, dp]
     lib.ppcx_fit_get_timing.argtypes = [C.c_void_p, dp, C.POINTER(C.c_longlong), dp, C.POINTER(C.c_longlong), dp]
     lib.ppcx_fit_get_kernel_times.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(C.c_longlong)]
@@ -150,6 +153,8 @@ def load() -> C.CDLL:
         lib.ppcx_testing_loo_predict_approx.argtypes = [dp, dp, ip, C.c_int, C.c_int, ip, ip, C.c_double, C.c_double, dp]
     if hasattr(lib, "ppcx_testing_relative_eff"):
         lib.ppcx_testing_relative_eff.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp]
+    if hasattr(lib, "ppcx_testing_ppc_exact"):
+        lib.ppcx_testing_ppc_exact.argtypes = [C.c_int, C.c_int, dp, dp, ip, ip, C.c_double, C.c_double, C.c_double, dp]
     lib.ppcx_fit_free.restype = None
     lib.ppcx_advi_config_default.argtypes = [C.POINTER(AdviConfig)]
     lib.ppcx_advi_config_default.restype = None
@@ -195,6 +200,9 @@ def testing_set_nccl_provider(path: str):
 # function ids of ppcx_testing_eval_math (csrc/ppcx_testing.h PPCX_MATH_*)
 TESTING_MATH = ("fast_rcp", "fast_log", "fast_exp", "table_log", "window_log", "stirling_tails", "stirling_excess",
                 "log_erfc_ratio", "cell", "cell_win", "cell_y", "cell_win_y", "sincos_2pi", "lgamma_int1", "rng_exp", "rng_div")
+# ... and those of the headers beside ppcx_math.h / ppcx_model.h, whose ids go on from there (ppcx_nbcdf.h: PPCX_MATH_NB2_TAILS);
+# the CPU emulation harness knows the ids of TESTING_MATH only
+TESTING_MATH_MORE = ("nb2_tails",)
 
 
 def testing_eval_math(fn: str, a, b=None, y=None):
@@ -209,7 +217,7 @@ def testing_eval_math(fn: str, a, b=None, y=None):
     b = np.ascontiguousarray(np.zeros(n) if b is None else np.broadcast_to(b, (n,)), dtype=np.float64)
     y = np.ascontiguousarray(np.zeros(n) if y is None else np.broadcast_to(y, (n,)), dtype=np.int32)
     o0, o1 = np.zeros(n), np.zeros(n)
-    rc = lib.ppcx_testing_eval_math(TESTING_MATH.index(fn), n, _p(a, C.c_double), _p(b, C.c_double), _p(y, C.c_int32),
+    rc = lib.ppcx_testing_eval_math((TESTING_MATH + TESTING_MATH_MORE).index(fn), n, _p(a, C.c_double), _p(b, C.c_double), _p(y, C.c_int32),
                                     _p(o0, C.c_double), _p(o1, C.c_double))
     if rc != 0:
         raise PpcxError(f"ppcx_testing_eval_math({fn}) failed with code {rc}")
@@ -343,6 +351,41 @@ def testing_relative_eff(ll, chains):
     out = np.zeros(nc)
     _check(lib.ppcx_testing_relative_eff(chains, rows // chains, nc, _p(cols, C.c_double), _p(out, C.c_double)))
     return out
+
+
+def _ppc_exact_dict(out):
+    """[.., PPC_EXACT_FIELDS] as the dict of Fit.ppc_exact: y and the interval ends integers (-1 where the cell is NaN), excluded
+    and outside booleans (outside False where the cell is NaN)"""
+    res = {k: out[..., i].copy() for i, k in enumerate(PPC_EXACT_FIELDS)}
+    nan = np.isnan(res["lower"]) | np.isnan(res["upper"])
+    for k in ("lower", "upper"):
+        res[k] = np.where(nan, -1, res[k]).astype(np.int64)
+    res["y"] = res["y"].astype(np.int64)
+    res["excluded"] = res["excluded"] != 0
+    res["outside"] = np.where(nan, 0, res["outside"]) != 0
+    return res
+
+
+def testing_ppc_exact(eta, sigma_raw, y, excluded=None, truncation_compensation=1.0, p_lo=0.025, p_hi=0.975, raw=False):
+    """The kernel of ppcx_fit_ppc_exact on host-given columns (testing build only; csrc/ppcx_testing.h ppcx_testing_ppc_exact):
+    eta, sigma_raw [n_draws, n_cells], y [n_cells] observed counts, excluded None or [n_cells]. Returns Fit.ppc_exact's dict of
+    [n_cells] arrays, or with raw=True the [n_cells, 9] doubles as the kernel wrote them."""
+    lib = load()
+    if not hasattr(lib, "ppcx_testing_ppc_exact"):
+        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before ppcx_testing_ppc_exact existed: rebuild it "
+                        "(`python -m ppcseq_amd.build --testing --force`)")
+    eta = np.asarray(eta, dtype=np.float64)
+    eta = eta.reshape(eta.shape[0], -1)
+    n, nc = eta.shape
+    ec = np.ascontiguousarray(eta.T)
+    sc = np.ascontiguousarray(np.asarray(sigma_raw, dtype=np.float64).reshape(n, nc).T)
+    ys = np.ascontiguousarray(np.broadcast_to(np.asarray(y), (nc,)), dtype=np.int32)
+    ex = None if excluded is None else np.ascontiguousarray(excluded, dtype=np.int32).ravel()
+    out = np.zeros((nc, len(PPC_EXACT_FIELDS)))
+    _check(lib.ppcx_testing_ppc_exact(n, nc, _p(ec, C.c_double), _p(sc, C.c_double), _p(ys, C.c_int32),
+                                      _p(ex, C.c_int32) if ex is not None else None, float(truncation_compensation), float(p_lo),
+                                      float(p_hi), _p(out, C.c_double)))
+    return out if raw else _ppc_exact_dict(out)
 
 
 def loo_estimates(pointwise, excluded):
@@ -798,6 +841,25 @@ class Fit:
         g, res, last = self._loo_cells(genes, None, LOO_PREDICT_FIELDS, lambda n, g, re, out: load().ppcx_fit_loo_predict_approx(
             self._h, n, g, float(truncation_compensation), float(p_lo), float(p_hi), int(seed), out))
         return self._loo_predict_result(g, res, last)
+
+    def ppc_exact(self, genes=None, p_lo=0.025, p_hi=0.975, truncation_compensation=1.0):
+        """The exact posterior-predictive tail probabilities and interval per cell of checked genes on the device
+        (ppcx_fit_ppc_exact): the predictive cdf of a cell is the average over the kept draws of negative-binomial cdfs, so nothing
+        is sampled -- what Fit.ppc estimates from one drawn count per draw. NUTS, ADVI and fit_from_draws fits. A dict of
+        [n_genes, S] arrays: mean, sd, p_le = P(X <= y), p_ge = P(X >= y) (floats), lower, upper (integers: the smallest k with
+        F(k) >= p_lo, p_hi -- the distribution's inverse-cdf quantiles, where Fit.ppc reports type-7 sample quantiles that
+        interpolate between integers; the two agree in the limit of draws), y (integers), excluded, outside = (y < lower) |
+        (y > upper) (booleans), and `genes`, `n_draws`. A cell with an invalid draw: NaN floats, lower = upper = -1, outside
+        False. genes=None: all K checked genes; ids are those of checked genes (0 .. K - 1)."""
+        g = np.ascontiguousarray(np.arange(self.model.K) if genes is None else np.asarray(genes, dtype=np.int64).ravel(), dtype=np.int32)
+        out = np.zeros((g.size, self.model.S, len(PPC_EXACT_FIELDS)))
+        if g.size:
+            _check(load().ppcx_fit_ppc_exact(self._h, int(g.size), _p(g, C.c_int32), float(truncation_compensation), float(p_lo),
+                                             float(p_hi), _p(out, C.c_double)))
+        res = _ppc_exact_dict(out)
+        res["genes"] = g.astype(np.int64)
+        res["n_draws"] = self.chains * self.n_keep
+        return res
 
     def diagnostics(self):
         lp = np.zeros((self.chains, self.n_keep))

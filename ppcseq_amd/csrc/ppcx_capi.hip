@@ -2101,6 +2101,45 @@ extern "C" int ppcx_testing_loo_predict_approx(const double* ll, const double* l
   return testing_loo_predict(ll, log_ratio, x, n, n_cols, y, excluded, nullptr, p_lo, p_hi, out);
 }
 #endif
+// ---- the exact posterior-predictive tails and interval of the checked genes' cells (ppcx_ppc_exact.h): every kind of fit
+static int ppc_exact_check(double truncation_compensation, double p_lo, double p_hi) {
+  if (!(p_lo > 0.0 && p_lo < p_hi && p_hi < 1.0)) return fail(PPCX_ERR_ARG, "need 0 < p_lo < p_hi < 1");
+  if (!(isfinite(truncation_compensation) && truncation_compensation > 0.0))
+    return fail(PPCX_ERR_ARG, "truncation_compensation must be finite and > 0");
+  return PPCX_OK;
+}
+extern "C" int ppcx_fit_ppc_exact(ppcx_fit* f, int n_genes, const int32_t* genes, double truncation_compensation, double p_lo,
+                                  double p_hi, double* out) {
+  const char* who = "ppcx_fit_ppc_exact";
+  if (!f) return fail(PPCX_ERR_ARG, "fit is NULL");
+  const int K = f->m->d.K;
+  std::vector<int32_t> all;
+  if (!genes) {                                  // all the checked genes
+    if (n_genes != K) return fail(PPCX_ERR_ARG, std::string(who) + ": genes = NULL takes n_genes = K");
+    all.resize((size_t)K);
+    for (int i = 0; i < K; ++i) all[i] = i;
+    genes = all.data();
+  }
+  for (int i = 0; i < n_genes; ++i) if (genes[i] < 0 || genes[i] >= K) return fail(PPCX_ERR_ARG, "gene out of range (a checked gene: 0 .. K - 1)");
+  int rc = ppc_exact_check(truncation_compensation, p_lo, p_hi);
+  if (rc != PPCX_OK) return rc;
+  std::vector<int> yenc; FitCells fc;
+  if ((rc = loo_prepare_cells(f, n_genes, genes, out, yenc, fc)) != PPCX_OK) return rc;
+  return loo_done(who, ppc_exact_fit_cells(fc, truncation_compensation, p_lo, p_hi, out, loo_scratch_bytes(), f->m->stream));
+}
+#ifdef PPCX_TESTING
+// testing build only (ppcx_testing.h): the kernel of ppcx_fit_ppc_exact on host-given columns, on the current device
+extern "C" int ppcx_testing_ppc_exact(int n, int n_cols, const double* eta, const double* sigma_raw, const int32_t* y,
+                                      const int32_t* excluded, double truncation_compensation, double p_lo, double p_hi, double* out) {
+  if (n < 1 || n_cols < 1 || !eta || !sigma_raw || !y || !out) return fail(PPCX_ERR_ARG, "bad arguments");
+  for (int i = 0; i < n_cols; ++i) if (y[i] < 0) return fail(PPCX_ERR_ARG, "counts must be >= 0");
+  const int rc = ppc_exact_check(truncation_compensation, p_lo, p_hi);
+  if (rc != PPCX_OK) return rc;
+  GivenCells gc;
+  gc.cols = eta; gc.n = n; gc.n_cols = n_cols; gc.excl = excluded;
+  return loo_done(nullptr, ppc_exact_columns(gc, sigma_raw, y, truncation_compensation, p_lo, p_hi, out, loo_scratch_bytes(), nullptr));
+}
+#endif
 // ---- the relative efficiency of the same cells (loo::relative_eff(exp(log_lik), chain_id): what rstan::loo(fit) passes as r_eff)
 extern "C" int ppcx_fit_relative_eff(ppcx_fit* f, int n_genes, const int32_t* genes, double* out) {
   std::vector<int> yenc; FitCells fc;

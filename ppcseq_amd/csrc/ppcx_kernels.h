@@ -277,6 +277,15 @@ hipError_t loo_predict_fit_cells(const FitCells& fc, double tc, double p_lo, dou
 // ... of given columns with predictive counts x [n_cols][n] and observed counts y [n_cols]
 hipError_t loo_predict_columns(const GivenCells& gc, const int* x, const int* y, double p_lo, double p_hi, double* out,
                                size_t scratch_bytes, hipStream_t st);
+// The exact posterior-predictive tails and interval of the same cells (ppcx_ppc_exact.hip, statistic in ppcx_ppc_exact.h): one
+// workgroup per cell; (eta, ln phi) of the draws (16 bytes per draw) in LDS up to kPsisLdsDraws draws, beyond that in the scratch.
+// tc: truncation compensation. out [cells][kPpcExactFields]. Of `fc` neither r_eff nor log_ratio is used: NUTS, ADVI and
+// given-draws fits alike.
+hipError_t ppc_exact_fit_cells(const FitCells& fc, double tc, double p_lo, double p_hi, double* out, size_t scratch_bytes,
+                               hipStream_t st);
+// ... of given columns: gc.cols the linear predictors [n_cols][n], sigma_raw [n_cols][n], y [n_cols] the observed counts
+hipError_t ppc_exact_columns(const GivenCells& gc, const double* sigma_raw, const int* y, double tc, double p_lo, double p_hi,
+                             double* out, size_t scratch_bytes, hipStream_t st);
 // The relative efficiency of the same cells (ppcx_reff.hip, statistic in ppcx_reff.h): one workgroup per cell; the split values
 // (8 bytes each) in LDS for fits of up to kPsisLdsDraws draws, beyond that in the scratch. Of `l` it uses T / y / expo / X / S / C
 // or cols, n = chains n_keep, cell0, n_cells, scratch ([launch's cells][2 chains (n_keep / 2)]) and out ([cells], one value

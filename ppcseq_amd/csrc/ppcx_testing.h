@@ -42,11 +42,12 @@ PPCX_API int ppcx_testing_sm_trace(double* out6);
  *   CELL_Y / CELL_WIN_Y: the same cells' y ln w and y / w accumulations
  *   the posterior-predictive sampler's own functions (ppcx_math.h, the __HIP_DEVICE_COMPILE__ branch):
  *   SINCOS_2PI: out0, out1 = sin, cos of 2 pi a         LGAMMA_INT1: out0 = lgamma_int1(a)
- *   RNG_EXP: out0 = rng_exp(a)                          RNG_DIV: out0 = rng_div(a, b) */
+ *   RNG_EXP: out0 = rng_exp(a)                          RNG_DIV: out0 = rng_div(a, b)
+ *   NB2_TAILS (ppcx_nbcdf.h nb2_log_tails): out0, out1 = P(X <= y), P(X >= y) of X ~ NB(mean e^a, size b) */
 enum { PPCX_MATH_FAST_RCP = 0, PPCX_MATH_FAST_LOG = 1, PPCX_MATH_FAST_EXP = 2, PPCX_MATH_TABLE_LOG = 3, PPCX_MATH_WINDOW_LOG = 4,
        PPCX_MATH_STIRLING_TAILS = 5, PPCX_MATH_STIRLING_EXCESS = 6, PPCX_MATH_LOG_ERFC_RATIO = 7, PPCX_MATH_CELL = 8,
        PPCX_MATH_CELL_WIN = 9, PPCX_MATH_CELL_Y = 10, PPCX_MATH_CELL_WIN_Y = 11, PPCX_MATH_SINCOS_2PI = 12, PPCX_MATH_LGAMMA_INT1 = 13,
-       PPCX_MATH_RNG_EXP = 14, PPCX_MATH_RNG_DIV = 15, PPCX_MATH_COUNT = 16 };
+       PPCX_MATH_RNG_EXP = 14, PPCX_MATH_RNG_DIV = 15, PPCX_MATH_NB2_TAILS = 16, PPCX_MATH_COUNT = 17 };
 PPCX_API int ppcx_testing_eval_math(int fn, int n, const double* a, const double* b, const int* y, double* out0, double* out1);
 /* the model's dispersion tables as the device built them: G x 768 doubles (ppcx_disp.h layout) */
 PPCX_API int ppcx_testing_get_disp_table(ppcx_model* m, double* out);
@@ -72,6 +73,11 @@ PPCX_API int ppcx_testing_loo_predict_approx(const double* ll, const double* log
 /* The kernel of ppcx_fit_relative_eff on host-given log-likelihood columns, on the current device (ppcx_reff.hip): ll
  * [n_cols][chains n] (a cell's draws contiguous, chain-major), out [n_cols]. */
 PPCX_API int ppcx_testing_relative_eff(int chains, int n, int n_cols, const double* ll, double* out);
+/* The kernel of ppcx_fit_ppc_exact on host-given columns, on the current device (ppcx_ppc_exact.hip): eta [n_cols][n] the linear
+ * predictors and sigma_raw [n_cols][n] (a cell's n draws contiguous), y [n_cols] the observed counts (>= 0), excluded NULL or
+ * [n_cols] flags; out [n_cols][9]: mean, sd, p_le, p_ge, lower, upper, y, excluded, outside. */
+PPCX_API int ppcx_testing_ppc_exact(int n, int n_cols, const double* eta, const double* sigma_raw, const int32_t* y,
+                                    const int32_t* excluded, double truncation_compensation, double p_lo, double p_hi, double* out);
 #ifdef __cplusplus
 }
 #endif

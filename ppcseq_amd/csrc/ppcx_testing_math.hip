@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <vector>
 #include "ppcx_model.h"
+#include "ppcx_nbcdf.h"
 #include "ppcx_testing.h"
 
 namespace ppcx {
@@ -44,6 +45,7 @@ __global__ __launch_bounds__(kMathThreads) void ppcx_testing_math_kernel(int fn,
     case PPCX_MATH_LGAMMA_INT1: r0 = lgamma_int1(x); break;
     case PPCX_MATH_RNG_EXP: r0 = rng_exp(x); break;
     case PPCX_MATH_RNG_DIV: r0 = rng_div(x, x2); break;
+    case PPCX_MATH_NB2_TAILS: (void)nb2_log_tails(y[i], x, x2, &r0, &r1); break;
     default: r0 = r1 = 0.0; break;
   }
   out0[i] = r0; out1[i] = r1;

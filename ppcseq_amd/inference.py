@@ -66,6 +66,7 @@ class InferenceResult:
     loo: dict | None = None            # check_loo: Fit.loo of the checked genes' cells ([K, S] arrays and loo's estimates)
     loo_intervals: dict | None = None  # check_loo_intervals: Fit.loo_predict of the checked genes' cells ([K, S] arrays)
     approximation_loo: dict | None = None            # check_approximation_loo: Fit.loo_approximate_posterior of those cells
+    exact_intervals: dict | None = None  # exact_intervals: Fit.ppc_exact of the checked genes' cells ([K, S] arrays)
     approximation_loo_intervals: dict | None = None  # check_approximation_loo_intervals: Fit.loo_predict_approximate_posterior
 
     def to_frame(self):
@@ -234,7 +235,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                  loo_r_eff=None,
                  loo_mcse=False,
                  check_approximation_loo=False,
-                 check_approximation_loo_intervals=False):
+                 check_approximation_loo_intervals=False,
+                 exact_intervals=False):
     """One inference pass (discovery or test) of ppcseq on the GPU.
 
     counts            G x S integer matrix, genes ordered with the `how_many_to_check` checked genes first
@@ -280,6 +282,10 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
     check_approximation_loo_intervals  check_loo_intervals for an ADVI pass, under the same weights
                       (Fit.loo_predict_approximate_posterior) at the pass's interval probabilities, seed and truncation
                       compensation, kept as `res.approximation_loo_intervals`. No warning, no flag changes. Not for a NUTS pass.
+    exact_intervals   the exact posterior-predictive tail probabilities and interval of every checked cell (Fit.ppc_exact: the
+                      average over the kept draws of negative-binomial cdfs, nothing sampled) at the pass's interval
+                      probabilities and truncation compensation, kept as `res.exact_intervals`. NUTS and ADVI passes;
+                      devices=[...]: over the pooled chains. Reported, not acted on: the flags stay those of the sampled intervals.
     Returns an InferenceResult.
     """
     counts = np.asarray(counts)
@@ -323,7 +329,7 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
         return _do_inference_devices(counts, X, exposure_rate, K, list(devices), chains, n_iter, warmup, excl,
                                      lambda_mu_mu, approximate_posterior_analysis, adj_prob_theshold,
                                      how_many_posterior_draws, truncation_compensation, seed, launch, check_convergence,
-                                     check_loo, check_loo_intervals, loo_r_eff, loo_mcse)
+                                     check_loo, check_loo_intervals, loo_r_eff, loo_mcse, exact_intervals)
     if devices is not None and len(devices) >= 1 and model is None:
         device = devices[0]
     own_model = model is None
@@ -382,6 +388,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
             if check_loo_intervals:
                 res.loo_intervals = fit.loo_predict(np.arange(K), r_eff=loo_r_eff, p_lo=p, p_hi=1 - p, seed=seed,
                                                     truncation_compensation=truncation_compensation)
+        if exact_intervals:
+            res.exact_intervals = fit.ppc_exact(np.arange(K), p_lo=p, p_hi=1 - p, truncation_compensation=truncation_compensation)
         res.counts_rng = rng
         if pass_fit:
             res.fit = fit
@@ -459,7 +467,7 @@ def checked_columns(G, C, K):
 
 def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, approximate_posterior_analysis,
                    adj_prob_theshold, how_many_posterior_draws, truncation_compensation, seed, device=0, convergence=False,
-                   loo=False, excl=None, loo_intervals=False, loo_r_eff=None, loo_mcse=False):
+                   loo=False, excl=None, loo_intervals=False, loo_r_eff=None, loo_mcse=False, exact_intervals=False):
     """Credible intervals, slopes and flags from the pooled draws of all chains (rstan::summary over merged chains,
     R/utilities.R:685-703): `draws_checked` is [chains, n_keep, len(checked_columns)] in global chain order. The
     posterior-predictive kernel runs on a model that holds the K checked genes only -- cell ids g*S+s and draw indices are
@@ -468,11 +476,13 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
     the pooled chains (res.loo; Fit.loo); the small model then carries the checked genes' cells of `excl` (0-based cell ids of
     the full model), so that the cells excluded from the fit are held out. loo_intervals: also their leave-one-out predictive
     intervals (res.loo_intervals; Fit.loo_predict), likewise. loo_r_eff: their r_eff (None or "auto", do_inference). loo_mcse:
-    res.loo with mcse_elpd_loo and n_eff (Fit.loo(mcse=True))."""
+    res.loo with mcse_elpd_loo and n_eff (Fit.loo(mcse=True)). exact_intervals: also the exact posterior-predictive tails and
+    intervals of the checked cells over the pooled chains (res.exact_intervals; Fit.ppc_exact), with the checked genes' cells of
+    `excl` reported as excluded."""
     counts = np.asarray(counts)
     X = np.asarray(X, dtype=np.float64).reshape(counts.shape[1], -1)
     small_excl = None
-    if (loo or loo_intervals) and excl is not None:
+    if (loo or loo_intervals or exact_intervals) and excl is not None:
         e = np.asarray(excl, dtype=np.int64).ravel()
         small_excl = e[e < K * counts.shape[1]].astype(np.int32)
     small = _lib.Model(counts[:K], X, exposure_rate, K, lambda_mu_mu=lambda_mu_mu, device=device, excl=small_excl)
@@ -491,6 +501,9 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
             if loo_intervals and K:
                 loo_int = fit.loo_predict(np.arange(K), r_eff=loo_r_eff, p_lo=p, p_hi=1 - p, seed=seed,
                                           truncation_compensation=truncation_compensation)
+            exact = None
+            if exact_intervals and K:
+                exact = fit.ppc_exact(np.arange(K), p_lo=p, p_hi=1 - p, truncation_compensation=truncation_compensation)
         finally:
             fit.close()
     finally:
@@ -500,13 +513,14 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
     res.convergence = conv
     res.loo = loo_res
     res.loo_intervals = loo_int
+    res.exact_intervals = exact
     return res
 
 
 def _do_inference_devices(counts, X, exposure_rate, K, devices, chains, n_iter, warmup, excl, lambda_mu_mu,
                           approximate_posterior_analysis, adj_prob_theshold, how_many_posterior_draws,
                           truncation_compensation, seed, launch=None, check_convergence=False, check_loo=False,
-                          check_loo_intervals=False, loo_r_eff=None, loo_mcse=False):
+                          check_loo_intervals=False, loo_r_eff=None, loo_mcse=False, exact_intervals=False):
     """Chains split over several devices of this process (one host thread per device; the C ABI allows different handles
     on different threads), pooled summary on the first device."""
     import threading
@@ -548,7 +562,8 @@ def _do_inference_devices(counts, X, exposure_rate, K, devices, chains, n_iter, 
                          approximate_posterior_analysis=approximate_posterior_analysis, adj_prob_theshold=adj_prob_theshold,
                          how_many_posterior_draws=how_many_posterior_draws, truncation_compensation=truncation_compensation,
                          seed=seed, device=devices[0], convergence=check_convergence, loo=check_loo, excl=excl,
-                         loo_intervals=check_loo_intervals, loo_r_eff=loo_r_eff, loo_mcse=loo_mcse)
+                         loo_intervals=check_loo_intervals, loo_r_eff=loo_r_eff, loo_mcse=loo_mcse,
+                         exact_intervals=exact_intervals)
     res.chains, res.iter = chains, n_iter
     if check_convergence:
         _warn_convergence(res.convergence, chains)

@@ -119,7 +119,7 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                       just_discovery=False, seed=None, adj_prob_theshold_2=None, device=0, devices=None, launch=None, _pass=None,
                       check_convergence=False, check_approximation=False, check_loo=False,
                       check_loo_intervals=False, loo_r_eff=None, loo_mcse=False,
-                      check_approximation_loo=False, check_approximation_loo_intervals=False):
+                      check_approximation_loo=False, check_approximation_loo_intervals=False, exact_intervals=False):
     """Mirror of ppcseq::identify_outliers (R/methods.R:74-367): same arguments, same defaults.
 
     data is a tidy pandas DataFrame (one row per transcript x sample); column arguments are strings. As in the
@@ -159,6 +159,11 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
     predictive interval and LOO-PIT of the checked cells under those weights (Fit.loo_predict_approximate_posterior) at the
     pass's interval probabilities, seed and truncation compensation, in out.attrs["approximation_loo_intervals_discovery"] and
     ["approximation_loo_intervals_test"]; reported only.
+    `exact_intervals` = True (NUTS and ADVI): both passes also keep the exact posterior-predictive tail probabilities and interval
+    of the checked cells (Fit.ppc_exact: [K, S] mean, sd, p_le, p_ge, lower, upper, y, excluded, outside -- the average over the
+    kept draws of negative-binomial cdfs, nothing sampled) at the pass's interval probabilities and truncation compensation, in
+    out.attrs["exact_intervals_discovery"] and ["exact_intervals_test"]; with `devices` over the pooled chains. They are reported,
+    not acted on: the flags and the frame are those of the same call without it.
     """
     import os
     import pandas as pd
@@ -193,6 +198,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                          "intervals of an ADVI fit are check_approximation_loo_intervals")
     if check_loo_intervals and _pass is not None:
         raise ValueError("check_loo_intervals is not available for passes over several ranks")
+    if exact_intervals and _pass is not None:
+        raise ValueError("exact_intervals is not available for passes over several ranks")
     _check_loo_r_eff(loo_r_eff, check_loo, check_loo_intervals)
     _check_loo_mcse(loo_mcse, check_loo)
     _check_approximation_loo(approximate_posterior_inference, check_approximation_loo, check_approximation_loo_intervals)
@@ -291,6 +298,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
             where.update(check_approximation_loo=True)
         if check_approximation_loo_intervals:
             where.update(check_approximation_loo_intervals=True)
+        if exact_intervals:
+            where.update(exact_intervals=True)
     try:
         # ---- pass 1: discovery (R/methods.R:268-286); always the full posterior analysis
         res1 = run_pass(counts, X, exposure_rate, K,
@@ -311,6 +320,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                 out1.attrs["approximation_loo_discovery"] = res1.approximation_loo
             if check_approximation_loo_intervals:
                 out1.attrs["approximation_loo_intervals_discovery"] = res1.approximation_loo_intervals
+            if exact_intervals:
+                out1.attrs["exact_intervals_discovery"] = res1.exact_intervals
             return out1
         # ---- cells to exclude (R/methods.R:292-300)
         flag = res1.deleterious_outliers if (do_check_only_on_detrimental and res1.deleterious_outliers is not None) else ~res1.ppc
@@ -365,6 +376,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
     if check_approximation_loo_intervals:
         out.attrs["approximation_loo_intervals_discovery"] = res1.approximation_loo_intervals
         out.attrs["approximation_loo_intervals_test"] = res2.approximation_loo_intervals
+    if exact_intervals:
+        out.attrs["exact_intervals_discovery"], out.attrs["exact_intervals_test"] = res1.exact_intervals, res2.exact_intervals
     if pass_fit:                                                           # R/methods.R:353-357: attrs "fit 1" / "fit 2"
         out.attrs["fit 1"], out.attrs["fit 2"] = res1.fit, res2.fit        # device-resident; the library keeps the model
     return out                                                             # alive until both fits are closed
