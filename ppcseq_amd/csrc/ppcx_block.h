@@ -1,5 +1,7 @@
-// ppcx_block.h -- the workgroup toolkit of the fit diagnostics on gfx950 (ppcx_summary.hip, ppcx_psis.hip, ppcx_loo.hip): a
-// workgroup of kBlockThreads threads in kBlockWaves wavefronts. Device code only: the `__host__ __device__` statistic headers
+// ppcx_block.h -- the workgroup toolkit of the fit diagnostics on gfx950 (ppcx_summary.hip, ppcx_psis.hip, ppcx_loo.hip,
+// ppcx_loo_predict.hip, ppcx_reff.hip, ppcx_ppc_exact.hip): a workgroup of kBlockThreads threads in kBlockWaves wavefronts; and
+// the cross-lane reduction of one wavefront, which the posterior-predictive kernels (ppcx_ppc.hip: workgroups of 512) share with
+// it. Device code only: the `__host__ __device__` statistic headers
 // (ppcx_summary.h, ppcx_psis.h, ppcx_loo.h) never include it, the CPU checks compile without it.
 // The reduction order is part of the contract (a column's result is the same bits on every call): an xor butterfly within a
 // wavefront, then the wavefronts' values red[0 .. kBlockWaves) in index order.
@@ -15,11 +17,14 @@ constexpr int kBlockWaves = kBlockThreads / 64;
 // the smallest power of two >= n (1 for n <= 1)
 __host__ __device__ __forceinline__ int pow2_at_least(long n) { int p = 1; while (p < n) p <<= 1; return p; }
 
-__device__ __forceinline__ double block_wave_sum(double v) {
+// op over the wavefront by the xor butterfly (neighbours, pairs of pairs, ...): the same bits in every lane
+template <class T, class Op>
+__device__ __forceinline__ T wave_reduce(T v, Op op) {
 #pragma unroll
-  for (int msk = 1; msk < 64; msk <<= 1) v += __shfl_xor(v, msk, 64);
-  return v;                                    // the same bits in every lane
+  for (int msk = 1; msk < 64; msk <<= 1) v = op(v, __shfl_xor(v, msk, 64));
+  return v;
 }
+__device__ __forceinline__ double block_wave_sum(double v) { return wave_reduce(v, [](double a, double b) { return a + b; }); }
 // sum over the workgroup in a fixed order; every thread gets it. red: kBlockWaves doubles of LDS
 __device__ inline double block_sum(double v, double* red) {
   v = block_wave_sum(v);
@@ -33,8 +38,7 @@ __device__ inline double block_sum(double v, double* red) {
 }
 // maximum over the workgroup (NaN-free inputs); every thread gets it
 __device__ inline double block_max(double v, double* red) {
-#pragma unroll
-  for (int msk = 1; msk < 64; msk <<= 1) v = fmax(v, __shfl_xor(v, msk, 64));
+  v = wave_reduce(v, [](double a, double b) { return fmax(a, b); });
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   __syncthreads();
   if (lane == 0) red[wave] = v;

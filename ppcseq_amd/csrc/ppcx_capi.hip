@@ -1930,7 +1930,7 @@ static size_t loo_scratch_bytes() {
   return kPsisScratchBytes;
 }
 // the end of an entry point: the driver's error as PPCX_ERR_HIP under the entry's name (null: the bare text)
-static int loo_done(const char* who, hipError_t e) {
+static int hip_done(const char* who, hipError_t e) {
   return e == hipSuccess ? PPCX_OK : who ? hip_fail(e, who) : fail(PPCX_ERR_HIP, hipGetErrorString(e));
 }
 // the fit, the genes, the cells' counts (an excluded cell as -(y + 1), kept in yenc) and the output as the record of these
@@ -1967,7 +1967,7 @@ extern "C" int ppcx_fit_get_log_lik(ppcx_fit* f, int n_genes, const int32_t* gen
   std::vector<int> yenc; FitCells fc;
   const int rc = loo_prepare(f, n_genes, genes, out, yenc, fc);
   if (rc != PPCX_OK) return rc;
-  return loo_done("ppcx_fit_get_log_lik", loo_fit_log_lik(fc, out, loo_scratch_bytes(), f->m->stream));
+  return hip_done("ppcx_fit_get_log_lik", loo_fit_log_lik(fc, out, loo_scratch_bytes(), f->m->stream));
 }
 // r_eff of `cells` cells of n draws (null: all 1): every value finite and > 0; *r_eff_min the smallest (the longest tail of the
 // cells, for the selection buffer), whose tail has to fit that buffer. who: the entry point, null in the testing build
@@ -1992,7 +1992,7 @@ static int fit_loo(const char* who, ppcx_fit* f, int n_genes, const int32_t* gen
   int rc = loo_prepare(f, n_genes, genes, out, yenc, fc);
   if (rc == PPCX_OK) rc = loo_fit_reff(who, fc, r_eff);
   if (rc != PPCX_OK) return rc;
-  return loo_done(who, loo_fit_cells(fc, fields, out, loo_scratch_bytes(), f->m->stream));
+  return hip_done(who, loo_fit_cells(fc, fields, out, loo_scratch_bytes(), f->m->stream));
 }
 extern "C" int ppcx_fit_loo(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double* out) {
   return fit_loo("ppcx_fit_loo", f, n_genes, genes, r_eff, kLooFields, out);
@@ -2015,7 +2015,7 @@ extern "C" int ppcx_fit_loo_predict(ppcx_fit* f, int n_genes, const int32_t* gen
   if (!(isfinite(truncation_compensation) && truncation_compensation > 0.0))
     return fail(PPCX_ERR_ARG, "truncation_compensation must be finite and > 0");
   if ((rc = loo_fit_reff(who, fc, r_eff)) != PPCX_OK) return rc;
-  return loo_done(who, loo_predict_fit_cells(fc, truncation_compensation, p_lo, p_hi, seed32(seed), out, loo_scratch_bytes(),
+  return hip_done(who, loo_predict_fit_cells(fc, truncation_compensation, p_lo, p_hi, seed32(seed), out, loo_scratch_bytes(),
                                              f->m->stream));
 }
 // ---- the same two for an ADVI fit (loo::loo_approximate_posterior; ppcx_loo_ap.h): the draws come from the approximation, the
@@ -2041,7 +2041,7 @@ extern "C" int ppcx_fit_loo_approx(ppcx_fit* f, int n_genes, const int32_t* gene
   int rc = loo_approx_prepare(who, f, n_genes, genes, out, yenc, fc);
   if (rc == PPCX_OK) rc = loo_approx_ratios(f, fc);
   if (rc != PPCX_OK) return rc;
-  return loo_done(who, loo_fit_cells(fc, kLooFields, out, loo_scratch_bytes(), f->m->stream));
+  return hip_done(who, loo_fit_cells(fc, kLooFields, out, loo_scratch_bytes(), f->m->stream));
 }
 extern "C" int ppcx_fit_loo_predict_approx(ppcx_fit* f, int n_genes, const int32_t* genes, double truncation_compensation, double p_lo,
                                            double p_hi, unsigned long long seed, double* out) {
@@ -2053,7 +2053,7 @@ extern "C" int ppcx_fit_loo_predict_approx(ppcx_fit* f, int n_genes, const int32
   if (!(isfinite(truncation_compensation) && truncation_compensation > 0.0))
     return fail(PPCX_ERR_ARG, "truncation_compensation must be finite and > 0");
   if ((rc = loo_approx_ratios(f, fc)) != PPCX_OK) return rc;
-  return loo_done(who, loo_predict_fit_cells(fc, truncation_compensation, p_lo, p_hi, seed32(seed), out, loo_scratch_bytes(),
+  return hip_done(who, loo_predict_fit_cells(fc, truncation_compensation, p_lo, p_hi, seed32(seed), out, loo_scratch_bytes(),
                                              f->m->stream));
 }
 #ifdef PPCX_TESTING
@@ -2065,7 +2065,7 @@ static int testing_loo(int n, int n_cols, const double* ll, const int32_t* exclu
   gc.cols = ll; gc.n = n; gc.n_cols = n_cols; gc.excl = excluded; gc.r_eff = r_eff; gc.log_ratio = log_ratio;
   const int rc = loo_reff_limits(nullptr, r_eff, n_cols, n, &gc.r_eff_min);
   if (rc != PPCX_OK) return rc;
-  return loo_done(nullptr, loo_columns(gc, fields, out, loo_scratch_bytes(), nullptr));
+  return hip_done(nullptr, loo_columns(gc, fields, out, loo_scratch_bytes(), nullptr));
 }
 extern "C" int ppcx_testing_loo(int n, int n_cols, const double* ll, const int32_t* excluded, const double* r_eff, double* out) {
   return testing_loo(n, n_cols, ll, excluded, r_eff, kLooFields, out);
@@ -2089,7 +2089,7 @@ static int testing_loo_predict(const double* ll, const double* log_ratio, const 
   int rc = loo_predict_check_probs(p_lo, p_hi);
   if (rc == PPCX_OK) rc = loo_reff_limits(nullptr, r_eff, n_cols, n, &gc.r_eff_min);
   if (rc != PPCX_OK) return rc;
-  return loo_done(nullptr, loo_predict_columns(gc, x, y, p_lo, p_hi, out, loo_scratch_bytes(), nullptr));
+  return hip_done(nullptr, loo_predict_columns(gc, x, y, p_lo, p_hi, out, loo_scratch_bytes(), nullptr));
 }
 extern "C" int ppcx_testing_loo_predict(const double* ll, const int32_t* x, int n, int n_cols, const int32_t* y, const int32_t* excluded,
                                         const double* r_eff, double p_lo, double p_hi, double* out) {
@@ -2125,7 +2125,7 @@ extern "C" int ppcx_fit_ppc_exact(ppcx_fit* f, int n_genes, const int32_t* genes
   if (rc != PPCX_OK) return rc;
   std::vector<int> yenc; FitCells fc;
   if ((rc = loo_prepare_cells(f, n_genes, genes, out, yenc, fc)) != PPCX_OK) return rc;
-  return loo_done(who, ppc_exact_fit_cells(fc, truncation_compensation, p_lo, p_hi, out, loo_scratch_bytes(), f->m->stream));
+  return hip_done(who, ppc_exact_fit_cells(fc, truncation_compensation, p_lo, p_hi, out, loo_scratch_bytes(), f->m->stream));
 }
 #ifdef PPCX_TESTING
 // testing build only (ppcx_testing.h): the kernel of ppcx_fit_ppc_exact on host-given columns, on the current device
@@ -2137,7 +2137,7 @@ extern "C" int ppcx_testing_ppc_exact(int n, int n_cols, const double* eta, cons
   if (rc != PPCX_OK) return rc;
   GivenCells gc;
   gc.cols = eta; gc.n = n; gc.n_cols = n_cols; gc.excl = excluded;
-  return loo_done(nullptr, ppc_exact_columns(gc, sigma_raw, y, truncation_compensation, p_lo, p_hi, out, loo_scratch_bytes(), nullptr));
+  return hip_done(nullptr, ppc_exact_columns(gc, sigma_raw, y, truncation_compensation, p_lo, p_hi, out, loo_scratch_bytes(), nullptr));
 }
 #endif
 // ---- the relative efficiency of the same cells (loo::relative_eff(exp(log_lik), chain_id): what rstan::loo(fit) passes as r_eff)
@@ -2146,7 +2146,7 @@ extern "C" int ppcx_fit_relative_eff(ppcx_fit* f, int n_genes, const int32_t* ge
   const int rc = loo_prepare(f, n_genes, genes, out, yenc, fc);
   if (rc != PPCX_OK) return rc;
   if (f->chains > kSummaryMaxChains) return fail(PPCX_ERR_LIMIT, "ppcx_fit_relative_eff takes at most 128 chains");
-  return loo_done("ppcx_fit_relative_eff", reff_fit_cells(fc, out, loo_scratch_bytes(), f->m->stream));
+  return hip_done("ppcx_fit_relative_eff", reff_fit_cells(fc, out, loo_scratch_bytes(), f->m->stream));
 }
 #ifdef PPCX_TESTING
 // testing build only (ppcx_testing.h): the relative-efficiency kernel on host-given columns, on the current device
@@ -2155,7 +2155,7 @@ extern "C" int ppcx_testing_relative_eff(int chains, int n, int n_cols, const do
   if (chains > kSummaryMaxChains) return fail(PPCX_ERR_LIMIT, "too many chains");
   GivenCells gc;
   gc.cols = ll; gc.n = (long)chains * n; gc.n_cols = n_cols; gc.chains = chains; gc.n_keep = n;
-  return loo_done(nullptr, reff_columns(gc, out, loo_scratch_bytes(), nullptr));
+  return hip_done(nullptr, reff_columns(gc, out, loo_scratch_bytes(), nullptr));
 }
 #endif
 extern "C" int ppcx_fit_get_diagnostics(ppcx_fit* f, double* lp, double* stepsize, int32_t* treedepth,
@@ -2220,39 +2220,14 @@ extern "C" int ppcx_fit_ppc(ppcx_fit* f, double truncation_compensation, double 
   if (!resample && n_gen > n_draws) return fail(PPCX_ERR_ARG, "n_gen exceeds the kept draws (use resample)");
   if (!(p_lo >= 0.0 && p_hi <= 1.0 && p_lo <= p_hi)) return fail(PPCX_ERR_ARG, "need 0 <= p_lo <= p_hi <= 1");
   HIPCHK(hipSetDevice(m->device));
-  const int n_cells = m->d.K * m->d.S;
-  DeviceBuffer<double> d_ci, d_T;                // d_T: the checked genes' parameters, transposed: [K][C + 1][draws]
-  DeviceBuffer<int> d_rng, d_scratch;
-  // a cell's draws live in LDS (160 KB per CU; 4 KB of it is the kernel's static scratch) when they fit; beyond that
-  // 1024 workgroups share the cells and keep the current cell's draws in their slice of a global scratch buffer
-  const int kLdsDraws = 39680;
-  int nblocks = n_cells;
-  const bool wave_kernel = n_gen <= ppc_wave_max_draws();      // one wavefront per cell (else one workgroup per cell)
-  if (wave_kernel) { nblocks = (n_cells + 3) / 4; if (nblocks > 4096) nblocks = 4096; }
-  else if (n_gen > kLdsDraws) nblocks = n_cells < 1024 ? n_cells : 1024;
-  hipError_t e = d_ci.alloc((size_t)n_cells * 4);
-  if (e == hipSuccess) e = d_T.alloc((size_t)m->d.K * (m->d.C + 1) * (size_t)n_draws);
-  if (e == hipSuccess && !wave_kernel && n_gen > kLdsDraws) e = d_scratch.alloc((size_t)nblocks * n_gen);
-  if (e == hipSuccess && counts_rng) e = d_rng.alloc((size_t)n_gen * n_cells);
-  if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
-  PpcArgs pa;
+  PpcArgs pa{};
   pa.d = m->d; pa.draws = f->d_draws.p; pa.n_draws = n_draws; pa.exposure = m->d_expo; pa.X = m->d_X;
   pa.truncation_compensation = truncation_compensation; pa.p_lo = p_lo; pa.p_hi = p_hi; pa.k0 = seed32(seed);
-  pa.n_gen = n_gen; pa.resample = resample ? 1 : 0; pa.n_cells = n_cells; pa.ci = d_ci.p; pa.counts_rng = d_rng.p; pa.scratch = d_scratch.p;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  (void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1);
-  if (ev0) (void)hipEventRecord(ev0, m->stream);
-  e = launch_ppc_table_kernel(f->d_draws.p, n_draws, m->d, truncation_compensation, d_T.p, m->stream);
-  if (e == hipSuccess) e = wave_kernel ? launch_ppc_wave_kernel(pa, d_T.p, nblocks, m->stream) : launch_ppc_kernel(pa, d_T.p, nblocks, m->stream);
-  if (ev1) (void)hipEventRecord(ev1, m->stream);
-  e = finish(e, m->stream);                      // drained whatever happened: the buffers go out of scope below
-  if (e == hipSuccess && ev0 && ev1) { float ms = 0; if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) { f->ppc_ms = ms; f->ppc_draws = (long long)n_gen * n_cells; } }
-  if (ev0) (void)hipEventDestroy(ev0);
-  if (ev1) (void)hipEventDestroy(ev1);
-  if (e == hipSuccess) e = hipMemcpy(ci, d_ci.p, sizeof(double) * (size_t)n_cells * 4, hipMemcpyDeviceToHost);
-  if (e == hipSuccess && counts_rng) e = hipMemcpy(counts_rng, d_rng.p, sizeof(int) * (size_t)n_gen * n_cells, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) return fail(PPCX_ERR_HIP, hipGetErrorString(e));
-  return PPCX_OK;
+  pa.n_gen = n_gen; pa.resample = resample ? 1 : 0; pa.n_cells = m->d.K * m->d.S;
+  float ms = -1.0f;
+  const hipError_t e = ppc_fit(pa, ci, counts_rng, &ms, m->stream);
+  if (e == hipSuccess && ms >= 0.0f) { f->ppc_ms = ms; f->ppc_draws = (long long)n_gen * pa.n_cells; }
+  return hip_done(nullptr, e);
 }
 
 // vb_iterative (R/utilities.R:246-278): rstan::vb is retried until it returns; the reference passes no seed, so every

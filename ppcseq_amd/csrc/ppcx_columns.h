@@ -1,5 +1,6 @@
-// ppcx_columns.h -- the host side that the fit diagnostics share (ppcx_summary.hip, ppcx_psis.hip, ppcx_loo.hip and their entry
-// points in ppcx_capi.hip): an owning device buffer -- also what a fit holds its draws and diagnostics in, and the scratch of a
+// ppcx_columns.h -- the host side that the fit diagnostics and the posterior-predictive driver share (ppcx_summary.hip,
+// ppcx_psis.hip, ppcx_loo.hip, ppcx_loo_predict.hip, ppcx_reff.hip, ppcx_ppc_exact.hip, ppcx_ppc.hip and their entry points in
+// ppcx_capi.hip): an owning device buffer -- also what a fit holds its draws and diagnostics in, and the scratch of a
 // call (ppcx_capi.hip) --, the column-batch driver and the launch of a kernel with dynamic LDS.
 // Every driver built from these synchronises its stream before a buffer goes out of scope (finish() below), also after a
 // failed launch: nothing is freed under a running kernel.
@@ -64,13 +65,13 @@ hipError_t for_column_batches(const double* draws, const double* lp, long rows, 
 }
 
 // a kernel with `bytes` of dynamic LDS, the kernel's limit raised above the 64 KB default where that takes it
-template <class Args>
-hipError_t launch_dynamic_lds(void (*kernel)(Args), int n_blocks, int threads, size_t bytes, hipStream_t st, const Args& a) {
+template <class... Args>
+hipError_t launch_dynamic_lds(void (*kernel)(Args...), int n_blocks, int threads, size_t bytes, hipStream_t st, const Args&... a) {
   if (bytes > 64u * 1024u) {
     const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e != hipSuccess) return e;
   }
-  hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(threads), bytes, st, a);
+  hipLaunchKernelGGL(kernel, dim3(n_blocks), dim3(threads), bytes, st, a...);
   return hipGetLastError();
 }
 

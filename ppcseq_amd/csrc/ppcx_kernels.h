@@ -1,4 +1,5 @@
-// ppcx_kernels.h -- argument blocks and launchers of the gfx950 kernels (ppcx_kernels.hip).
+// ppcx_kernels.h -- argument blocks, launchers and drivers of the gfx950 kernels (ppcx_kernels.hip and the translation units of
+// the predictive kernels and the fit diagnostics).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ppcx_gene.h"
@@ -122,6 +123,7 @@ struct AdviArgs {
 };
 struct AdviElboArgs { Dims d; const Cmd* cmds; const double* red; int n_slots; double* acc; const double* omega_part; int n_omega_parts; };
 
+// the posterior-predictive draws and intervals of the K checked genes' cells (ppcx_ppc.hip, statistic in ppcx_ppc.h)
 struct PpcArgs {
   Dims d;
   const double* draws;          // [n_draws][D]
@@ -152,12 +154,6 @@ hipError_t launch_sum_shards_kernel(const ShardSumArgs& a, hipStream_t st);
 hipError_t launch_update_kernel(const UpdateArgs& a, int nblocks, int nchains, hipStream_t st);
 hipError_t launch_advi_kernel(const AdviArgs& a, int nblocks, hipStream_t st);
 hipError_t launch_advi_elbo_kernel(const AdviElboArgs& a, hipStream_t st);
-hipError_t launch_ppc_kernel(const PpcArgs& a, const double* T, int nblocks, hipStream_t st);   // one workgroup per cell
-// one wavefront per cell (n_gen <= ppc_wave_max_draws()): the parameter table T[K][C + 1][n_draws], then the draws
-size_t ppc_wave_lds_bytes(int n_gen);
-int ppc_wave_max_draws();
-hipError_t launch_ppc_table_kernel(const double* draws, long n_draws, const Dims& d, double tc, double* T, hipStream_t st);
-hipError_t launch_ppc_wave_kernel(const PpcArgs& a, const double* T, int nblocks, hipStream_t st);
 // the dispersion tables (ppcx_disp.h) of the genes in `genes` (null: genes 0 .. n_genes - 1), one workgroup per gene
 hipError_t launch_disp_build_kernel(const int* counts, int G, int S, const int* genes, int n_genes, const DispFit& fit, double* table, hipStream_t st);
 hipError_t launch_gather_kernel(const double* draws, long n_rows, int D, const int* cols, int n_cols, double* out, hipStream_t st);
@@ -250,6 +246,10 @@ struct FitCells {
   double r_eff_min = 1.0;          // the smallest r_eff (1 without r_eff)
   const double* log_ratio = nullptr;   // [n] (device) log_p - log_g of an ADVI fit, or null: the draws are the posterior's
 };
+// The driver of ppcx_fit_ppc: the table, then one wavefront per cell up to 4096 predictive draws per cell, one workgroup per cell
+// beyond. Of `a` the inputs (device) are the caller's, ci / counts_rng / scratch the driver's own; ci [n_cells][4] and counts_rng
+// [n_gen][n_cells] (or null) are host; kernel_ms: table + kernel by HIP events, left alone where there are none. Synchronous.
+hipError_t ppc_fit(PpcArgs a, double* ci, int32_t* counts_rng, float* kernel_ms, hipStream_t st);
 // Host-given log-likelihood columns in place of a fit's cells (testing build): cols [n_cols][n], n = chains n_keep where the
 // statistic needs chains
 struct GivenCells {

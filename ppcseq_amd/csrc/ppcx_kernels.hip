@@ -1,4 +1,4 @@
-// ppcx_kernels.hip -- gfx950 kernels of the NB hierarchical NUTS / posterior-predictive engine.
+// ppcx_kernels.hip -- gfx950 kernels of the NB hierarchical NUTS / ADVI engine (the posterior-predictive kernels: ppcx_ppc.hip).
 //
 //   ppcx_loglik_kernel<CM,GEN>  streams the int32 count matrix once per gradient evaluation and reduces it to a handful
 //                           of sums per gene. Replaces lp_reduce + map_rect + X*alpha of
@@ -12,9 +12,7 @@
 //   ppcx_step_kernel        reduction of the close kernel's block partials, hyper-parameters, NUTS / adaptation state
 //                           machine (ppcx_nuts.h) and, in the same launch, the per-coordinate work of the next command.
 //   ppcx_update_kernel      that per-coordinate work as a launch of its own (initialisation, ADVI).
-//   ppcx_ppc_kernel         generated quantities (.stan:259-266) + credible-interval summary
-//                           (R/utilities.R:685-703 / :733-784): NB draws straight into LDS, order
-//                           statistics by bisection on the value, type-7 quantiles, mean, sd.
+//   ppcx_advi_kernel        the per-coordinate work of ADVI (draws, steps); ppcx_advi_elbo_kernel its ELBO.
 //   ppcx_gather_kernel      column gather of the retained draws.
 //
 // Work decomposition of the log-likelihood kernel: a gene is owned by L lanes of one wavefront
@@ -1085,292 +1083,6 @@ __global__ void ppcx_advi_elbo_kernel(AdviElboArgs a) {
 }
 
 // -----------------------------------------------------------------------------------------------------
-// posterior-predictive draws + credible intervals, one workgroup per (gene <= K, sample) cell
-// -----------------------------------------------------------------------------------------------------
-constexpr int kPpcThreads = 512;              // 8 wavefronts share the cell's draws in LDS (2 per SIMD; the kernel needs 233 VGPRs)
-constexpr int kPpcWaves = kPpcThreads / 64;
-// number of the workgroup's draws that are <= v (every thread gets the total; two barriers)
-__device__ __forceinline__ int block_count_le(const int* vals, int n, int v, int* s_cnt, int tid) {
-  int c = 0;
-  for (int j = tid; j < n; j += kPpcThreads) c += vals[j] <= v ? 1 : 0;
-#pragma unroll
-  for (int msk = 1; msk < 64; msk <<= 1) c += __shfl_xor(c, msk, 64);
-  if ((tid & 63) == 0) s_cnt[tid >> 6] = c;
-  __syncthreads();
-  int tot = 0;
-#pragma unroll
-  for (int w = 0; w < kPpcWaves; ++w) tot += s_cnt[w];
-  __syncthreads();
-  return tot;
-}
-// order statistics r and r+1 (0-based, r+1 < n or equal to r when r = n-1) of the non-negative draws by bisection on the
-// value: the smallest v with #{draws <= v} >= r+1. Exact for integers; ~log2(max) counting passes instead of a sort.
-__device__ __forceinline__ void block_select_pair(const int* vals, int n, int r, int vmax, int* s_cnt, int tid, int* v_r, int* v_r1) {
-  int lo = 0, hi = vmax;
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (block_count_le(vals, n, mid, s_cnt, tid) >= r + 1) hi = mid; else lo = mid + 1;
-  }
-  *v_r = lo;
-  // the next order statistic: the same value if it occurs again at rank r+1, else the smallest draw above it
-  int nxt = lo;
-  if (r + 1 < n && block_count_le(vals, n, lo, s_cnt, tid) < r + 2) {
-    int mn = 2147483647;
-    for (int j = tid; j < n; j += kPpcThreads) { const int x = vals[j]; mn = (x > lo && x < mn) ? x : mn; }
-#pragma unroll
-    for (int msk = 1; msk < 64; msk <<= 1) { const int o = __shfl_xor(mn, msk, 64); mn = o < mn ? o : mn; }
-    if ((tid & 63) == 0) s_cnt[tid >> 6] = mn;
-    __syncthreads();
-    nxt = s_cnt[0];
-#pragma unroll
-    for (int w = 1; w < kPpcWaves; ++w) nxt = min(nxt, s_cnt[w]);
-    __syncthreads();
-  }
-  *v_r1 = nxt;
-}
-
-// The predictive draws of one cell by `stride` cooperating lanes (lane `first` takes draws first, first + stride, ...):
-// ONE loop of attempts for the wavefront. Per turn a lane makes one attempt at the gamma variate of its current draw (or begins
-// the draw) and, once it has it, one attempt at the Poisson variate; a lane whose draw is complete stores it and begins its next
-// draw in the next turn. A draw costs a lane ~1.15 turns (the two samplers' rejection rates) instead of every draw waiting for
-// the slowest lane's rejections. The parameters come from the transposed table T[g][c][draw] (ppcx_ppc_table_kernel).
-__device__ __forceinline__ void cell_draws(const PpcArgs& a, const double* T, int cell, int* vals, int first, int stride,
-                                           double* sum_out, int* vmax_out) {
-  const Dims& d = a.d;
-  const int n = a.n_gen;
-  const int g = cell / d.S, s = cell - g * d.S;
-  const double* Tg = T + (long)g * (d.C + 1) * a.n_draws;
-  const double expo = a.exposure[s];
-  double sum = 0.0; int vmax = 0;
-  int j = first, phase = 0;                     // 0: begin the draw, 1: gamma attempts, 2: Poisson attempts
-  GammaDraw gd; PoissonDraw pq; double scale = 0.0;
-  while (PPCX_WAVE_ANY(j < n)) {
-    if (j < n) {
-      int val = 0; bool done = false;
-      if (phase == 0) {                         // the draw's parameters, eta, the gamma stream
-        long src = j;
-        if (a.resample) {                       // R/utilities.R:760: sample(draws, n, replace = TRUE)
-          const double u = coord_uniform((uint32_t)j, (uint32_t)cell, 5u, 0u, a.k0, 0x50504331u);
-          src = (long)(u * (double)a.n_draws); if (src >= a.n_draws) src = a.n_draws - 1;
-        }
-        double eta = expo + a.X[s] * Tg[src];
-        for (int cc = 1; cc < d.C; ++cc) eta += a.X[(long)cc * d.S + s] * Tg[(long)cc * a.n_draws + src];
-        const double phi = Tg[(long)d.C * a.n_draws + src];
-        if (nb2_invalid(eta, phi)) { val = 2147483647; done = true; }        // invalid draw: sorts last
-        else { gamma_begin(gd, phi, a.k0, (uint32_t)cell, (uint32_t)j); scale = rng_div(rng_exp(eta), phi); phase = 1; }
-      }
-      if (phase == 1) {
-        double gam;
-        if (gamma_attempt(gd, &gam)) {
-          const double lam = gam * scale;
-          if (!(lam < 1073741824.0)) { val = 1073741823; done = true; }      // Stan raises above 2^30; we saturate
-          else { poisson_begin(pq, lam, a.k0, (uint32_t)cell, (uint32_t)j); phase = 2; }
-        }
-      }
-      if (phase == 2 && !done) {
-        long long k;
-        if (poisson_attempt(pq, &k)) { val = k > 2147483647LL ? 2147483647 : (int)k; done = true; }
-      }
-      if (done) {
-        vals[j] = val;
-        sum += (double)val; vmax = val > vmax ? val : vmax;
-        if (a.counts_rng) a.counts_rng[(long)j * a.n_cells + cell] = val;
-        j += stride; phase = 0;
-      }
-    }
-  }
-  *sum_out = sum; *vmax_out = vmax;
-}
-
-__global__ __launch_bounds__(kPpcThreads) void ppcx_ppc_kernel(PpcArgs a, const double* T) {
-  extern __shared__ int ldsi[];
-  __shared__ double sred[kPpcThreads];
-  __shared__ int s_cnt[kPpcWaves];
-  const Dims& d = a.d;
-  const int tid = threadIdx.x;
-  // a cell's draws live in LDS when they fit (one workgroup per cell), otherwise in this workgroup's slice of a global
-  // scratch buffer, and the workgroup takes cells in turn (how_many_posterior_draws = draws_after_tail / threshold
-  // reaches 100 000 at the reference's defaults with 200 samples, R/methods.R:166-167)
-  int* vals = a.scratch ? a.scratch + (long)blockIdx.x * a.n_gen : ldsi;
-  const int n = a.n_gen;
-  for (int cell = blockIdx.x; cell < a.n_cells; cell += gridDim.x) {   // g * S + s
-    double sum = 0.0;
-    int vmax = 0;
-    {
-      // eight wavefronts share the cell here: every lane has few draws, and draw after draw (each wavefront waiting for its
-      // slowest lane) measured faster than the one loop of attempts that the wavefront-per-cell kernel runs (145 vs 185 ms at
-      // 10 500 draws per cell x 200 000 cells)
-      const int g = cell / d.S, s = cell - g * d.S;
-      const double* Tg = T + (long)g * (d.C + 1) * a.n_draws;
-      const double expo = a.exposure[s];
-      for (int j = tid; j < n; j += kPpcThreads) {
-        long src = j;
-        if (a.resample) {                        // R/utilities.R:760: sample(draws, n, replace = TRUE)
-          const double u = coord_uniform((uint32_t)j, (uint32_t)cell, 5u, 0u, a.k0, 0x50504331u);
-          src = (long)(u * (double)a.n_draws); if (src >= a.n_draws) src = a.n_draws - 1;
-        }
-        double eta = expo + a.X[s] * Tg[src];
-        for (int cc = 1; cc < d.C; ++cc) eta += a.X[(long)cc * d.S + s] * Tg[(long)cc * a.n_draws + src];
-        const int val = nb2_log_rng(eta, Tg[(long)d.C * a.n_draws + src], a.k0, (uint32_t)cell, (uint32_t)j);
-        sum += (double)val;
-        vmax = val > vmax ? val : vmax;
-        if (a.counts_rng) a.counts_rng[(long)j * a.n_cells + cell] = val;
-        vals[j] = val;
-      }
-    }
-    // mean (fixed-order block reduction)
-    sred[tid] = sum;
-    __syncthreads();
-    for (int st = kPpcThreads / 2; st > 0; st >>= 1) { if (tid < st) sred[tid] += sred[tid + st]; __syncthreads(); }
-    const double mean = sred[0] / (double)n;
-    __syncthreads();
-    double ss = 0.0;
-    for (int j = tid; j < n; j += kPpcThreads) { const double t = (double)vals[j] - mean; ss += t * t; }
-    sred[tid] = ss;
-    __syncthreads();
-    for (int st = kPpcThreads / 2; st > 0; st >>= 1) { if (tid < st) sred[tid] += sred[tid + st]; __syncthreads(); }
-    const double sd = n > 1 ? sqrt(sred[0] / (double)(n - 1)) : NAN;
-    __syncthreads();
-    // largest draw of the workgroup (upper end of the bisections)
-#pragma unroll
-    for (int msk = 1; msk < 64; msk <<= 1) { const int o = __shfl_xor(vmax, msk, 64); vmax = o > vmax ? o : vmax; }
-    if ((tid & 63) == 0) s_cnt[tid >> 6] = vmax;
-    __syncthreads();
-    vmax = s_cnt[0];
-#pragma unroll
-    for (int w = 1; w < kPpcWaves; ++w) vmax = max(vmax, s_cnt[w]);
-    __syncthreads();
-    // type-7 quantiles (R quantile default; rstan::summary) from the two order statistics around (n-1) p
-    double q[2];
-    const double pr[2] = {a.p_lo, a.p_hi};
-    for (int k = 0; k < 2; ++k) {
-      double h = (double)(n - 1) * pr[k];
-      PPCX_OPAQUE(h);                            // rounded here: the product must not be fused into h - lo below
-      int lo = (int)floor(h);
-      if (lo > n - 1) lo = n - 1;
-      if (lo < 0) lo = 0;
-      int v0, v1;
-      block_select_pair(vals, n, lo, vmax, s_cnt, tid, &v0, &v1);
-      q[k] = lo >= n - 1 ? (double)v0 : fma(h - (double)lo, (double)v1 - (double)v0, (double)v0);   // one rounding, as in the oracle
-    }
-    if (tid == 0) {
-      double* o = a.ci + (long)cell * 4;
-      o[0] = mean; o[1] = sd; o[2] = q[0]; o[3] = q[1];
-    }
-    __syncthreads();                             // the next cell reuses vals
-  }
-}
-
-// -----------------------------------------------------------------------------------------------------
-// posterior-predictive draws + credible intervals, ONE WAVEFRONT per (gene <= K, sample) cell (up to kPpcWaveMaxDraws
-// predictive draws per cell; the workgroup-per-cell kernel above serves longer ones).
-//   * the checked genes' parameters are first gathered into a transposed table T[g][c][draw] (ppcx_ppc_table_kernel:
-//     intercept, slopes, phi = exp(-sigma_raw) x truncation_compensation -- the per-gene work, done once per draw instead
-//     of once per draw and sample), so that a wavefront's lanes read consecutive draws of one parameter;
-//   * the lanes' rejection samplers run in ONE loop of attempts (gamma_attempt / poisson_attempt, ppcx_math.h): a lane that
-//     has accepted goes on to its next draw at once -- the wavefront pays ~1.15 turns per draw instead of the slowest lane's;
-//   * mean, sd and the order statistics around the two type-7 quantiles are taken inside the wavefront (cross-lane moves, no
-//     workgroup barrier): bisection on the value over the LDS-resident integers, as in the workgroup kernel.
-// -----------------------------------------------------------------------------------------------------
-constexpr int kPpcWaveMaxDraws = 4096;        // per cell: 16 KB of integers per wavefront, 64 KB per workgroup, two workgroups per CU
-// T[g][c][j], c = 0 intercept, 1 .. C - 1 slopes, C phi: one thread per (draw j, gene g), 32 x 32 tiles through LDS so that
-// both the reads (along g) and the writes (along j) are coalesced
-__global__ __launch_bounds__(256) void ppcx_ppc_table_kernel(const double* draws, long n_draws, Dims d, double tc, double* T) {
-  __shared__ double tile[32][33];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;          // 32 x 8
-  const long j0 = (long)blockIdx.x * 32; const int g0 = blockIdx.y * 32;
-  const int ncol = d.C + 1;
-  for (int c = 0; c < ncol; ++c) {
-    for (int r = ty; r < 32; r += 8) {
-      const long j = j0 + r; const int g = g0 + tx;
-      double v = 0.0;
-      if (j < n_draws && g < d.K) {
-        const double* u = draws + j * (long)d.D;
-        if (c == 0) v = u[d.off_intercept + g];
-        else if (c < d.C) v = u[coef_index(d, c, g)];
-        else v = exp(-u[d.off_sigma_raw + g]) * tc;                  // sigma = 1 ./ exp(sigma_raw), .stan:203,:264
-      }
-      tile[r][tx] = v;
-    }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-      const int g = g0 + r; const long j = j0 + tx;
-      if (j < n_draws && g < d.K) T[((long)g * ncol + c) * n_draws + j] = tile[tx][r];
-    }
-    __syncthreads();
-  }
-}
-__device__ __forceinline__ int wave_sum_int(int v) {
-#pragma unroll
-  for (int msk = 1; msk < 64; msk <<= 1) v += __shfl_xor(v, msk, 64);
-  return v;
-}
-__device__ __forceinline__ int wave_count_le(const int* vals, int n, int v, int lane) {
-  int c = 0;
-  for (int j = lane; j < n; j += 64) c += vals[j] <= v ? 1 : 0;
-  return wave_sum_int(c);
-}
-__device__ __forceinline__ void wave_select_pair(const int* vals, int n, int r, int vmax, int lane, int* v_r, int* v_r1) {
-  int lo = 0, hi = vmax;
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (wave_count_le(vals, n, mid, lane) >= r + 1) hi = mid; else lo = mid + 1;
-  }
-  *v_r = lo;
-  int nxt = lo;
-  if (r + 1 < n && wave_count_le(vals, n, lo, lane) < r + 2) {     // the next order statistic is the smallest draw above lo
-    int mn = 2147483647;
-    for (int j = lane; j < n; j += 64) { const int x = vals[j]; mn = (x > lo && x < mn) ? x : mn; }
-#pragma unroll
-    for (int msk = 1; msk < 64; msk <<= 1) { const int o = __shfl_xor(mn, msk, 64); mn = o < mn ? o : mn; }
-    nxt = mn;
-  }
-  *v_r1 = nxt;
-}
-__device__ __forceinline__ double wave_sum_double(double v) {
-#pragma unroll
-  for (int msk = 1; msk < 64; msk <<= 1) v += __shfl_xor(v, msk, 64);
-  return v;
-}
-
-__global__ __launch_bounds__(256) void ppcx_ppc_wave_kernel(PpcArgs a, const double* T) {
-  extern __shared__ int ldsw[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int n = a.n_gen;
-  int* vals = ldsw + (long)wave * ((n + 1) & ~1);                            // [n] the cell's draws
-  for (int cell = blockIdx.x * 4 + wave; cell < a.n_cells; cell += gridDim.x * 4) {   // g * S + s
-    double sum = 0.0; int vmax = 0;
-    cell_draws(a, T, cell, vals, lane, 64, &sum, &vmax);
-    // ---- mean, sd, type-7 quantiles (R quantile default; rstan::summary), all inside the wavefront
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");      // the lanes' integers are in LDS before any lane reads another's
-    __builtin_amdgcn_wave_barrier();
-    const double mean = wave_sum_double(sum) / (double)n;
-    double ss = 0.0;
-    for (int j = lane; j < n; j += 64) { const double t = (double)vals[j] - mean; ss += t * t; }
-    const double sd = n > 1 ? sqrt(wave_sum_double(ss) / (double)(n - 1)) : NAN;
-#pragma unroll
-    for (int msk = 1; msk < 64; msk <<= 1) { const int o = __shfl_xor(vmax, msk, 64); vmax = o > vmax ? o : vmax; }
-    double q[2];
-    const double pr[2] = {a.p_lo, a.p_hi};
-    for (int k = 0; k < 2; ++k) {
-      double h = (double)(n - 1) * pr[k];
-      PPCX_OPAQUE(h);                            // rounded here: the product must not be fused into h - lo below
-      int lo = (int)floor(h);
-      if (lo > n - 1) lo = n - 1;
-      if (lo < 0) lo = 0;
-      int v0, v1;
-      wave_select_pair(vals, n, lo, vmax, lane, &v0, &v1);
-      q[k] = lo >= n - 1 ? (double)v0 : fma(h - (double)lo, (double)v1 - (double)v0, (double)v0);   // one rounding, as in the oracle
-    }
-    if (lane == 0) {
-      double* o = a.ci + (long)cell * 4;
-      o[0] = mean; o[1] = sd; o[2] = q[0]; o[3] = q[1];
-    }
-    __builtin_amdgcn_wave_barrier();             // the next cell reuses vals
-  }
-}
-
-// -----------------------------------------------------------------------------------------------------
 // The genes' dispersion tables (ppcx_disp.h), built once per model and whenever the exclusions change: one workgroup per
 // gene. Phase 1: thread (panel, node) evaluates Fh and Dh at its node -- a loop over the gene's row in LDS, every thread on
 // the same cell (so the y < 8 / y >= 8 branch of disp_cell is uniform). Phase 2: thread (panel, function) turns the panel's
@@ -1536,26 +1248,6 @@ hipError_t launch_advi_kernel(const AdviArgs& a, int nblocks, hipStream_t st) {
 }
 hipError_t launch_advi_elbo_kernel(const AdviElboArgs& a, hipStream_t st) {
   hipLaunchKernelGGL(ppcx_advi_elbo_kernel, dim3(1), dim3(64), 0, st, a);
-  return hipGetLastError();
-}
-hipError_t launch_ppc_kernel(const PpcArgs& a, const double* T, int nblocks, hipStream_t st) {
-  hipLaunchKernelGGL(ppcx_ppc_kernel, dim3(nblocks), dim3(kPpcThreads), a.scratch ? 0 : sizeof(int) * (size_t)a.n_gen, st, a, T);
-  return hipGetLastError();
-}
-size_t ppc_wave_lds_bytes(int n_gen) { return sizeof(int) * 4 * (size_t)((n_gen + 1) & ~1); }
-int ppc_wave_max_draws() { return kPpcWaveMaxDraws; }
-hipError_t launch_ppc_table_kernel(const double* draws, long n_draws, const Dims& d, double tc, double* T, hipStream_t st) {
-  const dim3 grid((unsigned)((n_draws + 31) / 32), (unsigned)((d.K + 31) / 32));
-  hipLaunchKernelGGL(ppcx_ppc_table_kernel, grid, dim3(256), 0, st, draws, n_draws, d, tc, T);
-  return hipGetLastError();
-}
-hipError_t launch_ppc_wave_kernel(const PpcArgs& a, const double* T, int nblocks, hipStream_t st) {
-  const size_t lds = ppc_wave_lds_bytes(a.n_gen);
-  if (lds > 64u * 1024u) {
-    hipError_t e = hipFuncSetAttribute((const void*)ppcx_ppc_wave_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(ppcx_ppc_wave_kernel, dim3(nblocks), dim3(256), lds, st, a, T);
   return hipGetLastError();
 }
 size_t disp_build_lds_bytes(int S) { return sizeof(int) * (size_t)((S + 1) & ~1) + sizeof(double) * 2 * kDispPanels * kDispN; }

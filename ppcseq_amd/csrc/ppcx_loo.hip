@@ -3,9 +3,8 @@
 // the end of this file add the kernel to it.
 //
 //   ppcx_loo_table_kernel  the per-draw parameters of the requested genes, transposed: T[g][c][draw], c = 0 intercept,
-//                          1 .. C - 1 slopes (0 for a gene without slopes), C sigma_raw. One thread per (draw, gene), 32 x 32
-//                          tiles through LDS so that both the reads (along the genes) and the writes (along the draws) are
-//                          coalesced -- ppcx_ppc_table_kernel's layout, for a gene list and without truncation compensation.
+//                          1 .. C - 1 slopes (0 for a gene without slopes), C sigma_raw: the table of ppcx_table.h (table_tiles,
+//                          which ppcx_ppc_table_kernel of ppcx_ppc.hip runs too) for a gene list, the last row left as it is.
 //   ppcx_loo_ll_kernel     the log-likelihood matrix itself, [draw][cell] (ppcx_fit_get_log_lik): one thread per (draw, cell).
 //   ppcx_loo_kernel        one workgroup per cell: the cell's n log-likelihoods from T (the S cells of a gene read the same rows
 //                          of T, through L2), as ratios r = -ll in LDS (up to kPsisLdsDraws draws) or in the workgroup's slice
@@ -32,30 +31,7 @@ namespace ppcx {
 
 __global__ __launch_bounds__(256) void ppcx_loo_table_kernel(const double* draws, long n_draws, Dims d, const int* genes,
                                                              int n_genes, double* T) {
-  __shared__ double tile[32][33];
-  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;          // 32 x 8
-  const long j0 = (long)blockIdx.x * 32; const int g0 = blockIdx.y * 32;
-  const int ncol = d.C + 1;
-  for (int c = 0; c < ncol; ++c) {
-    for (int r = ty; r < 32; r += 8) {
-      const long j = j0 + r; const int gi = g0 + tx;
-      double v = 0.0;
-      if (j < n_draws && gi < n_genes) {
-        const double* u = draws + j * (long)d.D;
-        const int g = genes[gi];
-        if (c == 0) v = u[d.off_intercept + g];
-        else if (c < d.C) v = g < d.K ? u[coef_index(d, c, g)] : 0.0;
-        else v = u[d.off_sigma_raw + g];
-      }
-      tile[r][tx] = v;
-    }
-    __syncthreads();
-    for (int r = ty; r < 32; r += 8) {
-      const int gi = g0 + r; const long j = j0 + tx;
-      if (j < n_draws && gi < n_genes) T[((long)gi * ncol + c) * n_draws + j] = tile[tx][r];
-    }
-    __syncthreads();
-  }
+  table_tiles<false>(draws, n_draws, d, genes, n_genes, 1.0, T);
 }
 
 __global__ __launch_bounds__(256) void ppcx_loo_ll_kernel(LooArgs a, long j0, long n_rows, double* out) {

@@ -2,16 +2,17 @@
 // leave-one-out predictive interval per cell; ppcx_reff.hip: the relative efficiency per cell). On the device: which cell a
 // workgroup has, the cell's linear predictor and log-likelihood from the transposed table, its ratios r = -ll (an ADVI fit:
 // (log_p - log_g) - ll, ppcx_loo_ap.h), the fitted tail with the copies of the cutoff, a draw's log weight under the tie rule.
-// On the host: the one walk over a fit's cells in gene batches (for_gene_batches), its
-// counterpart for host-given columns (for_given_columns) and the batches of cells under the scratch bound
-// (loo_cell_batches); a statistic's drivers add their argument block and their kernel. The statistic is ppcx_loo.h; the
-// workgroup pieces are ppcx_block.h and ppcx_psis_dev.h.
+// The table itself and a cell's read of it are ppcx_table.h's, shared with the posterior-predictive kernels.
+// On the host: the one walk over a fit's cells in gene batches (for_gene_batches), its counterpart for host-given columns
+// (for_given_columns) and the batches of cells under the scratch bound (loo_cell_batches); a statistic's drivers add their
+// argument block and their kernel. The statistic is ppcx_loo.h; the workgroup pieces are ppcx_block.h and ppcx_psis_dev.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ppcx_psis_dev.h"
 #include "ppcx_loo.h"
 #include "ppcx_loo_ap.h"
 #include "ppcx_columns.h"
+#include "ppcx_table.h"
 
 namespace ppcx {
 
@@ -27,16 +28,20 @@ __device__ __forceinline__ LooCell loo_cell(const LooArgs& a, const int* ycols =
   return c;
 }
 
-// linear predictor of cell (gene gi of the table, sample s) at draw j: the expression of the posterior-predictive kernels
-__device__ __forceinline__ double loo_cell_eta(const LooArgs& a, const double* Tg, int s, long j) {
-  double eta = a.expo[s] + a.X[s] * Tg[j];
-  for (int cc = 1; cc < a.C; ++cc) eta += a.X[(long)cc * a.S + s] * Tg[(long)cc * a.n + j];
+// linear predictor of cell (gene gi of the table, sample s) at draw j, with sigma_raw where asked for: table_draw, as the
+// posterior-predictive kernels read it
+__device__ __forceinline__ double loo_cell_eta(const LooArgs& a, const double* Tg, int s, long j, double* sigma_raw = nullptr) {
+  double eta, last;
+  table_draw(Tg, a.n, a.C, a.expo[s], a.X, a.S, s, j, &eta, &last);
+  if (sigma_raw) *sigma_raw = last;
   return eta;
 }
 // log-likelihood of cell (gene gi of the table, sample s) at draw j, count y >= 0
 __device__ __forceinline__ double loo_cell_ll(const LooArgs& a, int gi, int s, long j, int y) {
   const double* Tg = a.T + (long)gi * (a.C + 1) * a.n;
-  return loo_ll(y, loo_cell_eta(a, Tg, s, j), Tg[(long)a.C * a.n + j]);
+  double sigma_raw;
+  const double eta = loo_cell_eta(a, Tg, s, j, &sigma_raw);
+  return loo_ll(y, eta, sigma_raw);
 }
 
 // The cell's ratios r = -ll into V[0 .. n). Returns whether the cell is NaN (a NaN ratio, or +Inf where the cell is not

@@ -27,24 +27,19 @@
 //      Q = v- + (v* - v-) (p - F(v-)) / (F(v*) - F(v-))   (loo's weighted quantile on the distinct values);
 //      khat as ppcx_fit_loo.
 //   4. A cell the model excludes is already held out: uniform weights, khat = NaN, mean = (sum x_i) / n (an integer sum),
-//      lower / upper the type-7 quantiles of x in the form of ppcx_fit_ppc's kernels (loo_predict_type7), pit_lt = #{x_i < y} / n,
-//      pit_le = #{x_i <= y} / n. With phi formed as exp(-sigma_raw) truncation_compensation these are ppcx_fit_ppc's mean,
+//      lower / upper the type-7 quantiles of x as ppcx_fit_ppc's kernels take them (type7, ppcx_ppc.h), pit_lt = #{x_i < y} / n,
+//      pit_le = #{x_i <= y} / n. With phi formed by the same ppc_phi these are ppcx_fit_ppc's mean,
 //      .lower and .upper bit for bit (the log-likelihood decides nothing but NaN).
 // Every reduction runs in a fixed order: a cell's fields depend on its own column only.
 #pragma once
 #include <stdint.h>
 #include "ppcx_loo.h"
+#include "ppcx_ppc.h"
 
 namespace ppcx {
 
 constexpr int kLooPredictFields = 6;           // mean, lower, upper, pit_lt, pit_le, khat (include/ppcx.h PPCX_LOO_PREDICT_FIELDS)
-constexpr int32_t kLooPredictInvalid = 2147483647;   // nb2_log_rng's "invalid draw"
 
-// phi of the predictive draw, formed as the posterior-predictive table forms it
-PPCX_HD double loo_predict_phi(double sigma_raw, double truncation_compensation) {
-  PPCX_NO_CONTRACT
-  return exp(-sigma_raw) * truncation_compensation;
-}
 // first index j in the ascending K[0 .. M] with K[j] >= k (k is one of them)
 PPCX_HD int loo_predict_lower_bound(const uint64_t* K, int M, uint64_t k) {
   int lo = 0, hi = M;
@@ -76,20 +71,6 @@ PPCX_HD double loo_predict_interp(double vm, double vs, double Fm, double Fs, do
   PPCX_NO_CONTRACT
   return vm + (vs - vm) * (p - Fm) / (Fs - Fm);
 }
-// type-7 quantile of n values in the form of the posterior-predictive kernels: h = (n - 1) p rounded on its own, lo = floor(h)
-// clamped to 0 .. n - 1; from the order statistics v0 (rank lo) and v1 (rank lo + 1) with one fma
-PPCX_HD void loo_predict_type7_rank(long n, double p, double* h_out, long* lo_out) {
-  PPCX_NO_CONTRACT
-  const double h = (double)(n - 1) * p;
-  long lo = (long)floor(h);
-  if (lo > n - 1) lo = n - 1;
-  if (lo < 0) lo = 0;
-  *h_out = h; *lo_out = lo;
-}
-PPCX_HD double loo_predict_type7(double h, long lo, long n, double v0, double v1) {
-  PPCX_NO_CONTRACT
-  return lo >= n - 1 ? v0 : fma(h - (double)lo, v1 - v0, v0);
-}
 
 }  // namespace ppcx
 
@@ -104,7 +85,7 @@ inline void loo_predict_cell_host(const double* ll, const int32_t* x, long n, in
   const double pr[2] = {p_lo, p_hi};
   for (long i = 0; i < n; ++i) {
     const double r = -ll[i];
-    if (isnan(r) || (!excluded && r == INFINITY) || x[i] == kLooPredictInvalid) { all_nan(); return; }
+    if (isnan(r) || (!excluded && r == INFINITY) || x[i] == kPpcInvalid) { all_nan(); return; }
   }
   if (excluded) {
     double sum = 0.0; long lt = 0, le = 0;
@@ -114,8 +95,8 @@ inline void loo_predict_cell_host(const double* ll, const int32_t* x, long n, in
     out[0] = sum / (double)n;
     for (int k = 0; k < 2; ++k) {
       double h; long lo;
-      loo_predict_type7_rank(n, pr[k], &h, &lo);
-      out[1 + k] = loo_predict_type7(h, lo, n, (double)xs[lo], (double)xs[lo + 1 < n ? lo + 1 : lo]);
+      type7_rank(n, pr[k], &h, &lo);
+      out[1 + k] = type7(h, lo, n, (double)xs[lo], (double)xs[lo + 1 < n ? lo + 1 : lo]);
     }
     out[3] = (double)lt / (double)n; out[4] = (double)le / (double)n; out[5] = NAN;
     return;

@@ -79,13 +79,15 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_predict_kernel(LooPred
   // ---- the predictive count of every draw
   bool inval = false;
   if (COLS) {
-    for (long i = tid; i < n; i += kBlockThreads) { const int v = p.xcols[(long)cell * n + i]; XI[i] = v; inval = inval || v == kLooPredictInvalid; }
+    for (long i = tid; i < n; i += kBlockThreads) { const int v = p.xcols[(long)cell * n + i]; XI[i] = v; inval = inval || v == kPpcInvalid; }
   } else {
     const double* Tg = a.T + (long)gi * (a.C + 1) * n;
-    const uint32_t addr = (uint32_t)(p.genes[gi] * a.S + s);
+    const uint32_t addr = ppc_cell_address(p.genes[gi], a.S, s);
     for (long i = tid; i < n; i += kBlockThreads) {
-      const int v = nb2_log_rng(loo_cell_eta(a, Tg, s, i), loo_predict_phi(Tg[(long)a.C * n + i], p.tc), p.k0, addr, (uint32_t)i);
-      XI[i] = v; inval = inval || v == kLooPredictInvalid;
+      double sigma_raw;
+      const double eta = loo_cell_eta(a, Tg, s, i, &sigma_raw);
+      const int v = nb2_log_rng(eta, ppc_phi(sigma_raw, p.tc), p.k0, addr, (uint32_t)i);
+      XI[i] = v; inval = inval || v == kPpcInvalid;
     }
   }
   if (block_any(inval) || (!excluded && N == 0)) { all_nan(); return; }   // block_any: XI is visible to every thread
@@ -96,14 +98,12 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_predict_kernel(LooPred
     const double sum = draws_sum(n, sh.red, [&](long i) { return (double)XI[i]; });
     const int vmax = (int)draws_max(n, sh.red, [&](long i) { return (double)XI[i]; });
     auto count_le = [&](int v) { return (long)draws_sum(n, sh.red, [&](long i) { return XI[i] <= v ? 1.0 : 0.0; }); };
+    auto min_above = [&](int v) { return (int)-draws_max(n, sh.red, [&](long i) { return XI[i] > v ? -(double)XI[i] : -INFINITY; }); };
     for (int k = 0; k < 2; ++k) {
-      double h; long r;
-      loo_predict_type7_rank(n, pr[k], &h, &r);
-      int lo = 0, hi = vmax;                              // order statistic r: the smallest v with #{x <= v} >= r + 1
-      while (lo < hi) { const int mid = lo + ((hi - lo) >> 1); if (count_le(mid) >= r + 1) hi = mid; else lo = mid + 1; }
-      int nxt = lo;                                       // order statistic r + 1: lo again, or the smallest draw above it
-      if (r + 1 < n && count_le(lo) < r + 2) nxt = (int)-draws_max(n, sh.red, [&](long i) { return XI[i] > lo ? -(double)XI[i] : -INFINITY; });
-      q[k] = loo_predict_type7(h, r, n, (double)lo, (double)nxt);
+      double h; long r; int v0, v1;
+      type7_rank(n, pr[k], &h, &r);
+      select_pair(n, r, vmax, count_le, min_above, &v0, &v1);
+      q[k] = type7(h, r, n, (double)v0, (double)v1);
     }
     const double lt = draws_sum(n, sh.red, [&](long i) { return XI[i] < y ? 1.0 : 0.0; });
     const double le = draws_sum(n, sh.red, [&](long i) { return XI[i] <= y ? 1.0 : 0.0; });
