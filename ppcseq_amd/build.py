@@ -4,6 +4,7 @@ from __future__ import annotations
 import os
 import subprocess
 import sys
+import threading
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
@@ -11,9 +12,11 @@ LIB = os.path.join(HERE, "libppcx.so")
 # the testing build (-DPPCX_TESTING: fault injection, forced cell paths, kernel-level timing; csrc/ppcx_testing.h) lives
 # with the tests, not in the package
 TESTING_LIB = os.path.join(os.path.dirname(HERE), "tests", "libppcx_testing.so")
-SOURCES = ["ppcx_kernels.hip", "ppcx_summary.hip", "ppcx_psis.hip", "ppcx_loo.hip", "ppcx_loo_predict.hip", "ppcx_reff.hip", "ppcx_ppc_exact.hip", "ppcx_ppc.hip", "ppcx_capi.hip"]
+# ppcx_kernels.hip first: it takes minutes, the others seconds, and the compilers start in this order
+SOURCES = ["ppcx_kernels.hip", "ppcx_summary.hip", "ppcx_psis.hip", "ppcx_loo.hip", "ppcx_loo_predict.hip", "ppcx_reff.hip", "ppcx_ppc_exact.hip", "ppcx_ppc.hip",
+           "ppcx_capi.hip", "ppcx_run.hip", "ppcx_fit_nuts.hip", "ppcx_fit_advi.hip", "ppcx_fit_api.hip"]
 TESTING_SOURCES = ["ppcx_testing_math.hip"]      # the device's building blocks one by one (csrc/ppcx_testing.h): testing build only
-HEADERS = ["ppcx_math.h", "ppcx_disp.h", "ppcx_model.h", "ppcx_nuts.h", "ppcx_gene.h", "ppcx_kernels.h", "ppcx_summary.h", "ppcx_summary_dev.h", "ppcx_psis.h", "ppcx_psis_dev.h", "ppcx_loo.h", "ppcx_loo_ap.h", "ppcx_loo_dev.h", "ppcx_loo_predict.h", "ppcx_reff.h", "ppcx_nbcdf.h", "ppcx_ppc_exact.h", "ppcx_ppc.h", "ppcx_table.h", "ppcx_block.h", "ppcx_columns.h", "ppcx_testing.h",
+HEADERS = ["ppcx_math.h", "ppcx_disp.h", "ppcx_model.h", "ppcx_nuts.h", "ppcx_gene.h", "ppcx_kernels.h", "ppcx_summary.h", "ppcx_summary_dev.h", "ppcx_psis.h", "ppcx_psis_dev.h", "ppcx_loo.h", "ppcx_loo_ap.h", "ppcx_loo_dev.h", "ppcx_loo_predict.h", "ppcx_reff.h", "ppcx_nbcdf.h", "ppcx_ppc_exact.h", "ppcx_ppc.h", "ppcx_table.h", "ppcx_block.h", "ppcx_columns.h", "ppcx_host.h", "ppcx_testing.h",
            os.path.join("..", "..", "include", "ppcx.h")]
 
 
@@ -38,6 +41,17 @@ def _stale(lib: str, extra=()) -> bool:
     return any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in _sources(extra) + HEADERS)
 
 
+# at most 16 compilers at a time in this process, however many builds run side by side (build_all)
+_COMPILERS = threading.BoundedSemaphore(16)
+
+
+def _start_compiler(cmd):
+    _COMPILERS.acquire()                         # released when this compiler ends
+    p = subprocess.Popen(cmd)
+    threading.Thread(target=lambda: (p.wait(), _COMPILERS.release()), daemon=True).start()
+    return p
+
+
 def _compile(lib: str, extra, verbose: bool) -> None:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objs = []
@@ -49,7 +63,7 @@ def _compile(lib: str, extra, verbose: bool) -> None:
               ["-c", "-o", o, os.path.join(CSRC, s)]
         if verbose:
             print(" ".join(cmd), file=sys.stderr)
-        procs.append(subprocess.Popen(cmd))
+        procs.append(_start_compiler(cmd))
     for p in procs:
         if p.wait() != 0:
             raise subprocess.CalledProcessError(p.returncode, p.args)
@@ -71,8 +85,7 @@ def build_testing(force: bool = False, verbose: bool = False) -> str:
 
 
 def build_all(force: bool = False, verbose: bool = False):
-    """The product and the testing build side by side (four hipcc processes: the kernels' translation unit takes minutes)."""
-    import threading
+    """The product and the testing build side by side (the kernels' translation unit takes minutes)."""
     jobs = []
     if force or _stale(LIB):
         jobs.append((LIB, []))

@@ -1,7 +1,7 @@
 // ppcx_columns.h -- the host side that the fit diagnostics and the posterior-predictive driver share (ppcx_summary.hip,
 // ppcx_psis.hip, ppcx_loo.hip, ppcx_loo_predict.hip, ppcx_reff.hip, ppcx_ppc_exact.hip, ppcx_ppc.hip and their entry points in
-// ppcx_capi.hip): an owning device buffer -- also what a fit holds its draws and diagnostics in, and the scratch of a
-// call (ppcx_capi.hip) --, the column-batch driver and the launch of a kernel with dynamic LDS.
+// ppcx_fit_api.hip): the owners -- a device buffer, a pinned host buffer, a stream: what a model, a fit, a run and the scratch
+// of a call hold their resources in (ppcx_host.h) --, the column-batch driver and the launch of a kernel with dynamic LDS.
 // Every driver built from these synchronises its stream before a buffer goes out of scope (finish() below), also after a
 // failed launch: nothing is freed under a running kernel.
 #pragma once
@@ -29,6 +29,28 @@ struct DeviceBuffer {
     return e == hipSuccess ? hipMemcpyAsync(p, host, sizeof(T) * n, hipMemcpyHostToDevice, st) : e;
   }
   hipError_t download(T* host, size_t n, hipStream_t st) const { return hipMemcpyAsync(host, p, sizeof(T) * n, hipMemcpyDeviceToHost, st); }
+};
+
+// n elements of T in pinned host memory, freed with the object
+template <class T>
+struct PinnedBuffer {
+  T* p = nullptr;
+  PinnedBuffer() = default;
+  PinnedBuffer(const PinnedBuffer&) = delete;
+  PinnedBuffer& operator=(const PinnedBuffer&) = delete;
+  ~PinnedBuffer() { if (p) (void)hipHostFree(p); }
+  hipError_t alloc(size_t n) { return hipHostMalloc(&p, sizeof(T) * n); }
+};
+
+// a non-blocking stream of the current device, destroyed with the object. An owner declares it before the buffers that
+// work on it: members go in reverse order, the stream after them.
+struct DeviceStream {
+  hipStream_t s = nullptr;
+  DeviceStream() = default;
+  DeviceStream(const DeviceStream&) = delete;
+  DeviceStream& operator=(const DeviceStream&) = delete;
+  ~DeviceStream() { if (s) (void)hipStreamDestroy(s); }
+  hipError_t create() { return hipStreamCreateWithFlags(&s, hipStreamNonBlocking); }
 };
 
 // the end of every driver: the stream drained whatever happened before, the first error kept

@@ -230,7 +230,7 @@ struct LooArgs {
 int loo_sel_pad(long n, double r_eff_min);     // power of two >= M + 1 for n draws at the smallest r_eff
 hipError_t launch_loo_table_kernel(const double* draws, long n_draws, const Dims& d, const int* genes, int n_genes, double* T,
                                    hipStream_t st);    // T[g][c][draw] of the genes (device ids), ppcx_loo.hip
-// These cells of this fit: what every per-cell driver below receives (ppcx_capi.hip loo_prepare fills it). The cells are those
+// These cells of this fit: what every per-cell driver below receives (ppcx_fit_api.hip loo_prepare fills it). The cells are those
 // of genes[0 .. n_genes), S each, gene-major.
 struct FitCells {
   const double* draws = nullptr;   // [n][D] (device)

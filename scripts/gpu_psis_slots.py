@@ -1,4 +1,4 @@
-"""Draws evaluated per launch for log_p of the Pareto-k diagnostic (ppcx_capi.hip kPsisSlots), measured on the MI355X: a
+"""Draws evaluated per launch for log_p of the Pareto-k diagnostic (ppcx_fit_advi.hip kPsisSlots), measured on the MI355X: a
 BASELINE cfg3 model (D = 41 006), the reference's ADVI call (1 000 output draws), and the first Fit.log_ratios() of a fresh fit
 of the same seed per slot count, through the testing build's "psis_slots" hook; the slot counts in two passes of opposite
 order. A record, not a gate. Writes the JSON line to stdout and to the path given as the first argument, if any."""

@@ -76,7 +76,7 @@ def test_product_does_not_import_oracle():
 
 def test_guard_decision_of_the_gene_shard_ranks():
     """What the ranks of a gene-sharded run conclude at a poll from the max-reduced vector [rounds, -rounds, done, -done,
-    -(error)] (ppcx_capi.hip comm_guard): agreement, a peer's error, their own error, disagreement on rounds or chains."""
+    -(error)] (ppcx_run.hip comm_guard): agreement, a peer's error, their own error, disagreement on rounds or chains."""
     import numpy as np
     from ppcseq_amd import build
     lib = ctypes.CDLL(build.build())
