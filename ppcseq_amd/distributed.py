@@ -97,37 +97,24 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *, device=0, coll_
     `launch` = (lanes_per_gene, workgroups) pins the log-likelihood launch (0 = automatic) (bit-identical results across rank counts need
     the same geometry: the automatic choice depends on the chains per launch)."""
     import math
-    from . import _lib
-    from .inference import _to_cell_ids, checked_columns, find_optimal_number_of_chains, pooled_summary
+    from .inference import _to_cell_ids, checked_columns, fit_chain_block, pass_plan, pooled_summary
     dist = _dist()
     rank, world = dist.get_rank(), dist.get_world_size()
     counts = np.asarray(counts)
     G, S = counts.shape
     K = int(how_many_to_check)
     X = np.asarray(X, dtype=np.float64).reshape(S, -1)
-    practical = 1000 if approximate_posterior_analysis else how_many_posterior_draws
-    if chains is None:
-        chains = max(3, min(int(cores) if cores else world, find_optimal_number_of_chains(practical)))
-    n_iter = int(math.ceil(practical / chains)) + 150
+    chains, n_iter, warmup = pass_plan(how_many_posterior_draws, approximate_posterior_analysis, chains, cores or world)
     per = int(math.ceil(chains / world))
     n_local = max(0, min(per, chains - rank * per))
     cols = checked_columns(G, X.shape[1], K)
-    n_keep = n_iter - 150
-    local = np.zeros((per, n_keep, cols.size))
+    local = np.zeros((per, n_iter - warmup, cols.size))
     err = None
     if n_local > 0:
         try:
-            m = _lib.Model(counts, X, exposure_rate, K, lambda_mu_mu=lambda_mu_mu, excl=_to_cell_ids(to_exclude, S), device=device)
-            try:
-                if launch is not None:
-                    m.set_launch(*launch)
-                f = m.fit_nuts(chains=n_local, iter=n_iter, warmup=150, seed=seed, chain_id_offset=rank * per)
-                try:
-                    local[:n_local] = f.columns(cols)
-                finally:
-                    f.close()
-            finally:
-                m.close()
+            local[:n_local] = fit_chain_block(counts, X, exposure_rate, K, cols, device=device, chains=n_local, n_iter=n_iter,
+                                              warmup=warmup, seed=seed, chain_id_offset=rank * per, lambda_mu_mu=lambda_mu_mu,
+                                              excl=_to_cell_ids(to_exclude, S), launch=launch)
         except Exception as e:                     # out of memory, no finite initial point, a limit of this build ...
             err = e
     raise_if_any_rank_failed(err, device=coll_device, what="chains over ranks")      # before anybody waits in the gather
@@ -165,10 +152,9 @@ def do_inference_shards(counts, X, exposure_rate, how_many_to_check, *, device=0
     host threads, never yet between GPUs (no multi-GPU box was available to any round): if its set-up fails on ANY rank -- the
     allocation of uncached memory, an IPC handle that a peer cannot open, peer access -- ALL ranks fall back to the RCCL path
     together, with a warning; a failure of that path is raised on every rank."""
-    import math
     import warnings
     from . import _lib
-    from .inference import _to_cell_ids, find_optimal_number_of_chains, pooled_summary
+    from .inference import _to_cell_ids, checked_columns, pass_plan, pooled_summary
     if exchange not in ("direct", "rccl"):
         raise ValueError("exchange must be 'direct' or 'rccl'")
     dist = _dist()
@@ -179,11 +165,8 @@ def do_inference_shards(counts, X, exposure_rate, how_many_to_check, *, device=0
     X = np.asarray(X, dtype=np.float64).reshape(S, -1)
     C = X.shape[1]
     n2 = max(C - 2, 0)
-    practical = 1000 if approximate_posterior_analysis else how_many_posterior_draws
-    if chains is None:
-        chains = max(3, min(int(cores) if cores else 8, find_optimal_number_of_chains(practical)))
-    n_iter = int(math.ceil(practical / chains)) + 150
-    n_keep = n_iter - 150
+    chains, n_iter, warmup = pass_plan(how_many_posterior_draws, approximate_posterior_analysis, chains, cores or 8)
+    n_keep = n_iter - warmup
     # genes are dealt to the ranks round-robin, as the reference deals them to its shards (R/utilities.R:125-136): every rank gets
     # its share of the K checked genes -- which come first -- and with them of the slope coordinates and the dearer passes
     mine = np.arange(rank, G, world)
@@ -240,17 +223,13 @@ def do_inference_shards(counts, X, exposure_rate, how_many_to_check, *, device=0
         if launch is not None:
             m.set_launch(*launch)
         if comm is not None:
-            f = m.fit_nuts_comm(comm, chains=chains, iter=n_iter, warmup=150, seed=seed)
+            f = m.fit_nuts_comm(comm, chains=chains, iter=n_iter, warmup=warmup, seed=seed)
         else:
-            f = m.fit_nuts_xchg(xg, chains=chains, iter=n_iter, warmup=150, seed=seed)
+            f = m.fit_nuts_xchg(xg, chains=chains, iter=n_iter, warmup=warmup, seed=seed)
         try:
             diag = f.diagnostics()
             Gl, Kl = len(mine), m.K                 # this shard's genes and checked genes (local unconstrained vector, Stan order)
-            a1, a2 = 3 + Gl, 3 + Gl + Kl
-            sr = a2 + n2 * Kl
-            cols = np.concatenate([np.arange(3), 3 + np.arange(Kl), a1 + np.arange(Kl), a2 + np.arange(n2 * Kl),
-                                   sr + np.arange(Kl), sr + Gl + np.arange(3)]).astype(np.int32)
-            part = (Kl, f.columns(cols))
+            part = (Kl, f.columns(checked_columns(Gl, C, Kl)))
         finally:
             f.close()
     except Exception as e:                          # noqa: BLE001

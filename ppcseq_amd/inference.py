@@ -10,6 +10,7 @@ logical G x S matrix. There is no CPU fallback.
 from __future__ import annotations
 
 import math
+import warnings
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -199,16 +200,129 @@ def pareto_k_table(loo):
     return dict(threshold=thr, bins=bins)
 
 
-def _warn_loo(loo, n_draws):
-    import warnings
-    for msg in loo_warnings(loo["khat"], n_draws):
-        warnings.warn(msg, RuntimeWarning, stacklevel=3)
+WARMUP = 150                   # R/utilities.R:1503
 
 
-def _warn_convergence(summary, chains):
-    import warnings
-    for msg in convergence_warnings(summary, chains):
-        warnings.warn(msg, RuntimeWarning, stacklevel=3)
+def pass_plan(how_many_posterior_draws, approximate_posterior_analysis, chains, cores):
+    """(chains, n_iter, warmup) of one pass (R/utilities.R:1372-1386, :1502-1503): the chains as given, or what `cores` and the
+    draws the fit has to keep allow."""
+    draws_practical = 1000 if approximate_posterior_analysis else how_many_posterior_draws
+    if chains is None:
+        chains = max(3, min(int(cores), find_optimal_number_of_chains(draws_practical)))
+    return chains, int(math.ceil(draws_practical / chains)) + WARMUP, WARMUP
+
+
+# ---- the optional diagnostics of a pass: each stated once, here; do_inference's docstring says what they report
+
+@dataclass
+class CheckContext:
+    """What the readers of the diagnostics need beside the fit."""
+    K: int
+    p: float                     # the pass's interval probabilities are p and 1 - p
+    seed: int
+    truncation_compensation: float
+    loo_r_eff: object = None     # the modifiers of loo / loo_intervals
+    loo_mcse: bool = False
+    pooled: bool = False         # a fit over the pooled draws of several fits' chains (pooled_summary): it holds no lp__
+
+
+@dataclass(frozen=True)
+class Check:
+    keyword: str                 # the option of do_inference / identify_outliers
+    field: str                   # the InferenceResult field it fills; attrs["<field>_discovery"], ["<field>_test"] of the frame
+    order: int                   # its place in the order of refusals (the order in which the options were added)
+    kind: str | None             # the pass it needs: "nuts", "advi" or None (either)
+    pooled: bool                 # available over pooled chains (devices=[...])
+    ranks: bool                  # available to passes over several ranks (identify_outliers' _pass)
+    refusal: str | None          # what the other kind of pass is told
+    read: object                 # read(fit, ctx) -> dict
+    warn: object = None          # warn(result, fit) -> messages
+    cells: bool = True           # it reads the checked genes' cells: the pooled model then carries their exclusions, and
+                                 # without a checked gene the pooled fit is not read (the field stays None)
+
+
+def _alpha_sub_1(fit, K):
+    return 3 + fit.model.G + np.arange(K)
+
+
+def _interval(ctx):
+    return dict(p_lo=ctx.p, p_hi=1 - ctx.p, truncation_compensation=ctx.truncation_compensation)
+
+
+def _loo_warnings(result, fit):
+    return loo_warnings(result["khat"], fit.chains * fit.n_keep)
+
+
+CHECKS = (          # in the order of the reads
+    Check("check_approximation", "approximation", 2, "advi", False, False,
+          "check_approximation needs an ADVI pass (approximate_posterior_inference = True): the Pareto k diagnostic judges the "
+          "variational approximation",
+          lambda fit, ctx: fit.psis(_alpha_sub_1(fit, ctx.K), overall=True),
+          lambda result, fit: approximation_warnings(result["khat"][-1]), cells=False),
+    Check("check_approximation_loo", "approximation_loo", 5, "advi", False, False,
+          "check_approximation_loo needs an ADVI pass (approximate_posterior_inference = True): it corrects PSIS-LOO for the "
+          "variational approximation; PSIS-LOO of a NUTS pass is check_loo",
+          lambda fit, ctx: fit.loo_approximate_posterior(np.arange(ctx.K)), _loo_warnings),
+    Check("check_approximation_loo_intervals", "approximation_loo_intervals", 6, "advi", False, False,
+          "check_approximation_loo_intervals needs an ADVI pass (approximate_posterior_inference = True): the leave-one-out "
+          "intervals of a NUTS pass are check_loo_intervals",
+          lambda fit, ctx: fit.loo_predict_approximate_posterior(np.arange(ctx.K), seed=ctx.seed, **_interval(ctx))),
+    Check("check_convergence", "convergence", 1, "nuts", True, False,
+          "check_convergence needs a NUTS pass: the draws of an ADVI fit are independent (rstan::vb reports no R-hat or ESS)",
+          lambda fit, ctx: fit.summary(_alpha_sub_1(fit, ctx.K), lp=not ctx.pooled),
+          lambda result, fit: convergence_warnings(result, fit.chains), cells=False),
+    Check("check_loo", "loo", 3, "nuts", True, False,
+          "check_loo needs a NUTS pass: PSIS-LOO of an ADVI fit (loo_approximate_posterior) is check_approximation_loo",
+          lambda fit, ctx: fit.loo(np.arange(ctx.K), r_eff=ctx.loo_r_eff, mcse=bool(ctx.loo_mcse)), _loo_warnings),
+    Check("check_loo_intervals", "loo_intervals", 4, "nuts", True, False,
+          "check_loo_intervals needs a NUTS pass: the leave-one-out intervals of an ADVI fit (loo_approximate_posterior) are "
+          "check_approximation_loo_intervals",
+          lambda fit, ctx: fit.loo_predict(np.arange(ctx.K), r_eff=ctx.loo_r_eff, seed=ctx.seed, **_interval(ctx))),
+    Check("exact_intervals", "exact_intervals", 7, None, True, False, None,
+          lambda fit, ctx: fit.ppc_exact(np.arange(ctx.K), **_interval(ctx))),
+)
+
+MODIFIERS = (       # (option, the options of which it needs one, what it is told without one)
+    ("loo_r_eff", ("check_loo", "check_loo_intervals"),
+     "loo_r_eff needs check_loo or check_loo_intervals: it is the r_eff of their PSIS"),
+    ("loo_mcse", ("check_loo",),
+     "loo_mcse needs check_loo: it adds the Monte-Carlo standard error and n_eff to its PSIS-LOO"),
+)
+
+CHECK_OPTIONS = tuple(c.keyword for c in CHECKS) + tuple(m[0] for m in MODIFIERS)
+
+
+def select_checks(options, approximate_posterior_inference, over_ranks=False):
+    """Refuses what a pass of this kind cannot report (ValueError, the option's name first) and returns the options that are
+    set, {keyword: value}: what travels from identify_outliers to the pass and on to read_checks. `options` maps every keyword
+    of CHECK_OPTIONS to its value (the caller's locals() will do)."""
+    kind = "advi" if approximate_posterior_inference else "nuts"
+    for chk in sorted(CHECKS, key=lambda c: c.order):
+        if options[chk.keyword]:
+            if chk.kind not in (None, kind):
+                raise ValueError(chk.refusal)
+            if over_ranks and not chk.ranks:
+                raise ValueError(f"{chk.keyword} is not available for passes over several ranks")
+    r_eff = options["loo_r_eff"]
+    if r_eff is not None and not (isinstance(r_eff, str) and r_eff == "auto"):
+        raise ValueError(f'loo_r_eff must be None or "auto", not {r_eff!r}')
+    for keyword, needs, refusal in MODIFIERS:
+        if options[keyword] and not any(options[k] for k in needs):
+            raise ValueError(refusal)
+    return {k: options[k] for k in CHECK_OPTIONS if options[k]}
+
+
+def read_checks(fit, ctx, selected, res):
+    """Runs the selected diagnostics' readers on `fit` in the order of CHECKS, fills their fields of `res` and returns their
+    warning messages."""
+    msgs = []
+    for chk in CHECKS:
+        if selected.get(chk.keyword) and not (chk.cells and ctx.pooled and ctx.K == 0):
+            result = chk.read(fit, ctx)
+            setattr(res, chk.field, result)
+            if chk.warn is not None:
+                msgs += chk.warn(result, fit)
+    return msgs
 
 
 def do_inference(counts, X, exposure_rate, how_many_to_check, *,
@@ -299,37 +413,16 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
     K = int(how_many_to_check)
     X = np.asarray(X, dtype=np.float64).reshape(S, -1)
 
-    # R/utilities.R:1372-1386
-    draws_practical = 1000 if approximate_posterior_analysis else how_many_posterior_draws
-    if chains is None:
-        chains = max(3, min(int(cores), find_optimal_number_of_chains(draws_practical)))
-    n_iter = int(math.ceil(draws_practical / chains)) + 150       # R/utilities.R:1502
-    warmup = 150                                                    # R/utilities.R:1503
-
+    chains, n_iter, warmup = pass_plan(how_many_posterior_draws, approximate_posterior_analysis, chains, cores)
     excl = _to_cell_ids(to_exclude, S)
-    if check_convergence and approximate_posterior_inference:
-        raise ValueError("check_convergence needs a NUTS pass: the draws of an ADVI fit are independent (rstan::vb reports no "
-                         "R-hat or ESS)")
-    if check_approximation and not approximate_posterior_inference:
-        raise ValueError("check_approximation needs an ADVI pass (approximate_posterior_inference = True): the Pareto k "
-                         "diagnostic judges the variational approximation")
-    if check_loo and approximate_posterior_inference:
-        raise ValueError("check_loo needs a NUTS pass: PSIS-LOO of an ADVI fit (loo_approximate_posterior) is "
-                         "check_approximation_loo")
-    if check_loo_intervals and approximate_posterior_inference:
-        raise ValueError("check_loo_intervals needs a NUTS pass: the leave-one-out intervals of an ADVI fit "
-                         "(loo_approximate_posterior) are check_approximation_loo_intervals")
-    _check_approximation_loo(approximate_posterior_inference, check_approximation_loo, check_approximation_loo_intervals)
-    _check_loo_r_eff(loo_r_eff, check_loo, check_loo_intervals)
-    _check_loo_mcse(loo_mcse, check_loo)
+    checks = select_checks(locals(), approximate_posterior_inference)
     if devices is not None and len(devices) > 1 and (save_generated_quantities or pass_fit or model is not None or approximate_posterior_inference):
         raise ValueError("devices=[...] splits the chains of a NUTS fit over several devices and pools their draws: it cannot "
                          "be combined with save_generated_quantities, pass_fit, a caller's model or approximate_posterior_inference")
     if devices is not None and len(devices) > 1 and not approximate_posterior_inference:
         return _do_inference_devices(counts, X, exposure_rate, K, list(devices), chains, n_iter, warmup, excl,
                                      lambda_mu_mu, approximate_posterior_analysis, adj_prob_theshold,
-                                     how_many_posterior_draws, truncation_compensation, seed, launch, check_convergence,
-                                     check_loo, check_loo_intervals, loo_r_eff, loo_mcse, exact_intervals)
+                                     how_many_posterior_draws, truncation_compensation, seed, launch, checks)
     if devices is not None and len(devices) >= 1 and model is None:
         device = devices[0]
     own_model = model is None
@@ -343,7 +436,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
         # vb_iterative(model, output_samples = draws_practical, iter = 50000, tol_rel_obj = 0.005)
         # (R/utilities.R:1487-1494; the reference passes no seed to vb -- here the run is seeded and reproducible)
         # vb_iterative retries a failed vb() call (R/utilities.R:246-278): here bounded, attempt k with seed + k
-        fit = model.fit_advi(output_samples=int(draws_practical), iter=50000, tol_rel_obj=0.005, seed=seed, max_attempts=5)
+        output_samples = 1000 if approximate_posterior_analysis else how_many_posterior_draws      # R/utilities.R:1372
+        fit = model.fit_advi(output_samples=int(output_samples), iter=50000, tol_rel_obj=0.005, seed=seed, max_attempts=5)
     else:
         fit = model.fit_nuts(chains=chains, iter=n_iter, warmup=warmup, seed=seed)
     try:
@@ -358,38 +452,16 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                           return_counts_rng=bool(save_generated_quantities))
             ci, rng = out if save_generated_quantities else (out, None)
         # slope = posterior mean of alpha_sub_1 (R/utilities.R:1531, :1250-1263)
-        off_alpha1 = 3 + G
-        slope = fit.columns(np.arange(off_alpha1, off_alpha1 + K)).reshape(-1, K).mean(axis=0) if K else np.zeros(0)
+        slope = fit.columns(_alpha_sub_1(fit, K)).reshape(-1, K).mean(axis=0) if K else np.zeros(0)
         res = _post_process(counts[:K], ci, slope, X)
         res.total_draws = S * K * int(how_many_posterior_draws)   # R/utilities.R:1544
         res.chains, res.iter = chains, n_iter
         res.diagnostics = fit.advi_info() if approximate_posterior_inference else fit.diagnostics()
-        if approximate_posterior_inference and check_approximation:
-            import warnings
-            res.approximation = fit.psis(np.arange(off_alpha1, off_alpha1 + K), overall=True)
-            for msg in approximation_warnings(res.approximation["khat"][-1]):
-                warnings.warn(msg, RuntimeWarning, stacklevel=2)
-        if check_approximation_loo:
-            res.approximation_loo = fit.loo_approximate_posterior(np.arange(K))
-            _warn_loo(res.approximation_loo, fit.chains * fit.n_keep)
-        if check_approximation_loo_intervals:
-            res.approximation_loo_intervals = fit.loo_predict_approximate_posterior(
-                np.arange(K), p_lo=p, p_hi=1 - p, seed=seed, truncation_compensation=truncation_compensation)
-        if not approximate_posterior_inference:
-            import warnings
-            for msg in hmc_warnings(res.diagnostics, warmup):
-                warnings.warn(msg, RuntimeWarning, stacklevel=2)
-            if check_convergence:
-                res.convergence = fit.summary(np.arange(off_alpha1, off_alpha1 + K), lp=True)
-                _warn_convergence(res.convergence, chains)
-            if check_loo:
-                res.loo = fit.loo(np.arange(K), r_eff=loo_r_eff, mcse=bool(loo_mcse))
-                _warn_loo(res.loo, fit.chains * fit.n_keep)
-            if check_loo_intervals:
-                res.loo_intervals = fit.loo_predict(np.arange(K), r_eff=loo_r_eff, p_lo=p, p_hi=1 - p, seed=seed,
-                                                    truncation_compensation=truncation_compensation)
-        if exact_intervals:
-            res.exact_intervals = fit.ppc_exact(np.arange(K), p_lo=p, p_hi=1 - p, truncation_compensation=truncation_compensation)
+        msgs = [] if approximate_posterior_inference else hmc_warnings(res.diagnostics, warmup)
+        msgs += read_checks(fit, CheckContext(K, p, seed, truncation_compensation, checks.get("loo_r_eff"),
+                                              checks.get("loo_mcse", False)), checks, res)
+        for msg in msgs:
+            warnings.warn(msg, RuntimeWarning, stacklevel=2)
         res.counts_rng = rng
         if pass_fit:
             res.fit = fit
@@ -399,31 +471,6 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
             if own_model:
                 model.close()
     return res
-
-
-def _check_loo_r_eff(loo_r_eff, check_loo, check_loo_intervals):
-    if loo_r_eff is None:
-        return
-    if not (isinstance(loo_r_eff, str) and loo_r_eff == "auto"):
-        raise ValueError(f'loo_r_eff must be None or "auto", not {loo_r_eff!r}')
-    if not (check_loo or check_loo_intervals):
-        raise ValueError("loo_r_eff needs check_loo or check_loo_intervals: it is the r_eff of their PSIS")
-
-
-def _check_approximation_loo(approximate_posterior_inference, check_approximation_loo, check_approximation_loo_intervals):
-    if approximate_posterior_inference:
-        return
-    if check_approximation_loo:
-        raise ValueError("check_approximation_loo needs an ADVI pass (approximate_posterior_inference = True): it corrects "
-                         "PSIS-LOO for the variational approximation; PSIS-LOO of a NUTS pass is check_loo")
-    if check_approximation_loo_intervals:
-        raise ValueError("check_approximation_loo_intervals needs an ADVI pass (approximate_posterior_inference = True): the "
-                         "leave-one-out intervals of a NUTS pass are check_loo_intervals")
-
-
-def _check_loo_mcse(loo_mcse, check_loo):
-    if loo_mcse and not check_loo:
-        raise ValueError("loo_mcse needs check_loo: it adds the Monte-Carlo standard error and n_eff to its PSIS-LOO")
 
 
 def _to_cell_ids(to_exclude, S):
@@ -466,23 +513,22 @@ def checked_columns(G, C, K):
 
 
 def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, approximate_posterior_analysis,
-                   adj_prob_theshold, how_many_posterior_draws, truncation_compensation, seed, device=0, convergence=False,
-                   loo=False, excl=None, loo_intervals=False, loo_r_eff=None, loo_mcse=False, exact_intervals=False):
+                   adj_prob_theshold, how_many_posterior_draws, truncation_compensation, seed, device=0, excl=None, checks=None):
     """Credible intervals, slopes and flags from the pooled draws of all chains (rstan::summary over merged chains,
     R/utilities.R:685-703): `draws_checked` is [chains, n_keep, len(checked_columns)] in global chain order. The
     posterior-predictive kernel runs on a model that holds the K checked genes only -- cell ids g*S+s and draw indices are
-    those of the full model, so the result is what a single fit of all the chains gives, bit for bit. convergence: also the
-    summary of alpha_sub_1 over the pooled chains (res.convergence; Fit.summary). loo: also PSIS-LOO of the checked cells over
-    the pooled chains (res.loo; Fit.loo); the small model then carries the checked genes' cells of `excl` (0-based cell ids of
-    the full model), so that the cells excluded from the fit are held out. loo_intervals: also their leave-one-out predictive
-    intervals (res.loo_intervals; Fit.loo_predict), likewise. loo_r_eff: their r_eff (None or "auto", do_inference). loo_mcse:
-    res.loo with mcse_elpd_loo and n_eff (Fit.loo(mcse=True)). exact_intervals: also the exact posterior-predictive tails and
-    intervals of the checked cells over the pooled chains (res.exact_intervals; Fit.ppc_exact), with the checked genes' cells of
-    `excl` reported as excluded."""
+    those of the full model, so the result is what a single fit of all the chains gives, bit for bit. `checks`: the diagnostics
+    to read over the pooled chains as well, as select_checks returns them (do_inference says what each reports; their warnings
+    are raised here, on the caller). For those that read the checked genes' cells the small model carries those cells of `excl`
+    (0-based cell ids of the full model), so that the cells excluded from the fit are held out or reported as excluded."""
     counts = np.asarray(counts)
     X = np.asarray(X, dtype=np.float64).reshape(counts.shape[1], -1)
+    checks = checks or {}
+    for chk in CHECKS:
+        if checks.get(chk.keyword) and not chk.pooled:
+            raise ValueError(f"{chk.keyword} is not available over pooled chains")
     small_excl = None
-    if (loo or loo_intervals or exact_intervals) and excl is not None:
+    if excl is not None and any(chk.cells for chk in CHECKS if checks.get(chk.keyword)):
         e = np.asarray(excl, dtype=np.int64).ravel()
         small_excl = e[e < K * counts.shape[1]].astype(np.int32)
     small = _lib.Model(counts[:K], X, exposure_rate, K, lambda_mu_mu=lambda_mu_mu, device=device, excl=small_excl)
@@ -494,40 +540,47 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
                 ci = fit.ppc(truncation_compensation, p, 1 - p, seed=seed, n_gen=int(how_many_posterior_draws), resample=True)
             else:
                 ci = fit.ppc(truncation_compensation, p, 1 - p, seed=seed, n_gen=0, resample=False)
-            slope = fit.columns(np.arange(3 + K, 3 + 2 * K)).reshape(-1, K).mean(axis=0) if K else np.zeros(0)
-            conv = fit.summary(np.arange(3 + K, 3 + 2 * K), lp=False) if convergence else None
-            loo_res = fit.loo(np.arange(K), r_eff=loo_r_eff, mcse=bool(loo_mcse)) if loo and K else None
-            loo_int = None
-            if loo_intervals and K:
-                loo_int = fit.loo_predict(np.arange(K), r_eff=loo_r_eff, p_lo=p, p_hi=1 - p, seed=seed,
-                                          truncation_compensation=truncation_compensation)
-            exact = None
-            if exact_intervals and K:
-                exact = fit.ppc_exact(np.arange(K), p_lo=p, p_hi=1 - p, truncation_compensation=truncation_compensation)
+            slope = fit.columns(_alpha_sub_1(fit, K)).reshape(-1, K).mean(axis=0) if K else np.zeros(0)
+            res = _post_process(counts[:K], ci, slope, X)
+            res.total_draws = counts.shape[1] * K * int(how_many_posterior_draws)
+            msgs = read_checks(fit, CheckContext(K, p, seed, truncation_compensation, checks.get("loo_r_eff"),
+                                                 checks.get("loo_mcse", False), pooled=True), checks, res)
         finally:
             fit.close()
     finally:
         small.close()
-    res = _post_process(counts[:K], ci, slope, X)
-    res.total_draws = counts.shape[1] * K * int(how_many_posterior_draws)
-    res.convergence = conv
-    res.loo = loo_res
-    res.loo_intervals = loo_int
-    res.exact_intervals = exact
+    for msg in msgs:
+        warnings.warn(msg, RuntimeWarning, stacklevel=2)
     return res
+
+
+def fit_chain_block(counts, X, exposure_rate, K, cols, *, device, chains, n_iter, warmup, seed, chain_id_offset, lambda_mu_mu,
+                    excl, launch):
+    """One device's share of a pass whose chains are dealt out (to the devices of this process, or to the ranks of a job): fits
+    `chains` chains with the global ids chain_id_offset, ... on `device` and returns their columns `cols`,
+    [chains, n_keep, len(cols)]."""
+    m = _lib.Model(counts, X, exposure_rate, K, lambda_mu_mu=lambda_mu_mu, excl=excl, device=device)
+    try:
+        if launch is not None:
+            m.set_launch(*launch)
+        f = m.fit_nuts(chains=chains, iter=n_iter, warmup=warmup, seed=seed, chain_id_offset=chain_id_offset)
+        try:
+            return f.columns(cols)
+        finally:
+            f.close()
+    finally:
+        m.close()
 
 
 def _do_inference_devices(counts, X, exposure_rate, K, devices, chains, n_iter, warmup, excl, lambda_mu_mu,
                           approximate_posterior_analysis, adj_prob_theshold, how_many_posterior_draws,
-                          truncation_compensation, seed, launch=None, check_convergence=False, check_loo=False,
-                          check_loo_intervals=False, loo_r_eff=None, loo_mcse=False, exact_intervals=False):
+                          truncation_compensation, seed, launch, checks):
     """Chains split over several devices of this process (one host thread per device; the C ABI allows different handles
     on different threads), pooled summary on the first device."""
     import threading
-    G, S = counts.shape
     nd = min(len(devices), chains)
     per = int(math.ceil(chains / nd))
-    cols = checked_columns(G, X.shape[1], K)
+    cols = checked_columns(counts.shape[0], X.shape[1], K)
     parts, errs = [None] * nd, [None] * nd
 
     def work(r):
@@ -535,17 +588,9 @@ def _do_inference_devices(counts, X, exposure_rate, K, devices, chains, n_iter, 
         if n <= 0:
             return
         try:
-            m = _lib.Model(counts, X, exposure_rate, K, lambda_mu_mu=lambda_mu_mu, excl=excl, device=devices[r])
-            try:
-                if launch is not None:
-                    m.set_launch(*launch)
-                f = m.fit_nuts(chains=n, iter=n_iter, warmup=warmup, seed=seed, chain_id_offset=r * per)
-                try:
-                    parts[r] = f.columns(cols)
-                finally:
-                    f.close()
-            finally:
-                m.close()
+            parts[r] = fit_chain_block(counts, X, exposure_rate, K, cols, device=devices[r], chains=n, n_iter=n_iter,
+                                       warmup=warmup, seed=seed, chain_id_offset=r * per, lambda_mu_mu=lambda_mu_mu,
+                                       excl=excl, launch=launch)
         except Exception as e:          # re-raised on the calling thread
             errs[r] = e
 
@@ -561,12 +606,6 @@ def _do_inference_devices(counts, X, exposure_rate, K, devices, chains, n_iter, 
     res = pooled_summary(counts, X, exposure_rate, K, pooled, lambda_mu_mu=lambda_mu_mu,
                          approximate_posterior_analysis=approximate_posterior_analysis, adj_prob_theshold=adj_prob_theshold,
                          how_many_posterior_draws=how_many_posterior_draws, truncation_compensation=truncation_compensation,
-                         seed=seed, device=devices[0], convergence=check_convergence, loo=check_loo, excl=excl,
-                         loo_intervals=check_loo_intervals, loo_r_eff=loo_r_eff, loo_mcse=loo_mcse,
-                         exact_intervals=exact_intervals)
+                         seed=seed, device=devices[0], excl=excl, checks=checks)
     res.chains, res.iter = chains, n_iter
-    if check_convergence:
-        _warn_convergence(res.convergence, chains)
-    if check_loo and res.loo is not None:
-        _warn_loo(res.loo, pooled.shape[0] * pooled.shape[1])
     return res

@@ -15,7 +15,7 @@ import warnings
 
 import numpy as np
 
-from .inference import _check_approximation_loo, _check_loo_mcse, _check_loo_r_eff, do_inference
+from .inference import CHECKS, do_inference, select_checks
 
 
 def parse_formula(formula: str):
@@ -110,6 +110,14 @@ def required_device_memory(G, C, K, S, how_many_posterior_draws, cores, approxim
     return 8 * (chains * n_keep * D + chains * 67 * Dpad) + 4 * G * S
 
 
+def _report_checks(frame, checks, **passes):
+    """frame.attrs["<field>_<pass>"] of the selected diagnostics (inference.CHECKS), passes: discovery=, test= results"""
+    for chk in CHECKS:
+        if chk.keyword in checks:
+            for name, res in passes.items():
+                frame.attrs[f"{chk.field}_{name}"] = getattr(res, chk.field)
+
+
 def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcript", abundance="count",
                       significance="PValue", do_check="do_check", scaling_factor=None,
                       percent_false_positive_genes=1, how_many_negative_controls=500,
@@ -137,33 +145,16 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
     pooled chains. Not with save_generated_quantities / pass_fit (the draws then live on several devices). One process per GPU
     over torch.distributed: ppcseq_amd.distributed.identify_outliers. `launch` = (lanes_per_gene, workgroups) pins the
     log-likelihood launch of both passes (results are bit-identical across device counts only at equal lanes per gene).
-    `check_convergence` = True (NUTS only): both passes run rstan::sampling's R-hat / ESS checks (inference.do_inference); their
-    summaries go to out.attrs["convergence_discovery"] and ["convergence_test"], failures are RuntimeWarnings.
-    `check_approximation` = True (ADVI only): both passes compute the Pareto k diagnostic rstan::vb reports (inference.do_inference);
-    the k-hats go to out.attrs["approximation_discovery"] and ["approximation_test"], rstan's warnings are RuntimeWarnings.
-    `check_loo` = True (NUTS only): both passes compute PSIS-LOO of the checked cells, as rstan::loo(fit) would
-    (inference.do_inference; pass 2 holds its excluded cells out); the results (Fit.loo: [K, S] elpd_loo, p_loo, looic, khat and
-    loo's estimates) go to out.attrs["loo_discovery"] and ["loo_test"], loo's k-hat warning is a RuntimeWarning.
-    `check_loo_intervals` = True (NUTS only): both passes also keep the leave-one-out predictive interval and LOO-PIT of the
-    checked cells from their own fit (Fit.loo_predict: [K, S] mean, lower, upper, pit_lt, pit_le, khat, y, outside, excluded) at
-    the pass's interval probabilities, seed and truncation compensation, in out.attrs["loo_intervals_discovery"] and
-    ["loo_intervals_test"]. They are reported only: the cells flagged stay those of the reference's rule, no warning is raised.
-    `loo_r_eff` = "auto" (with check_loo or check_loo_intervals): their PSIS takes the relative efficiency of every checked cell
-    from the pass's own chains (Fit.relative_eff), as rstan::loo(fit) does, and the results carry it as `r_eff`; None: r_eff = 1.
-    `loo_mcse` = True (with check_loo): out.attrs["loo_discovery"] and ["loo_test"] also carry loo's pointwise `mcse_elpd_loo` and
-    `n_eff` of the checked cells and `mcse_elpd_loo_total` (Fit.loo(mcse=True); inference.pareto_k_table tabulates them).
-    `check_approximation_loo` = True (ADVI only): both passes compute PSIS-LOO of the checked cells with the correction for the
-    variational approximation, as loo::loo_approximate_posterior would (Fit.loo_approximate_posterior; pass 2 holds its
-    excluded cells out); the results go to out.attrs["approximation_loo_discovery"] and ["approximation_loo_test"], loo's k-hat
-    warning is a RuntimeWarning. `check_approximation_loo_intervals` = True (ADVI only): both passes also keep the leave-one-out
-    predictive interval and LOO-PIT of the checked cells under those weights (Fit.loo_predict_approximate_posterior) at the
-    pass's interval probabilities, seed and truncation compensation, in out.attrs["approximation_loo_intervals_discovery"] and
-    ["approximation_loo_intervals_test"]; reported only.
-    `exact_intervals` = True (NUTS and ADVI): both passes also keep the exact posterior-predictive tail probabilities and interval
-    of the checked cells (Fit.ppc_exact: [K, S] mean, sd, p_le, p_ge, lower, upper, y, excluded, outside -- the average over the
-    kept draws of negative-binomial cdfs, nothing sampled) at the pass's interval probabilities and truncation compensation, in
-    out.attrs["exact_intervals_discovery"] and ["exact_intervals_test"]; with `devices` over the pooled chains. They are reported,
-    not acted on: the flags and the frame are those of the same call without it.
+    The optional diagnostics of a pass (inference.do_inference says what each reports, which kind of pass it needs and what it
+    warns of) are run by both passes; the results go to out.attrs, the flags and the frame stay those of the call without them:
+    `check_convergence` (NUTS)                    -> attrs["convergence_discovery"], ["convergence_test"]
+    `check_approximation` (ADVI)                  -> attrs["approximation_discovery"], ["approximation_test"]
+    `check_loo` (NUTS)                            -> attrs["loo_discovery"], ["loo_test"] (pass 2 holds its excluded cells out)
+    `check_loo_intervals` (NUTS)                  -> attrs["loo_intervals_discovery"], ["loo_intervals_test"]
+    `loo_r_eff` = "auto", `loo_mcse` = True       -> modify check_loo / check_loo_intervals; in the same attrs
+    `check_approximation_loo` (ADVI)              -> attrs["approximation_loo_discovery"], ["approximation_loo_test"]
+    `check_approximation_loo_intervals` (ADVI)    -> attrs["approximation_loo_intervals_discovery"], [..."_test"]
+    `exact_intervals` (NUTS and ADVI)             -> attrs["exact_intervals_discovery"], ["exact_intervals_test"]
     """
     import os
     import pandas as pd
@@ -183,28 +174,7 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
         warnings.warn("ppcseq says: There are not transcripts with the category .to_check. NULL is returned.")
         return pd.DataFrame({transcript: [], "sample_wise_data": [], "ppc samples failed": [],
                              "tot deleterious_outliers": []})
-    if check_convergence and approximate_posterior_inference:
-        raise ValueError("check_convergence needs NUTS (approximate_posterior_inference = False): ADVI draws are independent")
-    if check_approximation and not approximate_posterior_inference:
-        raise ValueError("check_approximation needs ADVI (approximate_posterior_inference = True): it judges the variational "
-                         "approximation")
-    if check_loo and approximate_posterior_inference:
-        raise ValueError("check_loo needs NUTS (approximate_posterior_inference = False): PSIS-LOO of an ADVI fit is "
-                         "check_approximation_loo")
-    if check_loo and _pass is not None:
-        raise ValueError("check_loo is not available for passes over several ranks")
-    if check_loo_intervals and approximate_posterior_inference:
-        raise ValueError("check_loo_intervals needs NUTS (approximate_posterior_inference = False): the leave-one-out "
-                         "intervals of an ADVI fit are check_approximation_loo_intervals")
-    if check_loo_intervals and _pass is not None:
-        raise ValueError("check_loo_intervals is not available for passes over several ranks")
-    if exact_intervals and _pass is not None:
-        raise ValueError("exact_intervals is not available for passes over several ranks")
-    _check_loo_r_eff(loo_r_eff, check_loo, check_loo_intervals)
-    _check_loo_mcse(loo_mcse, check_loo)
-    _check_approximation_loo(approximate_posterior_inference, check_approximation_loo, check_approximation_loo_intervals)
-    if check_convergence and _pass is not None:
-        raise ValueError("check_convergence is not available for passes over several ranks")
+    checks = select_checks(locals(), approximate_posterior_inference, over_ranks=_pass is not None)
     if approximate_posterior_inference and save_generated_quantities:
         raise ValueError("Variational Bayes does not support tidybayes needed for save_generated_quantities, use sampling")
     pfp = percent_false_positive_genes
@@ -281,25 +251,7 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
     model = None if multi else _lib.Model(counts, X, exposure_rate, K, device=device)
     where = {} if _pass is not None else (dict(devices=list(devices)) if multi else dict(model=model))
     if _pass is None:
-        where.update(approximate_posterior_inference=approximate_posterior_inference, pass_fit=pass_fit, launch=launch)
-        if check_convergence:
-            where.update(check_convergence=True)
-        if check_approximation:
-            where.update(check_approximation=True)
-        if check_loo:
-            where.update(check_loo=True)
-        if check_loo_intervals:
-            where.update(check_loo_intervals=True)
-        if loo_r_eff is not None:
-            where.update(loo_r_eff=loo_r_eff)
-        if loo_mcse:
-            where.update(loo_mcse=True)
-        if check_approximation_loo:
-            where.update(check_approximation_loo=True)
-        if check_approximation_loo_intervals:
-            where.update(check_approximation_loo_intervals=True)
-        if exact_intervals:
-            where.update(exact_intervals=True)
+        where.update(approximate_posterior_inference=approximate_posterior_inference, pass_fit=pass_fit, launch=launch, **checks)
     try:
         # ---- pass 1: discovery (R/methods.R:268-286); always the full posterior analysis
         res1 = run_pass(counts, X, exposure_rate, K,
@@ -308,20 +260,7 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                             seed=seed, **where)
         if just_discovery:
             out1 = res1.to_frame()
-            if check_convergence:
-                out1.attrs["convergence_discovery"] = res1.convergence
-            if check_approximation:
-                out1.attrs["approximation_discovery"] = res1.approximation
-            if check_loo:
-                out1.attrs["loo_discovery"] = res1.loo
-            if check_loo_intervals:
-                out1.attrs["loo_intervals_discovery"] = res1.loo_intervals
-            if check_approximation_loo:
-                out1.attrs["approximation_loo_discovery"] = res1.approximation_loo
-            if check_approximation_loo_intervals:
-                out1.attrs["approximation_loo_intervals_discovery"] = res1.approximation_loo_intervals
-            if exact_intervals:
-                out1.attrs["exact_intervals_discovery"] = res1.exact_intervals
+            _report_checks(out1, checks, discovery=res1)
             return out1
         # ---- cells to exclude (R/methods.R:292-300)
         flag = res1.deleterious_outliers if (do_check_only_on_detrimental and res1.deleterious_outliers is not None) else ~res1.ppc
@@ -363,21 +302,7 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
     out.attrs.update(total_draws=res2.total_draws, transcript_column=transcript, abundance_column=abundance,
                      sample_column=sample, formula=formula, seed=seed,
                      diagnostics_discovery=res1.diagnostics, diagnostics_test=res2.diagnostics)
-    if check_convergence:
-        out.attrs["convergence_discovery"], out.attrs["convergence_test"] = res1.convergence, res2.convergence
-    if check_approximation:
-        out.attrs["approximation_discovery"], out.attrs["approximation_test"] = res1.approximation, res2.approximation
-    if check_loo:
-        out.attrs["loo_discovery"], out.attrs["loo_test"] = res1.loo, res2.loo
-    if check_loo_intervals:
-        out.attrs["loo_intervals_discovery"], out.attrs["loo_intervals_test"] = res1.loo_intervals, res2.loo_intervals
-    if check_approximation_loo:
-        out.attrs["approximation_loo_discovery"], out.attrs["approximation_loo_test"] = res1.approximation_loo, res2.approximation_loo
-    if check_approximation_loo_intervals:
-        out.attrs["approximation_loo_intervals_discovery"] = res1.approximation_loo_intervals
-        out.attrs["approximation_loo_intervals_test"] = res2.approximation_loo_intervals
-    if exact_intervals:
-        out.attrs["exact_intervals_discovery"], out.attrs["exact_intervals_test"] = res1.exact_intervals, res2.exact_intervals
+    _report_checks(out, checks, discovery=res1, test=res2)
     if pass_fit:                                                           # R/methods.R:353-357: attrs "fit 1" / "fit 2"
         out.attrs["fit 1"], out.attrs["fit 2"] = res1.fit, res2.fit        # device-resident; the library keeps the model
     return out                                                             # alive until both fits are closed
