@@ -75,6 +75,7 @@ class Oracle:
         L.ppco_nb2_log_rng.restype = C.c_int32
         L.ppco_nb2_log_rng.argtypes = [C.c_double, C.c_double, C.c_uint64, C.c_uint32, C.c_uint32]
         L.ppco_nuts_model.restype = C.c_int
+        L.ppco_nuts_model_offset.restype = C.c_int
         L.ppco_nuts_gauss.restype = C.c_int
         L.ppco_generated_quantities.restype = None
         L.ppco_summarise.restype = None
@@ -113,15 +114,15 @@ class Oracle:
                     n_leapfrog=np.zeros((cfg.chains, cfg.iter), np.int32),
                     divergent=np.zeros((cfg.chains, cfg.iter), np.int32), accept=np.zeros((cfg.chains, cfg.iter)))
 
-    def nuts_model(self, m, cfg) -> NutsResult:
+    def nuts_model(self, m, cfg, chain_id_offset=0) -> NutsResult:
         D = self.dim(m.G, m.C, m.K)
         o = self._alloc(cfg, D)
         metric = np.zeros((cfg.chains, D))
         done = np.zeros(cfg.chains, np.int32)
-        rc = self.lib.ppco_nuts_model(C.byref(m), C.byref(cfg), _p(o["draws"], C.c_double), _p(o["lp"], C.c_double),
-                                      _p(o["stepsize"], C.c_double), _p(o["treedepth"], C.c_int),
-                                      _p(o["n_leapfrog"], C.c_int), _p(o["divergent"], C.c_int),
-                                      _p(o["accept"], C.c_double), _p(metric, C.c_double), _p(done, C.c_int))
+        rc = self.lib.ppco_nuts_model_offset(C.byref(m), C.byref(cfg), C.c_int(int(chain_id_offset)), _p(o["draws"], C.c_double),
+                                             _p(o["lp"], C.c_double), _p(o["stepsize"], C.c_double), _p(o["treedepth"], C.c_int),
+                                             _p(o["n_leapfrog"], C.c_int), _p(o["divergent"], C.c_int),
+                                             _p(o["accept"], C.c_double), _p(metric, C.c_double), _p(done, C.c_int))
         if rc != 0:
             raise RuntimeError("oracle NUTS: initialisation failed")
         return NutsResult(metric=metric, iters_done=done, **o)

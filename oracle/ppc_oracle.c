@@ -609,12 +609,13 @@ static int run_chain(ppco_lp_fn fn, const void* ctx, int D, const ppco_nuts_cfg*
 }
 
 /* draws: [chains][n_keep][D]; diagnostics: [chains][iter]; returns 0 ok. iters_done[chains]. */
-PPCO_EXPORT int ppco_nuts_model(const ppco_model* m, const ppco_nuts_cfg* cfg, double* draws, double* lp,
-                                double* stepsize, int* treedepth, int* n_leapfrog, int* divergent,
-                                double* accept, double* metric, int* iters_done) {
+/* chain ch runs on the Philox stream of global chain id chain_id_offset + ch (DESIGN.md "RNG specification") */
+PPCO_EXPORT int ppco_nuts_model_offset(const ppco_model* m, const ppco_nuts_cfg* cfg, int chain_id_offset, double* draws, double* lp,
+                                       double* stepsize, int* treedepth, int* n_leapfrog, int* divergent,
+                                       double* accept, double* metric, int* iters_done) {
   int D = ppco_dim(m->G, m->C, m->K); int nk = cfg->iter - cfg->warmup; int rc = 0;
   for (int ch = 0; ch < cfg->chains; ++ch) {
-    int r = run_chain(model_lp, m, D, cfg, ch,
+    int r = run_chain(model_lp, m, D, cfg, chain_id_offset + ch,
                       draws ? draws + (size_t)ch * nk * D : NULL, lp ? lp + (size_t)ch * nk : NULL,
                       stepsize ? stepsize + (size_t)ch * cfg->iter : NULL, treedepth ? treedepth + (size_t)ch * cfg->iter : NULL,
                       n_leapfrog ? n_leapfrog + (size_t)ch * cfg->iter : NULL, divergent ? divergent + (size_t)ch * cfg->iter : NULL,
@@ -623,6 +624,11 @@ PPCO_EXPORT int ppco_nuts_model(const ppco_model* m, const ppco_nuts_cfg* cfg, d
     if (r < 0) rc = -1;
   }
   return rc;
+}
+PPCO_EXPORT int ppco_nuts_model(const ppco_model* m, const ppco_nuts_cfg* cfg, double* draws, double* lp,
+                                double* stepsize, int* treedepth, int* n_leapfrog, int* divergent,
+                                double* accept, double* metric, int* iters_done) {
+  return ppco_nuts_model_offset(m, cfg, 0, draws, lp, stepsize, treedepth, n_leapfrog, divergent, accept, metric, iters_done);
 }
 /* One chain of the same sampler on a caller-supplied log density (fn(ctx, u, grad) returns lp and fills grad): bench.py's
  * `--cpu-full-cfg2` leg drives the optimised CPU comparator (oracle/cpu_fast.cpp) through it, one chain per host thread, so

@@ -457,7 +457,13 @@ PPCX_HD void end_transition(ChainScalars& st, Cmd& nc, const ChainOut& out) {
       }
       ++st.win_counter;
     }
-    if (it == st.warmup - 1 && !metric_updated) st.eps = exp(st.x_bar);   // complete_adaptation
+    // complete_adaptation, without conditions (Stan's disengage_adaptation). After a metric update at this very iteration
+    // (term_buffer = 0) Stan searches a step size, restarts dual averaging (x_bar = 0) and then samples with exp(x_bar) = 1
+    // exactly -- Stan's behaviour, kept. That search leaves no trace (momenta from a stream of its own, the
+    // position restored, its result replaced), so it is not run.
+    const bool last_warmup = it == st.warmup - 1;
+    if (last_warmup) st.eps = metric_updated ? 1.0 : exp(st.x_bar);
+    if (last_warmup) metric_updated = false;       // PRE_METRIC stays in the command; no search follows
   } else {
     const int k = it - st.warmup;
     nc.pre_flags |= PRE_STORE_DRAW; nc.draw_index = k;

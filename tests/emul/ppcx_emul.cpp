@@ -94,6 +94,18 @@ static double update_pass(const EmulModel& m, ChainState& st, const Cmd& ex, con
 struct EmulCfg { int chains, iter, warmup; unsigned long long seed; double adapt_delta; int max_treedepth;
                  double init_radius, stepsize0; int init_buffer, term_buffer, window, chain_id_offset; };
 
+// where the fits below leave each chain's inverse metric at its end ([chains][D], gene and hyper coordinates; null: nowhere)
+static double* g_minv_out = nullptr;
+extern "C" __attribute__((visibility("default")))
+void emul_set_inv_metric_out(double* out) { g_minv_out = out; }
+static void store_inv_metric(const EmulModel& m, int ch, const std::vector<double>& vecs, const std::vector<double>& hv) {
+  if (!g_minv_out) return;
+  const int D = m.d.D;
+  double* o = g_minv_out + (size_t)ch * D;
+  for (int i = 0; i < D; ++i) o[i] = vecs[(size_t)V_MINV * D + i];
+  for (int k = 0; k < 6; ++k) o[hyper_index(m.d, k)] = hv[V_MINV * 8 + k];   // the hyper coordinates live in their own copy
+}
+
 extern "C" __attribute__((visibility("default")))
 int emul_log_prob_grad(int G, int S, int C, int K, const int32_t* counts, const double* X, const double* expo,
                        double lmm, int n_excl, const int32_t* excl, const double* u, double* lp, double* grad) {
@@ -150,6 +162,7 @@ int emul_fit_nuts(int G, int S, int C, int K, const int32_t* counts, const doubl
       if (++guard > 50000000L) { rc = -5; break; }
     }
     if (st.sc.error) rc = -3;
+    store_inv_metric(m, ch, vecs, hv);
   }
   return rc;
 }
@@ -215,7 +228,7 @@ static int pipelined_chain(const EmulModel& m, const NutsConfig& nc, int ch, con
     if (ls_first_s) pipelined_loglik<CM>(m, x_seen, v, sums);
     ++*rounds; if (!stepped) ++*carried;
     x = y;
-    if (x.type == CMD_DONE) return st.sc.error ? -3 : 0;
+    if (x.type == CMD_DONE) { store_inv_metric(m, ch, vecs, hv); return st.sc.error ? -3 : 0; }
     pipelined_gene<CM>(m, x, v, io.draws, spec, sums, red.data());
   }
   return -5;
