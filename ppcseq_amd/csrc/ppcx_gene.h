@@ -1,7 +1,7 @@
 // ppcx_gene.h -- the per-gene bodies of the kernels:
 //   log-likelihood kernel : lane_gene_sums (per lane) -> [L-lane butterfly] -> per-gene sums
-//   close kernel          : gene_load -> gene_finish -> tree bookkeeping (coord_merge_dots / coord_store_slot /
-//                           coord_top_dots)
+//   close kernel          : gene_load -> gene_finish -> leaf_close (tree bookkeeping: coord_merge_dots / coord_store_slot /
+//                           coord_top_dots); the gene kernel of a pipelined round closes a leaf by the same two
 //   update kernel         : coord_update (per coordinate: the command's coordinate work + coord_consts)
 //   step kernel           : chain_step (scalar state machine)
 // Shared by the gfx950 kernel (ppcx_kernels.hip) and the CPU emulation harness in tests/emul.
@@ -434,6 +434,95 @@ PPCX_HD void gene_finish(const Dims& d, const Cmd& c, const VecRef& v, const Gen
   gene_finish_vals<CM>(d, c, v, x, acc, gd, p_in, minv, part, pn, gn);
 }
 
+// the sums the log-likelihood launch left for gene g (sums: the chain's [GeneSums<CM>::N][G]); zeros for a lane without a gene
+template <int CM>
+PPCX_HD void gene_sums_load(const Dims& d, const double* sums, int g, bool active, GeneSumsV<CM>& acc) {
+  const bool any_generic = !d.x0_is_one || (d.C >= 2 && d.K > 0);      // sum X_sc rho: left by models with such genes only
+  acc.lik = acc.dph = acc.Sr = 0.0;
+#pragma unroll
+  for (int cc = 0; cc < CM; ++cc) acc.Tx[cc] = 0.0;
+  if (active) {
+    const long G = d.G;
+    acc.lik = sums[0 * G + g]; acc.dph = sums[1 * G + g]; acc.Sr = sums[2 * G + g];
+    if (any_generic) {
+#pragma unroll
+      for (int cc = 0; cc < CM; ++cc) if (cc < d.C) acc.Tx[cc] = sums[(3 + cc) * G + g];
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// The close of a leaf, once for the close kernel, the gene kernel and the emulation: the tree bookkeeping of the gene's
+// coordinates after gene_finish has left their momenta pn[] -- merge the parked subtrees of levels 0 .. n_merge - 1, then
+// park the node this leaf closes (coord_store_slot) or, the subtree complete, take the top products (coord_top_dots).
+// The parked subtrees of the first PRE levels can be requested ahead (slot_prefetch; closes: the caller closes a position at
+// all): one round trip for all of them, behind the gene's arithmetic, instead of one per level after it (a chain closing
+// three levels kept the close launch 4 us longer).
+// ---------------------------------------------------------------------------------------------------------------
+template <int CM, int PRE>
+struct SlotPre { int n; double s[PRE > 0 ? PRE : 1][CM + 1][3]; };       // n = min(n_merge, PRE) levels of (rho, p_begin, p_end)
+template <int CM, int PRE>
+PPCX_HD void slot_prefetch(const Cmd& c, const VecRef& v, const GeneCtx<CM>& x, bool closes, SlotPre<CM, PRE>& p) {
+  p.n = (closes && c.type == CMD_LEAF) ? (c.n_merge < PRE ? c.n_merge : PRE) : 0;
+#pragma unroll
+  for (int lev = 0; lev < PRE; ++lev) {
+#pragma unroll
+    for (int j = 0; j < CM + 1; ++j) {
+      p.s[lev][j][0] = p.s[lev][j][1] = p.s[lev][j][2] = 0.0;
+      if (lev < p.n && j < x.ncoord) coord_load_slot(v, x.idx[j], lev, &p.s[lev][j][0], &p.s[lev][j][1], &p.s[lev][j][2]);
+    }
+  }
+}
+// Every group of six products -- level lev's at offset PT_DOTS + 6 lev, the top products at PT_TOP -- goes to a Reducer:
+//   double* begin(int off, double* own)   where the group is accumulated (own: six doubles of the caller's), ready to be added to
+//   void end(int off, double* six)        the group is complete: sum it over the genes
+//   kLevel0WithLeaf                       level 0's group leaves in one batch with the leaf's own sums, so it leaves whether
+//                                         or not the leaf closes a level (needs PRE >= 1)
+template <int CM, int PRE, class Reducer>
+PPCX_HD void leaf_close(const Cmd& c, const VecRef& v, const GeneCtx<CM>& x, const double* pn, const double* minv,
+                        const SlotPre<CM, PRE>& pre, Reducer& r) {
+  constexpr int NCM = CM + 1;
+  NodeVals nv[NCM];
+#pragma unroll
+  for (int j = 0; j < NCM; ++j) nv[j] = NodeVals{pn[j], pn[j]};
+#pragma unroll
+  for (int lev = 0; lev < PRE; ++lev) {
+    if (lev < pre.n || (Reducer::kLevel0WithLeaf && lev == 0)) {
+      double own[6];
+      double* dots = r.begin(PT_DOTS + 6 * lev, own);
+      if (lev < pre.n) {
+#pragma unroll
+        for (int j = 0; j < NCM; ++j) if (j < x.ncoord) coord_merge_dots_vals(pre.s[lev][j][0], pre.s[lev][j][1], pre.s[lev][j][2], pn[j], minv[j], &nv[j], dots);
+      }
+      r.end(PT_DOTS + 6 * lev, dots);
+    }
+  }
+  for (int lev = PRE; lev < c.n_merge; ++lev) {
+    double own[6];
+    double* dots = r.begin(PT_DOTS + 6 * lev, own);
+#pragma unroll
+    for (int j = 0; j < NCM; ++j) if (j < x.ncoord) coord_merge_dots(v, x.idx[j], lev, pn[j], minv[j], &nv[j], dots);
+    r.end(PT_DOTS + 6 * lev, dots);
+  }
+  if (!c.subtree_complete) {
+#pragma unroll
+    for (int j = 0; j < NCM; ++j) if (j < x.ncoord) coord_store_slot(v, x.idx[j], c.n_merge, pn[j], nv[j]);
+  } else {
+    double own[6];
+    double* top = r.begin(PT_TOP, own);
+#pragma unroll
+    for (int j = 0; j < NCM; ++j) if (j < x.ncoord) coord_top_dots(v, x.idx[j], c.dir, pn[j], minv[j], nv[j], top);
+    r.end(PT_TOP, top);
+  }
+}
+// the emulation's reducer: one thread walks the genes, so a group is added to in place, red[off .. off + 5]
+struct SerialSums {
+  static constexpr bool kLevel0WithLeaf = false;
+  double* red;
+  PPCX_HD double* begin(int off, double*) { return red + off; }
+  PPCX_HD void end(int, double*) {}
+};
+
 // update kernel, one gene-owned coordinate: pre-operations of the new command, then the first half kick and the drift of
 // the next leapfrog (written in place into the end being advanced) and the constants of the new position. A command
 // without a step (eps = 0: the evaluation of a given point) leaves position and momentum as they are.
@@ -454,7 +543,7 @@ PPCX_HD void coord_update(const Dims& d, const Cmd& nc, const VecRef& v, int i, 
 // ---------------------------------------------------------------------------------------------------------------
 // Pipelined rounds (two launches per leapfrog: ppcx_ls_kernel, ppcx_gene_kernel). The gene kernel does everything that
 // belongs to ONE gene, one thread per gene: the per-coordinate work of the command (gene_coord_update: what coord_update
-// does per coordinate), the close of the evaluated leaf (gene_finish + tree bookkeeping), and -- ahead of the state
+// does per coordinate), the close of the evaluated leaf (gene_finish + leaf_close), and -- ahead of the state
 // machine's decision -- the constants of the position the next leaf of the same subtree would evaluate (gene_spec_consts),
 // so that the next log-likelihood launch can run beside the state machine instead of after it.
 // ---------------------------------------------------------------------------------------------------------------

@@ -281,6 +281,27 @@ __device__ __forceinline__ void block_accumulate(double* vals, double* wacc, int
     for (int k = 0; k < N; ++k) wacc[wave * PT_COUNT + k] = vals[k];
   }
 }
+// leaf_close's reducer of the close kernel: every group of six by the cross-lane scan
+struct ScanSums {
+  static constexpr bool kLevel0WithLeaf = false;
+  double* wacc; int wave, lane;
+  __device__ __forceinline__ double* begin(int, double* own) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) own[k] = 0.0;
+    return own;
+  }
+  __device__ __forceinline__ void end(int off, double* six) { block_accumulate<6>(six, wacc + off, wave, lane); }
+};
+// after a workgroup barrier: the four wavefronts' partial sums -> the workgroup's row of the slab, zeros where the command
+// produced nothing. keep_t0: column PT_T0 was left by the round that applied the command (gene kernel) and stays
+__device__ __forceinline__ void slab_row_write(const Cmd& c, const double* wacc, double* slab, int tid, bool keep_t0) {
+  const int np = parts_used(c);
+  for (int k = tid; k < np; k += 256) {
+    if (keep_t0 && k == PT_T0) continue;
+    const bool used = k < 10 || (k >= PT_DOTS && k < PT_DOTS + 6 * c.n_merge) || (k >= PT_TOP && c.subtree_complete);
+    slab[k] = used ? ((wacc[k] + wacc[PT_COUNT + k]) + wacc[2 * PT_COUNT + k]) + wacc[3 * PT_COUNT + k] : 0.0;
+  }
+}
 
 // Sums of up to 16 quantities over the 64 lanes of a wavefront THROUGH LDS: row k = quantity k, one column per lane, rows padded
 // to 65 doubles; lane 4 k + part adds columns 16 part .. 16 part + 15 of row k, the four parts meet by two cross-lane
@@ -326,75 +347,21 @@ __global__ __launch_bounds__(256) void ppcx_close_kernel(CloseArgs a) {
   const VecRef v{a.vecs + (long)chain * V_COUNT * a.Dpad, a.Dpad};
   const double* sums = a.sums + (long)chain * NS * d.G;
   const int g = blockIdx.x * 256 + tid;
-  const bool any_generic = !d.x0_is_one || (d.C >= 2 && d.K > 0);
   GeneCtx<CM> x;
   gene_load<CM>(d, c, v, g, x);
   GeneSumsV<CM> acc;
-  acc.lik = acc.dph = acc.Sr = 0.0;
-#pragma unroll
-  for (int cc = 0; cc < CM; ++cc) acc.Tx[cc] = 0.0;
-  if (x.active) {
-    const long G = d.G;
-    acc.lik = sums[0 * G + g]; acc.dph = sums[1 * G + g]; acc.Sr = sums[2 * G + g];
-    if (any_generic) {
-#pragma unroll
-      for (int cc = 0; cc < CM; ++cc) if (cc < d.C) acc.Tx[cc] = sums[(3 + cc) * G + g];
-    }
-  }
-  // the parked subtrees of the first levels this leaf closes are requested now: one round trip for all of them, behind the
-  // gene's arithmetic, instead of one per level after it (a chain closing three levels kept the launch 4 us longer)
-  constexpr int kPreLev = 3;
-  double pre[kPreLev][NCM][3];
-  const int n_pre = c.type == CMD_LEAF ? (c.n_merge < kPreLev ? c.n_merge : kPreLev) : 0;
-#pragma unroll
-  for (int lev = 0; lev < kPreLev; ++lev) {
-#pragma unroll
-    for (int j = 0; j < NCM; ++j) {
-      pre[lev][j][0] = pre[lev][j][1] = pre[lev][j][2] = 0.0;
-      if (lev < n_pre && j < x.ncoord) {
-        coord_load_slot(v, x.idx[j], lev, &pre[lev][j][0], &pre[lev][j][1], &pre[lev][j][2]);
-      }
-    }
-  }
+  gene_sums_load<CM>(d, sums, g, x.active, acc);
+  SlotPre<CM, 3> pre;                          // requested now, behind the gene's arithmetic
+  slot_prefetch<CM, 3>(c, v, x, true, pre);
   double pn[NCM], minv[NCM], part[10];
   gene_finish<CM>(d, c, v, x, acc, a.Sy, a.SyE, a.SyX, a.SX, a.ncell, a.Lg1, part, pn, minv);
   block_accumulate<10>(part, wacc, wave, lane);
   if (c.type == CMD_LEAF) {
-    NodeVals nv[NCM];
-#pragma unroll
-    for (int j = 0; j < NCM; ++j) nv[j] = NodeVals{pn[j], pn[j]};
-#pragma unroll
-    for (int lev = 0; lev < kPreLev; ++lev) {
-      if (lev < n_pre) {
-        double dots[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-        for (int j = 0; j < NCM; ++j) if (j < x.ncoord) coord_merge_dots_vals(pre[lev][j][0], pre[lev][j][1], pre[lev][j][2], pn[j], minv[j], &nv[j], dots);
-        block_accumulate<6>(dots, wacc + PT_DOTS + 6 * lev, wave, lane);
-      }
-    }
-    for (int lev = kPreLev; lev < c.n_merge; ++lev) {
-      double dots[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-      for (int j = 0; j < NCM; ++j) if (j < x.ncoord) coord_merge_dots(v, x.idx[j], lev, pn[j], minv[j], &nv[j], dots);
-      block_accumulate<6>(dots, wacc + PT_DOTS + 6 * lev, wave, lane);
-    }
-    if (!c.subtree_complete) {
-#pragma unroll
-      for (int j = 0; j < NCM; ++j) if (j < x.ncoord) coord_store_slot(v, x.idx[j], c.n_merge, pn[j], nv[j]);
-    } else {
-      double top[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-      for (int j = 0; j < NCM; ++j) if (j < x.ncoord) coord_top_dots(v, x.idx[j], c.dir, pn[j], minv[j], nv[j], top);
-      block_accumulate<6>(top, wacc + PT_TOP, wave, lane);
-    }
+    ScanSums r{wacc, wave, lane};
+    leaf_close<CM, 3>(c, v, x, pn, minv, pre, r);
   }
   __syncthreads();
-  const int np = parts_used(c);
-  double* slab = a.partials + ((long)chain * gridDim.x + blockIdx.x) * PT_COUNT;
-  for (int k = tid; k < np; k += 256) {
-    const bool used = k < 10 || (k >= PT_DOTS && k < PT_DOTS + 6 * c.n_merge) || (k >= PT_TOP && c.subtree_complete);
-    slab[k] = used ? ((wacc[k] + wacc[PT_COUNT + k]) + wacc[2 * PT_COUNT + k]) + wacc[3 * PT_COUNT + k] : 0.0;
-  }
+  slab_row_write(c, wacc, a.partials + ((long)chain * gridDim.x + blockIdx.x) * PT_COUNT, tid, false);
 }
 
 // -----------------------------------------------------------------------------------------------------
@@ -420,130 +387,155 @@ struct WaveLanes {                              // cooperating lanes 0..7 of one
   __device__ __forceinline__ double pick(const double* own, int k) const { return __shfl(own[0], k, 8); }
 };
 
+// ---- what a chain's state machine is staged with, in the step kernel and in the state-machine role of a pipelined round
+struct ChainStage {                             // LDS
+  double sm[3][8][32];
+  double red[PT_COUNT];
+  double hv[V_COUNT * 8];                      // the six hyper coordinates of every per-coordinate vector
+  Cmd ex;
+  ChainState st;
+  Reduced rd;
+};
+constexpr int kStWords = (int)(sizeof(ChainState) / sizeof(int)), kCmdWords = (int)(sizeof(Cmd) / sizeof(int)), kHvDoubles = V_COUNT * 8;
+static_assert(kStWords <= 4 * 256 && kCmdWords <= 256 && kHvDoubles <= 3 * 256 && PT_COUNT <= 96, "state machine staging sizes");
+// the chain's state, command and hyper vectors, requested at the start and parked in registers, so that their round trip
+// overlaps the reduction of the slab
+struct ChainRegs { int st[4], cmd; double hv[3]; };
+__device__ __forceinline__ ChainRegs chain_prefetch(const StepArgs& a, int chain, int tid) {
+  ChainRegs r;
+  const word_t* s2 = reinterpret_cast<const word_t*>(a.states_in + chain);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) r.st[k] = tid + 256 * k < kStWords ? s2[tid + 256 * k] : 0;
+  r.cmd = tid < kCmdWords ? reinterpret_cast<const word_t*>(a.cmds_in + chain)[tid] : 0;
+  const double* hvg = a.hyper_in + (long)chain * kHvDoubles;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) r.hv[k] = tid + 256 * k < kHvDoubles ? hvg[tid + 256 * k] : 0.0;
+  return r;
+}
+__device__ __forceinline__ void chain_stage(const ChainRegs& r, ChainStage& s, int tid) {      // followed by a barrier
+  word_t* d2 = reinterpret_cast<word_t*>(&s.st);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) if (tid + 256 * k < kStWords) d2[tid + 256 * k] = r.st[k];
+  if (tid < kCmdWords) reinterpret_cast<word_t*>(&s.ex)[tid] = r.cmd;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) if (tid + 256 * k < kHvDoubles) s.hv[tid + 256 * k] = r.hv[k];
+}
+// The fold of the chain's slab into s.red, in a fixed order. One pass: thread (c, ch) sums rows ch, ch+8, ... of columns c, c+32,
+// c+64, loads of several rows in flight (slab_row_groups; returns the number of sums the command produced); then, after a
+// barrier, column v = sum over the eight row groups (slab_fold). All columns are loaded (stale ones included) so that these
+// loads do not wait for the command that says which sums it produced; the selection happens afterwards.
+// with_t0: column PT_T0 comes with the slab (the gene kernel's); otherwise it is left 0 for the T0 slab of the update launch.
+__device__ __forceinline__ int slab_row_groups(const StepArgs& a, int chain, bool done, ChainStage& s, int tid) {
+  const double* slab = a.partials + (long)chain * a.slab_stride * PT_COUNT;
+  const int c = tid & 31, ch = tid >> 5;
+  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  const bool in2 = c + 64 < PT_COUNT;
+#pragma unroll 4
+  for (int b = ch; b < a.nblocks_close; b += 8) {
+    const double* row = slab + (long)b * PT_COUNT;
+    const double v0 = row[c], v1 = row[c + 32], v2 = in2 ? row[c + 64] : 0.0;
+    s0 += v0; s1 += v1; s2 += v2;
+  }
+  const Cmd& exg = a.cmds_in[chain];
+  const int np = (done || exg.type == CMD_DONE || exg.type == CMD_FLUSH) ? 0 : parts_used(exg);   // uniform
+  s.sm[0][ch][c] = c < np ? s0 : 0.0; s.sm[1][ch][c] = c + 32 < np ? s1 : 0.0; s.sm[2][ch][c] = c + 64 < np ? s2 : 0.0;
+  return np;
+}
+__device__ __forceinline__ void slab_fold(ChainStage& s, int np, bool with_t0, int tid) {
+  if (tid < PT_COUNT) {
+    double t = 0.0;
+    if (tid < np && (with_t0 || tid != PT_T0)) {
+#pragma unroll
+      for (int k = 0; k < 8; ++k) t += s.sm[tid >> 5][k][tid & 31];
+    }
+    s.red[tid] = t;
+  }
+}
+// a finished chain: its final state is carried across the double buffer
+__device__ __forceinline__ void chain_carry_done(const StepArgs& a, int chain, int tid) {
+  if (tid == 0) { a.states_out[chain] = a.states_in[chain]; a.cmds_out[chain] = a.cmds_in[chain]; }
+  const double* hi = a.hyper_in + (long)chain * kHvDoubles;
+  double* ho = a.hyper_out + (long)chain * kHvDoubles;
+  for (int i = tid; i < kHvDoubles; i += 256) ho[i] = hi[i];
+}
+// where the chain's draws and diagnostics go (writer: the workgroup that writes what the step leaves in memory)
+__device__ __forceinline__ ChainIO chain_io(const StepArgs& a, int chain, bool writer) {
+  ChainIO io;
+  io.draws = (writer && a.draws) ? a.draws + (long)chain * a.draws_chain_stride : nullptr;
+  io.out.lp = (writer && a.out_lp) ? a.out_lp + (long)chain * a.n_keep : nullptr;
+  io.out.stepsize = (writer && a.out_stepsize) ? a.out_stepsize + (long)chain * a.iter : nullptr;
+  io.out.treedepth = (writer && a.out_treedepth) ? a.out_treedepth + (long)chain * a.iter : nullptr;
+  io.out.n_leapfrog = (writer && a.out_n_leapfrog) ? a.out_n_leapfrog + (long)chain * a.iter : nullptr;
+  io.out.divergent = (writer && a.out_divergent) ? a.out_divergent + (long)chain * a.iter : nullptr;
+  io.out.accept = (writer && a.out_accept) ? a.out_accept + (long)chain * a.iter : nullptr;
+  return io;
+}
+// after a barrier: what the step left in LDS -- hyper vectors and state -- to the other half of the double buffer (the new command
+// is written from where the kernel keeps it: lane 0's registers in the step kernel, LDS in the pipelined role)
+__device__ __forceinline__ void chain_write_out(const StepArgs& a, int chain, const ChainStage& s, int tid) {
+  double* hvo = a.hyper_out + (long)chain * kHvDoubles;
+  for (int i = tid; i < kHvDoubles; i += 256) hvo[i] = s.hv[i];
+  const word_t* s2 = reinterpret_cast<const word_t*>(&s.st); word_t* d2 = reinterpret_cast<word_t*>(a.states_out + chain);
+  for (int i = tid; i < kStWords; i += 256) d2[i] = s2[i];
+}
+// sum of v over the 256 threads of the workgroup, left in s256[0] (a binary tree over s256)
+__device__ __forceinline__ void tree_sum_256(double v, double* s256, int tid) {
+  s256[tid] = v;
+  __syncthreads();
+  for (int stp = 128; stp > 0; stp >>= 1) { if (tid < stp) s256[tid] += s256[tid + stp]; __syncthreads(); }
+}
+
 __global__ __launch_bounds__(256) void ppcx_step_kernel(StepArgs a) {
-  __shared__ double sm[3][8][32];
+  __shared__ ChainStage s;
   __shared__ double sT0[256];
-  __shared__ double red[PT_COUNT];
-  __shared__ double hv[V_COUNT * 8];           // the six hyper coordinates of every per-coordinate vector
-  __shared__ Cmd s_ex;
-  __shared__ ChainState s_st;
-  __shared__ Reduced s_rd;
-  constexpr int NST = (int)(sizeof(ChainState) / sizeof(int)), NCMD = (int)(sizeof(Cmd) / sizeof(int)), NHV = V_COUNT * 8;
-  static_assert(NST <= 4 * 256 && NCMD <= 256 && NHV <= 3 * 256 && PT_COUNT <= 96, "step kernel staging sizes");
   __shared__ Cmd s_nc;
   const int chain = blockIdx.y, tid = threadIdx.x;
   const bool lead = blockIdx.x == 0;           // with a.upd_vecs the grid has several workgroups per chain: all of them run the
                                                // step on the same inputs, the first one writes what the step leaves in memory
-  const ChainState* st_in = a.states_in + chain;
-  const bool done = st_in->sc.phase == PH_DONE;
+  const bool done = a.states_in[chain].sc.phase == PH_DONE;
   double* rg = a.red + (long)chain * PT_COUNT;
-  // the chain's command, state and hyper vectors are requested now and parked in registers, so that their round trip
-  // overlaps the reduction below
-  int r_st[4], r_cmd = 0; double r_hv[3];
-  {
-    const word_t* s2 = reinterpret_cast<const word_t*>(st_in);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) r_st[k] = tid + 256 * k < NST ? s2[tid + 256 * k] : 0;
-    if (tid < NCMD) r_cmd = reinterpret_cast<const word_t*>(a.cmds_in + chain)[tid];
-    const double* hvg = a.hyper_in + (long)chain * NHV;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) r_hv[k] = tid + 256 * k < NHV ? hvg[tid + 256 * k] : 0.0;
-  }
+  const ChainRegs regs = chain_prefetch(a, chain, tid);
   if (a.phases & STEP_REDUCE) {
-    const double* slab = a.partials + (long)chain * a.slab_stride * PT_COUNT;
-    // one pass: thread (c, ch) sums rows ch, ch+8, ... of columns c, c+32, c+64, loads of several rows in flight; then
-    // column v = sum over the eight row groups in a fixed order. All columns are loaded (stale ones included) so that
-    // these loads do not wait for the command that says which sums it produced; the selection happens afterwards.
-    const int c = tid & 31, ch = tid >> 5;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    {
-      const bool in2 = c + 64 < PT_COUNT;
-#pragma unroll 4
-      for (int b = ch; b < a.nblocks_close; b += 8) {
-        const double* row = slab + (long)b * PT_COUNT;
-        const double v0 = row[c], v1 = row[c + 32], v2 = in2 ? row[c + 64] : 0.0;
-        s0 += v0; s1 += v1; s2 += v2;
-      }
-    }
-    const Cmd& exg = a.cmds_in[chain];
-    const int np = (done || exg.type == CMD_DONE || exg.type == CMD_FLUSH) ? 0 : parts_used(exg);   // uniform
-    sm[0][ch][c] = c < np ? s0 : 0.0; sm[1][ch][c] = c + 32 < np ? s1 : 0.0; sm[2][ch][c] = c + 64 < np ? s2 : 0.0;
+    const int np = slab_row_groups(a, chain, done, s, tid);
     __syncthreads();
-    if (tid < PT_COUNT) {
-      double t = 0.0;
-      if (tid < np && tid != PT_T0) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) t += sm[tid >> 5][k][tid & 31];
-      }
-      red[tid] = t;
-    }
+    slab_fold(s, np, false, tid);
     // kinetic energy of freshly drawn momenta: only commands that drew momenta left something in the T0 slab
-    const bool fresh = !done && (exg.pre_flags & (PRE_NEW_TRANSITION | PRE_EPS_TRY)) != 0;
+    const bool fresh = !done && (a.cmds_in[chain].pre_flags & (PRE_NEW_TRANSITION | PRE_EPS_TRY)) != 0;
     if (fresh) {
       const double* t0s = a.t0 + (long)chain * a.nblocks_update;
-      double s = 0.0;
-      for (int b = tid; b < a.nblocks_update; b += 256) s += t0s[b];
-      sT0[tid] = s;
-      __syncthreads();
-      for (int stp = 128; stp > 0; stp >>= 1) { if (tid < stp) sT0[tid] += sT0[tid + stp]; __syncthreads(); }
-      if (tid == 0) red[PT_T0] = sT0[0];
+      double t = 0.0;
+      for (int b = tid; b < a.nblocks_update; b += 256) t += t0s[b];
+      tree_sum_256(t, sT0, tid);
+      if (tid == 0) s.red[PT_T0] = sT0[0];
     }
     __syncthreads();
-    if (!(a.phases & STEP_ADVANCE)) { if (lead) for (int i = tid; i < PT_COUNT; i += 256) rg[i] = red[i]; return; }
+    if (!(a.phases & STEP_ADVANCE)) { if (lead) for (int i = tid; i < PT_COUNT; i += 256) rg[i] = s.red[i]; return; }
   } else {
-    for (int i = tid; i < PT_COUNT; i += 256) red[i] = rg[i];     // sums completed by the shard exchange
+    for (int i = tid; i < PT_COUNT; i += 256) s.red[i] = rg[i];     // sums completed by the shard exchange
     __syncthreads();
   }
   // ---- phase STEP
-  if (done) {                                  // finished chain: carry its final state across the double buffer
-    if (!lead) return;
-    if (tid == 0) { a.states_out[chain] = *st_in; a.cmds_out[chain] = a.cmds_in[chain]; }
-    const double* hi = a.hyper_in + (long)chain * V_COUNT * 8;
-    double* ho = a.hyper_out + (long)chain * V_COUNT * 8;
-    for (int i = tid; i < V_COUNT * 8; i += 256) ho[i] = hi[i];
-    return;
-  }
-  {
-    word_t* d2 = reinterpret_cast<word_t*>(&s_st);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) if (tid + 256 * k < NST) d2[tid + 256 * k] = r_st[k];
-    if (tid < NCMD) reinterpret_cast<word_t*>(&s_ex)[tid] = r_cmd;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) if (tid + 256 * k < NHV) hv[tid + 256 * k] = r_hv[k];
-  }
+  if (done) { if (lead) chain_carry_done(a, chain, tid); return; }
+  chain_stage(regs, s, tid);
   __syncthreads();
-  const bool have_parts = s_st.sc.phase != PH_START;
-  Cmd* nc_out = a.cmds_out + chain;
+  const bool have_parts = s.st.sc.phase != PH_START;
   if (tid < 8) {
-    ChainScalars st = s_st.sc;                 // scalars in registers; the run-time-indexed arrays stay in LDS
-    ChainIO io;
-    io.draws = (lead && a.draws) ? a.draws + (long)chain * a.draws_chain_stride : nullptr;
-    io.out.lp = (lead && a.out_lp) ? a.out_lp + (long)chain * a.n_keep : nullptr;
-    io.out.stepsize = (lead && a.out_stepsize) ? a.out_stepsize + (long)chain * a.iter : nullptr;
-    io.out.treedepth = (lead && a.out_treedepth) ? a.out_treedepth + (long)chain * a.iter : nullptr;
-    io.out.n_leapfrog = (lead && a.out_n_leapfrog) ? a.out_n_leapfrog + (long)chain * a.iter : nullptr;
-    io.out.divergent = (lead && a.out_divergent) ? a.out_divergent + (long)chain * a.iter : nullptr;
-    io.out.accept = (lead && a.out_accept) ? a.out_accept + (long)chain * a.iter : nullptr;
+    ChainScalars st = s.st.sc;                 // scalars in registers; the run-time-indexed arrays stay in LDS
     Cmd nc;
-    chain_step(WaveLanes{tid}, a.d, st, s_st.ta, s_ex, red, have_parts, VecRef{hv, 8}, io, s_rd, nc);
+    chain_step(WaveLanes{tid}, a.d, st, s.st.ta, s.ex, s.red, have_parts, VecRef{s.hv, 8}, chain_io(a, chain, lead), s.rd, nc);
     if (tid == 0) {
-      s_st.sc = st;
+      s.st.sc = st;
       s_nc = nc;
       if (lead) {
-        *nc_out = nc;
+        a.cmds_out[chain] = nc;
         if (st.phase == PH_DONE) a.done[chain] = 1 + st.error;
       }
     }
   }
   __syncthreads();
-  if (lead) {
-    double* hvo = a.hyper_out + (long)chain * V_COUNT * 8;
-    for (int i = tid; i < V_COUNT * 8; i += 256) hvo[i] = hv[i];
-    const word_t* s2 = reinterpret_cast<const word_t*>(&s_st); word_t* d2 = reinterpret_cast<word_t*>(a.states_out + chain);
-    for (int i = tid; i < (int)(sizeof(ChainState) / sizeof(int)); i += 256) d2[i] = s2[i];
-  }
+  if (lead) chain_write_out(a, chain, s, tid);
   if (!a.upd_vecs) return;
-  // ---- the per-coordinate work of the command just decided (what ppcx_update_kernel does after a separate step launch)
+  // ---- the per-coordinate work of the command just decided
   const Dims& d = a.d;
   double T0 = 0.0;
   if (s_nc.type != CMD_DONE) {
@@ -553,13 +545,9 @@ __global__ __launch_bounds__(256) void ppcx_step_kernel(StepArgs a) {
   }
   if ((s_nc.pre_flags & (PRE_NEW_TRANSITION | PRE_EPS_TRY)) == 0) return;
   __syncthreads();                             // sT0 was used by the reduction above
-  sT0[tid] = T0;
-  __syncthreads();
-  for (int stp = 128; stp > 0; stp >>= 1) { if (tid < stp) sT0[tid] += sT0[tid + stp]; __syncthreads(); }
+  tree_sum_256(T0, sT0, tid);
   if (tid == 0) a.upd_t0_out[(long)chain * gridDim.x + blockIdx.x] = sT0[0];
 }
-
-
 
 // -----------------------------------------------------------------------------------------------------
 // Pipelined rounds: two launches per leapfrog instead of three, and the state machine off the critical path.
@@ -577,13 +565,8 @@ __global__ __launch_bounds__(256) void ppcx_step_kernel(StepArgs a) {
 // The three-launch round stays for gene shards (their sums cross processes between reduce and advance), ADVI,
 // single evaluations and models with a per-cell linear predictor (whose cells read the positions themselves).
 // -----------------------------------------------------------------------------------------------------
-struct StepShared {
-  double sm[3][8][32];
-  double red[PT_COUNT];
-  double hv[V_COUNT * 8];
-  Cmd ex, nc;
-  ChainState st;
-  Reduced rd;
+struct StepShared : ChainStage {
+  Cmd nc;                                      // the new command: written where it is staged (step_role_pipelined)
   int x_ok[kMaxRanks]; long long x_wait;       // direct exchange: has rank k's contribution arrived; ticks waited
 };
 // system-scope accesses to the peer-mapped exchange buffers (uncached memory: nothing may be served from a cache line that a
@@ -633,8 +616,6 @@ __device__ __forceinline__ bool xchg_sums(const XchgArgs& x, int chain, unsigned
   return ok;
 }
 __device__ __forceinline__ void step_role_pipelined(const StepArgs& a, int chain, StepShared& s, bool spec) {
-  constexpr int NST = (int)(sizeof(ChainState) / sizeof(int)), NCMD = (int)(sizeof(Cmd) / sizeof(int)), NHV = V_COUNT * 8;
-  static_assert(NST <= 4 * 256 && NCMD <= 256 && NHV <= 3 * 256 && PT_COUNT <= 96, "step role staging sizes");
   const int tid = threadIdx.x;
 #ifdef PPCX_TESTING
   long long tr_t[7] = {0, 0, 0, 0, 0, 0, 0};
@@ -643,60 +624,16 @@ __device__ __forceinline__ void step_role_pipelined(const StepArgs& a, int chain
 #define PPCX_SM_STAMP(k) ((void)0)
 #endif
   PPCX_SM_STAMP(0);
-  const ChainState* st_in = a.states_in + chain;
-  const bool done = st_in->sc.phase == PH_DONE;
-  int r_st[4], r_cmd = 0; double r_hv[3];
-  {
-    const word_t* s2 = reinterpret_cast<const word_t*>(st_in);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) r_st[k] = tid + 256 * k < NST ? s2[tid + 256 * k] : 0;
-    if (tid < NCMD) r_cmd = reinterpret_cast<const word_t*>(a.cmds_in + chain)[tid];
-    const double* hvg = a.hyper_in + (long)chain * NHV;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) r_hv[k] = tid + 256 * k < NHV ? hvg[tid + 256 * k] : 0.0;
-  }
-  {
-    // the gene kernel's slab, every column (the kinetic energy of fresh momenta arrives in column PT_T0 here); a carried
-    // round reads a stale slab and ignores the sums
-    const double* slab = a.partials + (long)chain * a.slab_stride * PT_COUNT;
-    const int c = tid & 31, ch = tid >> 5;
-    double s0 = 0.0, s1 = 0.0, s2 = 0.0;
-    const bool in2 = c + 64 < PT_COUNT;
-#pragma unroll 4
-    for (int b = ch; b < a.nblocks_close; b += 8) {
-      const double* row = slab + (long)b * PT_COUNT;
-      const double v0 = row[c], v1 = row[c + 32], v2 = in2 ? row[c + 64] : 0.0;
-      s0 += v0; s1 += v1; s2 += v2;
-    }
-    const Cmd& exg = a.cmds_in[chain];
-    const int np = (done || exg.type == CMD_DONE || exg.type == CMD_FLUSH) ? 0 : parts_used(exg);   // uniform
-    s.sm[0][ch][c] = c < np ? s0 : 0.0; s.sm[1][ch][c] = c + 32 < np ? s1 : 0.0; s.sm[2][ch][c] = c + 64 < np ? s2 : 0.0;
-    PPCX_SM_STAMP(1);                          // the state, the command, the hyper vectors and the slab have arrived
-    __syncthreads();
-    if (tid < PT_COUNT) {
-      double t = 0.0;
-      if (tid < np) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) t += s.sm[tid >> 5][k][tid & 31];
-      }
-      s.red[tid] = t;
-    }
-  }
-  if (done) {                                  // finished chain: carry its final state across the double buffer
-    if (tid == 0) { a.states_out[chain] = *st_in; a.cmds_out[chain] = a.cmds_in[chain]; }
-    const double* hi = a.hyper_in + (long)chain * NHV;
-    double* ho = a.hyper_out + (long)chain * NHV;
-    for (int i = tid; i < NHV; i += 256) ho[i] = hi[i];
-    return;
-  }
-  {
-    word_t* d2 = reinterpret_cast<word_t*>(&s.st);
-#pragma unroll
-    for (int k = 0; k < 4; ++k) if (tid + 256 * k < NST) d2[tid + 256 * k] = r_st[k];
-    if (tid < NCMD) reinterpret_cast<word_t*>(&s.ex)[tid] = r_cmd;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) if (tid + 256 * k < NHV) s.hv[tid + 256 * k] = r_hv[k];
-  }
+  const bool done = a.states_in[chain].sc.phase == PH_DONE;
+  const ChainRegs regs = chain_prefetch(a, chain, tid);
+  // the gene kernel's slab, every column (the kinetic energy of fresh momenta arrives in column PT_T0 here); a carried
+  // round reads a stale slab and ignores the sums
+  const int np = slab_row_groups(a, chain, done, s, tid);
+  PPCX_SM_STAMP(1);                            // the state, the command, the hyper vectors and the slab have arrived
+  __syncthreads();
+  slab_fold(s, np, true, tid);
+  if (done) { chain_carry_done(a, chain, tid); return; }
+  chain_stage(regs, s, tid);
   __syncthreads();
   PPCX_SM_STAMP(2);                            // sums folded, everything staged in LDS
   // gene shards, one per rank: the other ranks' sums. Every rank's copy of this chain reaches this point the same number of times.
@@ -721,17 +658,8 @@ __device__ __forceinline__ void step_role_pipelined(const StepArgs& a, int chain
         a.done[chain] = 1 + st.error;
       }
     } else {
-    ChainIO io;
-    io.draws = a.draws ? a.draws + (long)chain * a.draws_chain_stride : nullptr;
-    io.out.lp = a.out_lp ? a.out_lp + (long)chain * a.n_keep : nullptr;
-    io.out.stepsize = a.out_stepsize ? a.out_stepsize + (long)chain * a.iter : nullptr;
-    io.out.treedepth = a.out_treedepth ? a.out_treedepth + (long)chain * a.iter : nullptr;
-    io.out.n_leapfrog = a.out_n_leapfrog ? a.out_n_leapfrog + (long)chain * a.iter : nullptr;
-    io.out.divergent = a.out_divergent ? a.out_divergent + (long)chain * a.iter : nullptr;
-    io.out.accept = a.out_accept ? a.out_accept + (long)chain * a.iter : nullptr;
-    Cmd& nc = s.nc;
     PPCX_SM_STAMP(3);
-    (void)chain_step_pipelined(WaveLanes{tid}, a.d, st, s.st.ta, s.ex, s.red, VecRef{s.hv, 8}, io, s.rd, nc, spec);
+    (void)chain_step_pipelined(WaveLanes{tid}, a.d, st, s.st.ta, s.ex, s.red, VecRef{s.hv, 8}, chain_io(a, chain, true), s.rd, s.nc, spec);
     PPCX_SM_STAMP(4);
     if (tid == 0 && st.phase == PH_DONE) a.done[chain] = 1 + st.error;
     }
@@ -745,12 +673,9 @@ __device__ __forceinline__ void step_role_pipelined(const StepArgs& a, int chain
   }
 #endif
   __syncthreads();
-  double* hvo = a.hyper_out + (long)chain * NHV;
-  for (int i = tid; i < NHV; i += 256) hvo[i] = s.hv[i];
-  const word_t* s2 = reinterpret_cast<const word_t*>(&s.st); word_t* d2 = reinterpret_cast<word_t*>(a.states_out + chain);
-  for (int i = tid; i < NST; i += 256) d2[i] = s2[i];
+  chain_write_out(a, chain, s, tid);
   const word_t* c2 = reinterpret_cast<const word_t*>(&s.nc); word_t* e2 = reinterpret_cast<word_t*>(a.cmds_out + chain);
-  if (tid < NCMD) e2[tid] = c2[tid];
+  if (tid < kCmdWords) e2[tid] = c2[tid];
 }
 
 // Grid: runs of 8 x (chains of the launch) workgroups, as in ppcx_loglik_kernel: position r & 7 of a run is a range block,
@@ -774,6 +699,25 @@ __global__ __launch_bounds__(256, GEN ? PPCX_LOGLIK_OCC : PPCX_LOGLIK_OCC_FAST) 
   loglik_role<CM, GEN, true>(a, jb, col, lds);
 }
 
+// leaf_close's reducer of the gene kernel: sums through LDS. The ten sums of the leaf travel with the six U-turn products of the
+// first level it closes, one batch of 16: part[0 .. 9] the leaf, part[10 .. 15] level 0, which lands in
+// wrow[PT_DOTS .. PT_DOTS + 5]; every other group in a batch of its own.
+struct LdsSums {
+  static constexpr bool kLevel0WithLeaf = true;
+  static_assert(PT_DOTS == 10, "the first level's products follow the leaf's ten sums");
+  double* part; double* rows; double* wrow; int lane;
+  __device__ __forceinline__ double* begin(int off, double* own) {
+    double* six = off == PT_DOTS ? part + 10 : own;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) six[k] = 0.0;
+    return six;
+  }
+  __device__ __forceinline__ void end(int off, double* six) {
+    if (off == PT_DOTS) wave_sums_lds<16>(part, rows, wrow, lane);
+    else wave_sums_lds<6>(six, rows, wrow + off, lane);
+  }
+};
+
 // One gene's part of a pipelined round, for the lane that owns gene g (g >= G: a lane without a gene, which only takes part
 // in the reductions): the command's work on the gene's coordinates, the close of the evaluated position, the anticipated
 // constants. No workgroup barrier inside; the wavefront's partial sums go to wacc[wave][...]. Everything the lane reads is
@@ -790,7 +734,6 @@ __device__ __forceinline__ void gene_wave_part(const GeneArgs& ga, const Cmd& c,
   const Dims& d = a.d;
   const VecRef v{a.vecs + (long)chain * V_COUNT * a.Dpad, a.Dpad};
   const double* sums = a.sums + (long)chain * NS * d.G;
-  const bool any_generic = !d.x0_is_one || (d.C >= 2 && d.K > 0);
   GeneCtx<CM> x;
   gene_index<CM>(d, g, x);
   // ---- a command with rare pre-operations: those first, through memory (gene_rare_pre)
@@ -809,38 +752,18 @@ __device__ __forceinline__ void gene_wave_part(const GeneArgs& ga, const Cmd& c,
     }
   }
   GeneSumsV<CM> acc;
-  acc.lik = acc.dph = acc.Sr = 0.0;
-#pragma unroll
-  for (int cc = 0; cc < CM; ++cc) acc.Tx[cc] = 0.0;
   GeneData gd;
   double phi = 1.0;
   constexpr int kPreLev = 2;                   // tree levels whose slots travel with the burst of loads (a third: 18 registers; see the kernel)
-  double pre[kPreLev][NCM][3];
-  const int n_pre = (do_close && c.type == CMD_LEAF) ? (c.n_merge < kPreLev ? c.n_merge : kPreLev) : 0;
+  SlotPre<CM, kPreLev> pre;
+  gene_sums_load<CM>(d, sums, g, do_close && x.active, acc);
   if (do_close) {
-    if (x.active) {
-      const long G = d.G;
-      acc.lik = sums[0 * G + g]; acc.dph = sums[1 * G + g]; acc.Sr = sums[2 * G + g];
-      if (any_generic) {
-#pragma unroll
-        for (int cc = 0; cc < CM; ++cc) if (cc < d.C) acc.Tx[cc] = sums[(3 + cc) * G + g];
-      }
-      // phi of the position being closed: written with the constants the log-likelihood part evaluated (for a leaf
-      // anticipated by the previous round the update below does not touch them)
-      phi = v.at(V_C0, x.idx[1]);
-    }
+    // phi of the position being closed: written with the constants the log-likelihood part evaluated (for a leaf
+    // anticipated by the previous round the update below does not touch them)
+    if (x.active) phi = v.at(V_C0, x.idx[1]);
     gene_data_load<CM>(d, x.gg, a.Sy, a.SyE, a.SyX, a.SX, a.ncell, a.Lg1, gd);
-#pragma unroll
-    for (int lev = 0; lev < kPreLev; ++lev) {
-#pragma unroll
-      for (int j = 0; j < NCM; ++j) {
-        pre[lev][j][0] = pre[lev][j][1] = pre[lev][j][2] = 0.0;
-        if (lev < n_pre && j < x.ncoord) {
-          coord_load_slot(v, x.idx[j], lev, &pre[lev][j][0], &pre[lev][j][1], &pre[lev][j][2]);
-        }
-      }
-    }
   }
+  slot_prefetch<CM, kPreLev>(c, v, x, do_close, pre);
   // ---- the command's work on the gene's coordinates
   if (do_update) gene_coord_update<CM, true>(d, c, v, x, draws, &T0, !do_close, cache, p_cur, minv, !do_close, fmask);
   if (!do_close) {                             // the command's position has not been evaluated yet: nothing to close
@@ -859,52 +782,10 @@ __device__ __forceinline__ void gene_wave_part(const GeneArgs& ga, const Cmd& c,
   part[PT_T0] = T0;
   double* wrow = wacc + wave * PT_COUNT;
   if (c.type != CMD_LEAF) { wave_sums_lds<10>(part, rows, wrow, lane); return; }
-  {
-    NodeVals nv[NCM];
-#pragma unroll
-    for (int j = 0; j < NCM; ++j) nv[j] = NodeVals{pn[j], pn[j]};
-    // the ten sums of the leaf travel with the six U-turn products of the first level it closes (one batch of 16), the
-    // further prefetched levels in a batch of their own
-#pragma unroll
-    for (int k = 0; k < 6; ++k) part[10 + k] = 0.0;
-    if (n_pre > 0) {
-#pragma unroll
-      for (int j = 0; j < NCM; ++j) if (j < x.ncoord) coord_merge_dots_vals(pre[0][j][0], pre[0][j][1], pre[0][j][2], pn[j], minv[j], &nv[j], part + 10);
-    }
-    wave_sums_lds<16>(part, rows, wrow, lane);   // wrow[0 .. 9] the leaf, wrow[PT_DOTS .. PT_DOTS + 5] level 0 (PT_DOTS = 10)
-    static_assert(PT_DOTS == 10, "the first level's products follow the leaf's ten sums");
-    if constexpr (kPreLev > 1) if (n_pre > 1) {
-      constexpr int NB = 6 * (kPreLev - 1);
-      double more[NB];
-#pragma unroll
-      for (int k = 0; k < NB; ++k) more[k] = 0.0;
-#pragma unroll
-      for (int lev = 1; lev < kPreLev; ++lev) {
-        if (lev < n_pre) {
-#pragma unroll
-          for (int j = 0; j < NCM; ++j) if (j < x.ncoord) coord_merge_dots_vals(pre[lev][j][0], pre[lev][j][1], pre[lev][j][2], pn[j], minv[j], &nv[j], more + 6 * (lev - 1));
-        }
-      }
-      wave_sums_lds<NB>(more, rows, wrow + PT_DOTS + 6, lane);
-    }
-    for (int lev = kPreLev; lev < c.n_merge; ++lev) {
-      double dots[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-      for (int j = 0; j < NCM; ++j) if (j < x.ncoord) coord_merge_dots(v, x.idx[j], lev, pn[j], minv[j], &nv[j], dots);
-      wave_sums_lds<6>(dots, rows, wrow + PT_DOTS + 6 * lev, lane);
-    }
-    if (!c.subtree_complete) {
-#pragma unroll
-      for (int j = 0; j < NCM; ++j) if (j < x.ncoord) coord_store_slot(v, x.idx[j], c.n_merge, pn[j], nv[j]);
-    } else {
-      double top[6] = {0, 0, 0, 0, 0, 0};
-#pragma unroll
-      for (int j = 0; j < NCM; ++j) if (j < x.ncoord) coord_top_dots(v, x.idx[j], c.dir, pn[j], minv[j], nv[j], top);
-      wave_sums_lds<6>(top, rows, wrow + PT_TOP, lane);
-    }
-    // ahead of the state machine: the constants of the position the next leaf evaluates if the tree goes on
-    if (ga.spec) gene_spec_consts<CM>(d, c, v, x, pn, gn, minv);
-  }
+  LdsSums r{part, rows, wrow, lane};
+  leaf_close<CM, kPreLev>(c, v, x, pn, minv, pre, r);
+  // ahead of the state machine: the constants of the position the next leaf evaluates if the tree goes on
+  if (ga.spec) gene_spec_consts<CM>(d, c, v, x, pn, gn, minv);
 }
 // after a workgroup barrier: the four wavefronts' partial sums -> the workgroup's row of the slab
 __device__ __forceinline__ void gene_block_finish(const Cmd& c, bool do_update, bool do_close, const double* wacc, double* slab, int tid) {
@@ -912,12 +793,7 @@ __device__ __forceinline__ void gene_block_finish(const Cmd& c, bool do_update, 
     if (tid == 0) slab[PT_T0] = ((wacc[0] + wacc[PT_COUNT]) + wacc[2 * PT_COUNT]) + wacc[3 * PT_COUNT];
     return;
   }
-  const int np = parts_used(c);
-  for (int k = tid; k < np; k += 256) {
-    if (k == PT_T0 && !do_update) continue;    // left by the round that applied the command
-    const bool used = k < 10 || (k >= PT_DOTS && k < PT_DOTS + 6 * c.n_merge) || (k >= PT_TOP && c.subtree_complete);
-    slab[k] = used ? ((wacc[k] + wacc[PT_COUNT + k]) + wacc[2 * PT_COUNT + k]) + wacc[3 * PT_COUNT + k] : 0.0;
-  }
+  slab_row_write(c, wacc, slab, tid, !do_update);
 }
 
 // Register budget of the two-column instantiation: 128 vector registers, four wavefronts per SIMD -- what a log-likelihood
@@ -974,9 +850,7 @@ __global__ __launch_bounds__(256) void ppcx_update_kernel(UpdateArgs a) {
   // kinetic energy of freshly drawn momenta: only commands that draw momenta leave something (the step kernel's reduce
   // phase reads the slab for exactly those commands)
   if ((nc.pre_flags & (PRE_NEW_TRANSITION | PRE_EPS_TRY)) == 0) return;
-  sT0[tid] = T0;
-  __syncthreads();
-  for (int stp = 128; stp > 0; stp >>= 1) { if (tid < stp) sT0[tid] += sT0[tid + stp]; __syncthreads(); }
+  tree_sum_256(T0, sT0, tid);
   if (tid == 0) a.t0_out[(long)chain * gridDim.x + blockIdx.x] = sT0[0];
 }
 
@@ -1158,23 +1032,25 @@ size_t loglik_lds_bytes(const Dims& d) {
     else if ((CM) <= 8) { if ((GEN) == 0) { auto k_ = KERNEL<8, 0>; EXPR; } else if ((GEN) == 1) { auto k_ = KERNEL<8, 1>; EXPR; } else { auto k_ = KERNEL<8, 2>; EXPR; } } \
     else { auto k_ = KERNEL<16, 0>; EXPR; }   /* 9 .. 16 columns: indicator designs only (ppcx_model_create refuses the others) */ \
   } while (0)
+// the instantiation of a kernel that has one per number of design columns only
+#define PPCX_BY_CM(KERNEL, CM) \
+  ((CM) <= 2 ? (const void*)KERNEL<2> : (CM) <= 4 ? (const void*)KERNEL<4> : (CM) <= 8 ? (const void*)KERNEL<8> : (const void*)KERNEL<16>)
 static const void* loglik_kernel_ptr(int CM, int gen) {
   const void* f = nullptr;
   PPCX_BY_CM_GEN(ppcx_loglik_kernel, CM, gen, f = (const void*)k_);
   return f;
 }
-int loglik_resident_workgroups_per_cu(int CM, const Dims& d) {
-  int n = 0;
-  const size_t lds_bytes = loglik_lds_bytes(d);
-  const int gen = loglik_generic_possible(d);
-  const void* f = loglik_kernel_ptr(CM, gen);
+// workgroups of 256 threads of kernel f that a CU holds with lds_bytes of dynamic LDS each (0: the query failed)
+static int resident_workgroups_per_cu(const void* f, size_t lds_bytes) {
   if (lds_bytes > 64u * 1024u) {               // more than the default limit of dynamic LDS: ask for it once
     if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) { (void)hipGetLastError(); return 0; }
   }
-  hipError_t e = hipSuccess;
-  PPCX_BY_CM_GEN(ppcx_loglik_kernel, CM, gen, e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_, 256, lds_bytes));
-  if (e != hipSuccess) { (void)hipGetLastError(); return 0; }
+  int n = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 256, lds_bytes) != hipSuccess) { (void)hipGetLastError(); return 0; }
   return n;
+}
+int loglik_resident_workgroups_per_cu(int CM, const Dims& d) {
+  return resident_workgroups_per_cu(loglik_kernel_ptr(CM, loglik_generic_possible(d)), loglik_lds_bytes(d));
 }
 hipError_t launch_loglik_kernel(int CM, const LoglikArgs& a, hipStream_t st) {
   const size_t lds_bytes = loglik_lds_bytes(a.d);
@@ -1184,12 +1060,9 @@ hipError_t launch_loglik_kernel(int CM, const LoglikArgs& a, hipStream_t st) {
   return hipLaunchKernel(loglik_kernel_ptr(CM, loglik_generic_possible(a.d)), grid, dim3(256), params, lds_bytes, st);
 }
 hipError_t launch_close_kernel(int CM, const CloseArgs& a, int nblocks, int nchains, hipStream_t st) {
-  const dim3 grid(nblocks, nchains);
-  if (CM <= 2) hipLaunchKernelGGL((ppcx_close_kernel<2>), grid, dim3(256), 0, st, a);
-  else if (CM <= 4) hipLaunchKernelGGL((ppcx_close_kernel<4>), grid, dim3(256), 0, st, a);
-  else if (CM <= 8) hipLaunchKernelGGL((ppcx_close_kernel<8>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((ppcx_close_kernel<16>), grid, dim3(256), 0, st, a);
-  return hipGetLastError();
+  CloseArgs args = a;
+  void* params[] = {&args};
+  return hipLaunchKernel(PPCX_BY_CM(ppcx_close_kernel, CM), dim3(nblocks, nchains), dim3(256), params, 0, st);
 }
 static const void* ls_kernel_ptr(int CM, int gen) {
   const void* f = nullptr;
@@ -1198,16 +1071,7 @@ static const void* ls_kernel_ptr(int CM, int gen) {
 }
 static size_t ls_lds_bytes(const Dims& d) { const size_t a = loglik_lds_bytes(d); return a > sizeof(StepShared) ? a : sizeof(StepShared); }
 int ls_resident_workgroups_per_cu(int CM, const Dims& d) {
-  int n = 0;
-  const size_t lds_bytes = ls_lds_bytes(d);
-  const int gen = loglik_generic_possible(d);
-  if (lds_bytes > 64u * 1024u) {
-    if (hipFuncSetAttribute(ls_kernel_ptr(CM, gen), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes) != hipSuccess) { (void)hipGetLastError(); return 0; }
-  }
-  hipError_t e = hipSuccess;
-  PPCX_BY_CM_GEN(ppcx_ls_kernel, CM, gen, e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, k_, 256, lds_bytes));
-  if (e != hipSuccess) { (void)hipGetLastError(); return 0; }
-  return n;
+  return resident_workgroups_per_cu(ls_kernel_ptr(CM, loglik_generic_possible(d)), ls_lds_bytes(d));
 }
 hipError_t launch_ls_kernel(int CM, const LoglikArgs& a, const StepArgs& sa, int n_srun, int n_chains_total, int spec, hipStream_t st,
                             hipEvent_t ev_start, hipEvent_t ev_stop) {
@@ -1223,12 +1087,9 @@ hipError_t launch_ls_kernel(int CM, const LoglikArgs& a, const StepArgs& sa, int
   return hipLaunchKernel(ls_kernel_ptr(CM, loglik_generic_possible(a.d)), grid, dim3(256), params, lds_bytes, st);
 }
 hipError_t launch_gene_kernel(int CM, const GeneArgs& a, int nblocks, int nchains, hipStream_t st) {
-  const dim3 grid(nblocks, nchains);
-  if (CM <= 2) hipLaunchKernelGGL((ppcx_gene_kernel<2>), grid, dim3(256), 0, st, a);
-  else if (CM <= 4) hipLaunchKernelGGL((ppcx_gene_kernel<4>), grid, dim3(256), 0, st, a);
-  else if (CM <= 8) hipLaunchKernelGGL((ppcx_gene_kernel<8>), grid, dim3(256), 0, st, a);
-  else hipLaunchKernelGGL((ppcx_gene_kernel<16>), grid, dim3(256), 0, st, a);
-  return hipGetLastError();
+  GeneArgs args = a;
+  void* params[] = {&args};
+  return hipLaunchKernel(PPCX_BY_CM(ppcx_gene_kernel, CM), dim3(nblocks, nchains), dim3(256), params, 0, st);
 }
 hipError_t launch_step_kernel(const StepArgs& a, int nblocks, int nchains, hipStream_t st) {
   hipLaunchKernelGGL(ppcx_step_kernel, dim3(a.upd_vecs ? nblocks : 1, nchains), dim3(256), 0, st, a);

@@ -62,14 +62,7 @@ static void gene_pass(const EmulModel& m, const Cmd& c, const VecRef& v, double*
     double pn[NCM], minv[NCM], part[10];
     gene_finish<CM>(d, c, v, x2, o, m.Sy.data(), m.SyE.data(), m.SyX.data(), m.SX.data(), m.ncell.data(), m.Lg1.data(), part, pn, minv);
     for (int k = 0; k < 10; ++k) red[k] += part[k];
-    if (c.type == CMD_LEAF) {
-      NodeVals nv[NCM];
-      for (int j = 0; j < NCM; ++j) nv[j] = NodeVals{pn[j], pn[j]};
-      for (int lev = 0; lev < c.n_merge; ++lev)
-        for (int j = 0; j < x2.ncoord; ++j) coord_merge_dots(v, x2.idx[j], lev, pn[j], minv[j], &nv[j], red + PT_DOTS + 6 * lev);
-      if (!c.subtree_complete) { for (int j = 0; j < x2.ncoord; ++j) coord_store_slot(v, x2.idx[j], c.n_merge, pn[j], nv[j]); }
-      else for (int j = 0; j < x2.ncoord; ++j) coord_top_dots(v, x2.idx[j], c.dir, pn[j], minv[j], nv[j], red + PT_TOP);
-    }
+    if (c.type == CMD_LEAF) { SerialSums r{red}; SlotPre<CM, 0> none; none.n = 0; leaf_close<CM, 0>(c, v, x2, pn, minv, none, r); }
   }
 }
 static void gene_pass_dispatch(const EmulModel& m, const Cmd& c, const VecRef& v, double* red) {
@@ -94,6 +87,25 @@ static double update_pass(const EmulModel& m, ChainState& st, const Cmd& ex, con
 struct EmulCfg { int chains, iter, warmup; unsigned long long seed; double adapt_delta; int max_treedepth;
                  double init_radius, stepsize0; int init_buffer, term_buffer, window, chain_id_offset; };
 
+static NutsConfig nuts_config(const EmulCfg& cfg) {
+  NutsConfig nc;
+  nc.chains = cfg.chains; nc.iter = cfg.iter; nc.warmup = cfg.warmup; nc.seed = cfg.seed;
+  nc.adapt_delta = cfg.adapt_delta; nc.max_treedepth = cfg.max_treedepth; nc.init_radius = cfg.init_radius;
+  nc.stepsize0 = cfg.stepsize0; nc.init_buffer = cfg.init_buffer; nc.term_buffer = cfg.term_buffer;
+  nc.window = cfg.window; nc.chain_id_offset = cfg.chain_id_offset;
+  return nc;
+}
+// chain ch's part of the fits' output arrays: draws [chains][nk][D], lp [chains][nk], diagnostics [chains][iter]
+static ChainIO chain_io(int ch, int nk, int D, int iter, double* draws, double* lp, double* stepsize, int* treedepth,
+                        int* n_leapfrog, int* divergent, double* accept) {
+  ChainIO io;
+  io.draws = draws + (size_t)ch * nk * D;
+  io.out.lp = lp + (size_t)ch * nk; io.out.stepsize = stepsize + (size_t)ch * iter;
+  io.out.treedepth = treedepth + (size_t)ch * iter; io.out.n_leapfrog = n_leapfrog + (size_t)ch * iter;
+  io.out.divergent = divergent + (size_t)ch * iter; io.out.accept = accept + (size_t)ch * iter;
+  return io;
+}
+
 // where the fits below leave each chain's inverse metric at its end ([chains][D], gene and hyper coordinates; null: nowhere)
 static double* g_minv_out = nullptr;
 extern "C" __attribute__((visibility("default")))
@@ -114,7 +126,8 @@ int emul_log_prob_grad(int G, int S, int C, int K, const int32_t* counts, const 
   std::vector<double> vecs((size_t)V_COUNT * D, 0.0), hv((size_t)V_COUNT * 8, 0.0), red(PT_COUNT, 0.0);
   for (int i = 0; i < D; ++i) { vecs[(size_t)V_Q1 * D + i] = u[i]; vecs[(size_t)V_MINV * D + i] = 1.0; }
   for (int k = 0; k < 6; ++k) { hv[V_Q1 * 8 + k] = u[hyper_index(m.d, k)]; hv[V_MINV * 8 + k] = 1.0; }
-  NutsConfig nc; memset(&nc, 0, sizeof nc); nc.chains = 1; nc.max_treedepth = 10; nc.adapt_delta = 0.8; nc.init_radius = 2; nc.stepsize0 = 1;
+  EmulCfg one; memset(&one, 0, sizeof one); one.chains = 1; one.max_treedepth = 10; one.adapt_delta = 0.8; one.init_radius = 2; one.stepsize0 = 1;
+  const NutsConfig nc = nuts_config(one);
   ChainState st; state_init(st, nc, 0, 1);
   Cmd c, n; cmd_clear(c);
   ChainIO io; memset(&io, 0, sizeof io);
@@ -137,10 +150,7 @@ int emul_fit_nuts(int G, int S, int C, int K, const int32_t* counts, const doubl
                   int* treedepth, int* n_leapfrog, int* divergent, double* accept) {
   EmulModel m = make_model(G, S, C, K, counts, X, expo, lmm, n_excl, excl);
   const int D = m.d.D, nk = cfg->iter - cfg->warmup;
-  NutsConfig nc; nc.chains = cfg->chains; nc.iter = cfg->iter; nc.warmup = cfg->warmup; nc.seed = cfg->seed;
-  nc.adapt_delta = cfg->adapt_delta; nc.max_treedepth = cfg->max_treedepth; nc.init_radius = cfg->init_radius;
-  nc.stepsize0 = cfg->stepsize0; nc.init_buffer = cfg->init_buffer; nc.term_buffer = cfg->term_buffer;
-  nc.window = cfg->window; nc.chain_id_offset = cfg->chain_id_offset;
+  const NutsConfig nc = nuts_config(*cfg);
   int rc = 0;
   for (int ch = 0; ch < cfg->chains; ++ch) {
     std::vector<double> vecs((size_t)V_COUNT * D, 0.0), hv((size_t)V_COUNT * 8, 0.0), red(PT_COUNT, 0.0);
@@ -148,11 +158,7 @@ int emul_fit_nuts(int G, int S, int C, int K, const int32_t* counts, const doubl
     for (int k = 0; k < 8; ++k) hv[V_MINV * 8 + k] = 1.0;
     ChainState st; state_init(st, nc, ch, 0);
     Cmd c, n; cmd_clear(c);
-    ChainIO io;
-    io.draws = draws + (size_t)ch * nk * D;
-    io.out.lp = lp + (size_t)ch * nk; io.out.stepsize = stepsize + (size_t)ch * cfg->iter;
-    io.out.treedepth = treedepth + (size_t)ch * cfg->iter; io.out.n_leapfrog = n_leapfrog + (size_t)ch * cfg->iter;
-    io.out.divergent = divergent + (size_t)ch * cfg->iter; io.out.accept = accept + (size_t)ch * cfg->iter;
+    const ChainIO io = chain_io(ch, nk, D, cfg->iter, draws, lp, stepsize, treedepth, n_leapfrog, divergent, accept);
     VecRef v{vecs.data(), D}, h{hv.data(), 8};
     double T0 = update_pass(m, st, c, red.data(), 0.0, false, v, h, io, n); c = n;
     long guard = 0;
@@ -198,12 +204,8 @@ static void pipelined_gene(const EmulModel& m, const Cmd& y, const VecRef& v, do
     gene_finish<CM>(d, y, v, x, o, m.Sy.data(), m.SyE.data(), m.SyX.data(), m.SX.data(), m.ncell.data(), m.Lg1.data(), part, pn, minv, gn);
     for (int k = 0; k < 10; ++k) if (k != PT_T0) red[k] += part[k];
     if (y.type == CMD_LEAF) {
-      NodeVals nv[NCM];
-      for (int j = 0; j < NCM; ++j) nv[j] = NodeVals{pn[j], pn[j]};
-      for (int lev = 0; lev < y.n_merge; ++lev)
-        for (int j = 0; j < x.ncoord; ++j) coord_merge_dots(v, x.idx[j], lev, pn[j], minv[j], &nv[j], red + PT_DOTS + 6 * lev);
-      if (!y.subtree_complete) { for (int j = 0; j < x.ncoord; ++j) coord_store_slot(v, x.idx[j], y.n_merge, pn[j], nv[j]); }
-      else for (int j = 0; j < x.ncoord; ++j) coord_top_dots(v, x.idx[j], y.dir, pn[j], minv[j], nv[j], red + PT_TOP);
+      SerialSums r{red}; SlotPre<CM, 0> none; none.n = 0;
+      leaf_close<CM, 0>(y, v, x, pn, minv, none, r);
       if (spec) gene_spec_consts<CM>(d, y, v, x, pn, gn, minv);
     }
   }
@@ -241,17 +243,10 @@ int emul_fit_nuts_pipelined(int G, int S, int C, int K, const int32_t* counts, c
                             long* carried) {
   EmulModel m = make_model(G, S, C, K, counts, X, expo, lmm, n_excl, excl);
   const int D = m.d.D, nk = cfg->iter - cfg->warmup;
-  NutsConfig nc; nc.chains = cfg->chains; nc.iter = cfg->iter; nc.warmup = cfg->warmup; nc.seed = cfg->seed;
-  nc.adapt_delta = cfg->adapt_delta; nc.max_treedepth = cfg->max_treedepth; nc.init_radius = cfg->init_radius;
-  nc.stepsize0 = cfg->stepsize0; nc.init_buffer = cfg->init_buffer; nc.term_buffer = cfg->term_buffer;
-  nc.window = cfg->window; nc.chain_id_offset = cfg->chain_id_offset;
+  const NutsConfig nc = nuts_config(*cfg);
   int rc = 0;
   for (int ch = 0; ch < cfg->chains; ++ch) {
-    ChainIO io;
-    io.draws = draws + (size_t)ch * nk * D;
-    io.out.lp = lp + (size_t)ch * nk; io.out.stepsize = stepsize + (size_t)ch * cfg->iter;
-    io.out.treedepth = treedepth + (size_t)ch * cfg->iter; io.out.n_leapfrog = n_leapfrog + (size_t)ch * cfg->iter;
-    io.out.divergent = divergent + (size_t)ch * cfg->iter; io.out.accept = accept + (size_t)ch * cfg->iter;
+    const ChainIO io = chain_io(ch, nk, D, cfg->iter, draws, lp, stepsize, treedepth, n_leapfrog, divergent, accept);
     rounds[ch] = 0; carried[ch] = 0;
     int r;
     if (m.CM == 2) r = pipelined_chain<2>(m, nc, ch, io, spec != 0, ls_first_s != 0, rounds + ch, carried + ch);
