@@ -246,6 +246,38 @@ PPCX_API int ppcx_fit_loo_predict_approx(ppcx_fit* f, int n_genes, const int32_t
 #define PPCX_PPC_EXACT_FIELDS 9     /* mean, sd, p_le, p_ge, lower, upper, y, excluded, outside */
 PPCX_API int ppcx_fit_ppc_exact(ppcx_fit* f, int n_genes, const int32_t* genes, double truncation_compensation, double p_lo,
                                 double p_hi, double* out);
+/* The exact leave-one-out predictive tail probabilities and interval per cell of the checked genes of a NUTS fit: the fourth
+ * corner beside ppcx_fit_ppc (sampled, posterior), ppcx_fit_ppc_exact (exact, posterior) and ppcx_fit_loo_predict (sampled,
+ * leave-one-out). Given kept draw i the count of the cell is neg_binomial_2_log(eta_i, phi_i) as in ppcx_fit_ppc_exact, and draw i
+ * carries the PSIS weight w_i of ppcx_fit_loo_predict's cell (the same ratios, tail, tie rule and normalisation; the truncation
+ * compensation scales the predictive distribution only, never the likelihood behind the weights), so the leave-one-out
+ * predictive cdf of the cell is the weighted average of negative-binomial cdfs. Nothing is sampled: a tail probability that
+ * PSIS rests on a few heavy draws is not decided by as many sampled integers. In R: loo::E_loo on the draws' exact cdfs; no
+ * function of loo or bayesplot does it. Restated from the published definitions, not run against R.
+ * NUTS fits only (an ADVI fit: ppcx_fit_loo_predict_exact_approx; a ppcx_fit_from_draws fit holds the draws of a NUTS fit and
+ * is taken as one). genes: n_genes ids of checked genes (0 .. K - 1); r_eff NULL (all 1) or [n_genes][S] as ppcx_fit_loo.
+ * PPCX_ERR_ARG unless 0 < p_lo < p_hi < 1, truncation_compensation is finite and > 0, every gene is a checked one and every
+ * r_eff is finite and > 0; tail limit as ppcx_fit_loo. Synchronous on the model's stream; the same bits on every call, for any
+ * gene subset.
+ *   out [n_genes][S][PPCX_LOO_EXACT_FIELDS]:
+ *   mean = sum w_i mu_i;  sd = sqrt(sum w_i (mu_i + mu_i^2 / phi_i) + sum w_i (mu_i - mean)^2);
+ *   p_le = sum w_i P_i(X <= y), p_ge = sum w_i P_i(X >= y): the two ends of the randomised LOO-PIT of the observed count y are
+ *   1 - p_ge and p_le;
+ *   lower, upper = the smallest integers k with F(k) >= p_lo, p_hi, F the weighted cdf, by ppcx_fit_ppc_exact's search;
+ *   y;  excluded (0 / 1);  outside = (y < lower) | (y > upper) as 0 / 1;
+ *   khat: ppcx_fit_loo_predict's khat of the cell, bit for bit (above 0.7 the weights are not to be trusted).
+ *   A cell excluded by the model at the time of the call is already held out: uniform weights, its first nine fields are
+ *   ppcx_fit_ppc_exact's bit for bit, khat = NaN. A draw with invalid parameters, a NaN log_lik or one of -Inf (a ratio of +Inf)
+ *   in a cell that is not excluded: every statistic of the cell is NaN (y and excluded are still reported).                   */
+#define PPCX_LOO_EXACT_FIELDS 10    /* mean, sd, p_le, p_ge, lower, upper, y, excluded, outside, khat */
+PPCX_API int ppcx_fit_loo_predict_exact(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff,
+                                        double truncation_compensation, double p_lo, double p_hi, double* out);
+/* ppcx_fit_loo_predict_exact for an ADVI fit: the same fields under the normalised weights of ppcx_fit_loo_approx (ratios
+ * (log_p - log_g) - log_lik on the cached log_p - log_g, r_eff = 1). A cell excluded by the model is weighted too (by
+ * log_p - log_g; it has no uniform path, and its khat is the overall k-hat). A NUTS fit, or one made by ppcx_fit_from_draws:
+ * PPCX_ERR_ARG (theirs is ppcx_fit_loo_predict_exact). Genes, probabilities and truncation compensation as above.             */
+PPCX_API int ppcx_fit_loo_predict_exact_approx(ppcx_fit* f, int n_genes, const int32_t* genes, double truncation_compensation,
+                                               double p_lo, double p_hi, double* out);
 /* lp: [chains][n_keep]; the rest [chains][iter] (warmup included); any pointer may be NULL */
 PPCX_API int ppcx_fit_get_diagnostics(ppcx_fit* f, double* lp, double* stepsize, int32_t* treedepth,
                              int32_t* n_leapfrog, int32_t* divergent, double* accept);

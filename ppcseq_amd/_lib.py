@@ -26,7 +26,7 @@ EXPORTS = [
     "ppcx_fit_nuts_xchg", "ppcx_fit_get_xchg_timing", "ppcx_fit_get_inv_metric", "ppcx_fit_summary",
     "ppcx_fit_get_approximation", "ppcx_fit_get_log_ratios", "ppcx_fit_psis", "ppcx_fit_get_log_lik", "ppcx_fit_loo",
     "ppcx_fit_loo_predict", "ppcx_fit_relative_eff", "ppcx_fit_loo_mcse", "ppcx_fit_loo_approx", "ppcx_fit_loo_predict_approx",
-    "ppcx_fit_ppc_exact",
+    "ppcx_fit_ppc_exact", "ppcx_fit_loo_predict_exact", "ppcx_fit_loo_predict_exact_approx",
 ]
 ABI_VERSION = 400           # include/ppcx.h PPCX_VERSION this binding was written for
 SUMMARY_FIELDS = ("mean", "sd", "q05", "q50", "q95", "rhat", "ess_bulk", "ess_tail")   # PPCX_SUMMARY_FIELDS, in order
@@ -34,6 +34,7 @@ LOO_FIELDS = ("elpd_loo", "p_loo", "looic", "khat")                             
 LOO_MCSE_FIELDS = LOO_FIELDS + ("mcse_elpd_loo", "n_eff")                                # PPCX_LOO_MCSE_FIELDS, in order
 LOO_PREDICT_FIELDS = ("mean", "lower", "upper", "pit_lt", "pit_le", "khat")              # PPCX_LOO_PREDICT_FIELDS, in order
 PPC_EXACT_FIELDS = ("mean", "sd", "p_le", "p_ge", "lower", "upper", "y", "excluded", "outside")   # PPCX_PPC_EXACT_FIELDS, in order
+LOO_EXACT_FIELDS = PPC_EXACT_FIELDS + ("khat",)                                          # PPCX_LOO_EXACT_FIELDS, in order
 
 
 class PpcxError(RuntimeError):
@@ -112,6 +113,8 @@ def load() -> C.CDLL:
     lib.ppcx_fit_loo_approx.argtypes = [C.c_void_p, C.c_int, ip, dp]
     lib.ppcx_fit_loo_predict_approx.argtypes = [C.c_void_p, C.c_int, ip, C.c_double, C.c_double, C.c_double, C.c_ulonglong, dp]
     lib.ppcx_fit_ppc_exact.argtypes = [C.c_void_p, C.c_int, ip, C.c_double, C.c_double, C.c_double, dp]
+    lib.ppcx_fit_loo_predict_exact.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_double, C.c_double, C.c_double, dp]
+    lib.ppcx_fit_loo_predict_exact_approx.argtypes = [C.c_void_p, C.c_int, ip, C.c_double, C.c_double, C.c_double, dp]
     lib.ppcx_fit_get_diagnostics.argtypes = [C.c_void_p, dp, dp, ip, ip, ip, dp]
     lib.ppcx_fit_get_timing.argtypes = [C.c_void_p, dp, C.POINTER(C.c_longlong), dp, C.POINTER(C.c_longlong), dp]
     lib.ppcx_fit_get_kernel_times.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(C.c_longlong)]
@@ -155,6 +158,8 @@ def load() -> C.CDLL:
         lib.ppcx_testing_relative_eff.argtypes = [C.c_int, C.c_int, C.c_int, dp, dp]
     if hasattr(lib, "ppcx_testing_ppc_exact"):
         lib.ppcx_testing_ppc_exact.argtypes = [C.c_int, C.c_int, dp, dp, ip, ip, C.c_double, C.c_double, C.c_double, dp]
+    if hasattr(lib, "ppcx_testing_loo_exact"):
+        lib.ppcx_testing_loo_exact.argtypes = [C.c_int, C.c_int, dp, dp, dp, ip, ip, dp, dp, C.c_double, C.c_double, C.c_double, dp]
     lib.ppcx_fit_free.restype = None
     lib.ppcx_advi_config_default.argtypes = [C.POINTER(AdviConfig)]
     lib.ppcx_advi_config_default.restype = None
@@ -386,6 +391,46 @@ def testing_ppc_exact(eta, sigma_raw, y, excluded=None, truncation_compensation=
                                       _p(ex, C.c_int32) if ex is not None else None, float(truncation_compensation), float(p_lo),
                                       float(p_hi), _p(out, C.c_double)))
     return out if raw else _ppc_exact_dict(out)
+
+
+def _loo_exact_dict(out):
+    """[.., LOO_EXACT_FIELDS] as the dict of Fit.loo_predict_exact: _ppc_exact_dict's keys and dtypes, khat, and the two ends of
+    the randomised LOO-PIT under Fit.loo_predict's names: pit_lt = 1 - p_ge, pit_le = p_le"""
+    res = _ppc_exact_dict(out)
+    res["khat"] = out[..., len(PPC_EXACT_FIELDS)].copy()
+    res["pit_lt"] = 1.0 - res["p_ge"]
+    res["pit_le"] = res["p_le"].copy()
+    return res
+
+
+def testing_loo_exact(ll, eta, sigma_raw, y, excluded=None, r_eff=None, log_ratio=None, truncation_compensation=1.0, p_lo=0.025,
+                      p_hi=0.975, raw=False):
+    """The kernel of ppcx_fit_loo_predict_exact on host-given columns (testing build only; csrc/ppcx_testing.h
+    ppcx_testing_loo_exact): ll, eta, sigma_raw [n_draws, n_cells], y [n_cells] observed counts, excluded / r_eff None or
+    [n_cells]; log_ratio None, or [n_draws] (log_p - log_g of the draws): the kernel as ppcx_fit_loo_predict_exact_approx runs it.
+    Returns Fit.loo_predict_exact's dict of [n_cells] arrays, or with raw=True the [n_cells, 10] doubles as the kernel wrote them."""
+    lib = load()
+    if not hasattr(lib, "ppcx_testing_loo_exact"):
+        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before ppcx_testing_loo_exact existed: rebuild it "
+                        "(`python -m ppcseq_amd.build --testing --force`)")
+    ll = np.asarray(ll, dtype=np.float64)
+    ll = ll.reshape(ll.shape[0], -1)
+    n, nc = ll.shape
+    lc = np.ascontiguousarray(ll.T)
+    ec = np.ascontiguousarray(np.asarray(eta, dtype=np.float64).reshape(n, nc).T)
+    sc = np.ascontiguousarray(np.asarray(sigma_raw, dtype=np.float64).reshape(n, nc).T)
+    ys = np.ascontiguousarray(np.broadcast_to(np.asarray(y), (nc,)), dtype=np.int32)
+    ex = None if excluded is None else np.ascontiguousarray(excluded, dtype=np.int32).ravel()
+    re = None if r_eff is None else np.ascontiguousarray(np.broadcast_to(np.asarray(r_eff, dtype=np.float64), (nc,)))
+    lr = None if log_ratio is None else np.ascontiguousarray(log_ratio, dtype=np.float64).ravel()
+    if lr is not None and lr.size != n:
+        raise ValueError("log_ratio must hold one value per draw")
+    out = np.zeros((nc, len(LOO_EXACT_FIELDS)))
+    _check(lib.ppcx_testing_loo_exact(n, nc, _p(lc, C.c_double), _p(ec, C.c_double), _p(sc, C.c_double), _p(ys, C.c_int32),
+                                      _p(ex, C.c_int32) if ex is not None else None, _p(re, C.c_double) if re is not None else None,
+                                      _p(lr, C.c_double) if lr is not None else None, float(truncation_compensation), float(p_lo),
+                                      float(p_hi), _p(out, C.c_double)))
+    return out if raw else _loo_exact_dict(out)
 
 
 def loo_estimates(pointwise, excluded):
@@ -859,6 +904,41 @@ class Fit:
         res = _ppc_exact_dict(out)
         res["genes"] = g.astype(np.int64)
         res["n_draws"] = self.chains * self.n_keep
+        return res
+
+    def _loo_exact(self, genes, r_eff, call):
+        """What the two exact leave-one-out forms share: call(n_genes, genes, r_eff or None, out) fills [n_genes, S, 10]"""
+        g = np.ascontiguousarray(np.arange(self.model.K) if genes is None else np.asarray(genes, dtype=np.int64).ravel(), dtype=np.int32)
+        out = np.zeros((g.size, self.model.S, len(LOO_EXACT_FIELDS)))
+        re = self._r_eff(g, r_eff)
+        if g.size:
+            _check(call(int(g.size), _p(g, C.c_int32), _p(re, C.c_double) if re is not None else None, _p(out, C.c_double)))
+        res = _loo_exact_dict(out)
+        res["genes"] = g.astype(np.int64)
+        res["n_draws"] = self.chains * self.n_keep
+        if isinstance(r_eff, str):
+            res["r_eff"] = re
+        return res
+
+    def loo_predict_exact(self, genes=None, r_eff=None, p_lo=0.025, p_hi=0.975, truncation_compensation=1.0):
+        """The exact leave-one-out predictive tail probabilities and interval per cell of checked genes of a NUTS fit on the device
+        (ppcx_fit_loo_predict_exact): the predictive cdf of a cell under the posterior that has not seen it is the average of the
+        draws' negative-binomial cdfs under Fit.loo_predict's PSIS weights, so nothing is sampled -- what Fit.loo_predict
+        estimates from one drawn count per draw (in R: loo::E_loo on exact cdfs; restated from the published definitions, not
+        run against R). Fit.ppc_exact's dict of [n_genes, S] arrays (mean, sd, p_le, p_ge, lower, upper, y, excluded, outside,
+        `genes`, `n_draws`) under those weights, plus khat (Fit.loo_predict's, bit for bit) and the two ends of the randomised
+        LOO-PIT, pit_lt = 1 - p_ge and pit_le = p_le. A cell the model excludes is already held out: Fit.ppc_exact's values,
+        khat NaN. genes=None: all K checked genes (ids 0 .. K - 1); r_eff as Fit.loo_predict ("auto" adds `r_eff`)."""
+        return self._loo_exact(genes, r_eff, lambda n, g, re, out: load().ppcx_fit_loo_predict_exact(
+            self._h, n, g, re, float(truncation_compensation), float(p_lo), float(p_hi), out))
+
+    def loo_predict_exact_approximate_posterior(self, genes=None, p_lo=0.025, p_hi=0.975, truncation_compensation=1.0):
+        """Fit.loo_predict_exact for an ADVI fit (ppcx_fit_loo_predict_exact_approx): the same dict (without r_eff) under the
+        weights of loo_approximate_posterior, and `khat_approximation`, the overall k-hat of the approximation. An excluded cell
+        is weighted too (by log_p - log_g); its khat is the overall k-hat."""
+        res = self._loo_exact(genes, None, lambda n, g, re, out: load().ppcx_fit_loo_predict_exact_approx(
+            self._h, n, g, float(truncation_compensation), float(p_lo), float(p_hi), out))
+        res["khat_approximation"] = float(self.psis(cols=[], overall=True)["khat"][-1])
         return res
 
     def diagnostics(self):

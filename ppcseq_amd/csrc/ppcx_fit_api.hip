@@ -1,5 +1,5 @@
 // ppcx_fit_api.hip -- what is read from a fit: its release, a fit over draws made elsewhere, draws, columns, summary, diagnostics
-// and timings, the per-cell diagnostics (PSIS-LOO, LOO predictive, relative efficiency, exact posterior-predictive tails) with
+// and timings, the per-cell diagnostics (PSIS-LOO, LOO predictive, relative efficiency, exact posterior- and LOO-predictive tails) with
 // their testing twins, and the posterior-predictive check.
 #include <math.h>
 #include <string.h>
@@ -291,6 +291,58 @@ extern "C" int ppcx_testing_ppc_exact(int n, int n_cols, const double* eta, cons
   GivenCells gc;
   gc.cols = eta; gc.n = n; gc.n_cols = n_cols; gc.excl = excluded;
   return hip_done(nullptr, ppc_exact_columns(gc, sigma_raw, y, truncation_compensation, p_lo, p_hi, out, loo_scratch_bytes(), nullptr));
+}
+#endif
+// ---- the exact leave-one-out predictive tails and interval of the checked genes' cells (ppcx_loo_exact.h): the weights of
+// ppcx_fit_loo_predict / ppcx_fit_loo_predict_approx on the negative-binomial cdfs of ppcx_fit_ppc_exact
+static int loo_exact_check(const ppcx_fit* f, int n_genes, const int32_t* genes, double truncation_compensation, double p_lo,
+                           double p_hi) {
+  if (!genes || n_genes < 1) return fail(PPCX_ERR_ARG, "bad arguments");
+  const int K = f->m->d.K;
+  for (int i = 0; i < n_genes; ++i) if (genes[i] < 0 || genes[i] >= K) return fail(PPCX_ERR_ARG, "gene out of range (a checked gene: 0 .. K - 1)");
+  return ppc_exact_check(truncation_compensation, p_lo, p_hi);
+}
+extern "C" int ppcx_fit_loo_predict_exact(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff,
+                                          double truncation_compensation, double p_lo, double p_hi, double* out) {
+  const char* who = "ppcx_fit_loo_predict_exact";
+  if (!f) return fail(PPCX_ERR_ARG, "fit is NULL");
+  if (f->advi) return fail(PPCX_ERR_ARG, std::string(who) + " needs the draws of a NUTS fit: the exact leave-one-out intervals of "
+                                                             "an ADVI fit are ppcx_fit_loo_predict_exact_approx");
+  int rc = loo_exact_check(f, n_genes, genes, truncation_compensation, p_lo, p_hi);
+  if (rc != PPCX_OK) return rc;
+  std::vector<int> yenc; FitCells fc;
+  if ((rc = loo_prepare_cells(f, n_genes, genes, out, yenc, fc)) != PPCX_OK) return rc;
+  if ((rc = loo_fit_reff(who, fc, r_eff)) != PPCX_OK) return rc;
+  return hip_done(who, loo_exact_fit_cells(fc, truncation_compensation, p_lo, p_hi, out, loo_scratch_bytes(), f->m->stream.s));
+}
+extern "C" int ppcx_fit_loo_predict_exact_approx(ppcx_fit* f, int n_genes, const int32_t* genes, double truncation_compensation,
+                                                 double p_lo, double p_hi, double* out) {
+  const char* who = "ppcx_fit_loo_predict_exact_approx";
+  if (!f) return fail(PPCX_ERR_ARG, "fit is NULL");
+  if (!f->advi || !f->d_mu.p)
+    return fail(PPCX_ERR_ARG, std::string(who) + " needs an ADVI fit: a NUTS fit, or one over draws produced elsewhere, holds no "
+                                                 "approximation to correct for (theirs is ppcx_fit_loo_predict_exact)");
+  int rc = loo_exact_check(f, n_genes, genes, truncation_compensation, p_lo, p_hi);
+  if (rc != PPCX_OK) return rc;
+  std::vector<int> yenc; FitCells fc;
+  if ((rc = loo_approx_prepare(who, f, n_genes, genes, out, yenc, fc)) != PPCX_OK) return rc;
+  if ((rc = loo_approx_ratios(f, fc)) != PPCX_OK) return rc;
+  return hip_done(who, loo_exact_fit_cells(fc, truncation_compensation, p_lo, p_hi, out, loo_scratch_bytes(), f->m->stream.s));
+}
+#ifdef PPCX_TESTING
+// testing build only (ppcx_testing.h): the kernel of the two above on host-given columns, on the current device
+extern "C" int ppcx_testing_loo_exact(int n, int n_cols, const double* ll, const double* eta, const double* sigma_raw, const int32_t* y,
+                                      const int32_t* excluded, const double* r_eff, const double* log_ratio,
+                                      double truncation_compensation, double p_lo, double p_hi, double* out) {
+  if (n < 1 || n_cols < 1 || !ll || !eta || !sigma_raw || !y || !out) return fail(PPCX_ERR_ARG, "bad arguments");
+  for (int i = 0; i < n_cols; ++i) if (y[i] < 0) return fail(PPCX_ERR_ARG, "counts must be >= 0");
+  if (log_ratio && r_eff) return fail(PPCX_ERR_ARG, "log_ratio takes r_eff = NULL (the draws of an approximation are independent)");
+  int rc = ppc_exact_check(truncation_compensation, p_lo, p_hi);
+  if (rc != PPCX_OK) return rc;
+  GivenCells gc;
+  gc.cols = ll; gc.n = n; gc.n_cols = n_cols; gc.excl = excluded; gc.r_eff = r_eff; gc.log_ratio = log_ratio;
+  if ((rc = loo_reff_limits(nullptr, r_eff, n_cols, n, &gc.r_eff_min)) != PPCX_OK) return rc;
+  return hip_done(nullptr, loo_exact_columns(gc, eta, sigma_raw, y, truncation_compensation, p_lo, p_hi, out, loo_scratch_bytes(), nullptr));
 }
 #endif
 // ---- the relative efficiency of the same cells (loo::relative_eff(exp(log_lik), chain_id): what rstan::loo(fit) passes as r_eff)

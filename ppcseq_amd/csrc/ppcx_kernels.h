@@ -286,6 +286,15 @@ hipError_t ppc_exact_fit_cells(const FitCells& fc, double tc, double p_lo, doubl
 // ... of given columns: gc.cols the linear predictors [n_cols][n], sigma_raw [n_cols][n], y [n_cols] the observed counts
 hipError_t ppc_exact_columns(const GivenCells& gc, const double* sigma_raw, const int* y, double tc, double p_lo, double p_hi,
                              double* out, size_t scratch_bytes, hipStream_t st);
+// The exact leave-one-out predictive tails and interval of the same cells (ppcx_loo_exact.hip, statistic in ppcx_loo_exact.h): one
+// workgroup per cell; ratio / eta, weight and ln phi of the draws (24 bytes per draw) in LDS up to kPsisLdsDraws draws, beyond
+// that in the scratch. tc: truncation compensation. out [cells][kLooExactFields]. With log_ratio the weights are those of
+// ppcx_loo_ap.h
+hipError_t loo_exact_fit_cells(const FitCells& fc, double tc, double p_lo, double p_hi, double* out, size_t scratch_bytes,
+                               hipStream_t st);
+// ... of given columns: gc.cols the log-likelihoods [n_cols][n], eta and sigma_raw [n_cols][n], y [n_cols] the observed counts
+hipError_t loo_exact_columns(const GivenCells& gc, const double* eta, const double* sigma_raw, const int* y, double tc, double p_lo,
+                             double p_hi, double* out, size_t scratch_bytes, hipStream_t st);
 // The relative efficiency of the same cells (ppcx_reff.hip, statistic in ppcx_reff.h): one workgroup per cell; the split values
 // (8 bytes each) in LDS for fits of up to kPsisLdsDraws draws, beyond that in the scratch. Of `l` it uses T / y / expo / X / S / C
 // or cols, n = chains n_keep, cell0, n_cells, scratch ([launch's cells][2 chains (n_keep / 2)]) and out ([cells], one value

@@ -78,6 +78,14 @@ PPCX_API int ppcx_testing_relative_eff(int chains, int n, int n_cols, const doub
  * [n_cols] flags; out [n_cols][9]: mean, sd, p_le, p_ge, lower, upper, y, excluded, outside. */
 PPCX_API int ppcx_testing_ppc_exact(int n, int n_cols, const double* eta, const double* sigma_raw, const int32_t* y,
                                     const int32_t* excluded, double truncation_compensation, double p_lo, double p_hi, double* out);
+/* The kernel of ppcx_fit_loo_predict_exact on host-given columns, on the current device (ppcx_loo_exact.hip): ll, eta and sigma_raw
+ * [n_cols][n] (a cell's n draws contiguous; ll need not be the log-pmf of y at eta and sigma_raw), y [n_cols] the observed counts
+ * (>= 0), excluded NULL or [n_cols] flags, r_eff NULL or [n_cols]; log_ratio NULL, or [n] the draws' log_p - log_g: the kernel as
+ * ppcx_fit_loo_predict_exact_approx runs it (r_eff then NULL). Probabilities and truncation compensation as the entry points
+ * check them. out [n_cols][10]: mean, sd, p_le, p_ge, lower, upper, y, excluded, outside, khat. */
+PPCX_API int ppcx_testing_loo_exact(int n, int n_cols, const double* ll, const double* eta, const double* sigma_raw, const int32_t* y,
+                                    const int32_t* excluded, const double* r_eff, const double* log_ratio,
+                                    double truncation_compensation, double p_lo, double p_hi, double* out);
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,8 @@ class InferenceResult:
     approximation_loo: dict | None = None            # check_approximation_loo: Fit.loo_approximate_posterior of those cells
     exact_intervals: dict | None = None  # exact_intervals: Fit.ppc_exact of the checked genes' cells ([K, S] arrays)
     approximation_loo_intervals: dict | None = None  # check_approximation_loo_intervals: Fit.loo_predict_approximate_posterior
+    exact_loo_intervals: dict | None = None  # exact_loo_intervals: Fit.loo_predict_exact of the checked genes' cells ([K, S] arrays)
+    exact_approximation_loo_intervals: dict | None = None  # ...: Fit.loo_predict_exact_approximate_posterior of those cells
 
     def to_frame(self):
         import pandas as pd
@@ -267,6 +269,10 @@ CHECKS = (          # in the order of the reads
           "check_approximation_loo_intervals needs an ADVI pass (approximate_posterior_inference = True): the leave-one-out "
           "intervals of a NUTS pass are check_loo_intervals",
           lambda fit, ctx: fit.loo_predict_approximate_posterior(np.arange(ctx.K), seed=ctx.seed, **_interval(ctx))),
+    Check("exact_approximation_loo_intervals", "exact_approximation_loo_intervals", 9, "advi", False, False,
+          "exact_approximation_loo_intervals needs an ADVI pass (approximate_posterior_inference = True): the exact leave-one-out "
+          "intervals of a NUTS pass are exact_loo_intervals",
+          lambda fit, ctx: fit.loo_predict_exact_approximate_posterior(np.arange(ctx.K), **_interval(ctx))),
     Check("check_convergence", "convergence", 1, "nuts", True, False,
           "check_convergence needs a NUTS pass: the draws of an ADVI fit are independent (rstan::vb reports no R-hat or ESS)",
           lambda fit, ctx: fit.summary(_alpha_sub_1(fit, ctx.K), lp=not ctx.pooled),
@@ -280,11 +286,15 @@ CHECKS = (          # in the order of the reads
           lambda fit, ctx: fit.loo_predict(np.arange(ctx.K), r_eff=ctx.loo_r_eff, seed=ctx.seed, **_interval(ctx))),
     Check("exact_intervals", "exact_intervals", 7, None, True, False, None,
           lambda fit, ctx: fit.ppc_exact(np.arange(ctx.K), **_interval(ctx))),
+    Check("exact_loo_intervals", "exact_loo_intervals", 8, "nuts", True, False,
+          "exact_loo_intervals needs a NUTS pass: the exact leave-one-out intervals of an ADVI fit (loo_approximate_posterior) are "
+          "exact_approximation_loo_intervals",
+          lambda fit, ctx: fit.loo_predict_exact(np.arange(ctx.K), r_eff=ctx.loo_r_eff, **_interval(ctx))),
 )
 
 MODIFIERS = (       # (option, the options of which it needs one, what it is told without one)
-    ("loo_r_eff", ("check_loo", "check_loo_intervals"),
-     "loo_r_eff needs check_loo or check_loo_intervals: it is the r_eff of their PSIS"),
+    ("loo_r_eff", ("check_loo", "check_loo_intervals", "exact_loo_intervals"),
+     "loo_r_eff needs check_loo, check_loo_intervals or exact_loo_intervals: it is the r_eff of their PSIS"),
     ("loo_mcse", ("check_loo",),
      "loo_mcse needs check_loo: it adds the Monte-Carlo standard error and n_eff to its PSIS-LOO"),
 )
@@ -350,7 +360,9 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                  loo_mcse=False,
                  check_approximation_loo=False,
                  check_approximation_loo_intervals=False,
-                 exact_intervals=False):
+                 exact_intervals=False,
+                 exact_loo_intervals=False,
+                 exact_approximation_loo_intervals=False):
     """One inference pass (discovery or test) of ppcseq on the GPU.
 
     counts            G x S integer matrix, genes ordered with the `how_many_to_check` checked genes first
@@ -382,10 +394,11 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                       interval probabilities, seed and truncation compensation, kept as `res.loo_intervals`. It raises no
                       warning (the k-hat warnings are check_loo's) and changes no flag. devices=[...]: over the pooled chains.
                       Not for an ADVI pass.
-    loo_r_eff         None: check_loo and check_loo_intervals take r_eff = 1 (loo::loo(log_lik)). "auto": the relative efficiency
-                      of every checked cell from the fit's own chains on the device (Fit.relative_eff; 1 where it is not
-                      defined), as rstan::loo(fit) does; the results then carry it as `r_eff`. devices=[...]: over the pooled
-                      chains (the split is the same). Needs check_loo or check_loo_intervals.
+    loo_r_eff         None: check_loo, check_loo_intervals and exact_loo_intervals take r_eff = 1 (loo::loo(log_lik)). "auto": the
+                      relative efficiency of every checked cell from the fit's own chains on the device (Fit.relative_eff; 1
+                      where it is not defined), as rstan::loo(fit) does; the results then carry it as `r_eff`. devices=[...]:
+                      over the pooled chains (the split is the same). Needs check_loo, check_loo_intervals or
+                      exact_loo_intervals.
     loo_mcse          True: `res.loo` also carries loo's pointwise `mcse_elpd_loo` and `n_eff` of every checked cell and
                       `mcse_elpd_loo_total` (Fit.loo(mcse=True); pareto_k_table reads it). It raises no further warning.
                       devices=[...]: over the pooled chains. Needs check_loo.
@@ -400,6 +413,15 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                       average over the kept draws of negative-binomial cdfs, nothing sampled) at the pass's interval
                       probabilities and truncation compensation, kept as `res.exact_intervals`. NUTS and ADVI passes;
                       devices=[...]: over the pooled chains. Reported, not acted on: the flags stay those of the sampled intervals.
+    exact_loo_intervals  the exact leave-one-out predictive tail probabilities and interval of every checked cell
+                      (Fit.loo_predict_exact: the average of the draws' negative-binomial cdfs under check_loo_intervals' PSIS
+                      weights, nothing sampled; khat and the two ends of the LOO-PIT beside them) at the pass's interval
+                      probabilities and truncation compensation, kept as `res.exact_loo_intervals`. It raises no warning (the
+                      k-hat warnings are check_loo's) and changes no flag. devices=[...]: over the pooled chains. Not for an ADVI
+                      pass.
+    exact_approximation_loo_intervals  exact_loo_intervals for an ADVI pass, under the weights of check_approximation_loo
+                      (Fit.loo_predict_exact_approximate_posterior), kept as `res.exact_approximation_loo_intervals`. No
+                      warning, no flag changes. Not for a NUTS pass.
     Returns an InferenceResult.
     """
     counts = np.asarray(counts)
