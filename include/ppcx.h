@@ -174,6 +174,26 @@ PPCX_API int ppcx_fit_loo(ppcx_fit* f, int n_genes, const int32_t* genes, const 
  * both. The same bits on every call, whatever other genes are requested.                                                       */
 #define PPCX_LOO_MCSE_FIELDS 6  /* elpd_loo, p_loo, looic, khat, mcse_elpd_loo, n_eff */
 PPCX_API int ppcx_fit_loo_mcse(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double* out);
+/* ppcx_fit_loo with a second attempt at the cells whose khat exceeds k_threshold: importance-weighted moment matching (Paananen,
+ * Piironen, Buerkner, Vehtari 2021; loo::loo_moment_match), applied to the coordinates of the cell's own gene only -- intercept,
+ * slopes of a checked gene, sigma_raw -- because given the hyper-parameters the posterior factorises over the genes: the affine
+ * transform changes the log posterior by the gene's own likelihood and prior terms, so neither the full log density nor lp__ is
+ * needed (a ppcx_fit_from_draws fit is served). A deliberate deviation from loo, which transforms every coordinate; restated from
+ * the paper, not run against R. Per cell above the threshold, at most max_iters times: the draws of the gene are shifted to their
+ * weighted mean, or, if that does not lower khat, shifted and scaled to their weighted mean and variance; a step is kept only if
+ * the cell's PSIS khat on the new ratios is strictly lower. No covariance step (loo's default), no split transformation: a
+ * matched khat is necessary, not sufficient, and no mcse / n_eff is given for a matched cell.
+ * Fits, genes, r_eff, limits and refusals as ppcx_fit_loo (an ADVI fit: PPCX_ERR_ARG, moment matching under the weights of
+ * loo_approximate_posterior is not available); also PPCX_ERR_ARG for a k_threshold that is not finite or max_iters < 0.
+ * out [n_genes][S][PPCX_LOO_MM_FIELDS(C)]: elpd_loo, p_loo (lpd of the original draws - elpd_loo), looic, khat (the final one),
+ * khat_before (plain PSIS's), iterations (accepted steps), then scale[C + 1] and shift[C + 1] of the gene's coordinates in the
+ * order intercept, slopes, sigma_raw: the matched draws are scale * draw + shift (a row the gene does not have: 1 and 0). A cell
+ * that is excluded, NaN, at or below the threshold, run with max_iters = 0, or on which no step was accepted holds
+ * ppcx_fit_loo's four fields bit for bit, khat_before = khat, iterations 0, scale 1, shift 0. The same bits on every call,
+ * whatever other genes are requested.                                                                                          */
+#define PPCX_LOO_MM_FIELDS(C) (6 + 2 * ((C) + 1))
+PPCX_API int ppcx_fit_loo_moment_match(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double k_threshold,
+                                       int max_iters, double* out);
 /* The relative efficiency of the importance ratios per observed cell of a NUTS fit: what rstan::loo(fit) passes to loo::loo as
  * r_eff, loo::relative_eff(exp(log_lik), chain_id), so that ppcx_fit_loo / ppcx_fit_loo_predict with it report what rstan::loo(fit)
  * does without the log-likelihood matrix ever leaving the device. Fits, genes and refusals as ppcx_fit_loo; more than 128 chains:

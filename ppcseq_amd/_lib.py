@@ -26,7 +26,7 @@ EXPORTS = [
     "ppcx_fit_nuts_xchg", "ppcx_fit_get_xchg_timing", "ppcx_fit_get_inv_metric", "ppcx_fit_summary",
     "ppcx_fit_get_approximation", "ppcx_fit_get_log_ratios", "ppcx_fit_psis", "ppcx_fit_get_log_lik", "ppcx_fit_loo",
     "ppcx_fit_loo_predict", "ppcx_fit_relative_eff", "ppcx_fit_loo_mcse", "ppcx_fit_loo_approx", "ppcx_fit_loo_predict_approx",
-    "ppcx_fit_ppc_exact", "ppcx_fit_loo_predict_exact", "ppcx_fit_loo_predict_exact_approx",
+    "ppcx_fit_ppc_exact", "ppcx_fit_loo_predict_exact", "ppcx_fit_loo_predict_exact_approx", "ppcx_fit_loo_moment_match",
 ]
 ABI_VERSION = 400           # include/ppcx.h PPCX_VERSION this binding was written for
 SUMMARY_FIELDS = ("mean", "sd", "q05", "q50", "q95", "rhat", "ess_bulk", "ess_tail")   # PPCX_SUMMARY_FIELDS, in order
@@ -35,6 +35,7 @@ LOO_MCSE_FIELDS = LOO_FIELDS + ("mcse_elpd_loo", "n_eff")                       
 LOO_PREDICT_FIELDS = ("mean", "lower", "upper", "pit_lt", "pit_le", "khat")              # PPCX_LOO_PREDICT_FIELDS, in order
 PPC_EXACT_FIELDS = ("mean", "sd", "p_le", "p_ge", "lower", "upper", "y", "excluded", "outside")   # PPCX_PPC_EXACT_FIELDS, in order
 LOO_EXACT_FIELDS = PPC_EXACT_FIELDS + ("khat",)                                          # PPCX_LOO_EXACT_FIELDS, in order
+LOO_MM_HEAD = LOO_FIELDS + ("khat_before", "iterations")     # PPCX_LOO_MM_FIELDS(C): these, then scale[C + 1] and shift[C + 1]
 
 
 class PpcxError(RuntimeError):
@@ -108,6 +109,7 @@ def load() -> C.CDLL:
     lib.ppcx_fit_get_log_lik.argtypes = [C.c_void_p, C.c_int, ip, dp]
     lib.ppcx_fit_loo.argtypes = [C.c_void_p, C.c_int, ip, dp, dp]
     lib.ppcx_fit_loo_mcse.argtypes = [C.c_void_p, C.c_int, ip, dp, dp]
+    lib.ppcx_fit_loo_moment_match.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_double, C.c_int, dp]
     lib.ppcx_fit_loo_predict.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_double, C.c_double, C.c_double, C.c_ulonglong, dp]
     lib.ppcx_fit_relative_eff.argtypes = [C.c_void_p, C.c_int, ip, dp]
     lib.ppcx_fit_loo_approx.argtypes = [C.c_void_p, C.c_int, ip, dp]
@@ -845,6 +847,31 @@ class Fit:
         if mcse:
             from .inference import loo_mcse_total
             res["mcse_elpd_loo_total"] = loo_mcse_total(res)
+        return res
+
+    def loo_moment_match(self, genes=None, r_eff=None, k_threshold=None, max_iters=30):
+        """Fit.loo with gene-local moment matching of the cells whose khat exceeds k_threshold (ppcx_fit_loo_moment_match; the
+        importance-weighted moment matching of loo::loo_moment_match, applied to the coordinates of the cell's own gene only --
+        a deliberate deviation, restated from the paper and not run against R): Fit.loo's dict with `estimates` over the new
+        values, plus `khat_before` (plain PSIS's khat; `khat` is the final one), `iterations` (accepted steps, int64), `scale`
+        and `shift` [n_genes, S, C + 1] (the matched draws of the gene are scale * draw + shift, rows intercept, slopes,
+        sigma_raw; 1 and 0 for a row the gene does not have) and `k_threshold`. A cell with iterations == 0 holds Fit.loo's
+        bits. k_threshold=None: inference.loo_threshold(n_draws). There is no covariance step and no split transformation: a
+        matched khat is necessary, not sufficient; no mcse / n_eff. Not for an ADVI fit. r_eff as Fit.loo."""
+        if k_threshold is None:
+            from .inference import loo_threshold
+            k_threshold = loo_threshold(self.chains * self.n_keep)
+        k_threshold, max_iters = float(k_threshold), int(max_iters)
+        nc = self.model.C + 1
+        fields = LOO_MM_HEAD + tuple(f"scale{c}" for c in range(nc)) + tuple(f"shift{c}" for c in range(nc))
+        _, res, last = self._loo_cells(genes, r_eff, fields, lambda n, g, re, out: load().ppcx_fit_loo_moment_match(
+            self._h, n, g, re, k_threshold, max_iters, out))
+        for name in ("scale", "shift"):
+            res[name] = np.stack([res.pop(f"{name}{c}") for c in range(nc)], axis=-1)
+        res["iterations"] = res["iterations"].astype(np.int64)
+        res["k_threshold"] = k_threshold
+        res.update(last)
+        res["estimates"] = loo_estimates(res, res["excluded"])
         return res
 
     def _loo_predict_result(self, g, res, last):

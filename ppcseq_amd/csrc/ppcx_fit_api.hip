@@ -153,6 +153,21 @@ extern "C" int ppcx_fit_loo(ppcx_fit* f, int n_genes, const int32_t* genes, cons
 extern "C" int ppcx_fit_loo_mcse(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double* out) {
   return fit_loo("ppcx_fit_loo_mcse", f, n_genes, genes, r_eff, kLooMcseFields, out);
 }
+// ---- gene-local moment matching of the cells with a high k-hat (loo::loo_moment_match restated per gene; ppcx_loo_mm.h)
+extern "C" int ppcx_fit_loo_moment_match(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double k_threshold,
+                                         int max_iters, double* out) {
+  const char* who = "ppcx_fit_loo_moment_match";
+  if (f && f->advi)
+    return fail(PPCX_ERR_ARG, std::string(who) + " needs the draws of a NUTS fit: moment matching under the weights of an ADVI fit "
+                                                 "(loo_approximate_posterior) is not available");
+  if (!isfinite(k_threshold)) return fail(PPCX_ERR_ARG, std::string(who) + ": k_threshold must be finite");
+  if (max_iters < 0) return fail(PPCX_ERR_ARG, std::string(who) + ": max_iters must be >= 0");
+  std::vector<int> yenc; FitCells fc;
+  int rc = loo_prepare(f, n_genes, genes, out, yenc, fc);
+  if (rc == PPCX_OK) rc = loo_fit_reff(who, fc, r_eff);
+  if (rc != PPCX_OK) return rc;
+  return hip_done(who, loo_mm_fit_cells(fc, k_threshold, max_iters, out, loo_scratch_bytes(), f->m->stream.s));
+}
 // ---- the leave-one-out predictive interval and LOO-PIT of the same cells (loo::E_loo / bayesplot::ppc_loo_intervals, ppc_loo_pit)
 static int loo_predict_check_probs(double p_lo, double p_hi) {
   if (!(p_lo >= 0.0 && p_lo < p_hi && p_hi <= 1.0)) return fail(PPCX_ERR_ARG, "need 0 <= p_lo < p_hi <= 1");

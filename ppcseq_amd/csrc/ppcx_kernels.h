@@ -295,6 +295,13 @@ hipError_t loo_exact_fit_cells(const FitCells& fc, double tc, double p_lo, doubl
 // ... of given columns: gc.cols the log-likelihoods [n_cols][n], eta and sigma_raw [n_cols][n], y [n_cols] the observed counts
 hipError_t loo_exact_columns(const GivenCells& gc, const double* eta, const double* sigma_raw, const int* y, double tc, double p_lo,
                              double p_hi, double* out, size_t scratch_bytes, hipStream_t st);
+// Gene-local moment matching of the cells whose PSIS-LOO k-hat exceeds k_threshold (ppcx_loo_mm.hip, statistic in
+// ppcx_loo_mm.h): ppcx_loo_kernel over the cells (launch_loo_kernel, ppcx_loo.hip: `n_blocks` cells from a.cell0, fields as
+// loo_fit_cells), then one workgroup per cell; a candidate's ratios, the log weights and the local density at the original draws
+// (24 bytes per draw) in LDS up to kPsisLdsDraws draws, beyond that in the scratch. NUTS fits (fc.log_ratio null).
+// out [cells][loo_mm_fields(C)]
+hipError_t launch_loo_kernel(const LooArgs& a, int fields, int n_blocks, hipStream_t st);
+hipError_t loo_mm_fit_cells(const FitCells& fc, double k_threshold, int max_iters, double* out, size_t scratch_bytes, hipStream_t st);
 // The relative efficiency of the same cells (ppcx_reff.hip, statistic in ppcx_reff.h): one workgroup per cell; the split values
 // (8 bytes each) in LDS for fits of up to kPsisLdsDraws draws, beyond that in the scratch. Of `l` it uses T / y / expo / X / S / C
 // or cols, n = chains n_keep, cell0, n_cells, scratch ([launch's cells][2 chains (n_keep / 2)]) and out ([cells], one value

@@ -1,0 +1,230 @@
+// ppcx_loo_mm.hip -- gfx950 kernels of the gene-local moment matching of PSIS-LOO cells (ppcx_fit_loo_moment_match,
+// include/ppcx.h; the statistic: ppcx_loo_mm.h). The walk over the cells is ppcx_loo_dev.h's (for_gene_batches,
+// loo_cell_batches); the driver at the end of this file adds the argument block and the kernels.
+//
+//   ppcx_loo_mm_hyper_kernel  the draws' six unconstrained hyper-parameters, transposed: U[k][draw], once per call, so that a
+//                             wavefront's lanes read consecutive draws of one hyper-parameter as they do of the table T.
+//   ppcx_loo_mm_kernel        one workgroup of kBlockThreads per cell. ppcx_loo_kernel has run over the same cells before it
+//                             and left their four fields (ppcx_fit_loo's bits, by the same kernel); a cell that is finished in
+//                             step 0 copies them, writes khat_before = khat, iterations 0, scales 1, shifts 0 and leaves at
+//                             once, before a ratio is formed. A cell above the threshold forms its ratios, tail and the log
+//                             weight of every draw by loo_cell_ratios, loo_cell_tail and loo_draw_lw -- the calls and the order
+//                             of the other per-cell kernels -- then Q0, and iterates: per coordinate two sweeps over the draws
+//                             for the four moments (t formed from the table on the fly), per candidate one sweep that forms
+//                             q(t'; h) - Q0 - ll per draw (disp_point once per draw, disp_cell per sample of the gene) and
+//                             the cell's PSIS on it. The state (A, B) and the candidate's live in LDS, written by thread 0.
+//                             Every thread holds the same sums and the same k: the control flow is uniform per workgroup.
+//                             Three arrays of n doubles -- a candidate's ratios, the current log weights, Q0 -- in LDS up to
+//                             kPsisLdsDraws draws beside the two selection arrays (96 KB + 4 KB at 4 096 draws: one workgroup
+//                             per CU; 1 000 draws take 24 KB + 2 KB), in the workgroup's slice of the bounded scratch beyond.
+//                             A candidate's ratios overwrite the last candidate's: the current weights are enough for the
+//                             moments and for step 4. The kernel has NOT been timed.
+// Every reduction runs in a fixed order and a cell reads nothing of another gene: its fields are the same bits whatever else is
+// requested and however the work is batched.
+#include <hip/hip_runtime.h>
+#include "ppcx_loo_dev.h"
+#include "ppcx_loo_mm.h"
+
+namespace ppcx {
+
+struct LooMmArgs {
+  LooArgs l;                       // the table, y, r_eff, n, the cells, sel_pad (l.scratch / l.out: ppcx_loo_kernel's)
+  const int* genes = nullptr;      // [table's genes] their ids in the model (device)
+  const double* U = nullptr;       // [6][n] ppcx_loo_mm_hyper_kernel
+  const double* loo = nullptr;     // [cells][kLooFields] ppcx_loo_kernel's fields of the table's cells
+  int K = 0;                       // checked genes of the model
+  double lambda_mu_mu = 0.0, k_threshold = 0.7;
+  int max_iters = 0;
+  double* scratch = nullptr; long slice = 0;   // [launch's cells][slice] doubles: the long path's three arrays
+  double* out = nullptr;           // [cells][loo_mm_fields(C)]
+};
+
+// doubles of scratch per cell on the long path: a candidate's ratios [n], the log weights [n], Q0 [n]
+static long loo_mm_slice(long n) { return 3 * n; }
+
+__global__ __launch_bounds__(256) void ppcx_loo_mm_hyper_kernel(const double* draws, long n_draws, Dims d, double* U) {
+  const long t = (long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= 6 * n_draws) return;
+  const long j = t / 6; const int k = (int)(t - j * 6);
+  U[(long)k * n_draws + j] = draws[j * (long)d.D + hyper_index(d, k)];
+}
+
+struct LooMmShared { double A[kMaxC + 1], B[kMaxC + 1], A1[kMaxC + 1], B1[kMaxC + 1], A2[kMaxC + 1], B2[kMaxC + 1]; int ok2; };
+
+template <bool LDS>
+__global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_kernel(LooMmArgs p) {
+#pragma clang fp contract(off)
+  extern __shared__ uint64_t lds_u[];
+  __shared__ PsisShared sh;
+  __shared__ LooMmShared ms;
+  const LooArgs& a = p.l;
+  const int tid = threadIdx.x;
+  const long n = a.n;
+  const int C = a.C, nc = C + 1;
+  uint64_t* K = lds_u;                                   // [sel_pad] keys of the M + 1 largest ratios
+  double* X = reinterpret_cast<double*>(lds_u + a.sel_pad);            // [sel_pad] the tail's exceedances
+  double* V = LDS ? X + a.sel_pad : p.scratch + (long)blockIdx.x * p.slice;   // [n] the ratios (of the last candidate)
+  double* W = V + n;                                     // [n] the current log weights
+  double* Q0 = W + n;                                    // [n] the local density at the original draws
+  const LooCell c = loo_cell<false>(a);
+  const int cell = c.cell, gi = c.gi, s = c.s;
+  double* o = p.out + (long)cell * loo_mm_fields(C);
+  const double* lo = p.loo + (long)cell * kLooFields;
+  // ---- step 0: ppcx_loo_kernel's fields; a finished cell leaves
+  const double khat0 = lo[3];
+  if (tid == 0) {
+    o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = khat0;
+    loo_mm_store_state(o, C, khat0, 0, nullptr, nullptr);
+  }
+  if (loo_mm_finished(c.excluded, khat0, p.k_threshold, p.max_iters)) return;
+  long N; double rmax, lmax;
+  if (loo_cell_ratios<false>(a, cell, gi, s, c.y, false, V, sh, &N, &rmax, &lmax)) return;
+  if (N == 0) return;
+  double sl = 0.0;
+  for (long i = tid; i < n; i += kBlockThreads) { const double r = V[i]; if (r != -INFINITY) sl += exp(-r - lmax); }
+  sl = block_sum(sl, sh.red);
+  const double lpd = (lmax == -INFINITY ? -INFINITY : lmax + log(sl)) - log((double)N);
+  const double re = a.r_eff ? a.r_eff[cell] : 1.0;
+  double k;
+  {
+    const int M = psis_tail_len(N, re);
+    const LooTail lt = loo_cell_tail(V, n, N, M, K, X, a.sel_pad, sh);
+    for (long i = tid; i < n; i += kBlockThreads) W[i] = loo_draw_lw(V, i, rmax, lt, M, K);
+    k = lt.khat;
+  }
+  // ---- the gene, the state, Q0
+  LooMmGene g;
+  g.Tg = a.T + (long)gi * nc * n; g.U = p.U; g.n = n; g.C = C; g.S = a.S;
+  g.checked = C >= 2 && p.genes[gi] < p.K;
+  g.yrow = a.y + (long)gi * a.S; g.expo = a.expo; g.X = a.X; g.lambda_mu_mu = p.lambda_mu_mu;
+  if (tid < nc) { ms.A[tid] = 1.0; ms.B[tid] = 0.0; }
+  __syncthreads();
+  for (long i = tid; i < n; i += kBlockThreads) { double l; Q0[i] = loo_mm_density(g, i, ms.A, ms.B, s, &l); }
+  // ---- step 3
+  int iters = 0;
+  while (k > p.k_threshold && iters < p.max_iters) {
+    // the normaliser of the current weights
+    double mb = -INFINITY;
+    for (long i = tid; i < n; i += kBlockThreads) mb = fmax(mb, W[i]);
+    mb = block_max(mb, sh.red);
+    double sb = 0.0;
+    for (long i = tid; i < n; i += kBlockThreads) sb += exp(W[i] - mb);
+    sb = block_sum(sb, sh.red);
+    const double lse = mb + log(sb);
+    // the moments of every coordinate, the two candidates
+    bool ok2 = true;
+    for (int cc = 0; cc < nc; ++cc) {
+      const bool coord = loo_mm_is_coord(g, cc);           // uniform
+      double A1 = ms.A[cc], B1 = ms.B[cc], A2 = A1, B2 = B1;
+      if (coord) {
+        double st = 0.0, swt = 0.0, swt2 = 0.0;
+        for (long i = tid; i < n; i += kBlockThreads) {
+          const double t = loo_mm_coord(g, cc, i, ms.A, ms.B), w = exp(W[i] - lse);
+          st += t; swt += w * t; swt2 += w * (t * t);
+        }
+        st = block_sum(st, sh.red);
+        swt = block_sum(swt, sh.red);
+        swt2 = block_sum(swt2, sh.red);
+        const double m = loo_mm_mean(st, n);
+        double sd2 = 0.0;
+        for (long i = tid; i < n; i += kBlockThreads) { const double d = loo_mm_coord(g, cc, i, ms.A, ms.B) - m; sd2 += d * d; }
+        sd2 = block_sum(sd2, sh.red);
+        const double v = loo_mm_var(sd2, n), vw = loo_mm_wvar(swt2, swt);
+        B1 = loo_mm_shift(ms.B[cc], m, swt);
+        const double sc = loo_mm_scale(vw, v);
+        ok2 = ok2 && loo_mm_scale_ok(sc);
+        A2 = loo_mm_scaled_A(sc, ms.A[cc]); B2 = loo_mm_scaled_B(sc, ms.B[cc], m, swt);
+      }
+      if (tid == 0) { ms.A1[cc] = A1; ms.B1[cc] = B1; ms.A2[cc] = A2; ms.B2[cc] = B2; }
+    }
+    __syncthreads();
+    int kind = 0;
+    for (int cand = 1; cand <= 2 && !kind; ++cand) {
+      if (cand == 2 && !ok2) break;
+      const double* Ac = cand == 1 ? ms.A1 : ms.A2;
+      const double* Bc = cand == 1 ? ms.B1 : ms.B2;
+      double cnt = 0.0, rmx = -INFINITY;
+      for (long i = tid; i < n; i += kBlockThreads) {
+        double l;
+        const double q = loo_mm_density(g, i, Ac, Bc, s, &l);
+        const double r = loo_mm_ratio(q, Q0[i], l);
+        if (r != -INFINITY) { cnt += 1.0; rmx = fmax(rmx, r); }
+        V[i] = r;
+      }
+      const long N2 = (long)block_sum(cnt, sh.red);
+      rmx = block_max(rmx, sh.red);
+      const int M2 = psis_tail_len(N2, re);
+      const LooTail lt = loo_cell_tail(V, n, N2, M2, K, X, a.sel_pad, sh);
+      if (N2 > 0 && lt.khat < k) {
+        kind = cand; k = lt.khat;
+        for (long i = tid; i < n; i += kBlockThreads) W[i] = loo_draw_lw(V, i, rmx, lt, M2, K);
+        __syncthreads();
+        if (tid < nc) { ms.A[tid] = Ac[tid]; ms.B[tid] = Bc[tid]; }
+        __syncthreads();
+      }
+    }
+    if (!kind) break;
+    ++iters;
+  }
+  if (iters == 0) return;
+  // ---- step 4
+  double ma = -INFINITY, mb = -INFINITY;
+  for (long i = tid; i < n; i += kBlockThreads) {
+    const double lw = W[i];
+    if (lw == -INFINITY) continue;
+    ma = fmax(ma, lw + loo_mm_cell_ll(g, i, ms.A, ms.B, s)); mb = fmax(mb, lw);
+  }
+  ma = block_max(ma, sh.red);
+  mb = block_max(mb, sh.red);
+  double sa = 0.0, sb = 0.0;
+  for (long i = tid; i < n; i += kBlockThreads) {
+    const double lw = W[i];
+    if (lw == -INFINITY) continue;
+    sa += exp(lw + loo_mm_cell_ll(g, i, ms.A, ms.B, s) - ma); sb += exp(lw - mb);
+  }
+  sa = block_sum(sa, sh.red);
+  sb = block_sum(sb, sh.red);
+  const double elpd = loo_ap_lse(ma, sa) - loo_ap_lse(mb, sb);
+  if (tid == 0) {
+    o[0] = elpd; o[1] = lpd - elpd; o[2] = -2.0 * elpd; o[3] = k;
+    loo_mm_store_state(o, C, khat0, iters, ms.A, ms.B);
+  }
+}
+
+// ---- launch helpers (host)
+static hipError_t launch_loo_mm_kernel(const LooMmArgs& p, int n_blocks, hipStream_t st) {
+  const bool lds = p.l.n <= kPsisLdsDraws;
+  const size_t bytes = sizeof(double) * (2 * (size_t)p.l.sel_pad + (lds ? (size_t)loo_mm_slice(p.l.n) : 0));
+  return launch_dynamic_lds(lds ? ppcx_loo_mm_kernel<true> : ppcx_loo_mm_kernel<false>, n_blocks, kBlockThreads, bytes, st, p);
+}
+
+hipError_t loo_mm_fit_cells(const FitCells& fc, double k_threshold, int max_iters, double* out, size_t scratch_bytes, hipStream_t st) {
+  const long n = fc.n;
+  const size_t ncells = (size_t)fc.n_genes * fc.d.S;
+  DeviceBuffer<double> d_U, d_loo;                       // outlive the walk, which drains the stream before it returns
+  hipError_t e = d_U.alloc(6 * (size_t)n);
+  if (e == hipSuccess) e = d_loo.alloc(ncells * kLooFields);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(ppcx_loo_mm_hyper_kernel, dim3((unsigned)((6 * n + 255) / 256)), dim3(256), 0, st, fc.draws, n, fc.d, d_U.p);
+    e = hipGetLastError();
+  }
+  if (e != hipSuccess) return finish(e, st);
+  size_t done = 0;                                       // cells of the earlier gene batches
+  return for_gene_batches(fc, loo_mm_fields(fc.d.C), out, scratch_bytes, st,
+                          [&](const LooArgs& a, const int* genes, int n_cells, DeviceBuffer<double>& scratch) {
+    LooMmArgs p;
+    p.l = a; p.genes = genes; p.U = d_U.p; p.loo = d_loo.p + done * kLooFields; p.K = fc.d.K; p.lambda_mu_mu = fc.d.lambda_mu_mu;
+    p.k_threshold = k_threshold; p.max_iters = max_iters; p.out = a.out;
+    p.l.out = d_loo.p + done * kLooFields;
+    p.slice = n > kPsisLdsDraws ? loo_mm_slice(n) : 0;
+    done += (size_t)n_cells;
+    // per batch of cells: plain PSIS-LOO by its own kernel (its slice of the scratch is the first n of ours), then the matching
+    return loo_cell_batches(n_cells, p.slice, scratch_bytes, scratch, [&](int c0, int nc, double* scr) {
+      p.l.cell0 = c0; p.l.scratch = scr; p.scratch = scr;
+      const hipError_t e1 = launch_loo_kernel(p.l, kLooFields, nc, st);
+      return e1 == hipSuccess ? launch_loo_mm_kernel(p, nc, st) : e1;
+    });
+  });
+}
+
+}  // namespace ppcx

@@ -226,6 +226,7 @@ class CheckContext:
     loo_r_eff: object = None     # the modifiers of loo / loo_intervals
     loo_mcse: bool = False
     pooled: bool = False         # a fit over the pooled draws of several fits' chains (pooled_summary): it holds no lp__
+    loo_moment_match: bool = False   # check_loo reads Fit.loo_moment_match in place of Fit.loo
 
 
 @dataclass(frozen=True)
@@ -255,6 +256,13 @@ def _loo_warnings(result, fit):
     return loo_warnings(result["khat"], fit.chains * fit.n_keep)
 
 
+def _read_loo(fit, ctx):
+    """check_loo's read: Fit.loo(r_eff, mcse), or with loo_moment_match Fit.loo_moment_match(r_eff) (its khat is the final one)"""
+    if ctx.loo_moment_match:
+        return fit.loo_moment_match(np.arange(ctx.K), r_eff=ctx.loo_r_eff)
+    return fit.loo(np.arange(ctx.K), r_eff=ctx.loo_r_eff, mcse=bool(ctx.loo_mcse))
+
+
 CHECKS = (          # in the order of the reads
     Check("check_approximation", "approximation", 2, "advi", False, False,
           "check_approximation needs an ADVI pass (approximate_posterior_inference = True): the Pareto k diagnostic judges the "
@@ -279,7 +287,7 @@ CHECKS = (          # in the order of the reads
           lambda result, fit: convergence_warnings(result, fit.chains), cells=False),
     Check("check_loo", "loo", 3, "nuts", True, False,
           "check_loo needs a NUTS pass: PSIS-LOO of an ADVI fit (loo_approximate_posterior) is check_approximation_loo",
-          lambda fit, ctx: fit.loo(np.arange(ctx.K), r_eff=ctx.loo_r_eff, mcse=bool(ctx.loo_mcse)), _loo_warnings),
+          _read_loo, _loo_warnings),
     Check("check_loo_intervals", "loo_intervals", 4, "nuts", True, False,
           "check_loo_intervals needs a NUTS pass: the leave-one-out intervals of an ADVI fit (loo_approximate_posterior) are "
           "check_approximation_loo_intervals",
@@ -297,7 +305,11 @@ MODIFIERS = (       # (option, the options of which it needs one, what it is tol
      "loo_r_eff needs check_loo, check_loo_intervals or exact_loo_intervals: it is the r_eff of their PSIS"),
     ("loo_mcse", ("check_loo",),
      "loo_mcse needs check_loo: it adds the Monte-Carlo standard error and n_eff to its PSIS-LOO"),
+    ("loo_moment_match", ("check_loo",),
+     "loo_moment_match needs check_loo: it matches the moments of the cells whose k-hat its PSIS-LOO finds too high"),
 )
+LOO_MOMENT_MATCH_MCSE = ("loo_mcse cannot be combined with loo_moment_match: the Monte-Carlo standard error and n_eff are those of "
+                         "plain PSIS weights and are not given for a matched cell")
 
 CHECK_OPTIONS = tuple(c.keyword for c in CHECKS) + tuple(m[0] for m in MODIFIERS)
 
@@ -319,6 +331,8 @@ def select_checks(options, approximate_posterior_inference, over_ranks=False):
     for keyword, needs, refusal in MODIFIERS:
         if options[keyword] and not any(options[k] for k in needs):
             raise ValueError(refusal)
+    if options["loo_mcse"] and options["loo_moment_match"]:
+        raise ValueError(LOO_MOMENT_MATCH_MCSE)
     return {k: options[k] for k in CHECK_OPTIONS if options[k]}
 
 
@@ -358,6 +372,7 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                  check_loo_intervals=False,
                  loo_r_eff=None,
                  loo_mcse=False,
+                 loo_moment_match=False,
                  check_approximation_loo=False,
                  check_approximation_loo_intervals=False,
                  exact_intervals=False,
@@ -402,6 +417,12 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
     loo_mcse          True: `res.loo` also carries loo's pointwise `mcse_elpd_loo` and `n_eff` of every checked cell and
                       `mcse_elpd_loo_total` (Fit.loo(mcse=True); pareto_k_table reads it). It raises no further warning.
                       devices=[...]: over the pooled chains. Needs check_loo.
+    loo_moment_match  True: `res.loo` comes from Fit.loo_moment_match: the cells whose k-hat exceeds loo_threshold get gene-local
+                      moment matching (a restatement of loo::loo_moment_match on the cell's own gene, without its split and
+                      covariance steps); `res.loo` then also carries `khat_before`, `iterations`, `scale`, `shift` and
+                      `k_threshold`, and the k-hat warning reads the final `khat`. Flags and frame are those of the call
+                      without it. devices=[...]: over the pooled chains (no lp__ is needed). Needs check_loo; not with loo_mcse
+                      (a matched cell has no mcse / n_eff).
     check_approximation_loo  check_loo for an ADVI pass: PSIS-LOO of every checked cell with the correction for the approximation
                       (loo::loo_approximate_posterior; ratios (log_p - log_g) - log_lik, r_eff = 1) on the device
                       (Fit.loo_approximate_posterior), kept as `res.approximation_loo` and reported as RuntimeWarning when a k-hat
@@ -481,7 +502,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
         res.diagnostics = fit.advi_info() if approximate_posterior_inference else fit.diagnostics()
         msgs = [] if approximate_posterior_inference else hmc_warnings(res.diagnostics, warmup)
         msgs += read_checks(fit, CheckContext(K, p, seed, truncation_compensation, checks.get("loo_r_eff"),
-                                              checks.get("loo_mcse", False)), checks, res)
+                                              checks.get("loo_mcse", False),
+                                              loo_moment_match=bool(checks.get("loo_moment_match", False))), checks, res)
         for msg in msgs:
             warnings.warn(msg, RuntimeWarning, stacklevel=2)
         res.counts_rng = rng
@@ -566,7 +588,8 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
             res = _post_process(counts[:K], ci, slope, X)
             res.total_draws = counts.shape[1] * K * int(how_many_posterior_draws)
             msgs = read_checks(fit, CheckContext(K, p, seed, truncation_compensation, checks.get("loo_r_eff"),
-                                                 checks.get("loo_mcse", False), pooled=True), checks, res)
+                                                 checks.get("loo_mcse", False), pooled=True,
+                                                 loo_moment_match=bool(checks.get("loo_moment_match", False))), checks, res)
         finally:
             fit.close()
     finally:

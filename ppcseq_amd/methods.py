@@ -126,7 +126,7 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                       cores=None, pass_fit=False, do_check_only_on_detrimental=None, tol_rel_obj=0.01,
                       just_discovery=False, seed=None, adj_prob_theshold_2=None, device=0, devices=None, launch=None, _pass=None,
                       check_convergence=False, check_approximation=False, check_loo=False,
-                      check_loo_intervals=False, loo_r_eff=None, loo_mcse=False,
+                      check_loo_intervals=False, loo_r_eff=None, loo_mcse=False, loo_moment_match=False,
                       check_approximation_loo=False, check_approximation_loo_intervals=False, exact_intervals=False,
                       exact_loo_intervals=False, exact_approximation_loo_intervals=False):
     """Mirror of ppcseq::identify_outliers (R/methods.R:74-367): same arguments, same defaults.
@@ -153,6 +153,7 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
     `check_loo` (NUTS)                            -> attrs["loo_discovery"], ["loo_test"] (pass 2 holds its excluded cells out)
     `check_loo_intervals` (NUTS)                  -> attrs["loo_intervals_discovery"], ["loo_intervals_test"]
     `loo_r_eff` = "auto", `loo_mcse` = True       -> modify check_loo / check_loo_intervals / exact_loo_intervals; in the same attrs
+    `loo_moment_match` = True                     -> check_loo's results come from Fit.loo_moment_match; in the same attrs
     `check_approximation_loo` (ADVI)              -> attrs["approximation_loo_discovery"], ["approximation_loo_test"]
     `check_approximation_loo_intervals` (ADVI)    -> attrs["approximation_loo_intervals_discovery"], [..."_test"]
     `exact_intervals` (NUTS and ADVI)             -> attrs["exact_intervals_discovery"], ["exact_intervals_test"]
