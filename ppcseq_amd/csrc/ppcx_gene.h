@@ -105,12 +105,44 @@ struct CellData {                // the chain-independent inputs of the log-like
 // the launch starts and ends its passes at the same time -- equal costs since round 5 -- so a round trip at the start of a pass is
 // hidden by nobody; with the 17-instruction cell the sweep of 25 cells no longer dwarfs it.)
 struct GenePre { double phi, sigma, a0, Sy, n; int flags; };
+// Element i (i >= 0, i sizeof(T) < 2^32: arrays indexed by a gene or by a coordinate) of an array in GLOBAL memory whose base is
+// the same for the whole wavefront. On the device the address is formed as the uniform base plus a 32-bit byte offset -- the
+// scalar-base form of the global memory instructions: arrays indexed alike share one offset register, where base[i] costs
+// every array a sign extension, a shift and a 64-bit addition per lane. The address space is part of the parameter's type: a
+// caller says as_global(p) where it knows that p is global -- the log-likelihood kernel's arguments and what is derived from them
+// (ppcx_kernels.hip loglik_role: vecs, sums, order, the cell data); a VecRef in LDS (the state machine's hyper vectors) is not.
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PPCX_GLOBAL __attribute__((address_space(1)))
+#else
+#define PPCX_GLOBAL
+#endif
+template <class T>
+PPCX_HD PPCX_GLOBAL T* as_global(T* p) { return (PPCX_GLOBAL T*)p; }
+template <class T>
+PPCX_HD T ld32(const PPCX_GLOBAL T* base, int i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return *(const PPCX_GLOBAL T*)((const PPCX_GLOBAL char*)base + (unsigned)i * (unsigned)sizeof(T));
+#else
+  return base[i];
+#endif
+}
+template <class T>
+PPCX_HD void st32(PPCX_GLOBAL T* base, int i, T x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  *(PPCX_GLOBAL T*)((PPCX_GLOBAL char*)base + (unsigned)i * (unsigned)sizeof(T)) = x;
+#else
+  base[i] = x;
+#endif
+}
+// (called by the log-likelihood kernel only: its VecRef and its cell data lie in global memory)
 PPCX_HD GenePre gene_pre_load(const Dims& d, const VecRef& v, const CellData& m, int g) {
   GenePre r;
-  r.phi = v.at(V_C0, d.off_sigma_raw + g);       // phi = exp(-sigma_raw) and sigma_raw of the position being evaluated (coord_consts)
-  r.sigma = v.at(V_C2, d.off_sigma_raw + g);
-  r.a0 = v.at(V_C0, d.off_intercept + g);        // exp(intercept)
-  r.Sy = m.Sy[g]; r.n = m.ncell[g]; r.flags = m.gflags[g];
+  const PPCX_GLOBAL double* c0 = as_global<const double>(&v.at(V_C0, 0));
+  const PPCX_GLOBAL double* c2 = as_global<const double>(&v.at(V_C2, 0));
+  r.phi = ld32(c0, d.off_sigma_raw + g);         // phi = exp(-sigma_raw) and sigma_raw of the position being evaluated (coord_consts)
+  r.sigma = ld32(c2, d.off_sigma_raw + g);
+  r.a0 = ld32(c0, d.off_intercept + g);          // exp(intercept)
+  r.Sy = ld32(as_global(m.Sy), g); r.n = ld32(as_global(m.ncell), g); r.flags = ld32(as_global(m.gflags), g);
   return r;
 }
 // how the 2 x kDispStride coefficients of a gene's panel are dealt to its lanes: NL lanes per function, CH coefficients each
@@ -137,67 +169,96 @@ PPCX_HD void sweep_cells(int S, const int* row, const double* sE, const double* 
                          const GeneParams<CM>& gp, const double* tab, CellAcc<CM>& acc, const double* ec = nullptr, int C = 2) {
   const int nmin = S / L;                                  // cells every lane of the gene has
   const int nlane = nmin + (sub < S - nmin * L ? 1 : 0);
-  const int* p = row + sub;
+  const PPCX_GLOBAL int* p = as_global(row + sub);         // (row: the count matrix, in global memory)
   const double* q = sE + sub;
   const double* qx = sX1 + sub;
   int y0 = p[0], y1 = p[L], y2 = p[2 * L], y3 = p[3 * L];
   int k = 0;
+  double L4 = kCellL4;                                     // held in registers across the loop (ppcx_model.h cell_back)
+  PPCX_OPAQUE(L4);
 #define PPCX_SWEEP_CELL(Y, E, XB, OFF, COND)                                                    \
   if ((COND) && (!MASKED || (Y) >= 0)) {                                                        \
     if (MODE == 1) { const double a1_ = (XB) != 0.0 ? A1 : A;                                   \
-                     const double rho_ = WIN ? cell_eval_win<CM, true>(Y, E, a1_, one, gp, tab, acc) : cell_eval<CM, true>(Y, E, a1_, gp, tab, acc); \
+                     const double rho_ = WIN ? cell_eval_win<CM, true>(Y, E, a1_, one, gp, tab, acc, L4) : cell_eval<CM, true>(Y, E, a1_, gp, tab, acc, L4); \
                      acc.Tx[1] = fma(XB, rho_, acc.Tx[1]); }                                    \
     else if (MODE == 2) {                                                                       \
       double a_ = (XB) != 0.0 ? A1 : A; double xk_[CM];                                         \
       _Pragma("unroll") for (int cc = 2; cc < CM; ++cc) { xk_[cc] = cc < C ? qx[(cc - 1) * S + (OFF)] : 0.0; a_ = xk_[cc] != 0.0 ? a_ * ec[cc] : a_; } \
-      const double rho_ = WIN ? cell_eval_win<CM, true>(Y, E, a_, one, gp, tab, acc) : cell_eval<CM, true>(Y, E, a_, gp, tab, acc); \
+      const double rho_ = WIN ? cell_eval_win<CM, true>(Y, E, a_, one, gp, tab, acc, L4) : cell_eval<CM, true>(Y, E, a_, gp, tab, acc, L4); \
       acc.Tx[1] = fma(XB, rho_, acc.Tx[1]);                                                     \
       _Pragma("unroll") for (int cc = 2; cc < CM; ++cc) acc.Tx[cc] = fma(xk_[cc], rho_, acc.Tx[cc]); \
     }                                                                                           \
     else if (MODE == 3) {                                                                       \
       double t_ = (XB) * ec[1]; double xk_[CM];                                                 \
       _Pragma("unroll") for (int cc = 2; cc < CM; ++cc) { xk_[cc] = cc < C ? qx[(cc - 1) * S + (OFF)] : 0.0; t_ = fma(xk_[cc], ec[cc], t_); } \
-      const double rho_ = cell_eval<CM, true>(Y, E, A * fast_exp(t_), gp, tab, acc);           \
+      const double rho_ = cell_eval<CM, true>(Y, E, A * fast_exp(t_), gp, tab, acc, L4);       \
       acc.Tx[1] = fma(XB, rho_, acc.Tx[1]);                                                     \
       _Pragma("unroll") for (int cc = 2; cc < CM; ++cc) acc.Tx[cc] = fma(xk_[cc], rho_, acc.Tx[cc]); \
     }                                                                                           \
-    else if (WIN) (void)cell_eval_win<CM, false>(Y, E, A, one, gp, tab, acc);                   \
-    else (void)cell_eval<CM, false>(Y, E, A, gp, tab, acc);                                     \
+    else if (WIN) (void)cell_eval_win<CM, false>(Y, E, A, one, gp, tab, acc, L4);               \
+    else (void)cell_eval<CM, false>(Y, E, A, gp, tab, acc, L4);                                 \
   }
-  for (; k + 4 <= nmin; k += 4) {
-    const double e0 = q[0], e1 = q[L], e2 = q[2 * L], e3 = q[3 * L];
-    double x0 = 0.0, x1 = 0.0, x2 = 0.0, x3 = 0.0;
-    if (MODE != 0) { x0 = qx[0]; x1 = qx[L]; x2 = qx[2 * L]; x3 = qx[3 * L]; }
-    p += 4 * L; q += 4 * L; qx += 4 * L;
-    const int n0 = p[0], n1 = p[L], n2 = p[2 * L], n3 = p[3 * L];
-    if (MODE == 0 && !MASKED && WIN) {
-      // the common trip: the four first halves, then the four second halves (cell_front_win / cell_back_win, ppcx_model.h)
-      CellMidWin c0, c1, c2, c3;
-      (void)cell_front_win<CM, false>(y0, e0, A, one, gp, tab, acc, c0);
-      (void)cell_front_win<CM, false>(y1, e1, A, one, gp, tab, acc, c1);
-      (void)cell_front_win<CM, false>(y2, e2, A, one, gp, tab, acc, c2);
-      (void)cell_front_win<CM, false>(y3, e3, A, one, gp, tab, acc, c3);
+  // One trip: the four cells at offset B from the pointers, their counts in Y0 .. Y3; the next trip's counts are requested into
+  // N0 .. N3 before the cells are evaluated. The pointers do not move inside a trip: a trip's addresses are immediate offsets.
 #if defined(__HIP_DEVICE_COMPILE__)
-      __builtin_amdgcn_sched_barrier(0);
+#define PPCX_SWEEP_HALVES() __builtin_amdgcn_sched_barrier(0)
+#else
+#define PPCX_SWEEP_HALVES() ((void)0)
 #endif
-      cell_back_win<CM>(c0, acc); cell_back_win<CM>(c1, acc); cell_back_win<CM>(c2, acc); cell_back_win<CM>(c3, acc);
-    } else if (MODE == 0 && !MASKED) {
-      CellMid c0, c1, c2, c3;
-      (void)cell_front<CM, false>(y0, e0, A, gp, tab, acc, c0);
-      (void)cell_front<CM, false>(y1, e1, A, gp, tab, acc, c1);
-      (void)cell_front<CM, false>(y2, e2, A, gp, tab, acc, c2);
-      (void)cell_front<CM, false>(y3, e3, A, gp, tab, acc, c3);
-#if defined(__HIP_DEVICE_COMPILE__)
-      __builtin_amdgcn_sched_barrier(0);
-#endif
-      cell_back<CM>(c0, acc); cell_back<CM>(c1, acc); cell_back<CM>(c2, acc); cell_back<CM>(c3, acc);
-    } else {
-      PPCX_SWEEP_CELL(y0, e0, x0, -4 * L, true)            // (MODE 2 reads its further columns behind the advanced pointer)
-      PPCX_SWEEP_CELL(y1, e1, x1, -3 * L, true)
-      PPCX_SWEEP_CELL(y2, e2, x2, -2 * L, true)
-      PPCX_SWEEP_CELL(y3, e3, x3, -L, true)
+#define PPCX_SWEEP_TRIP(Y0, Y1, Y2, Y3, N0, N1, N2, N3, B)                                                                   \
+  {                                                                                                                          \
+    const double e0 = q[(B)], e1 = q[(B) + L], e2 = q[(B) + 2 * L], e3 = q[(B) + 3 * L];                                     \
+    double x0 = 0.0, x1 = 0.0, x2 = 0.0, x3 = 0.0;                                                                           \
+    if (MODE != 0) { x0 = qx[(B)]; x1 = qx[(B) + L]; x2 = qx[(B) + 2 * L]; x3 = qx[(B) + 3 * L]; }                           \
+    N0 = p[(B) + 4 * L]; N1 = p[(B) + 5 * L]; N2 = p[(B) + 6 * L]; N3 = p[(B) + 7 * L];                                      \
+    if (MODE == 0 && !MASKED && WIN) {                                                                                       \
+      /* the common trip: the four first halves, then the four second halves (cell_front_win / cell_back_win, ppcx_model.h) */ \
+      CellMidWin c0, c1, c2, c3;                                                                                             \
+      (void)cell_front_win<CM, false>(Y0, e0, A, one, gp, tab, acc, c0);                                                     \
+      (void)cell_front_win<CM, false>(Y1, e1, A, one, gp, tab, acc, c1);                                                     \
+      (void)cell_front_win<CM, false>(Y2, e2, A, one, gp, tab, acc, c2);                                                     \
+      (void)cell_front_win<CM, false>(Y3, e3, A, one, gp, tab, acc, c3);                                                     \
+      PPCX_SWEEP_HALVES();                                                                                                   \
+      cell_back_win<CM>(c0, acc, L4); cell_back_win<CM>(c1, acc, L4); cell_back_win<CM>(c2, acc, L4); cell_back_win<CM>(c3, acc, L4); \
+    } else if (MODE == 0 && !MASKED) {                                                                                       \
+      CellMid c0, c1, c2, c3;                                                                                                \
+      (void)cell_front<CM, false>(Y0, e0, A, gp, tab, acc, c0);                                                              \
+      (void)cell_front<CM, false>(Y1, e1, A, gp, tab, acc, c1);                                                              \
+      (void)cell_front<CM, false>(Y2, e2, A, gp, tab, acc, c2);                                                              \
+      (void)cell_front<CM, false>(Y3, e3, A, gp, tab, acc, c3);                                                              \
+      PPCX_SWEEP_HALVES();                                                                                                   \
+      cell_back<CM>(c0, acc, L4); cell_back<CM>(c1, acc, L4); cell_back<CM>(c2, acc, L4); cell_back<CM>(c3, acc, L4);         \
+    } else {                                                                                                                 \
+      PPCX_SWEEP_CELL(Y0, e0, x0, (B), true)                                                                                 \
+      PPCX_SWEEP_CELL(Y1, e1, x1, (B) + L, true)                                                                             \
+      PPCX_SWEEP_CELL(Y2, e2, x2, (B) + 2 * L, true)                                                                         \
+      PPCX_SWEEP_CELL(Y3, e3, x3, (B) + 3 * L, true)                                                                         \
+    }                                                                                                                        \
+  }
+  // Two trips per turn: the counts requested by the first are the second's and the other way round, so no register is copied to
+  // carry them over, and the three pointers move once per eight cells. (Two design columns only: the wider accumulators of the
+  // other instantiations leave no registers for a second trip's cells in flight -- their loop stays one trip per turn.)
+  if (CM <= 2) {
+    for (; k + 8 <= nmin; k += 8) {
+      int n0, n1, n2, n3;
+      PPCX_SWEEP_TRIP(y0, y1, y2, y3, n0, n1, n2, n3, 0)
+      PPCX_SWEEP_TRIP(n0, n1, n2, n3, y0, y1, y2, y3, 4 * L)
+      p += 8 * L; q += 8 * L; qx += 8 * L;
     }
-    y0 = n0; y1 = n1; y2 = n2; y3 = n3;
+    if (k + 4 <= nmin) {                                   // an odd number of whole trips: the last one
+      int n0, n1, n2, n3;
+      PPCX_SWEEP_TRIP(y0, y1, y2, y3, n0, n1, n2, n3, 0)
+      p += 4 * L; q += 4 * L; qx += 4 * L;
+      y0 = n0; y1 = n1; y2 = n2; y3 = n3;
+      k += 4;
+    }
+  } else {
+    for (; k + 4 <= nmin; k += 4) {
+      int n0, n1, n2, n3;
+      PPCX_SWEEP_TRIP(y0, y1, y2, y3, n0, n1, n2, n3, 0)
+      p += 4 * L; q += 4 * L; qx += 4 * L;
+      y0 = n0; y1 = n1; y2 = n2; y3 = n3;
+    }
   }
   if (k < nlane) {                                         // the last, partial trip
     const double e0 = q[0], e1 = q[L], e2 = q[2 * L], e3 = q[3 * L];
@@ -208,6 +269,8 @@ PPCX_HD void sweep_cells(int S, const int* row, const double* sE, const double* 
     PPCX_SWEEP_CELL(y2, e2, x2, 2 * L, k + 2 < nlane)
     PPCX_SWEEP_CELL(y3, e3, x3, 3 * L, k + 3 < nlane)
   }
+#undef PPCX_SWEEP_TRIP
+#undef PPCX_SWEEP_HALVES
 #undef PPCX_SWEEP_CELL
 }
 

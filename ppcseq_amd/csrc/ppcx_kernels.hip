@@ -84,10 +84,14 @@ __device__ __forceinline__ void loglik_passes(const LoglikArgs& a, const Cmd& c,
   constexpr int L = 1 << LG, GPW = 64 >> LG;     // lanes per gene, genes per wavefront and pass
   const Dims& d = a.d;
   const int sub = lane & (L - 1), gl = lane >> LG;
+  // the gene order's base as a value of its own: read out of the kernel's arguments where it is used, it is kept, spilled and
+  // brought back in every pass together with the fifteen other words of the argument block it arrived in
+  const PPCX_GLOBAL int* order = as_global(a.order);
+  asm volatile("" : "+s"(order));
   // One pass ahead: while pass p is swept, the constants of pass p + 1's genes (gene_pre_load) and the gene indices of pass
   // p + 2 are on their way.
-  int g_cur = a.order[p0 + gl < p1 ? p0 + gl : p1 - 1];
-  int g_next = a.order[p0 + GPW + gl < p1 ? p0 + GPW + gl : p1 - 1];
+  int g_cur = ld32(order, p0 + gl < p1 ? p0 + gl : p1 - 1);
+  int g_next = ld32(order, p0 + GPW + gl < p1 ? p0 + GPW + gl : p1 - 1);
   GenePre pre_cur = gene_pre_load(d, v, a.cd, g_cur);
 #ifdef PPCX_TRACE
   unsigned long long* tr = nullptr;
@@ -119,7 +123,7 @@ __device__ __forceinline__ void loglik_passes(const LoglikArgs& a, const Cmd& c,
       g_cur = g_next;
       pre_cur = gene_pre_load(d, v, a.cd, g_next);
       const int pn = p + 2 * GPW + gl;
-      g_next = a.order[pn < p1 ? pn : p1 - 1];
+      g_next = ld32(order, pn < p1 ? pn : p1 - 1);
     }
     if (CM > 2 && d.x0_is_one && !PPCX_WAVE_ANY(g < d.K)) {
       // a pass of plain genes in a model with more than two design columns: the two-column instantiation of the gene's work
@@ -128,7 +132,7 @@ __device__ __forceinline__ void loglik_passes(const LoglikArgs& a, const Cmd& c,
       GeneSumsV<2> o2;
       lane_gene_sums<2, L, 0>(d, c, v, a.cd, g, pre, sub, sE, sExpo, sX, stab, swin, o2);
       o2.lik = group_sum<L>(o2.lik); o2.dph = group_sum<L>(o2.dph); o2.Sr = group_sum<L>(o2.Sr);
-      if (act && sub == 0) { const long G = d.G; sums[0 * G + g] = o2.lik; sums[1 * G + g] = o2.dph; sums[2 * G + g] = o2.Sr; }
+      if (act && sub == 0) { const long G = d.G; st32(as_global(sums + 0 * G), g, o2.lik); st32(as_global(sums + 1 * G), g, o2.dph); st32(as_global(sums + 2 * G), g, o2.Sr); }
       continue;
     }
     GeneSumsV<CM> o;
@@ -151,10 +155,10 @@ __device__ __forceinline__ void loglik_passes(const LoglikArgs& a, const Cmd& c,
     }
     if (act && sub == 0) {
       const long G = d.G;
-      sums[0 * G + g] = o.lik; sums[1 * G + g] = o.dph; sums[2 * G + g] = o.Sr;
+      st32(as_global(sums + 0 * G), g, o.lik); st32(as_global(sums + 1 * G), g, o.dph); st32(as_global(sums + 2 * G), g, o.Sr);
       if (with_tx) {
 #pragma unroll
-        for (int cc = 0; cc < CM; ++cc) if (cc < d.C) sums[(3 + cc) * G + g] = o.Tx[cc];
+        for (int cc = 0; cc < CM; ++cc) if (cc < d.C) st32(as_global(sums + (3 + cc) * G), g, o.Tx[cc]);
       }
     }
     PPCX_STAMP(4);

@@ -177,12 +177,14 @@ PPCX_HD double cell_front(int y, double e, double A, const GeneParams<CM>& gp, c
   a.Sq += q; a.SYq = fma(c.yd, q, a.SYq);
   return SLOPES ? fma(c.yd, gp.invphi, 1.0) * q : 0.0;
 }
+// L4: the polynomial's -0.25, which the device's block takes from a vector register (a VOP3 instruction reads one scalar
+// operand): a sweep passes the one it keeps across its loop (kCellL4 made opaque once), or every trip builds it again
+constexpr double kCellL4 = -0.25;
 template <int CM>
-PPCX_HD void cell_back(const CellMid& c, CellAcc<CM>& a) {
+PPCX_HD void cell_back(const CellMid& c, CellAcc<CM>& a, double L4 = kCellL4) {
   double l;
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(PPCX_NO_ASM_CELL)
   double ed, r;
-  const double L4 = -0.25;
   asm("v_fma_f64 %[r], %[m], %[cinv], -1.0\n\t"      // r = m/c - 1
       "v_cvt_f64_i32_e32 %[ed], %[ex]\n\t"
       "v_fma_f64 %[p], %[r], %[L5], %[L4]\n\t"       // log1p(r) = r (1 - r/2 + r^2/3 - r^3/4 + r^4/5)
@@ -201,16 +203,17 @@ PPCX_HD void cell_back(const CellMid& c, CellAcc<CM>& a) {
   p = fma(r, p, -0.5);
   p = fma(r, p, 1.0);
   l = fma((double)c.ex, 6.93147180559945286227e-01, fma(r, p, c.logc));
+  (void)L4;
 #endif
   a.SA = fma(c.yd, l, a.SA);
   a.SL += l;
 }
 // the whole cell (partial trips, passes with excluded cells, per-cell linear predictors)
 template <int CM, bool SLOPES>
-PPCX_HD double cell_eval(int y, double e, double A, const GeneParams<CM>& gp, const double* tab, CellAcc<CM>& a) {
+PPCX_HD double cell_eval(int y, double e, double A, const GeneParams<CM>& gp, const double* tab, CellAcc<CM>& a, double L4 = kCellL4) {
   CellMid c;
   const double rho = cell_front<CM, SLOPES>(y, e, A, gp, tab, a, c);
-  cell_back<CM>(c, a);
+  cell_back<CM>(c, a, L4);
   return rho;
 }
 
@@ -234,6 +237,25 @@ PPCX_HD GeneWindow gene_window(double w_min, double w_max) {
   return g;
 }
 struct CellMidWin { double yd, w, cinv, logc; };
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(PPCX_NO_ASM_CELL)
+// The window table's entry of w' on the device, where every caller has staged the table in LDS: its 32-bit LDS address is
+// 16 x (bits 44 .. 53 of w') + the table's own, formed by two instructions with the table's address as the scalar operand of the
+// second. (Left to hipcc the index costs a shift, a mask and the addition of the workgroup's dynamic-LDS base -- which is zero, but
+// is resolved too late to be folded: three instructions.) No memory operation inside: the read itself stays the compiler's.
+// The address space is part of the parameter's type: cell_front_win, whose callers all stage the table in LDS (the kernels' swin,
+// the testing kernel's s_win), makes the cast.
+#define PPCX_LDS __attribute__((address_space(3)))
+__device__ __forceinline__ WinEntry window_entry_lds(const PPCX_LDS double* wt, double w) {
+  typedef double v2d_t __attribute__((ext_vector_type(2)));
+  const unsigned base = (unsigned)(unsigned long long)wt;
+  unsigned at;
+  asm("v_bfe_u32 %0, %1, 12, 10\n\t"
+      "v_lshl_add_u32 %0, %0, 4, %2"
+      : "=v"(at) : "v"(__double2hiint(w)), "s"(base));
+  const v2d_t e = *(const PPCX_LDS v2d_t*)at;        // 16-byte aligned: one ds_read_b128
+  return WinEntry{e.x, e.y};
+}
+#endif
 // e^t 2^-k = e A with A already scaled; one = 2^-k
 template <int CM, bool SLOPES>
 PPCX_HD double cell_front_win(int y, double e, double A, double one, const GeneParams<CM>& gp, const double* wt, CellAcc<CM>& a, CellMidWin& c) {
@@ -252,18 +274,21 @@ PPCX_HD double cell_front_win(int y, double e, double A, double one, const GeneP
   c.w = fma(e, A, one);
   q = fast_rcp(c.w);
 #endif
+#if defined(__HIP_DEVICE_COMPILE__) && !defined(PPCX_NO_ASM_CELL)
+  const WinEntry we = window_entry_lds((const PPCX_LDS double*)wt, c.w);     // wt: in LDS on the device
+#else
   const int j = (int)(dbl_bits(c.w) >> (52 - 8)) & (kWinTabSize - 1);
   const WinEntry we = window_entry(wt, j);
+#endif
   c.cinv = we.cinv; c.logc = we.logc;
   a.Sq += q; a.SYq = fma(c.yd, q, a.SYq);
   return SLOPES ? fma(c.yd, gp.invphi, 1.0) * q : 0.0;
 }
 template <int CM>
-PPCX_HD void cell_back_win(const CellMidWin& c, CellAcc<CM>& a) {
+PPCX_HD void cell_back_win(const CellMidWin& c, CellAcc<CM>& a, double L4 = kCellL4) {
   double l;
 #if defined(__HIP_DEVICE_COMPILE__) && !defined(PPCX_NO_ASM_CELL)
   double r;
-  const double L4 = -0.25;
   asm("v_fma_f64 %[r], %[w], %[cinv], -1.0\n\t"      // r = w/c - 1
       "v_fma_f64 %[p], %[r], %[L5], %[L4]\n\t"       // log1p(r) = r (1 - r/2 + r^2/3 - r^3/4 + r^4/5)
       "v_fma_f64 %[p], %[r], %[p], %[L3]\n\t"
@@ -279,15 +304,16 @@ PPCX_HD void cell_back_win(const CellMidWin& c, CellAcc<CM>& a) {
   p = fma(r, p, -0.5);
   p = fma(r, p, 1.0);
   l = fma(r, p, c.logc);
+  (void)L4;
 #endif
   a.SA = fma(c.yd, l, a.SA);
   a.SL += l;
 }
 template <int CM, bool SLOPES>
-PPCX_HD double cell_eval_win(int y, double e, double A, double one, const GeneParams<CM>& gp, const double* wt, CellAcc<CM>& a) {
+PPCX_HD double cell_eval_win(int y, double e, double A, double one, const GeneParams<CM>& gp, const double* wt, CellAcc<CM>& a, double L4 = kCellL4) {
   CellMidWin c;
   const double rho = cell_front_win<CM, SLOPES>(y, e, A, one, gp, wt, a, c);
-  cell_back_win<CM>(c, a);
+  cell_back_win<CM>(c, a, L4);
   return rho;
 }
 
