@@ -189,19 +189,24 @@ def _p(a, t):
     return a.ctypes.data_as(C.POINTER(t)) if a is not None else None
 
 
+def _testing_entry(name):
+    """The entry `name` of the testing build (csrc/ppcx_testing.h); the product build has none."""
+    lib = load()
+    if not hasattr(lib, name):
+        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before {name} existed: rebuild it "
+                        "(`python -m ppcseq_amd.build --testing --force`)")
+    return getattr(lib, name)
+
+
 def testing_set(key: str, value: int):
     """A test hook of the testing build (csrc/ppcx_testing.h); the product build has none."""
-    lib = load()
-    if not hasattr(lib, "ppcx_testing_set"):
-        raise PpcxError(f"{LIB_PATH} is not the testing build")
-    _check(lib.ppcx_testing_set(key.encode(), int(value)))
+    fn = _testing_entry("ppcx_testing_set")
+    _check(fn(key.encode(), int(value)))
 
 
 def testing_set_nccl_provider(path: str):
-    lib = load()
-    if not hasattr(lib, "ppcx_testing_set_nccl_provider"):
-        raise PpcxError(f"{LIB_PATH} is not the testing build")
-    _check(lib.ppcx_testing_set_nccl_provider(path.encode() if path else None))
+    fn = _testing_entry("ppcx_testing_set_nccl_provider")
+    _check(fn(path.encode() if path else None))
 
 
 # function ids of ppcx_testing_eval_math (csrc/ppcx_testing.h PPCX_MATH_*)
@@ -215,17 +220,14 @@ TESTING_MATH_MORE = ("nb2_tails",)
 def testing_eval_math(fn: str, a, b=None, y=None):
     """(out0, out1) of one of the device's building blocks at every element of a, b, y (testing build only;
     csrc/ppcx_testing.h ppcx_testing_eval_math)."""
-    lib = load()
-    if not hasattr(lib, "ppcx_testing_eval_math"):
-        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before ppcx_testing_math.hip existed: rebuild it "
-                        "(`python -m ppcseq_amd.build --testing --force`)")
+    entry = _testing_entry("ppcx_testing_eval_math")
     a = np.ascontiguousarray(a, dtype=np.float64).ravel()
     n = a.size
     b = np.ascontiguousarray(np.zeros(n) if b is None else np.broadcast_to(b, (n,)), dtype=np.float64)
     y = np.ascontiguousarray(np.zeros(n) if y is None else np.broadcast_to(y, (n,)), dtype=np.int32)
     o0, o1 = np.zeros(n), np.zeros(n)
-    rc = lib.ppcx_testing_eval_math((TESTING_MATH + TESTING_MATH_MORE).index(fn), n, _p(a, C.c_double), _p(b, C.c_double), _p(y, C.c_int32),
-                                    _p(o0, C.c_double), _p(o1, C.c_double))
+    rc = entry((TESTING_MATH + TESTING_MATH_MORE).index(fn), n, _p(a, C.c_double), _p(b, C.c_double), _p(y, C.c_int32),
+               _p(o0, C.c_double), _p(o1, C.c_double))
     if rc != 0:
         raise PpcxError(f"ppcx_testing_eval_math({fn}) failed with code {rc}")
     return o0, o1
@@ -234,16 +236,12 @@ def testing_eval_math(fn: str, a, b=None, y=None):
 def testing_psis(lr, cols=None):
     """k-hat of the PSIS kernel on host-given values (testing build only; csrc/ppcx_testing.h ppcx_testing_psis): lr [n] log
     ratios, cols [n, n_cols] parameter draws or None. Returns [n_cols + 1]: the columns' k-hat, then that of lr itself."""
-    lib = load()
-    if not hasattr(lib, "ppcx_testing_psis"):
-        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before ppcx_testing_psis existed: rebuild it "
-                        "(`python -m ppcseq_amd.build --testing --force`)")
+    fn = _testing_entry("ppcx_testing_psis")
     lr = np.ascontiguousarray(lr, dtype=np.float64).ravel()
     n = lr.size
     cols = np.zeros((n, 0)) if cols is None else np.ascontiguousarray(cols, dtype=np.float64).reshape(n, -1)
     out = np.zeros(cols.shape[1] + 1)
-    _check(lib.ppcx_testing_psis(n, int(cols.shape[1]), _p(lr, C.c_double), _p(cols, C.c_double) if cols.size else None,
-                                 _p(out, C.c_double)))
+    _check(fn(n, int(cols.shape[1]), _p(lr, C.c_double), _p(cols, C.c_double) if cols.size else None, _p(out, C.c_double)))
     return out
 
 
@@ -260,10 +258,7 @@ def testing_loo_mcse(ll, excluded=None, r_eff=None):
 
 
 def _testing_loo(entry, fields, ll, excluded, r_eff):
-    lib = load()
-    if not hasattr(lib, entry):
-        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before {entry} existed: rebuild it "
-                        "(`python -m ppcseq_amd.build --testing --force`)")
+    fn = _testing_entry(entry)
     ll = np.asarray(ll, dtype=np.float64)
     ll = ll.reshape(ll.shape[0], -1)
     n, nc = ll.shape
@@ -271,8 +266,7 @@ def _testing_loo(entry, fields, ll, excluded, r_eff):
     ex = None if excluded is None else np.ascontiguousarray(excluded, dtype=np.int32).ravel()
     re = None if r_eff is None else np.ascontiguousarray(r_eff, dtype=np.float64).ravel()
     out = np.zeros((nc, len(fields)))
-    _check(getattr(lib, entry)(n, nc, _p(cols, C.c_double), _p(ex, C.c_int32) if ex is not None else None,
-                               _p(re, C.c_double) if re is not None else None, _p(out, C.c_double)))
+    _check(fn(n, nc, _p(cols, C.c_double), _p(ex, C.c_int32), _p(re, C.c_double), _p(out, C.c_double)))
     return out
 
 
@@ -280,10 +274,7 @@ def testing_loo_predict(ll, x, y, excluded=None, r_eff=None, p_lo=0.025, p_hi=0.
     """The kernel of ppcx_fit_loo_predict on host-given columns (testing build only; csrc/ppcx_testing.h
     ppcx_testing_loo_predict): ll [n_draws, n_cells] log-likelihoods, x [n_draws, n_cells] predictive counts, y [n_cells] observed
     counts, excluded / r_eff None or [n_cells]. Returns [n_cells, 6]: mean, lower, upper, pit_lt, pit_le, khat."""
-    lib = load()
-    if not hasattr(lib, "ppcx_testing_loo_predict"):
-        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before ppcx_testing_loo_predict existed: rebuild it "
-                        "(`python -m ppcseq_amd.build --testing --force`)")
+    fn = _testing_entry("ppcx_testing_loo_predict")
     ll = np.asarray(ll, dtype=np.float64)
     ll = ll.reshape(ll.shape[0], -1)
     n, nc = ll.shape
@@ -293,61 +284,51 @@ def testing_loo_predict(ll, x, y, excluded=None, r_eff=None, p_lo=0.025, p_hi=0.
     ex = None if excluded is None else np.ascontiguousarray(excluded, dtype=np.int32).ravel()
     re = None if r_eff is None else np.ascontiguousarray(r_eff, dtype=np.float64).ravel()
     out = np.zeros((nc, len(LOO_PREDICT_FIELDS)))
-    _check(lib.ppcx_testing_loo_predict(_p(cols, C.c_double), _p(xs, C.c_int32), n, nc, _p(ys, C.c_int32),
-                                        _p(ex, C.c_int32) if ex is not None else None,
-                                        _p(re, C.c_double) if re is not None else None, float(p_lo), float(p_hi),
-                                        _p(out, C.c_double)))
+    _check(fn(_p(cols, C.c_double), _p(xs, C.c_int32), n, nc, _p(ys, C.c_int32), _p(ex, C.c_int32), _p(re, C.c_double),
+              float(p_lo), float(p_hi), _p(out, C.c_double)))
     return out
 
 
 def _testing_approx_columns(entry, ll, log_ratio, excluded):
     """What the two approximate-posterior test entries share: the library, ll as [n_cells][n], log_ratio [n], the flags"""
-    lib = load()
-    if not hasattr(lib, entry):
-        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before {entry} existed: rebuild it "
-                        "(`python -m ppcseq_amd.build --testing --force`)")
+    fn = _testing_entry(entry)
     ll = np.asarray(ll, dtype=np.float64)
     ll = ll.reshape(ll.shape[0], -1)
     lr = np.ascontiguousarray(log_ratio, dtype=np.float64).ravel()
     if lr.size != ll.shape[0]:
         raise ValueError("log_ratio must hold one value per draw")
     ex = None if excluded is None else np.ascontiguousarray(excluded, dtype=np.int32).ravel()
-    return lib, np.ascontiguousarray(ll.T), lr, ex
+    return fn, np.ascontiguousarray(ll.T), lr, ex
 
 
 def testing_loo_approx(ll, log_ratio, excluded=None):
     """The kernel of ppcx_fit_loo_approx on host-given columns (testing build only; csrc/ppcx_testing.h ppcx_testing_loo_approx):
     ll [n_draws, n_cells], log_ratio [n_draws] (log_p - log_g of the draws), excluded None or [n_cells]. Returns [n_cells, 4]:
     elpd_loo, p_loo, looic, khat."""
-    lib, cols, lr, ex = _testing_approx_columns("ppcx_testing_loo_approx", ll, log_ratio, excluded)
+    fn, cols, lr, ex = _testing_approx_columns("ppcx_testing_loo_approx", ll, log_ratio, excluded)
     nc, n = cols.shape
     out = np.zeros((nc, len(LOO_FIELDS)))
-    _check(lib.ppcx_testing_loo_approx(n, nc, _p(cols, C.c_double), _p(lr, C.c_double),
-                                       _p(ex, C.c_int32) if ex is not None else None, _p(out, C.c_double)))
+    _check(fn(n, nc, _p(cols, C.c_double), _p(lr, C.c_double), _p(ex, C.c_int32), _p(out, C.c_double)))
     return out
 
 
 def testing_loo_predict_approx(ll, log_ratio, x, y, excluded=None, p_lo=0.025, p_hi=0.975):
     """The kernel of ppcx_fit_loo_predict_approx on host-given columns (testing build only; csrc/ppcx_testing.h
     ppcx_testing_loo_predict_approx): as testing_loo_predict with log_ratio [n_draws] and r_eff = 1. Returns [n_cells, 6]."""
-    lib, cols, lr, ex = _testing_approx_columns("ppcx_testing_loo_predict_approx", ll, log_ratio, excluded)
+    fn, cols, lr, ex = _testing_approx_columns("ppcx_testing_loo_predict_approx", ll, log_ratio, excluded)
     nc, n = cols.shape
     xs = np.ascontiguousarray(np.asarray(x).reshape(n, nc).T, dtype=np.int32)
     ys = np.ascontiguousarray(np.broadcast_to(np.asarray(y), (nc,)), dtype=np.int32)
     out = np.zeros((nc, len(LOO_PREDICT_FIELDS)))
-    _check(lib.ppcx_testing_loo_predict_approx(_p(cols, C.c_double), _p(lr, C.c_double), _p(xs, C.c_int32), n, nc, _p(ys, C.c_int32),
-                                               _p(ex, C.c_int32) if ex is not None else None, float(p_lo), float(p_hi),
-                                               _p(out, C.c_double)))
+    _check(fn(_p(cols, C.c_double), _p(lr, C.c_double), _p(xs, C.c_int32), n, nc, _p(ys, C.c_int32), _p(ex, C.c_int32),
+              float(p_lo), float(p_hi), _p(out, C.c_double)))
     return out
 
 
 def testing_relative_eff(ll, chains):
     """The kernel of ppcx_fit_relative_eff on host-given log-likelihood columns (testing build only; csrc/ppcx_testing.h
     ppcx_testing_relative_eff): ll [chains * n, n_cells], the draws chain-major. Returns [n_cells]."""
-    lib = load()
-    if not hasattr(lib, "ppcx_testing_relative_eff"):
-        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before ppcx_testing_relative_eff existed: rebuild it "
-                        "(`python -m ppcseq_amd.build --testing --force`)")
+    fn = _testing_entry("ppcx_testing_relative_eff")
     ll = np.asarray(ll, dtype=np.float64)
     ll = ll.reshape(ll.shape[0], -1)
     rows, nc = ll.shape
@@ -356,7 +337,7 @@ def testing_relative_eff(ll, chains):
         raise ValueError("ll must hold chains * n rows")
     cols = np.ascontiguousarray(ll.T)
     out = np.zeros(nc)
-    _check(lib.ppcx_testing_relative_eff(chains, rows // chains, nc, _p(cols, C.c_double), _p(out, C.c_double)))
+    _check(fn(chains, rows // chains, nc, _p(cols, C.c_double), _p(out, C.c_double)))
     return out
 
 
@@ -377,10 +358,7 @@ def testing_ppc_exact(eta, sigma_raw, y, excluded=None, truncation_compensation=
     """The kernel of ppcx_fit_ppc_exact on host-given columns (testing build only; csrc/ppcx_testing.h ppcx_testing_ppc_exact):
     eta, sigma_raw [n_draws, n_cells], y [n_cells] observed counts, excluded None or [n_cells]. Returns Fit.ppc_exact's dict of
     [n_cells] arrays, or with raw=True the [n_cells, 9] doubles as the kernel wrote them."""
-    lib = load()
-    if not hasattr(lib, "ppcx_testing_ppc_exact"):
-        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before ppcx_testing_ppc_exact existed: rebuild it "
-                        "(`python -m ppcseq_amd.build --testing --force`)")
+    fn = _testing_entry("ppcx_testing_ppc_exact")
     eta = np.asarray(eta, dtype=np.float64)
     eta = eta.reshape(eta.shape[0], -1)
     n, nc = eta.shape
@@ -389,9 +367,8 @@ def testing_ppc_exact(eta, sigma_raw, y, excluded=None, truncation_compensation=
     ys = np.ascontiguousarray(np.broadcast_to(np.asarray(y), (nc,)), dtype=np.int32)
     ex = None if excluded is None else np.ascontiguousarray(excluded, dtype=np.int32).ravel()
     out = np.zeros((nc, len(PPC_EXACT_FIELDS)))
-    _check(lib.ppcx_testing_ppc_exact(n, nc, _p(ec, C.c_double), _p(sc, C.c_double), _p(ys, C.c_int32),
-                                      _p(ex, C.c_int32) if ex is not None else None, float(truncation_compensation), float(p_lo),
-                                      float(p_hi), _p(out, C.c_double)))
+    _check(fn(n, nc, _p(ec, C.c_double), _p(sc, C.c_double), _p(ys, C.c_int32), _p(ex, C.c_int32), float(truncation_compensation),
+              float(p_lo), float(p_hi), _p(out, C.c_double)))
     return out if raw else _ppc_exact_dict(out)
 
 
@@ -411,10 +388,7 @@ def testing_loo_exact(ll, eta, sigma_raw, y, excluded=None, r_eff=None, log_rati
     ppcx_testing_loo_exact): ll, eta, sigma_raw [n_draws, n_cells], y [n_cells] observed counts, excluded / r_eff None or
     [n_cells]; log_ratio None, or [n_draws] (log_p - log_g of the draws): the kernel as ppcx_fit_loo_predict_exact_approx runs it.
     Returns Fit.loo_predict_exact's dict of [n_cells] arrays, or with raw=True the [n_cells, 10] doubles as the kernel wrote them."""
-    lib = load()
-    if not hasattr(lib, "ppcx_testing_loo_exact"):
-        raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before ppcx_testing_loo_exact existed: rebuild it "
-                        "(`python -m ppcseq_amd.build --testing --force`)")
+    fn = _testing_entry("ppcx_testing_loo_exact")
     ll = np.asarray(ll, dtype=np.float64)
     ll = ll.reshape(ll.shape[0], -1)
     n, nc = ll.shape
@@ -428,10 +402,8 @@ def testing_loo_exact(ll, eta, sigma_raw, y, excluded=None, r_eff=None, log_rati
     if lr is not None and lr.size != n:
         raise ValueError("log_ratio must hold one value per draw")
     out = np.zeros((nc, len(LOO_EXACT_FIELDS)))
-    _check(lib.ppcx_testing_loo_exact(n, nc, _p(lc, C.c_double), _p(ec, C.c_double), _p(sc, C.c_double), _p(ys, C.c_int32),
-                                      _p(ex, C.c_int32) if ex is not None else None, _p(re, C.c_double) if re is not None else None,
-                                      _p(lr, C.c_double) if lr is not None else None, float(truncation_compensation), float(p_lo),
-                                      float(p_hi), _p(out, C.c_double)))
+    _check(fn(n, nc, _p(lc, C.c_double), _p(ec, C.c_double), _p(sc, C.c_double), _p(ys, C.c_int32), _p(ex, C.c_int32),
+              _p(re, C.c_double), _p(lr, C.c_double), float(truncation_compensation), float(p_lo), float(p_hi), _p(out, C.c_double)))
     return out if raw else _loo_exact_dict(out)
 
 
@@ -538,12 +510,9 @@ class Model:
 
     def testing_disp_table(self):
         """The dispersion tables the device built, [G][panel][function][12] (ppcx_disp.h layout; testing build only)."""
-        lib = load()
-        if not hasattr(lib, "ppcx_testing_get_disp_table"):
-            raise PpcxError(f"{LIB_PATH} is not the testing build, or one built before ppcx_testing_get_disp_table existed: "
-                            "rebuild it (`python -m ppcseq_amd.build --testing --force`)")
+        fn = _testing_entry("ppcx_testing_get_disp_table")
         out = np.zeros((self.G, 32, 2, 12))
-        _check(lib.ppcx_testing_get_disp_table(self._h, _p(out, C.c_double)))
+        _check(fn(self._h, _p(out, C.c_double)))
         return out
 
     def log_prob_grad(self, u):
@@ -618,11 +587,9 @@ class Model:
 
     def bench_kernel(self, which=0, nchains=1, warm_rounds=40, reps=50, n_merge=1):
         """(ms per launch, command type) of one kernel of the three-launch round -- testing build only."""
-        lib = load()
-        if not hasattr(lib, "ppcx_testing_bench_kernel"):
-            raise PpcxError(f"{LIB_PATH} is not the testing build")
+        fn = _testing_entry("ppcx_testing_bench_kernel")
         ms, t = C.c_double(), C.c_int()
-        _check(lib.ppcx_testing_bench_kernel(self._h, int(which), nchains, warm_rounds, reps, n_merge, C.byref(ms), C.byref(t)))
+        _check(fn(self._h, int(which), nchains, warm_rounds, reps, n_merge, C.byref(ms), C.byref(t)))
         return ms.value, t.value
 
     def close(self):
@@ -820,7 +787,7 @@ class Fit:
         out = np.zeros((g.size, S, len(fields)))
         re = self._r_eff(g, r_eff)
         if g.size:
-            _check(call(int(g.size), _p(g, C.c_int32), _p(re, C.c_double) if re is not None else None, _p(out, C.c_double)))
+            _check(call(int(g.size), _p(g, C.c_int32), _p(re, C.c_double), _p(out, C.c_double)))
         res = {k: out[:, :, i].copy() for i, k in enumerate(fields)}
         excl = np.zeros(self.model.G * S, bool)
         excl[np.asarray(self.model.excl, dtype=np.int64)] = True
@@ -939,7 +906,7 @@ class Fit:
         out = np.zeros((g.size, self.model.S, len(LOO_EXACT_FIELDS)))
         re = self._r_eff(g, r_eff)
         if g.size:
-            _check(call(int(g.size), _p(g, C.c_int32), _p(re, C.c_double) if re is not None else None, _p(out, C.c_double)))
+            _check(call(int(g.size), _p(g, C.c_int32), _p(re, C.c_double), _p(out, C.c_double)))
         res = _loo_exact_dict(out)
         res["genes"] = g.astype(np.int64)
         res["n_draws"] = self.chains * self.n_keep

@@ -1,5 +1,6 @@
 // ppcx_block.h -- the workgroup toolkit of the fit diagnostics on gfx950 (ppcx_summary.hip, ppcx_psis.hip, ppcx_loo.hip,
-// ppcx_loo_predict.hip, ppcx_reff.hip, ppcx_ppc_exact.hip): a workgroup of kBlockThreads threads in kBlockWaves wavefronts; and
+// ppcx_loo_predict.hip, ppcx_reff.hip, ppcx_ppc_exact.hip): a workgroup of kBlockThreads threads in kBlockWaves wavefronts, its
+// reductions and its strided sweeps over a cell's draws (draws_sum, draws_max); and
 // the cross-lane reduction of one wavefront, which the posterior-predictive kernels (ppcx_ppc.hip: workgroups of 512) share with
 // it. Device code only: the `__host__ __device__` statistic headers
 // (ppcx_summary.h, ppcx_psis.h, ppcx_loo.h) never include it, the CPU checks compile without it.
@@ -49,6 +50,20 @@ __device__ inline double block_max(double v, double* red) {
 }
 // whether b holds in any thread of the workgroup; every thread gets it (a barrier)
 __device__ __forceinline__ bool block_any(bool b) { return __syncthreads_or(b ? 1 : 0) != 0; }
+// sum over i = 0 .. n - 1 of f(i), thread t taking i = t, t + kBlockThreads, ...; every thread gets it (fixed order).
+// draws_max: their maximum (NaN-free values; -INFINITY for an i that takes no part)
+template <class F>
+__device__ __forceinline__ double draws_sum(long n, double* red, F f) {
+  double s = 0.0;
+  for (long i = threadIdx.x; i < n; i += kBlockThreads) s += f(i);
+  return block_sum(s, red);
+}
+template <class F>
+__device__ __forceinline__ double draws_max(long n, double* red, F f) {
+  double m = -INFINITY;
+  for (long i = threadIdx.x; i < n; i += kBlockThreads) m = fmax(m, f(i));
+  return block_max(m, red);
+}
 
 // ascending bitonic sort of s[0 .. npad) (npad a power of two; the caller pads with the largest value): double or uint64_t
 template <class T>

@@ -223,7 +223,8 @@ struct LooArgs {
   const double* lr = nullptr;   // [n] log_p - log_g of an ADVI fit's draws: the approximate-posterior statistic (ppcx_loo_ap.h)
   long n = 0;                   // draws
   int cell0 = 0, n_cells = 0;   // first cell of the launch; cells of the table / columns
-  double* scratch = nullptr;    // [launch's cells][n] the long path's ratios ([..][3 n] with lr: ratios, ll, log weights)
+  double* scratch = nullptr;    // [launch's cells][slice] the long path's arrays, `slice` doubles per cell as the statistic's kernel
+                                //  lays them out (set per batch by cells_in_batches, ppcx_loo_dev.h)
   int sel_pad = 0;              // loo_sel_pad: the selection buffer
   double* out = nullptr;        // [cells][kLooFields], or [cells][kLooMcseFields] (ppcx_fit_loo_mcse)
 };
@@ -259,7 +260,8 @@ struct GivenCells {
   const double* r_eff = nullptr; double r_eff_min = 1.0;
   const double* log_ratio = nullptr;   // [n] (host) log ratios of the draws, or null
 };
-// The drivers below walk the cells through for_gene_batches / for_given_columns (ppcx_loo_dev.h); out is host, scratch_bytes
+// The drivers below walk the cells through for_gene_batches / for_given_columns and launch through cells_in_batches
+// (ppcx_loo_dev.h: LDS against scratch, the kernel's instantiation and its dynamic LDS in one place); out is host, scratch_bytes
 // bounds the gene table of a batch and the cells' scratch of a launch alike (kPsisScratchBytes in the product). Synchronous.
 // LOO: fields = kLooFields, or kLooMcseFields for mcse_elpd_loo and n_eff as well (out holds that many per cell; the first four
 // are the same bits). With log_ratio (an ADVI fit; kLooFields only) the approximate-posterior statistic of ppcx_loo_ap.h: ratios,

@@ -80,34 +80,31 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_kernel(LooArgs a) {
   __shared__ PsisShared sh;
   const int tid = threadIdx.x;
   const long n = a.n;
-  uint64_t* K = lds_u;                                   // [sel_pad] keys of the M + 1 largest ratios
-  double* X = reinterpret_cast<double*>(lds_u + a.sel_pad);            // [sel_pad] the tail's exceedances
-  double* V = LDS ? X + a.sel_pad : a.scratch + (long)blockIdx.x * n;  // the cell's ratios r = -ll
+  const CellMem m = cell_mem<LDS>(lds_u, a, n);
+  uint64_t* K = m.K; double* X = m.X;
+  double* V = m.V;                                       // [n] the cell's ratios r = -ll
   const LooCell c = loo_cell<COLS>(a);                   // of this launch's cells (the table's genes, or the given columns)
-  const int cell = c.cell, gi = c.gi, s = c.s, y = c.y;
+  const int cell = c.cell;
   const bool excluded = c.excluded;
   double* o = a.out + (long)cell * (MCSE ? kLooMcseFields : kLooFields);
   // ---- the ratios; NaN / +Inf; N (the -Inf ratios take no part); the largest ratio and the largest ll
-  long N; double rmax, lmax;
-  if (loo_cell_ratios<COLS>(a, cell, gi, s, y, excluded, V, sh, &N, &rmax, &lmax)) {
+  CellRatios cr;
+  if (loo_cell_ratios<COLS, false>(a, c, excluded, V, nullptr, sh, &cr)) {
     if (tid == 0) {
       o[0] = o[1] = o[2] = o[3] = NAN;
       if constexpr (MCSE) o[4] = o[5] = NAN;
     }
     return;
   }
+  const long N = cr.N; const double rmax = cr.rmax, lmax = cr.lmax;
   // ---- lpd = logsumexp(ll) - log N
-  double sl = 0.0;
-  for (long i = tid; i < n; i += kBlockThreads) { const double r = V[i]; if (r != -INFINITY) sl += exp(-r - lmax); }
-  sl = block_sum(sl, sh.red);
+  const double sl = draws_sum(n, sh.red, [&](long i) { const double r = V[i]; return r != -INFINITY ? exp(-r - lmax) : 0.0; });
   const double lpd = N > 0 ? (lmax == -INFINITY ? -INFINITY : lmax + log(sl)) - log((double)N) : NAN;
   if (excluded) {                                        // already held out: the exact held-out predictive density
     if (tid == 0) { o[0] = lpd; o[1] = 0.0; o[2] = -2.0 * lpd; o[3] = NAN; }
     if constexpr (MCSE) {                                // uniform weights 1 / N
       const double e = loo_mcse_frame(lpd, -rmax, lmax), re = a.r_eff ? a.r_eff[cell] : 1.0;
-      double sd = 0.0;
-      for (long i = tid; i < n; i += kBlockThreads) { const double r = V[i]; if (r != -INFINITY) sd += loo_mcse_uniform_term(-r, e); }
-      sd = block_sum(sd, sh.red);
+      const double sd = draws_sum(n, sh.red, [&](long i) { const double r = V[i]; return r != -INFINITY ? loo_mcse_uniform_term(-r, e) : 0.0; });
       const double mc = N > 0 ? loo_mcse_blom(sqrt(loo_mcse_uniform_c2(sd, N)), re, sh.red) : NAN;
       if (tid == 0) { o[4] = mc; o[5] = N > 0 ? (double)N * re : NAN; }
     }
@@ -171,45 +168,32 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_ap_kernel(LooArgs a) {
   __shared__ PsisShared sh;
   const int tid = threadIdx.x;
   const long n = a.n;
-  uint64_t* K = lds_u;                                   // [sel_pad] keys of the M + 1 largest ratios
-  double* X = reinterpret_cast<double*>(lds_u + a.sel_pad);            // [sel_pad] the tail's exceedances
-  double* V = LDS ? X + a.sel_pad : a.scratch + (long)blockIdx.x * loo_ap_slice(n);   // [n] the ratios
-  double* L = V + n;                                     // [n] the log-likelihoods
+  const CellMem m = cell_mem<LDS>(lds_u, a, loo_ap_slice(n));
+  const double* V = m.V;                                 // [n] the ratios
+  double* L = m.V + n;                                   // [n] the log-likelihoods
   double* W = L + n;                                     // [n] the log weights
   const LooCell c = loo_cell<COLS>(a);
   double* o = a.out + (long)c.cell * kLooFields;
-  long N; double rmax, lmax;
-  if (loo_ap_cell_ratios<COLS>(a, c.cell, c.gi, c.s, c.y, c.excluded, V, L, sh, &N, &rmax, &lmax)) {
+  // ---- the ratios, the tail and the log weight of every draw
+  CellRatios cr;
+  if (loo_cell_verdict<COLS, true>(a, c, m, L, sh, &cr) == CELL_NAN) {
     if (tid == 0) o[0] = o[1] = o[2] = o[3] = NAN;
     return;
   }
-  // sum over the draws that take part of f(i), or their maximum; every thread gets it (fixed order)
-  auto part_sum = [&](auto f) {
-    double v = 0.0;
-    for (long i = tid; i < n; i += kBlockThreads) if (V[i] != -INFINITY) v += f(i);
-    return block_sum(v, sh.red);
-  };
-  auto part_max = [&](auto f) {
-    double v = -INFINITY;
-    for (long i = tid; i < n; i += kBlockThreads) if (V[i] != -INFINITY) v = fmax(v, f(i));
-    return block_max(v, sh.red);
-  };
-  // ---- the tail and the log weight of every draw
-  const int M = psis_tail_len(N);
-  const LooTail lt = loo_cell_tail(V, n, N, M, K, X, a.sel_pad, sh);
-  for (long i = tid; i < n; i += kBlockThreads) W[i] = loo_draw_lw(V, i, rmax, lt, M, K);
-  // ---- logsumexp(lw + ll) - logsumexp(lw); lpd = logsumexp(ll) - log N
-  const double ma = part_max([&](long i) { return W[i] + L[i]; });
-  const double mb = part_max([&](long i) { return W[i]; });
-  const double sa = part_sum([&](long i) { return exp(W[i] + L[i] - ma); });
-  const double sb = part_sum([&](long i) { return exp(W[i] - mb); });
+  const double khat = loo_cell_weights<false>(a, c, m, cr, W, sh);
+  // ---- logsumexp(lw + ll) - logsumexp(lw) over the draws that take part; lpd = logsumexp(ll) - log N
+  auto part = [&](long i) { return V[i] != -INFINITY; };
+  const double ma = draws_max(n, sh.red, [&](long i) { return part(i) ? W[i] + L[i] : -INFINITY; });
+  const double mb = draws_max(n, sh.red, [&](long i) { return part(i) ? W[i] : -INFINITY; });
+  const double sa = draws_sum(n, sh.red, [&](long i) { return part(i) ? exp(W[i] + L[i] - ma) : 0.0; });
+  const double sb = draws_sum(n, sh.red, [&](long i) { return part(i) ? exp(W[i] - mb) : 0.0; });
   const double elpd = loo_ap_lse(ma, sa) - loo_ap_lse(mb, sb);
   double p_loo = 0.0;
   if (!c.excluded) {
-    const double sl = part_sum([&](long i) { return exp(L[i] - lmax); });
-    p_loo = loo_ap_lse(lmax, sl) - log((double)N) - elpd;
+    const double sl = draws_sum(n, sh.red, [&](long i) { return part(i) ? exp(L[i] - cr.lmax) : 0.0; });
+    p_loo = loo_ap_lse(cr.lmax, sl) - log((double)cr.N) - elpd;
   }
-  if (tid == 0) { o[0] = elpd; o[1] = p_loo; o[2] = -2.0 * elpd; o[3] = lt.khat; }
+  if (tid == 0) { o[0] = elpd; o[1] = p_loo; o[2] = -2.0 * elpd; o[3] = khat; }
 }
 
 // ---- launch helpers (host)
@@ -225,32 +209,23 @@ hipError_t launch_loo_ll_kernel(const LooArgs& a, long j0, long n_rows, double* 
   hipLaunchKernelGGL(ppcx_loo_ll_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a, j0, n_rows, out);
   return hipGetLastError();
 }
-template <bool MCSE>
-static hipError_t launch_loo_kernel_of(const LooArgs& a, int n_blocks, hipStream_t st) {
-  const bool lds = a.n <= kPsisLdsDraws, cols = a.cols != nullptr;
-  const size_t bytes = sizeof(double) * (2 * (size_t)a.sel_pad + (lds ? (size_t)a.n : 0));
-  void (*const kernel)(LooArgs) = lds ? (cols ? ppcx_loo_kernel<true, true, MCSE> : ppcx_loo_kernel<true, false, MCSE>)
-                                      : (cols ? ppcx_loo_kernel<false, true, MCSE> : ppcx_loo_kernel<false, false, MCSE>);
-  return launch_dynamic_lds(kernel, n_blocks, kBlockThreads, bytes, st, a);
-}
-static hipError_t launch_loo_ap_kernel(const LooArgs& a, int n_blocks, hipStream_t st) {
-  const bool lds = a.n <= kPsisLdsDraws, cols = a.cols != nullptr;
-  const size_t bytes = sizeof(double) * (2 * (size_t)a.sel_pad + (lds ? (size_t)loo_ap_slice(a.n) : 0));
-  void (*const kernel)(LooArgs) = lds ? (cols ? ppcx_loo_ap_kernel<true, true> : ppcx_loo_ap_kernel<true, false>)
-                                      : (cols ? ppcx_loo_ap_kernel<false, true> : ppcx_loo_ap_kernel<false, false>);
-  return launch_dynamic_lds(kernel, n_blocks, kBlockThreads, bytes, st, a);
-}
+PPCX_KERNEL_OF(ppcx_loo_kernel);
+PPCX_KERNEL_OF(ppcx_loo_ap_kernel);
+// doubles per cell of the kernel that launch_loo_kernel picks
+static long loo_slice(const LooArgs& a) { return a.lr ? loo_ap_slice(a.n) : a.n; }
 // fields: kLooFields, or kLooMcseFields (a.out then holds six per cell); with a.lr the approximate-posterior kernel (kLooFields)
 hipError_t launch_loo_kernel(const LooArgs& a, int fields, int n_blocks, hipStream_t st) {
-  if (a.lr) return fields == kLooFields ? launch_loo_ap_kernel(a, n_blocks, st) : hipErrorInvalidValue;
-  return fields == kLooMcseFields ? launch_loo_kernel_of<true>(a, n_blocks, st) : launch_loo_kernel_of<false>(a, n_blocks, st);
+  const CellLaunch c = cell_launch(a, n_blocks);
+  if (a.lr && fields != kLooFields) return hipErrorInvalidValue;
+  void (*const kernel)(LooArgs) = a.lr ? pick_kernel<ppcx_loo_ap_kernel_of>(c.lds, c.cols)
+                                       : pick_kernel<ppcx_loo_kernel_of>(c.lds, c.cols, fields == kLooMcseFields);
+  return launch_cell_kernel(kernel, a, c, a.sel_pad, loo_slice(a), st);
 }
 
 // Cells of a launch in batches: all at once where the ratios live in LDS, else as many as the scratch bound holds.
-static hipError_t loo_cells(LooArgs a, int fields, int n_cells, size_t scratch_bytes, DeviceBuffer<double>& scratch, hipStream_t st) {
-  return loo_cell_batches(n_cells, a.n > kPsisLdsDraws ? (a.lr ? loo_ap_slice(a.n) : a.n) : 0, scratch_bytes, scratch, [&](int c0, int nc, double* scr) {
-    a.cell0 = c0; a.scratch = scr;
-    return launch_loo_kernel(a, fields, nc, st);
+static hipError_t loo_cells(const LooArgs& args, int fields, int n_cells, size_t scratch_bytes, DeviceBuffer<double>& scratch, hipStream_t st) {
+  return cells_in_batches(args, loo_slice(args), n_cells, scratch_bytes, scratch, [&](const LooArgs& a, const CellLaunch& c) {
+    return launch_loo_kernel(a, fields, c.n_blocks, st);
   });
 }
 

@@ -1,16 +1,21 @@
 // ppcx_loo_dev.h -- what the per-cell leave-one-out kernels share (ppcx_loo.hip: PSIS-LOO per cell; ppcx_loo_predict.hip: the
 // leave-one-out predictive interval per cell; ppcx_reff.hip: the relative efficiency per cell). On the device: which cell a
-// workgroup has, the cell's linear predictor and log-likelihood from the transposed table, its ratios r = -ll (an ADVI fit:
-// (log_p - log_g) - ll, ppcx_loo_ap.h), the fitted tail with the copies of the cutoff, a draw's log weight under the tie rule.
+// workgroup has and where its arrays live (cell_mem), the cell's linear predictor and log-likelihood from the transposed table,
+// its ratios r = -ll (an ADVI fit: (log_p - log_g) - ll, ppcx_loo_ap.h), the fitted tail with the copies of the cutoff, a draw's
+// log weight under the tie rule -- together the weights stage (loo_cell_verdict, loo_cell_weights) -- and the workgroup's sums
+// for the exact sweeps of ppcx_ppc_exact.h (ExactBlockSums).
 // The table itself and a cell's read of it are ppcx_table.h's, shared with the posterior-predictive kernels.
 // On the host: the one walk over a fit's cells in gene batches (for_gene_batches), its counterpart for host-given columns
-// (for_given_columns) and the batches of cells under the scratch bound (loo_cell_batches); a statistic's drivers add their
-// argument block and their kernel. The statistic is ppcx_loo.h; the workgroup pieces are ppcx_block.h and ppcx_psis_dev.h.
+// (for_given_columns) and the launch path: the batches of cells under the scratch bound (cells_in_batches), LDS against scratch
+// (cell_launch), a kernel template's instantiation (pick_kernel) and its dynamic LDS (launch_cell_kernel); a statistic states its
+// slice function, its kernel template and its argument block. The statistic is ppcx_loo.h; the workgroup pieces are ppcx_block.h
+// and ppcx_psis_dev.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ppcx_psis_dev.h"
 #include "ppcx_loo.h"
 #include "ppcx_loo_ap.h"
+#include "ppcx_ppc_exact.h"
 #include "ppcx_columns.h"
 #include "ppcx_table.h"
 
@@ -44,52 +49,47 @@ __device__ __forceinline__ double loo_cell_ll(const LooArgs& a, int gi, int s, l
   return loo_ll(y, eta, sigma_raw);
 }
 
-// The cell's ratios r = -ll into V[0 .. n). Returns whether the cell is NaN (a NaN ratio, or +Inf where the cell is not
-// excluded); otherwise N (the ratios that are not -Inf), the largest ratio and the largest ll. Every thread gets the same.
-template <bool COLS>
-__device__ inline bool loo_cell_ratios(const LooArgs& a, int cell, int gi, int s, int y, bool excluded, double* V, PsisShared& sh,
-                                       long* N, double* rmax_out, double* lmax_out) {
-  const int tid = threadIdx.x;
-  const long n = a.n;
-  bool bad = false; double cnt = 0.0, rmax = -INFINITY, lmax = -INFINITY;
-  for (long i = tid; i < n; i += kBlockThreads) {
-    const double ll = COLS ? a.cols[(long)cell * n + i] : loo_cell_ll(a, gi, s, i, y);
-    const double r = -ll;
-    bad = bad || isnan(r) || (!excluded && r == INFINITY);
-    if (r != -INFINITY) { cnt += 1.0; rmax = fmax(rmax, r); lmax = fmax(lmax, ll); }
-    V[i] = r;
-  }
-  bad = block_any(bad);
-  if (bad) return true;
-  *N = (long)block_sum(cnt, sh.red);
-  *rmax_out = block_max(rmax, sh.red);
-  *lmax_out = block_max(lmax, sh.red);
-  return false;
+// The workgroup's memory: the two selection arrays of sel_pad slots at the start of the dynamic LDS (K: the keys of the M + 1
+// largest ratios, X: the tail's exceedances), then the cell's own arrays from V on, `slice` doubles: behind them in LDS, or in
+// the workgroup's slice of the launch's scratch
+struct CellMem { uint64_t* K; double* X; double* V; };
+template <bool LDS>
+__device__ __forceinline__ CellMem cell_mem(uint64_t* lds_u, const LooArgs& a, long slice) {
+  double* X = reinterpret_cast<double*>(lds_u + a.sel_pad);
+  return CellMem{lds_u, X, LDS ? X + a.sel_pad : a.scratch + (long)blockIdx.x * slice};
 }
 
-// The same for the approximate-posterior statistic (ppcx_loo_ap.h step 0): r = a.lr - ll (an excluded cell: a.lr alone) into
-// V[0 .. n) and, where L is given, ll into L[0 .. n). Also NaN: a cell without a participating draw.
-template <bool COLS>
-__device__ inline bool loo_ap_cell_ratios(const LooArgs& a, int cell, int gi, int s, int y, bool excluded, double* V, double* L,
-                                          PsisShared& sh, long* N, double* rmax_out, double* lmax_out) {
-  const int tid = threadIdx.x;
+// The cell's ratios r = -ll into V[0 .. n); AP, the approximate-posterior statistic (ppcx_loo_ap.h step 0): r = a.lr - ll (an
+// excluded cell: a.lr alone) and, where L is given, ll into L[0 .. n). Returns whether the cell is NaN (a NaN ratio, or +Inf
+// where the cell is not excluded; AP: loo_ap_bad); otherwise N (the ratios that are not -Inf), the
+// largest ratio and the largest ll. Every thread gets the same.
+struct CellRatios { long N; double rmax, lmax; };
+template <bool COLS, bool AP>
+__device__ inline bool loo_cell_ratios(const LooArgs& a, const LooCell& c, bool excluded, double* V, double* L, PsisShared& sh,
+                                       CellRatios* out) {
   const long n = a.n;
   bool bad = false; double cnt = 0.0, rmax = -INFINITY, lmax = -INFINITY;
-  for (long i = tid; i < n; i += kBlockThreads) {
-    const double ll = COLS ? a.cols[(long)cell * n + i] : loo_cell_ll(a, gi, s, i, y);
-    const double lr = a.lr[i];
-    const double r = loo_ap_ratio(lr, ll, excluded);
-    bad = bad || loo_ap_bad(lr, ll, r, excluded);
+  for (long i = threadIdx.x; i < n; i += kBlockThreads) {
+    const double ll = COLS ? a.cols[(long)c.cell * n + i] : loo_cell_ll(a, c.gi, c.s, i, c.y);
+    double r;
+    if constexpr (AP) {
+      const double lr = a.lr[i];
+      r = loo_ap_ratio(lr, ll, excluded);
+      bad = bad || loo_ap_bad(lr, ll, r, excluded);
+    } else {
+      r = -ll;
+      bad = bad || isnan(r) || (!excluded && r == INFINITY);
+    }
     if (r != -INFINITY) { cnt += 1.0; rmax = fmax(rmax, r); lmax = fmax(lmax, ll); }
     V[i] = r;
-    if (L) L[i] = ll;
+    if (AP && L) L[i] = ll;
   }
   bad = block_any(bad);
   if (bad) return true;
-  *N = (long)block_sum(cnt, sh.red);
-  *rmax_out = block_max(rmax, sh.red);
-  *lmax_out = block_max(lmax, sh.red);
-  return *N == 0;
+  out->N = (long)block_sum(cnt, sh.red);
+  out->rmax = block_max(rmax, sh.red);
+  out->lmax = block_max(lmax, sh.red);
+  return false;
 }
 
 // The tail of the ratios V (ppcx_loo.h step 2): k-hat, sigma, whether the tail is smoothed, and where it is, n_eq = the copies
@@ -128,19 +128,113 @@ __device__ __forceinline__ double loo_draw_lw(const double* V, long i, double mx
   return loo_predict_lw(r, mx, loo_draw_tail_pos(V, i, r, lt, M, K), M, lt.khat, lt.sigma, lt.tl.ec);
 }
 
-// Cells of a launch in batches: all at once where a cell's arrays live in LDS (slice = 0), else as many as the scratch bound
-// holds at `slice` doubles per cell. launch(first cell, cells, scratch). Asynchronous: `scratch` belongs to the caller, who
-// synchronises before it goes.
-template <class Launch>
-hipError_t loo_cell_batches(int n_cells, long slice, size_t scratch_bytes, DeviceBuffer<double>& scratch, Launch launch) {
+// The log weight of every draw into W[0 .. n) from the ratios V (largest: mx) and their fitted tail; NORM: then the normalised
+// weights exp(W - max) / sum in their place (a barrier is the caller's, before another thread's W is read)
+template <bool NORM>
+__device__ __forceinline__ void loo_cell_lw(const double* V, double* W, long n, double mx, const LooTail& lt, int M, const uint64_t* K,
+                                            PsisShared& sh) {
+  const int tid = threadIdx.x;
+  if constexpr (!NORM) {
+    for (long i = tid; i < n; i += kBlockThreads) W[i] = loo_draw_lw(V, i, mx, lt, M, K);
+  } else {
+    double mxw = -INFINITY;
+    for (long i = tid; i < n; i += kBlockThreads) {
+      const double lw = loo_draw_lw(V, i, mx, lt, M, K);
+      W[i] = lw; mxw = fmax(mxw, lw);
+    }
+    mxw = block_max(mxw, sh.red);
+    double sw = 0.0;
+    for (long i = tid; i < n; i += kBlockThreads) { const double e = exp(W[i] - mxw); W[i] = e; sw += e; }
+    sw = block_sum(sw, sh.red);
+    for (long i = tid; i < n; i += kBlockThreads) W[i] = W[i] / sw;
+  }
+}
+
+// The weights stage of a cell, once for the kernels that materialise weights (ppcx_loo_ap_kernel: log weights; ppcx_loo_predict_
+// kernel, ppcx_loo_exact_kernel: normalised ones -- so their khat is the same bits by construction), in two steps:
+// loo_cell_verdict: the ratios into m.V and what becomes of the cell. CELL_UNIFORM: a cell that a NUTS fit excludes is held out
+// already -- the caller weights every draw alike and loo_cell_weights is not called.
+// loo_cell_weights: the tail of psis_tail_len(N, r_eff) draws and the (log) weight of every draw into W; returns khat.
+enum CellVerdict : int { CELL_NAN = 0, CELL_UNIFORM, CELL_WEIGHTED };
+template <bool COLS, bool AP>
+__device__ __forceinline__ CellVerdict loo_cell_verdict(const LooArgs& a, const LooCell& c, const CellMem& m, double* L, PsisShared& sh,
+                                                        CellRatios* r) {
+  if (loo_cell_ratios<COLS, AP>(a, c, c.excluded, m.V, L, sh, r)) return CELL_NAN;
+  if (!AP && c.excluded) return CELL_UNIFORM;
+  return r->N == 0 ? CELL_NAN : CELL_WEIGHTED;
+}
+template <bool NORM>
+__device__ __forceinline__ double loo_cell_weights(const LooArgs& a, const LooCell& c, const CellMem& m, const CellRatios& r, double* W,
+                                                   PsisShared& sh) {
+  const int M = psis_tail_len(r.N, a.r_eff ? a.r_eff[c.cell] : 1.0);
+  const LooTail lt = loo_cell_tail(m.V, a.n, r.N, M, m.K, m.X, a.sel_pad, sh);
+  loo_cell_lw<NORM>(m.V, W, a.n, r.rmax, lt, M, m.K, sh);
+  return lt.khat;
+}
+
+// The sums of ppc_exact_sweeps (ppcx_ppc_exact.h) by the workgroup over (eta_i, ln phi_i) = (E[i], LP[i]): a strided sweep and
+// block_sum per sum, in the fixed order; every thread holds them. WEIGHTED: each term under W[i] (loo_exact_term)
+template <bool WEIGHTED>
+struct ExactBlockSums {
+  const double* W; const double* E; const double* LP; long n; double* red;
+  template <class F, int K>
+  __device__ __forceinline__ void operator()(F f, double (&s)[K]) const {
+#pragma unroll
+    for (int k = 0; k < K; ++k) s[k] = 0.0;
+    for (long i = threadIdx.x; i < n; i += kBlockThreads) {
+      double t[K];
+      (void)f(E[i], LP[i], t);
+#pragma unroll
+      for (int k = 0; k < K; ++k) s[k] += WEIGHTED ? loo_exact_term(W[i], t[k]) : t[k];
+    }
+#pragma unroll
+    for (int k = 0; k < K; ++k) s[k] = block_sum(s[k], red);
+  }
+};
+
+// ---- the launch path (host)
+// A launch over cells: whether a cell's arrays live in LDS (up to kPsisLdsDraws draws) or in the scratch, whether the cells
+// are given columns, and how many there are. The one place that decides the first two.
+struct CellLaunch { bool lds, cols; int n_blocks; };
+inline CellLaunch cell_launch(const LooArgs& l, int n_blocks) { return CellLaunch{l.n <= kPsisLdsDraws, l.cols != nullptr, n_blocks}; }
+// the LooArgs of a statistic's argument block (the block itself, or its member l)
+inline LooArgs& cell_args(LooArgs& a) { return a; }
+template <class P> auto cell_args(P& p) -> decltype((p.l)) { return p.l; }
+
+// The instantiation of a kernel template for runtime flags, in the template's order: pick_kernel<KernelOf>(lds, cols, ..) where
+// KernelOf::get<flags...>() names it (PPCX_KERNEL_OF(kernel) declares kernel_of so)
+#define PPCX_KERNEL_OF(kernel) struct kernel##_of { template <bool... B> static constexpr auto get() { return &kernel<B...>; } }
+template <class KernelOf, bool... B>
+auto pick_kernel() { return KernelOf::template get<B...>(); }
+template <class KernelOf, bool... B, class... Rest>
+auto pick_kernel(bool flag, Rest... rest) {
+  return flag ? pick_kernel<KernelOf, B..., true>(rest...) : pick_kernel<KernelOf, B..., false>(rest...);
+}
+
+// One workgroup of kBlockThreads per cell of the launch c, its dynamic LDS the two selection arrays (sel_pad slots each; 0:
+// none) and, on the LDS path, the cell's `slice` doubles
+template <class P>
+hipError_t launch_cell_kernel(void (*kernel)(P), const P& p, const CellLaunch& c, int sel_pad, long slice, hipStream_t st) {
+  const size_t bytes = sizeof(double) * (2 * (size_t)sel_pad + (c.lds ? (size_t)slice : 0));
+  return launch_dynamic_lds(kernel, c.n_blocks, kBlockThreads, bytes, st, p);
+}
+
+// The cells of a statistic with argument block p (cell_args(p): its LooArgs) at `slice` doubles per cell, in batches: all at
+// once where a cell's arrays live in LDS, else as many as the scratch bound holds. each(p, CellLaunch) launches the statistic's
+// kernels over a batch, p's cell0 and scratch set. Asynchronous: `scratch` belongs to the caller, who synchronises before it goes.
+template <class P, class Each>
+hipError_t cells_in_batches(P p, long slice, int n_cells, size_t scratch_bytes, DeviceBuffer<double>& scratch, Each each) {
+  LooArgs& l = cell_args(p);
   hipError_t e = hipSuccess;
   int batch = n_cells;
-  if (slice > 0) {
+  if (!cell_launch(l, 0).lds) {
     batch = column_batch(scratch_bytes, slice, n_cells);
     if (!scratch.p) e = scratch.alloc((size_t)slice * batch);
   }
-  for (int c0 = 0; e == hipSuccess && c0 < n_cells; c0 += batch)
-    e = launch(c0, n_cells - c0 < batch ? n_cells - c0 : batch, scratch.p);
+  for (int c0 = 0; e == hipSuccess && c0 < n_cells; c0 += batch) {
+    l.cell0 = c0; l.scratch = scratch.p;
+    e = each(p, cell_launch(l, n_cells - c0 < batch ? n_cells - c0 : batch));
+  }
   return e;
 }
 
@@ -167,7 +261,7 @@ struct FitCellsDev {
 
 // The cells of a fit in batches of column_batch(scratch_bytes, ..) genes: each batch's transposed table T (never the table of
 // all the genes), then body(the batch's LooArgs with `out` at its part of the device output [cells][fields], its gene ids
-// (device), its cells, the scratch) launches the statistic over loo_cell_batches. The scratch is allocated by the first batch
+// (device), its cells, the scratch) launches the statistic over cells_in_batches. The scratch is allocated by the first batch
 // that needs it and serves the later ones; every buffer lives until the stream has drained. The output is copied to out (host)
 // at the end. Synchronous.
 template <class Body>

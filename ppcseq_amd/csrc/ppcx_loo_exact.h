@@ -28,7 +28,8 @@
 //      by n -- the blocks of ppcx_ppc_exact.h themselves, so the first nine fields are ppcx_fit_ppc_exact's bit for bit --
 //      and khat = NaN. An ADVI fit: weighted by a_i alone, khat the overall k-hat (ppcx_loo_ap.h).
 //      Both forms are ONE composition: every sum is sum_i w_i f_i, divided by `den` -- n with w_i = 1 for the uniform cell, 1 with
-//      the normalised weights otherwise (a product with 1 and a quotient by 1 are exact).
+//      the normalised weights otherwise (a product with 1 and a quotient by 1 are exact): ppc_exact_sweeps of ppcx_ppc_exact.h,
+//      which this header and that one both call.
 //   6. The fields: mean, sd, p_le, p_ge, lower, upper, y, excluded, outside as ppc_exact_store / ppc_exact_store_nan lay them
 //      out, then khat.
 // Every sum runs in a fixed order with contraction off: a cell's fields are a function of its own draws only.
@@ -41,14 +42,7 @@ namespace ppcx {
 
 constexpr int kLooExactFields = 10;            // kPpcExactFields, then khat (include/ppcx.h PPCX_LOO_EXACT_FIELDS)
 
-// a weighted term of a sum (w = 1 in the uniform cell: the product is exact)
-PPCX_HD double loo_exact_term(double w, double f) { PPCX_NO_CONTRACT return w * f; }
-// step 6
-PPCX_HD void loo_exact_store(double* o, double mean, double sd, double p_le, double p_ge, int lower, int upper, int y, bool excluded,
-                             double khat) {
-  ppc_exact_store(o, mean, sd, p_le, p_ge, lower, upper, y, excluded);
-  o[kPpcExactFields] = khat;
-}
+// step 6: the tenth field beside ppc_exact_sweeps' nine
 PPCX_HD void loo_exact_store_nan(double* o, int y, bool excluded) {
   ppc_exact_store_nan(o, y, excluded);
   o[kPpcExactFields] = NAN;
@@ -120,40 +114,10 @@ inline void loo_exact_cell_host(const double* ll, const double* eta, const doubl
     for (long i = 0; i < n; ++i) { w[i] = exp(w[i] - mxw); sw += w[i]; }
     for (long i = 0; i < n; ++i) w[i] = w[i] / sw;
   }
-  // ---- steps 2 - 4
-  double sm = 0.0;
-  for (long i = 0; i < n; ++i) sm += loo_exact_term(w[i], exp(eta[i]));
-  const double mean = sm / (double)den;
-  double ev = 0.0, dv = 0.0;
-  for (long i = 0; i < n; ++i) {
-    double e, d;
-    ppc_exact_var_terms(eta[i], ppc_exact_phi(lnphi(i)), mean, &e, &d);
-    ev += loo_exact_term(w[i], e); dv += loo_exact_term(w[i], d);
-  }
-  const double sd = ppc_exact_sd(ev, dv, den);
-  double sle = 0.0, sge = 0.0;
-  for (long i = 0; i < n; ++i) {
-    double t0, t1;
-    const int it = nb2_log_tails_ln(y, eta[i], ppc_exact_phi(lnphi(i)), lnphi(i), &t0, &t1);
-    mx = it > mx ? it : mx;
-    sle += loo_exact_term(w[i], t0); sge += loo_exact_term(w[i], t1);
-  }
-  auto F = [&](int k) {
-    double L = 0.0, U = 0.0;
-    for (long i = 0; i < n; ++i) {
-      double le, gt, pm; int it;
-      nb2_cdf_pair(k, eta[i], ppc_exact_phi(lnphi(i)), lnphi(i), &le, &gt, &pm, &it);
-      mx = it > mx ? it : mx;
-      L += loo_exact_term(w[i], le); U += loo_exact_term(w[i], gt);
-    }
-    return ppc_exact_F(L, U, den);
-  };
-  int c, w0;
-  ppc_exact_bracket(mean, sd, &c, &w0);
-  const int lower = ppc_exact_quantile(p_lo, c, w0, F), upper = ppc_exact_quantile(p_hi, c, w0, F);
+  // ---- steps 2 - 6
+  const bool ok = ppc_exact_sweeps(ExactHostSums{w.data(), eta, sigma_raw, log_tc, n, &mx}, y, excluded, den, p_lo, p_hi, true, out);
+  out[kPpcExactFields] = ok ? khat : NAN;
   if (max_iters) *max_iters = mx;
-  if (isnan(sle) || isnan(sge) || lower < 0 || upper < 0) { loo_exact_store_nan(out, y, excluded); return; }
-  loo_exact_store(out, mean, sd, sle / (double)den, sge / (double)den, lower, upper, y, excluded, khat);
 }
 }  // namespace ppcx
 #endif

@@ -1,6 +1,6 @@
 // ppcx_loo_mm.hip -- gfx950 kernels of the gene-local moment matching of PSIS-LOO cells (ppcx_fit_loo_moment_match,
 // include/ppcx.h; the statistic: ppcx_loo_mm.h). The walk over the cells is ppcx_loo_dev.h's (for_gene_batches,
-// loo_cell_batches); the driver at the end of this file adds the argument block and the kernels.
+// cells_in_batches); the driver at the end of this file adds the argument block and the kernels.
 //
 //   ppcx_loo_mm_hyper_kernel  the draws' six unconstrained hyper-parameters, transposed: U[k][draw], once per call, so that a
 //                             wavefront's lanes read consecutive draws of one hyper-parameter as they do of the table T.
@@ -8,8 +8,8 @@
 //                             and left their four fields (ppcx_fit_loo's bits, by the same kernel); a cell that is finished in
 //                             step 0 copies them, writes khat_before = khat, iterations 0, scales 1, shifts 0 and leaves at
 //                             once, before a ratio is formed. A cell above the threshold forms its ratios, tail and the log
-//                             weight of every draw by loo_cell_ratios, loo_cell_tail and loo_draw_lw -- the calls and the order
-//                             of the other per-cell kernels -- then Q0, and iterates: per coordinate two sweeps over the draws
+//                             weight of every draw by loo_cell_ratios, loo_cell_tail and loo_cell_lw (ppcx_loo_dev.h: the parts of
+//                             the other per-cell kernels' weights stage), then Q0, and iterates: per coordinate two sweeps over the draws
 //                             for the four moments (t formed from the table on the fly), per candidate one sweep that forms
 //                             q(t'; h) - Q0 - ll per draw (disp_point once per draw, disp_cell per sample of the gene) and
 //                             the cell's PSIS on it. The state (A, B) and the candidate's live in LDS, written by thread 0.
@@ -18,7 +18,7 @@
 //                             kPsisLdsDraws draws beside the two selection arrays (96 KB + 4 KB at 4 096 draws: one workgroup
 //                             per CU; 1 000 draws take 24 KB + 2 KB), in the workgroup's slice of the bounded scratch beyond.
 //                             A candidate's ratios overwrite the last candidate's: the current weights are enough for the
-//                             moments and for step 4. The kernel has NOT been timed.
+//                             moments and for step 4. Timed at the entry only (profiles/README.md, cell_entries_ab.json).
 // Every reduction runs in a fixed order and a cell reads nothing of another gene: its fields are the same bits whatever else is
 // requested and however the work is batched.
 #include <hip/hip_runtime.h>
@@ -28,19 +28,18 @@
 namespace ppcx {
 
 struct LooMmArgs {
-  LooArgs l;                       // the table, y, r_eff, n, the cells, sel_pad (l.scratch / l.out: ppcx_loo_kernel's)
+  LooArgs l;                       // the table, y, r_eff, n, the cells, sel_pad, the scratch of both kernels (l.out: ppcx_loo_kernel's)
   const int* genes = nullptr;      // [table's genes] their ids in the model (device)
   const double* U = nullptr;       // [6][n] ppcx_loo_mm_hyper_kernel
   const double* loo = nullptr;     // [cells][kLooFields] ppcx_loo_kernel's fields of the table's cells
   int K = 0;                       // checked genes of the model
   double lambda_mu_mu = 0.0, k_threshold = 0.7;
   int max_iters = 0;
-  double* scratch = nullptr; long slice = 0;   // [launch's cells][slice] doubles: the long path's three arrays
   double* out = nullptr;           // [cells][loo_mm_fields(C)]
 };
 
-// doubles of scratch per cell on the long path: a candidate's ratios [n], the log weights [n], Q0 [n]
-static long loo_mm_slice(long n) { return 3 * n; }
+// doubles per cell, in LDS or in the scratch: a candidate's ratios [n], the log weights [n], Q0 [n]
+__host__ __device__ inline long loo_mm_slice(long n) { return 3 * n; }
 
 __global__ __launch_bounds__(256) void ppcx_loo_mm_hyper_kernel(const double* draws, long n_draws, Dims d, double* U) {
   const long t = (long)blockIdx.x * 256 + threadIdx.x;
@@ -61,9 +60,9 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_kernel(LooMmArgs p)
   const int tid = threadIdx.x;
   const long n = a.n;
   const int C = a.C, nc = C + 1;
-  uint64_t* K = lds_u;                                   // [sel_pad] keys of the M + 1 largest ratios
-  double* X = reinterpret_cast<double*>(lds_u + a.sel_pad);            // [sel_pad] the tail's exceedances
-  double* V = LDS ? X + a.sel_pad : p.scratch + (long)blockIdx.x * p.slice;   // [n] the ratios (of the last candidate)
+  const CellMem m = cell_mem<LDS>(lds_u, a, loo_mm_slice(n));
+  uint64_t* K = m.K; double* X = m.X;
+  double* V = m.V;                                       // [n] the ratios (of the last candidate)
   double* W = V + n;                                     // [n] the current log weights
   double* Q0 = W + n;                                    // [n] the local density at the original draws
   const LooCell c = loo_cell<false>(a);
@@ -77,19 +76,18 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_kernel(LooMmArgs p)
     loo_mm_store_state(o, C, khat0, 0, nullptr, nullptr);
   }
   if (loo_mm_finished(c.excluded, khat0, p.k_threshold, p.max_iters)) return;
-  long N; double rmax, lmax;
-  if (loo_cell_ratios<false>(a, cell, gi, s, c.y, false, V, sh, &N, &rmax, &lmax)) return;
+  CellRatios cr;
+  if (loo_cell_ratios<false, false>(a, c, false, V, nullptr, sh, &cr)) return;
+  const long N = cr.N; const double rmax = cr.rmax, lmax = cr.lmax;
   if (N == 0) return;
-  double sl = 0.0;
-  for (long i = tid; i < n; i += kBlockThreads) { const double r = V[i]; if (r != -INFINITY) sl += exp(-r - lmax); }
-  sl = block_sum(sl, sh.red);
+  const double sl = draws_sum(n, sh.red, [&](long i) { const double r = V[i]; return r != -INFINITY ? exp(-r - lmax) : 0.0; });
   const double lpd = (lmax == -INFINITY ? -INFINITY : lmax + log(sl)) - log((double)N);
   const double re = a.r_eff ? a.r_eff[cell] : 1.0;
   double k;
   {
     const int M = psis_tail_len(N, re);
     const LooTail lt = loo_cell_tail(V, n, N, M, K, X, a.sel_pad, sh);
-    for (long i = tid; i < n; i += kBlockThreads) W[i] = loo_draw_lw(V, i, rmax, lt, M, K);
+    loo_cell_lw<false>(V, W, n, rmax, lt, M, K, sh);
     k = lt.khat;
   }
   // ---- the gene, the state, Q0
@@ -104,12 +102,8 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_kernel(LooMmArgs p)
   int iters = 0;
   while (k > p.k_threshold && iters < p.max_iters) {
     // the normaliser of the current weights
-    double mb = -INFINITY;
-    for (long i = tid; i < n; i += kBlockThreads) mb = fmax(mb, W[i]);
-    mb = block_max(mb, sh.red);
-    double sb = 0.0;
-    for (long i = tid; i < n; i += kBlockThreads) sb += exp(W[i] - mb);
-    sb = block_sum(sb, sh.red);
+    const double mb = draws_max(n, sh.red, [&](long i) { return W[i]; });
+    const double sb = draws_sum(n, sh.red, [&](long i) { return exp(W[i] - mb); });
     const double lse = mb + log(sb);
     // the moments of every coordinate, the two candidates
     bool ok2 = true;
@@ -157,7 +151,7 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_kernel(LooMmArgs p)
       const LooTail lt = loo_cell_tail(V, n, N2, M2, K, X, a.sel_pad, sh);
       if (N2 > 0 && lt.khat < k) {
         kind = cand; k = lt.khat;
-        for (long i = tid; i < n; i += kBlockThreads) W[i] = loo_draw_lw(V, i, rmx, lt, M2, K);
+        loo_cell_lw<false>(V, W, n, rmx, lt, M2, K, sh);
         __syncthreads();
         if (tid < nc) { ms.A[tid] = Ac[tid]; ms.B[tid] = Bc[tid]; }
         __syncthreads();
@@ -192,11 +186,7 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_kernel(LooMmArgs p)
 }
 
 // ---- launch helpers (host)
-static hipError_t launch_loo_mm_kernel(const LooMmArgs& p, int n_blocks, hipStream_t st) {
-  const bool lds = p.l.n <= kPsisLdsDraws;
-  const size_t bytes = sizeof(double) * (2 * (size_t)p.l.sel_pad + (lds ? (size_t)loo_mm_slice(p.l.n) : 0));
-  return launch_dynamic_lds(lds ? ppcx_loo_mm_kernel<true> : ppcx_loo_mm_kernel<false>, n_blocks, kBlockThreads, bytes, st, p);
-}
+PPCX_KERNEL_OF(ppcx_loo_mm_kernel);
 
 hipError_t loo_mm_fit_cells(const FitCells& fc, double k_threshold, int max_iters, double* out, size_t scratch_bytes, hipStream_t st) {
   const long n = fc.n;
@@ -216,13 +206,11 @@ hipError_t loo_mm_fit_cells(const FitCells& fc, double k_threshold, int max_iter
     p.l = a; p.genes = genes; p.U = d_U.p; p.loo = d_loo.p + done * kLooFields; p.K = fc.d.K; p.lambda_mu_mu = fc.d.lambda_mu_mu;
     p.k_threshold = k_threshold; p.max_iters = max_iters; p.out = a.out;
     p.l.out = d_loo.p + done * kLooFields;
-    p.slice = n > kPsisLdsDraws ? loo_mm_slice(n) : 0;
     done += (size_t)n_cells;
-    // per batch of cells: plain PSIS-LOO by its own kernel (its slice of the scratch is the first n of ours), then the matching
-    return loo_cell_batches(n_cells, p.slice, scratch_bytes, scratch, [&](int c0, int nc, double* scr) {
-      p.l.cell0 = c0; p.l.scratch = scr; p.scratch = scr;
-      const hipError_t e1 = launch_loo_kernel(p.l, kLooFields, nc, st);
-      return e1 == hipSuccess ? launch_loo_mm_kernel(p, nc, st) : e1;
+    // per batch of cells: plain PSIS-LOO by its own kernel (its slices of the scratch lie within ours), then the matching
+    return cells_in_batches(p, loo_mm_slice(n), n_cells, scratch_bytes, scratch, [&](const LooMmArgs& q, const CellLaunch& c) {
+      const hipError_t e1 = launch_loo_kernel(q.l, kLooFields, c.n_blocks, st);
+      return e1 == hipSuccess ? launch_cell_kernel(pick_kernel<ppcx_loo_mm_kernel_of>(c.lds), q, c, q.l.sel_pad, loo_mm_slice(n), st) : e1;
     });
   });
 }

@@ -23,32 +23,16 @@
 namespace ppcx {
 
 struct LooPredictArgs {
-  LooArgs l;                       // the table or the columns, y, r_eff, n, the cells, sel_pad (l.scratch unused)
+  LooArgs l;                       // the table or the columns, y, r_eff, n, the cells, sel_pad, the scratch, out [cells][kLooPredictFields]
   const int* genes = nullptr;      // [table's genes] their ids in the model: the Philox address is genes[gi] S + s
   const int* xcols = nullptr;      // [cells][n] predictive counts of the given columns (testing build)
   const int* ycols = nullptr;      // [cells] observed counts of the given columns
   double tc = 1.0, p_lo = 0.025, p_hi = 0.975;
   uint32_t k0 = 0;
-  double* scratch = nullptr; long slice = 0;   // [launch's cells][slice] doubles: the long path's r, w, x
-  double* out = nullptr;           // [cells][kLooPredictFields] (= l.out)
 };
 
-// doubles of scratch per cell on the long path: r [n], w [n], x [n] as integers
-static long loo_predict_slice(long n) { return 2 * n + (n + 1) / 2; }
-
-// sum over the cell's draws i of f(i); every thread gets it (fixed order)
-template <class F>
-__device__ __forceinline__ double draws_sum(long n, double* red, F f) {
-  double s = 0.0;
-  for (long i = threadIdx.x; i < n; i += kBlockThreads) s += f(i);
-  return block_sum(s, red);
-}
-template <class F>
-__device__ __forceinline__ double draws_max(long n, double* red, F f) {
-  double m = -INFINITY;
-  for (long i = threadIdx.x; i < n; i += kBlockThreads) m = fmax(m, f(i));
-  return block_max(m, red);
-}
+// doubles per cell, in LDS or in the scratch: r [n], w [n], x [n] as integers
+__host__ __device__ inline long loo_predict_slice(long n) { return 2 * n + (n + 1) / 2; }
 
 // AP: the weights of an ADVI fit (ppcx_loo_ap.h: ratios (log_p - log_g) - ll; an excluded cell is weighted too, by log_p - log_g)
 template <bool LDS, bool COLS, bool AP>
@@ -59,23 +43,18 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_predict_kernel(LooPred
   const LooArgs& a = p.l;
   const int tid = threadIdx.x;
   const long n = a.n;
-  uint64_t* K = lds_u;                                   // [sel_pad] keys of the M + 1 largest ratios
-  double* X = reinterpret_cast<double*>(lds_u + a.sel_pad);            // [sel_pad] the tail's exceedances
-  double* V = LDS ? X + a.sel_pad : p.scratch + (long)blockIdx.x * p.slice;   // [n] the ratios r = -ll
+  const CellMem m = cell_mem<LDS>(lds_u, a, loo_predict_slice(n));
+  double* V = m.V;                                       // [n] the ratios r = -ll
   double* W = V + n;                                     // [n] log weights, then weights
   int* XI = reinterpret_cast<int*>(W + n);               // [n] predictive counts
   const LooCell c = loo_cell<COLS>(a, p.ycols);
   const int cell = c.cell, gi = c.gi, s = c.s, y = c.y;
-  const bool excluded = c.excluded;
-  double* o = p.out + (long)cell * kLooPredictFields;
+  double* o = a.out + (long)cell * kLooPredictFields;
   auto all_nan = [&]() { if (tid == 0) for (int f = 0; f < kLooPredictFields; ++f) o[f] = NAN; };
   // ---- the ratios
-  long N; double rmax, lmax;
-  if constexpr (AP) {
-    if (loo_ap_cell_ratios<COLS>(a, cell, gi, s, y, excluded, V, nullptr, sh, &N, &rmax, &lmax)) { all_nan(); return; }
-  } else {
-    if (loo_cell_ratios<COLS>(a, cell, gi, s, y, excluded, V, sh, &N, &rmax, &lmax)) { all_nan(); return; }
-  }
+  CellRatios cr;
+  const CellVerdict verdict = loo_cell_verdict<COLS, AP>(a, c, m, nullptr, sh, &cr);
+  if (verdict == CELL_NAN) { all_nan(); return; }
   // ---- the predictive count of every draw
   bool inval = false;
   if (COLS) {
@@ -90,10 +69,10 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_predict_kernel(LooPred
       XI[i] = v; inval = inval || v == kPpcInvalid;
     }
   }
-  if (block_any(inval) || (!excluded && N == 0)) { all_nan(); return; }   // block_any: XI is visible to every thread
+  if (block_any(inval)) { all_nan(); return; }           // block_any: XI is visible to every thread
   const double pr[2] = {p.p_lo, p.p_hi};
   double q[2];
-  if (!AP && excluded) {
+  if (verdict == CELL_UNIFORM) {
     // ---- already held out: uniform weights over all n draws, the type-7 quantiles of the posterior-predictive kernels
     const double sum = draws_sum(n, sh.red, [&](long i) { return (double)XI[i]; });
     const int vmax = (int)draws_max(n, sh.red, [&](long i) { return (double)XI[i]; });
@@ -110,20 +89,8 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_predict_kernel(LooPred
     if (tid == 0) { o[0] = sum / (double)n; o[1] = q[0]; o[2] = q[1]; o[3] = lt / (double)n; o[4] = le / (double)n; o[5] = NAN; }
     return;
   }
-  // ---- the tail, and the log weight of every draw
-  const double mx = rmax;
-  const int M = psis_tail_len(N, a.r_eff ? a.r_eff[cell] : 1.0);
-  const LooTail lt = loo_cell_tail(V, n, N, M, K, X, a.sel_pad, sh);
-  double mxw = -INFINITY;
-  for (long i = tid; i < n; i += kBlockThreads) {
-    const double lw = loo_draw_lw(V, i, mx, lt, M, K);
-    W[i] = lw; mxw = fmax(mxw, lw);
-  }
-  mxw = block_max(mxw, sh.red);
-  double sw = 0.0;
-  for (long i = tid; i < n; i += kBlockThreads) { const double e = exp(W[i] - mxw); W[i] = e; sw += e; }
-  sw = block_sum(sw, sh.red);
-  for (long i = tid; i < n; i += kBlockThreads) W[i] = W[i] / sw;
+  // ---- the tail, and the normalised weight of every draw
+  const double khat = loo_cell_weights<true>(a, c, m, cr, W, sh);
   __syncthreads();
   // ---- sums of weights: the mean, the LOO-PIT, and F for the quantiles (a draw that takes no part has weight 0)
   const double mean = draws_sum(n, sh.red, [&](long i) { return W[i] * (double)XI[i]; });
@@ -138,25 +105,15 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_predict_kernel(LooPred
     const double vm = draws_max(n, sh.red, [&](long i) { return V[i] != -INFINITY && XI[i] < lo ? (double)XI[i] : -INFINITY; });
     q[k] = vm == -INFINITY ? (double)lo : loo_predict_interp(vm, (double)lo, F((int)vm), F(lo), pr[k]);
   }
-  if (tid == 0) { o[0] = mean; o[1] = q[0]; o[2] = q[1]; o[3] = plt; o[4] = ple; o[5] = lt.khat; }
+  if (tid == 0) { o[0] = mean; o[1] = q[0]; o[2] = q[1]; o[3] = plt; o[4] = ple; o[5] = khat; }
 }
 
 // ---- launch helpers (host)
-static hipError_t launch_loo_predict_kernel(const LooPredictArgs& p, int n_blocks, hipStream_t st) {
-  const bool lds = p.l.n <= kPsisLdsDraws, cols = p.l.cols != nullptr;
-  const size_t bytes = sizeof(double) * (2 * (size_t)p.l.sel_pad + (lds ? (size_t)loo_predict_slice(p.l.n) : 0));
-  void (*kernel)(LooPredictArgs);
-  if (p.l.lr) kernel = lds ? (cols ? ppcx_loo_predict_kernel<true, true, true> : ppcx_loo_predict_kernel<true, false, true>)
-                           : (cols ? ppcx_loo_predict_kernel<false, true, true> : ppcx_loo_predict_kernel<false, false, true>);
-  else kernel = lds ? (cols ? ppcx_loo_predict_kernel<true, true, false> : ppcx_loo_predict_kernel<true, false, false>)
-                    : (cols ? ppcx_loo_predict_kernel<false, true, false> : ppcx_loo_predict_kernel<false, false, false>);
-  return launch_dynamic_lds(kernel, n_blocks, kBlockThreads, bytes, st, p);
-}
-static hipError_t loo_predict_cells(LooPredictArgs p, int n_cells, size_t scratch_bytes, DeviceBuffer<double>& scratch, hipStream_t st) {
-  p.slice = p.l.n > kPsisLdsDraws ? loo_predict_slice(p.l.n) : 0;
-  return loo_cell_batches(n_cells, p.slice, scratch_bytes, scratch, [&](int c0, int nc, double* scr) {
-    p.l.cell0 = c0; p.scratch = scr;
-    return launch_loo_predict_kernel(p, nc, st);
+PPCX_KERNEL_OF(ppcx_loo_predict_kernel);
+static hipError_t loo_predict_cells(const LooPredictArgs& args, int n_cells, size_t scratch_bytes, DeviceBuffer<double>& scratch, hipStream_t st) {
+  const long slice = loo_predict_slice(args.l.n);
+  return cells_in_batches(args, slice, n_cells, scratch_bytes, scratch, [&](const LooPredictArgs& p, const CellLaunch& c) {
+    return launch_cell_kernel(pick_kernel<ppcx_loo_predict_kernel_of>(c.lds, c.cols, p.l.lr != nullptr), p, c, p.l.sel_pad, slice, st);
   });
 }
 
@@ -165,7 +122,7 @@ hipError_t loo_predict_fit_cells(const FitCells& fc, double tc, double p_lo, dou
   return for_gene_batches(fc, kLooPredictFields, out, scratch_bytes, st,
                           [&](const LooArgs& a, const int* genes, int n_cells, DeviceBuffer<double>& scratch) {
     LooPredictArgs p;
-    p.l = a; p.genes = genes; p.tc = tc; p.p_lo = p_lo; p.p_hi = p_hi; p.k0 = k0; p.out = a.out;
+    p.l = a; p.genes = genes; p.tc = tc; p.p_lo = p_lo; p.p_hi = p_hi; p.k0 = k0;
     return loo_predict_cells(p, n_cells, scratch_bytes, scratch, st);
   });
 }
@@ -179,7 +136,7 @@ hipError_t loo_predict_columns(const GivenCells& gc, const int* x, const int* y,
   if (e != hipSuccess) return finish(e, st);
   return for_given_columns(gc, kLooPredictFields, out, st, [&](const LooArgs& a, const int*, int n_cells, DeviceBuffer<double>& scratch) {
     LooPredictArgs p;
-    p.l = a; p.xcols = d_x.p; p.ycols = d_y.p; p.p_lo = p_lo; p.p_hi = p_hi; p.out = a.out;
+    p.l = a; p.xcols = d_x.p; p.ycols = d_y.p; p.p_lo = p_lo; p.p_hi = p_hi;
     return loo_predict_cells(p, n_cells, scratch_bytes, scratch, st);
   });
 }

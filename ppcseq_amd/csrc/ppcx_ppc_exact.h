@@ -7,7 +7,8 @@
 // inverse-cdf quantiles of the distribution (integers), and the two agree in the limit of draws.
 //
 // Shared by the gfx950 kernel (ppcx_ppc_exact.hip) and the CPU check (tests/ppc_exact_host): the blocks below are
-// `__host__ __device__`; ppc_exact_cell_host at the end is their sequential composition.
+// `__host__ __device__`; ppc_exact_sweeps composes them once for both, and for ppcx_loo_exact.h; ppc_exact_cell_host at the end
+// runs it sequentially.
 //
 // One cell from its count y and, per draw i = 0 .. n - 1, its linear predictor eta_i (loo_cell_eta) and sigma_raw_i:
 //   0. ln phi_i = ln(truncation_compensation) - sigma_raw_i, phi_i = exp(ln phi_i): ppcx_fit_ppc's exp(-sigma_raw_i)
@@ -106,48 +107,77 @@ PPCX_HD void ppc_exact_store_nan(double* o, int y, bool excluded) {
   o[6] = (double)y; o[7] = excluded ? 1.0 : 0.0;
 }
 
+
+// a weighted term of a sum (w = 1 in the uniform cell of ppcx_loo_exact.h: the product is exact)
+PPCX_HD double loo_exact_term(double w, double f) { PPCX_NO_CONTRACT return w * f; }
+
+// Steps 1 - 5 of this header and steps 2 - 6 of ppcx_loo_exact.h, once, over any "sum over the draws": sums(f, s) leaves in
+// s[0 .. K) the sums over the draws i of w_i t_k, where f(eta_i, ln phi_i, t) fills the draw's K terms and returns the
+// continued-fraction steps it took (0 where there are none). The operation carries the weight -- none here, loo_exact_term(w_i, .)
+// in ppcx_loo_exact.h -- the order (host: sequential; device: a workgroup's strided sweep and block_sum, so that every thread
+// holds the same sums and the control flow is uniform) and what becomes of the step counts. den: what every sum is divided by
+// (n, or 1 under normalised weights). Where `store`, the nine fields go to o (NaN where a sum or an interval end is NaN);
+// returns whether they are numbers.
+template <class Sums>
+PPCX_HD bool ppc_exact_sweeps(const Sums& sums, int y, bool excluded, long den, double p_lo, double p_hi, bool store, double* o) {
+  PPCX_NO_CONTRACT
+  double sm[1], var[2], tails[2];
+  sums([](double eta, double, double* t) { t[0] = exp(eta); return 0; }, sm);
+  const double mean = sm[0] / (double)den;
+  sums([mean](double eta, double lp, double* t) { ppc_exact_var_terms(eta, ppc_exact_phi(lp), mean, &t[0], &t[1]); return 0; }, var);
+  const double sd = ppc_exact_sd(var[0], var[1], den);
+  sums([y](double eta, double lp, double* t) { return nb2_log_tails_ln(y, eta, ppc_exact_phi(lp), lp, &t[0], &t[1]); }, tails);
+  // the interval: every F is one sweep
+  auto F = [&](int k) {
+    double LU[2];
+    sums([k](double eta, double lp, double* t) {
+      double pm; int it;
+      nb2_cdf_pair(k, eta, ppc_exact_phi(lp), lp, &t[0], &t[1], &pm, &it);
+      return it;
+    }, LU);
+    return ppc_exact_F(LU[0], LU[1], den);
+  };
+  int c, w;
+  ppc_exact_bracket(mean, sd, &c, &w);
+  const int lower = ppc_exact_quantile(p_lo, c, w, F), upper = ppc_exact_quantile(p_hi, c, w, F);
+  const bool ok = !(isnan(tails[0]) || isnan(tails[1]) || lower < 0 || upper < 0);
+  if (store) {
+    if (ok) ppc_exact_store(o, mean, sd, tails[0] / (double)den, tails[1] / (double)den, lower, upper, y, excluded);
+    else ppc_exact_store_nan(o, y, excluded);
+  }
+  return ok;
+}
+
 }  // namespace ppcx
 
 #if !defined(__HIP_DEVICE_COMPILE__)
 namespace ppcx {
+// the sums of ppc_exact_sweeps for the CPU checks: sequential, under the weights w (null: none), ln phi formed on the way;
+// *max_iters: the largest number of continued-fraction steps any evaluation took
+struct ExactHostSums {
+  const double* w; const double* eta; const double* sigma_raw; double log_tc; long n; int* max_iters;
+  template <class F, int K>
+  void operator()(F f, double (&s)[K]) const {
+    PPCX_NO_CONTRACT
+    for (int k = 0; k < K; ++k) s[k] = 0.0;
+    for (long i = 0; i < n; ++i) {
+      double t[K];
+      const int it = f(eta[i], ppc_exact_lnphi(sigma_raw[i], log_tc), t);
+      if (it > *max_iters) *max_iters = it;
+      for (int k = 0; k < K; ++k) s[k] += w ? loo_exact_term(w[i], t[k]) : t[k];
+    }
+  }
+};
 // the whole spec for one cell, sequentially, for the CPU check: out[kPpcExactFields]. max_iters (may be null): the largest
 // number of continued-fraction steps any evaluation took.
 inline void ppc_exact_cell_host(const double* eta, const double* sigma_raw, long n, int y, bool excluded, double tc, double p_lo,
                                 double p_hi, double* out, int* max_iters = nullptr) {
   const double log_tc = log(tc);
   int mx = 0;
-  auto lnphi = [&](long i) { return ppc_exact_lnphi(sigma_raw[i], log_tc); };
   for (long i = 0; i < n; ++i)
-    if (ppc_exact_invalid(eta[i], ppc_exact_phi(lnphi(i)))) { ppc_exact_store_nan(out, y, excluded); return; }
-  double sm = 0.0;
-  for (long i = 0; i < n; ++i) sm += exp(eta[i]);
-  const double mean = sm / (double)n;
-  double ev = 0.0, dv = 0.0;
-  for (long i = 0; i < n; ++i) { double e, d; ppc_exact_var_terms(eta[i], ppc_exact_phi(lnphi(i)), mean, &e, &d); ev += e; dv += d; }
-  const double sd = ppc_exact_sd(ev, dv, n);
-  double sle = 0.0, sge = 0.0;
-  for (long i = 0; i < n; ++i) {
-    double a, b;
-    const int it = nb2_log_tails_ln(y, eta[i], ppc_exact_phi(lnphi(i)), lnphi(i), &a, &b);
-    mx = it > mx ? it : mx;
-    sle += a; sge += b;
-  }
-  auto F = [&](int k) {
-    double L = 0.0, U = 0.0;
-    for (long i = 0; i < n; ++i) {
-      double le, gt, pm; int it;
-      nb2_cdf_pair(k, eta[i], ppc_exact_phi(lnphi(i)), lnphi(i), &le, &gt, &pm, &it);
-      mx = it > mx ? it : mx;
-      L += le; U += gt;
-    }
-    return ppc_exact_F(L, U, n);
-  };
-  int c, w;
-  ppc_exact_bracket(mean, sd, &c, &w);
-  const int lower = ppc_exact_quantile(p_lo, c, w, F), upper = ppc_exact_quantile(p_hi, c, w, F);
+    if (ppc_exact_invalid(eta[i], ppc_exact_phi(ppc_exact_lnphi(sigma_raw[i], log_tc)))) { ppc_exact_store_nan(out, y, excluded); return; }
+  ppc_exact_sweeps(ExactHostSums{nullptr, eta, sigma_raw, log_tc, n, &mx}, y, excluded, n, p_lo, p_hi, true, out);
   if (max_iters) *max_iters = mx;
-  if (isnan(sle) || isnan(sge) || lower < 0 || upper < 0) { ppc_exact_store_nan(out, y, excluded); return; }
-  ppc_exact_store(out, mean, sd, sle / (double)n, sge / (double)n, lower, upper, y, excluded);
 }
 }  // namespace ppcx
 #endif

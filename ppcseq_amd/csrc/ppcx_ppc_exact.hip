@@ -6,7 +6,8 @@
 //   ppcx_ppc_exact_kernel  one workgroup of kBlockThreads per cell, a sibling of ppcx_loo_kernel. Pass 0 forms (eta_i, ln phi_i)
 //                          of every draw once, from the transposed table T (ppcx_loo_table_kernel) or the given columns: 16
 //                          bytes per draw, in LDS up to kPsisLdsDraws draws (64 KB: two workgroups per CU), in the workgroup's
-//                          slice of a bounded global scratch beyond. Every later sweep reads them strided and reduces with
+//                          slice of a bounded global scratch beyond. Every later sweep (ppc_exact_sweeps, ppcx_ppc_exact.h, over
+//                          ExactBlockSums of ppcx_loo_dev.h, as ppcx_loo_exact_kernel runs it) reads them strided and reduces with
 //                          block_sum in the fixed order: the mean, the two variance sums, the two tails at y, and one sweep
 //                          (two sums) per step of the quantile search, whose control flow is uniform because every thread
 //                          holds the same sums. The draws of a wavefront run continued fractions of different lengths; the
@@ -22,16 +23,14 @@
 namespace ppcx {
 
 struct PpcExactArgs {
-  LooArgs l;                       // the table or the eta columns (l.cols), y, n, the cells
+  LooArgs l;                       // the table or the eta columns (l.cols), y, n, the cells, the scratch, out [cells][kPpcExactFields]
   const double* sgcols = nullptr;  // [cells][n] sigma_raw of the given columns (testing build)
   const int* ycols = nullptr;      // [cells] observed counts of the given columns
   double log_tc = 0.0, p_lo = 0.025, p_hi = 0.975;
-  double* scratch = nullptr; long slice = 0;   // [launch's cells][slice] doubles: the long path's (eta, ln phi)
-  double* out = nullptr;           // [cells][kPpcExactFields] (= l.out)
 };
 
-// doubles of scratch per cell on the long path
-static long ppc_exact_slice(long n) { return 2 * n; }
+// doubles per cell, in LDS or in the scratch: eta [n], ln phi [n]
+__host__ __device__ inline long ppc_exact_slice(long n) { return 2 * n; }
 
 template <bool LDS, bool COLS>
 __global__ __launch_bounds__(kBlockThreads) void ppcx_ppc_exact_kernel(PpcExactArgs p) {
@@ -41,11 +40,11 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_ppc_exact_kernel(PpcExactA
   const LooArgs& a = p.l;
   const int tid = threadIdx.x;
   const long n = a.n;
-  double* E = LDS ? lds_d : p.scratch + (long)blockIdx.x * p.slice;      // [n] eta, then [n] ln phi
+  double* E = LDS ? lds_d : a.scratch + (long)blockIdx.x * ppc_exact_slice(n);   // [n] eta, then [n] ln phi (no selection arrays)
   double* LP = E + n;
   const LooCell c = loo_cell<COLS>(a, p.ycols);
   const int cell = c.cell, gi = c.gi, s = c.s, y = c.y;
-  double* o = p.out + (long)cell * kPpcExactFields;
+  double* o = a.out + (long)cell * kPpcExactFields;
   // ---- pass 0: (eta, ln phi) of every draw
   bool inval = false;
   {
@@ -59,61 +58,16 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_ppc_exact_kernel(PpcExactA
     }
   }
   if (block_any(inval)) { if (tid == 0) ppc_exact_store_nan(o, y, c.excluded); return; }   // a barrier: E, LP are visible
-  // ---- the moments
-  double sm = 0.0;
-  for (long i = tid; i < n; i += kBlockThreads) sm += exp(E[i]);
-  const double mean = block_sum(sm, red) / (double)n;
-  double ev = 0.0, dv = 0.0;
-  for (long i = tid; i < n; i += kBlockThreads) { double e1, d1; ppc_exact_var_terms(E[i], ppc_exact_phi(LP[i]), mean, &e1, &d1); ev += e1; dv += d1; }
-  ev = block_sum(ev, red);
-  dv = block_sum(dv, red);
-  const double sd = ppc_exact_sd(ev, dv, n);
-  // ---- the two tails at y
-  double sle = 0.0, sge = 0.0;
-  for (long i = tid; i < n; i += kBlockThreads) {
-    double t0, t1;
-    const double lp = LP[i];
-    (void)nb2_log_tails_ln(y, E[i], ppc_exact_phi(lp), lp, &t0, &t1);
-    sle += t0; sge += t1;
-  }
-  sle = block_sum(sle, red);
-  sge = block_sum(sge, red);
-  // ---- the interval: every F is one sweep, every thread holds its value
-  auto F = [&](int k) {
-    double L = 0.0, U = 0.0;
-    for (long i = tid; i < n; i += kBlockThreads) {
-      double le, gt, pm; int it;
-      const double lp = LP[i];
-      nb2_cdf_pair(k, E[i], ppc_exact_phi(lp), lp, &le, &gt, &pm, &it);
-      L += le; U += gt;
-    }
-    L = block_sum(L, red);
-    U = block_sum(U, red);
-    return ppc_exact_F(L, U, n);
-  };
-  int c0, w0;
-  ppc_exact_bracket(mean, sd, &c0, &w0);
-  const int lower = ppc_exact_quantile(p.p_lo, c0, w0, F);
-  const int upper = ppc_exact_quantile(p.p_hi, c0, w0, F);
-  if (tid == 0) {
-    if (isnan(sle) || isnan(sge) || lower < 0 || upper < 0) ppc_exact_store_nan(o, y, c.excluded);
-    else ppc_exact_store(o, mean, sd, sle / (double)n, sge / (double)n, lower, upper, y, c.excluded);
-  }
+  // ---- the moments, the two tails at y, the interval: every sum unweighted and over n
+  ppc_exact_sweeps(ExactBlockSums<false>{nullptr, E, LP, n, red}, y, c.excluded, n, p.p_lo, p.p_hi, tid == 0, o);
 }
 
 // ---- launch helpers (host)
-static hipError_t launch_ppc_exact_kernel(const PpcExactArgs& p, int n_blocks, hipStream_t st) {
-  const bool lds = p.l.n <= kPsisLdsDraws, cols = p.l.cols != nullptr;
-  const size_t bytes = lds ? sizeof(double) * (size_t)ppc_exact_slice(p.l.n) : 0;
-  void (*kernel)(PpcExactArgs) = lds ? (cols ? ppcx_ppc_exact_kernel<true, true> : ppcx_ppc_exact_kernel<true, false>)
-                                     : (cols ? ppcx_ppc_exact_kernel<false, true> : ppcx_ppc_exact_kernel<false, false>);
-  return launch_dynamic_lds(kernel, n_blocks, kBlockThreads, bytes, st, p);
-}
-static hipError_t ppc_exact_cells(PpcExactArgs p, int n_cells, size_t scratch_bytes, DeviceBuffer<double>& scratch, hipStream_t st) {
-  p.slice = p.l.n > kPsisLdsDraws ? ppc_exact_slice(p.l.n) : 0;
-  return loo_cell_batches(n_cells, p.slice, scratch_bytes, scratch, [&](int c0, int nc, double* scr) {
-    p.l.cell0 = c0; p.scratch = scr;
-    return launch_ppc_exact_kernel(p, nc, st);
+PPCX_KERNEL_OF(ppcx_ppc_exact_kernel);
+static hipError_t ppc_exact_cells(const PpcExactArgs& args, int n_cells, size_t scratch_bytes, DeviceBuffer<double>& scratch, hipStream_t st) {
+  const long slice = ppc_exact_slice(args.l.n);
+  return cells_in_batches(args, slice, n_cells, scratch_bytes, scratch, [&](const PpcExactArgs& p, const CellLaunch& c) {
+    return launch_cell_kernel(pick_kernel<ppcx_ppc_exact_kernel_of>(c.lds, c.cols), p, c, 0, slice, st);
   });
 }
 
@@ -123,7 +77,7 @@ hipError_t ppc_exact_fit_cells(const FitCells& fc, double tc, double p_lo, doubl
   return for_gene_batches(fc, kPpcExactFields, out, scratch_bytes, st,
                           [&](const LooArgs& a, const int*, int n_cells, DeviceBuffer<double>& scratch) {
     PpcExactArgs p;
-    p.l = a; p.log_tc = log_tc; p.p_lo = p_lo; p.p_hi = p_hi; p.out = a.out;
+    p.l = a; p.log_tc = log_tc; p.p_lo = p_lo; p.p_hi = p_hi;
     return ppc_exact_cells(p, n_cells, scratch_bytes, scratch, st);
   });
 }
@@ -138,7 +92,7 @@ hipError_t ppc_exact_columns(const GivenCells& gc, const double* sigma_raw, cons
   if (e != hipSuccess) return finish(e, st);
   return for_given_columns(gc, kPpcExactFields, out, st, [&](const LooArgs& a, const int*, int n_cells, DeviceBuffer<double>& scratch) {
     PpcExactArgs p;
-    p.l = a; p.sgcols = d_sg.p; p.ycols = d_y.p; p.log_tc = log_tc; p.p_lo = p_lo; p.p_hi = p_hi; p.out = a.out;
+    p.l = a; p.sgcols = d_sg.p; p.ycols = d_y.p; p.log_tc = log_tc; p.p_lo = p_lo; p.p_hi = p_hi;
     return ppc_exact_cells(p, n_cells, scratch_bytes, scratch, st);
   });
 }

@@ -49,20 +49,12 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_reff_kernel(ReffArgs a) {
 }
 
 // ---- launch helpers (host)
-static hipError_t launch_reff_kernel(const ReffArgs& a, int n_blocks, hipStream_t st) {
-  const bool lds = a.l.n <= kPsisLdsDraws, cols = a.l.cols != nullptr;
-  const size_t bytes = lds ? sizeof(double) * 2 * (size_t)a.chains * (size_t)(a.n_keep / 2) : 0;
-  void (*const kernel)(ReffArgs) = lds ? (cols ? ppcx_reff_kernel<true, true> : ppcx_reff_kernel<true, false>)
-                                       : (cols ? ppcx_reff_kernel<false, true> : ppcx_reff_kernel<false, false>);
-  return launch_dynamic_lds(kernel, n_blocks, kBlockThreads, bytes, st, a);
-}
-
-// Cells of a launch in batches: all at once where the split values live in LDS, else as many as the scratch bound holds.
-static hipError_t reff_cells(ReffArgs a, int n_cells, size_t scratch_bytes, DeviceBuffer<double>& scratch, hipStream_t st) {
-  const long N = 2L * a.chains * (a.n_keep / 2);
-  return loo_cell_batches(n_cells, a.l.n > kPsisLdsDraws ? N : 0, scratch_bytes, scratch, [&](int c0, int nc, double* scr) {
-    a.l.cell0 = c0; a.l.scratch = scr;
-    return launch_reff_kernel(a, nc, st);
+PPCX_KERNEL_OF(ppcx_reff_kernel);
+// the split values of a cell [2 chains (n_keep / 2)]: its slice, in LDS or in the scratch (no selection arrays)
+static hipError_t reff_cells(const ReffArgs& args, int n_cells, size_t scratch_bytes, DeviceBuffer<double>& scratch, hipStream_t st) {
+  const long N = 2L * args.chains * (args.n_keep / 2);
+  return cells_in_batches(args, N, n_cells, scratch_bytes, scratch, [&](const ReffArgs& a, const CellLaunch& c) {
+    return launch_cell_kernel(pick_kernel<ppcx_reff_kernel_of>(c.lds, c.cols), a, c, 0, N, st);
   });
 }
 
