@@ -298,6 +298,26 @@ PPCX_API int ppcx_fit_loo_predict_exact(ppcx_fit* f, int n_genes, const int32_t*
  * PPCX_ERR_ARG (theirs is ppcx_fit_loo_predict_exact). Genes, probabilities and truncation compensation as above.             */
 PPCX_API int ppcx_fit_loo_predict_exact_approx(ppcx_fit* f, int n_genes, const int32_t* genes, double truncation_compensation,
                                                double p_lo, double p_hi, double* out);
+/* ppcx_fit_loo_predict_exact with a second attempt at the cells whose khat exceeds k_threshold: the cells a posterior-predictive
+ * check exists to find are outliers, and an outlier is the cell whose plain PSIS weights are not to be trusted. Such a cell is
+ * matched as ppcx_fit_loo_moment_match matches it (the same kernels, so khat, khat_before, iterations, scale and shift are that
+ * entry's bits), and its predictive is importance sampling with the matched draws t_i = scale * draw_i + shift as the proposal:
+ * the weights w_i are the normalised PSIS weights of the ratios q(t_i) - q(draw_i) - log_lik(t_i) (q the gene's local log
+ * density; the constant Jacobian cancels), and eta_i, phi_i of the negative binomials are evaluated at t_i. Nothing is sampled.
+ * Genes (checked ones), r_eff, probabilities, truncation compensation, limits and refusals as ppcx_fit_loo_predict_exact;
+ * k_threshold and max_iters as ppcx_fit_loo_moment_match (PPCX_ERR_ARG for a k_threshold that is not finite or max_iters < 0).
+ * An ADVI fit: PPCX_ERR_ARG; a ppcx_fit_from_draws fit is served. No covariance step, no split transformation: a matched khat
+ * is necessary, not sufficient. Synchronous on the model's stream; the same bits on every call, for any gene subset.
+ *   out [n_genes][S][PPCX_LOO_MM_EXACT_FIELDS(C)]: the ten fields of ppcx_fit_loo_predict_exact with khat the final one, then
+ *   khat_before (plain PSIS's), iterations (accepted steps), scale[C + 1] and shift[C + 1] as ppcx_fit_loo_moment_match.
+ *   A cell with iterations = 0 (excluded, NaN, at or below the threshold, max_iters = 0, or no step accepted) holds
+ *   ppcx_fit_loo_predict_exact's ten fields bit for bit (an excluded cell: ppcx_fit_ppc_exact's nine, khat = NaN). A matched
+ *   draw with invalid parameters makes every statistic of the cell NaN, khat included (y, excluded and the record of the
+ *   matching are still reported).                                                                                              */
+#define PPCX_LOO_MM_EXACT_FIELDS(C) (12 + 2 * ((C) + 1))
+PPCX_API int ppcx_fit_loo_predict_exact_moment_match(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff,
+                                                     double k_threshold, int max_iters, double truncation_compensation,
+                                                     double p_lo, double p_hi, double* out);
 /* lp: [chains][n_keep]; the rest [chains][iter] (warmup included); any pointer may be NULL */
 PPCX_API int ppcx_fit_get_diagnostics(ppcx_fit* f, double* lp, double* stepsize, int32_t* treedepth,
                              int32_t* n_leapfrog, int32_t* divergent, double* accept);

@@ -27,6 +27,7 @@ EXPORTS = [
     "ppcx_fit_get_approximation", "ppcx_fit_get_log_ratios", "ppcx_fit_psis", "ppcx_fit_get_log_lik", "ppcx_fit_loo",
     "ppcx_fit_loo_predict", "ppcx_fit_relative_eff", "ppcx_fit_loo_mcse", "ppcx_fit_loo_approx", "ppcx_fit_loo_predict_approx",
     "ppcx_fit_ppc_exact", "ppcx_fit_loo_predict_exact", "ppcx_fit_loo_predict_exact_approx", "ppcx_fit_loo_moment_match",
+    "ppcx_fit_loo_predict_exact_moment_match",
 ]
 ABI_VERSION = 400           # include/ppcx.h PPCX_VERSION this binding was written for
 SUMMARY_FIELDS = ("mean", "sd", "q05", "q50", "q95", "rhat", "ess_bulk", "ess_tail")   # PPCX_SUMMARY_FIELDS, in order
@@ -117,6 +118,8 @@ def load() -> C.CDLL:
     lib.ppcx_fit_ppc_exact.argtypes = [C.c_void_p, C.c_int, ip, C.c_double, C.c_double, C.c_double, dp]
     lib.ppcx_fit_loo_predict_exact.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_double, C.c_double, C.c_double, dp]
     lib.ppcx_fit_loo_predict_exact_approx.argtypes = [C.c_void_p, C.c_int, ip, C.c_double, C.c_double, C.c_double, dp]
+    lib.ppcx_fit_loo_predict_exact_moment_match.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_double, C.c_int, C.c_double, C.c_double,
+                                                            C.c_double, dp]
     lib.ppcx_fit_get_diagnostics.argtypes = [C.c_void_p, dp, dp, ip, ip, ip, dp]
     lib.ppcx_fit_get_timing.argtypes = [C.c_void_p, dp, C.POINTER(C.c_longlong), dp, C.POINTER(C.c_longlong), dp]
     lib.ppcx_fit_get_kernel_times.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(C.c_longlong)]
@@ -900,14 +903,17 @@ class Fit:
         res["n_draws"] = self.chains * self.n_keep
         return res
 
-    def _loo_exact(self, genes, r_eff, call):
-        """What the two exact leave-one-out forms share: call(n_genes, genes, r_eff or None, out) fills [n_genes, S, 10]"""
+    def _loo_exact(self, genes, r_eff, call, more=0, tail=None):
+        """What the exact leave-one-out forms share: call(n_genes, genes, r_eff or None, out) fills [n_genes, S, 10 + more];
+        tail(res, the `more` fields behind the ten) adds a form's own keys"""
         g = np.ascontiguousarray(np.arange(self.model.K) if genes is None else np.asarray(genes, dtype=np.int64).ravel(), dtype=np.int32)
-        out = np.zeros((g.size, self.model.S, len(LOO_EXACT_FIELDS)))
+        out = np.zeros((g.size, self.model.S, len(LOO_EXACT_FIELDS) + more))
         re = self._r_eff(g, r_eff)
         if g.size:
             _check(call(int(g.size), _p(g, C.c_int32), _p(re, C.c_double), _p(out, C.c_double)))
         res = _loo_exact_dict(out)
+        if tail is not None:
+            tail(res, out[..., len(LOO_EXACT_FIELDS):])
         res["genes"] = g.astype(np.int64)
         res["n_draws"] = self.chains * self.n_keep
         if isinstance(r_eff, str):
@@ -925,6 +931,32 @@ class Fit:
         khat NaN. genes=None: all K checked genes (ids 0 .. K - 1); r_eff as Fit.loo_predict ("auto" adds `r_eff`)."""
         return self._loo_exact(genes, r_eff, lambda n, g, re, out: load().ppcx_fit_loo_predict_exact(
             self._h, n, g, re, float(truncation_compensation), float(p_lo), float(p_hi), out))
+
+    def loo_predict_exact_moment_match(self, genes=None, r_eff=None, k_threshold=None, max_iters=30, p_lo=0.025, p_hi=0.975,
+                                       truncation_compensation=1.0):
+        """Fit.loo_predict_exact with gene-local moment matching of the cells whose khat exceeds k_threshold
+        (ppcx_fit_loo_predict_exact_moment_match): the outlying cells, whose plain PSIS weights are not to be trusted, are matched
+        as Fit.loo_moment_match matches them, and their predictive is importance sampling with the matched draws as the proposal
+        -- the weights are PSIS on the ratios of the local density, the negative binomials are evaluated at the matched draws;
+        nothing is sampled. Fit.loo_predict_exact's dict (`khat` is the final one), plus Fit.loo_moment_match's `khat_before`,
+        `iterations` (int64), `scale` and `shift` [n_genes, S, C + 1] (the same bits as that method's) and `k_threshold`. A cell
+        with iterations == 0 holds Fit.loo_predict_exact's bits. k_threshold=None: inference.loo_threshold(n_draws). No covariance
+        step and no split transformation: a matched khat is necessary, not sufficient. Not for an ADVI fit."""
+        if k_threshold is None:
+            from .inference import loo_threshold
+            k_threshold = loo_threshold(self.chains * self.n_keep)
+        k_threshold, max_iters = float(k_threshold), int(max_iters)
+        nc = self.model.C + 1
+
+        def tail(res, more):
+            res["khat_before"] = more[..., 0].copy()
+            res["iterations"] = more[..., 1].astype(np.int64)
+            res["scale"] = more[..., 2:2 + nc].copy()
+            res["shift"] = more[..., 2 + nc:2 + 2 * nc].copy()
+            res["k_threshold"] = k_threshold
+        return self._loo_exact(genes, r_eff, lambda n, g, re, out: load().ppcx_fit_loo_predict_exact_moment_match(
+            self._h, n, g, re, k_threshold, max_iters, float(truncation_compensation), float(p_lo), float(p_hi), out),
+            more=2 + 2 * nc, tail=tail)
 
     def loo_predict_exact_approximate_posterior(self, genes=None, p_lo=0.025, p_hi=0.975, truncation_compensation=1.0):
         """Fit.loo_predict_exact for an ADVI fit (ppcx_fit_loo_predict_exact_approx): the same dict (without r_eff) under the

@@ -344,6 +344,25 @@ extern "C" int ppcx_fit_loo_predict_exact_approx(ppcx_fit* f, int n_genes, const
   if ((rc = loo_approx_ratios(f, fc)) != PPCX_OK) return rc;
   return hip_done(who, loo_exact_fit_cells(fc, truncation_compensation, p_lo, p_hi, out, loo_scratch_bytes(), f->m->stream.s));
 }
+// ... with the cells above k_threshold matched first (ppcx_loo_mm_exact.h): ppcx_fit_loo_moment_match's kernels, then the
+// predictive under their weights at the matched draws
+extern "C" int ppcx_fit_loo_predict_exact_moment_match(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff,
+                                                       double k_threshold, int max_iters, double truncation_compensation, double p_lo,
+                                                       double p_hi, double* out) {
+  const char* who = "ppcx_fit_loo_predict_exact_moment_match";
+  if (!f) return fail(PPCX_ERR_ARG, "fit is NULL");
+  if (f->advi) return fail(PPCX_ERR_ARG, std::string(who) + " needs the draws of a NUTS fit: moment matching under the weights of an "
+                                                             "ADVI fit (loo_approximate_posterior) is not available");
+  if (!isfinite(k_threshold)) return fail(PPCX_ERR_ARG, std::string(who) + ": k_threshold must be finite");
+  if (max_iters < 0) return fail(PPCX_ERR_ARG, std::string(who) + ": max_iters must be >= 0");
+  int rc = loo_exact_check(f, n_genes, genes, truncation_compensation, p_lo, p_hi);
+  if (rc != PPCX_OK) return rc;
+  std::vector<int> yenc; FitCells fc;
+  if ((rc = loo_prepare_cells(f, n_genes, genes, out, yenc, fc)) != PPCX_OK) return rc;
+  if ((rc = loo_fit_reff(who, fc, r_eff)) != PPCX_OK) return rc;
+  return hip_done(who, loo_mm_exact_fit_cells(fc, k_threshold, max_iters, truncation_compensation, p_lo, p_hi, out, loo_scratch_bytes(),
+                                              f->m->stream.s));
+}
 #ifdef PPCX_TESTING
 // testing build only (ppcx_testing.h): the kernel of the two above on host-given columns, on the current device
 extern "C" int ppcx_testing_loo_exact(int n, int n_cols, const double* ll, const double* eta, const double* sigma_raw, const int32_t* y,

@@ -304,6 +304,11 @@ hipError_t loo_exact_columns(const GivenCells& gc, const double* eta, const doub
 // out [cells][loo_mm_fields(C)]
 hipError_t launch_loo_kernel(const LooArgs& a, int fields, int n_blocks, hipStream_t st);
 hipError_t loo_mm_fit_cells(const FitCells& fc, double k_threshold, int max_iters, double* out, size_t scratch_bytes, hipStream_t st);
+// The exact leave-one-out predictive under the matched weights (ppcx_loo_mm_exact.hip, statistic in ppcx_loo_mm_exact.h): per batch
+// of cells the two kernels above into a device record, then one workgroup per cell; ratio / eta, weight and ln phi of the draws
+// (24 bytes per draw) in LDS up to kPsisLdsDraws draws, beyond that in the scratch. out [cells][loo_mm_exact_fields(C)]
+hipError_t loo_mm_exact_fit_cells(const FitCells& fc, double k_threshold, int max_iters, double tc, double p_lo, double p_hi, double* out,
+                                  size_t scratch_bytes, hipStream_t st);
 // The relative efficiency of the same cells (ppcx_reff.hip, statistic in ppcx_reff.h): one workgroup per cell; the split values
 // (8 bytes each) in LDS for fits of up to kPsisLdsDraws draws, beyond that in the scratch. Of `l` it uses T / y / expo / X / S / C
 // or cols, n = chains n_keep, cell0, n_cells, scratch ([launch's cells][2 chains (n_keep / 2)]) and out ([cells], one value

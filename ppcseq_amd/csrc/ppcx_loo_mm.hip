@@ -1,6 +1,7 @@
 // ppcx_loo_mm.hip -- gfx950 kernels of the gene-local moment matching of PSIS-LOO cells (ppcx_fit_loo_moment_match,
 // include/ppcx.h; the statistic: ppcx_loo_mm.h). The walk over the cells is ppcx_loo_dev.h's (for_gene_batches,
-// cells_in_batches); the driver at the end of this file adds the argument block and the kernels.
+// cells_in_batches); the driver at the end of this file adds the kernels. The argument block, the gene a workgroup reads and the
+// walk's own buffers are ppcx_loo_mm_dev.h's, shared with ppcx_loo_mm_exact.hip, which runs these kernels before its own.
 //
 //   ppcx_loo_mm_hyper_kernel  the draws' six unconstrained hyper-parameters, transposed: U[k][draw], once per call, so that a
 //                             wavefront's lanes read consecutive draws of one hyper-parameter as they do of the table T.
@@ -22,24 +23,9 @@
 // Every reduction runs in a fixed order and a cell reads nothing of another gene: its fields are the same bits whatever else is
 // requested and however the work is batched.
 #include <hip/hip_runtime.h>
-#include "ppcx_loo_dev.h"
-#include "ppcx_loo_mm.h"
+#include "ppcx_loo_mm_dev.h"
 
 namespace ppcx {
-
-struct LooMmArgs {
-  LooArgs l;                       // the table, y, r_eff, n, the cells, sel_pad, the scratch of both kernels (l.out: ppcx_loo_kernel's)
-  const int* genes = nullptr;      // [table's genes] their ids in the model (device)
-  const double* U = nullptr;       // [6][n] ppcx_loo_mm_hyper_kernel
-  const double* loo = nullptr;     // [cells][kLooFields] ppcx_loo_kernel's fields of the table's cells
-  int K = 0;                       // checked genes of the model
-  double lambda_mu_mu = 0.0, k_threshold = 0.7;
-  int max_iters = 0;
-  double* out = nullptr;           // [cells][loo_mm_fields(C)]
-};
-
-// doubles per cell, in LDS or in the scratch: a candidate's ratios [n], the log weights [n], Q0 [n]
-__host__ __device__ inline long loo_mm_slice(long n) { return 3 * n; }
 
 __global__ __launch_bounds__(256) void ppcx_loo_mm_hyper_kernel(const double* draws, long n_draws, Dims d, double* U) {
   const long t = (long)blockIdx.x * 256 + threadIdx.x;
@@ -91,10 +77,7 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_kernel(LooMmArgs p)
     k = lt.khat;
   }
   // ---- the gene, the state, Q0
-  LooMmGene g;
-  g.Tg = a.T + (long)gi * nc * n; g.U = p.U; g.n = n; g.C = C; g.S = a.S;
-  g.checked = C >= 2 && p.genes[gi] < p.K;
-  g.yrow = a.y + (long)gi * a.S; g.expo = a.expo; g.X = a.X; g.lambda_mu_mu = p.lambda_mu_mu;
+  const LooMmGene g = loo_mm_gene(p, gi);
   if (tid < nc) { ms.A[tid] = 1.0; ms.B[tid] = 0.0; }
   __syncthreads();
   for (long i = tid; i < n; i += kBlockThreads) { double l; Q0[i] = loo_mm_density(g, i, ms.A, ms.B, s, &l); }
@@ -188,29 +171,40 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_kernel(LooMmArgs p)
 // ---- launch helpers (host)
 PPCX_KERNEL_OF(ppcx_loo_mm_kernel);
 
-hipError_t loo_mm_fit_cells(const FitCells& fc, double k_threshold, int max_iters, double* out, size_t scratch_bytes, hipStream_t st) {
+hipError_t LooMmWalk::prepare(const FitCells& fc, hipStream_t st) {
   const long n = fc.n;
-  const size_t ncells = (size_t)fc.n_genes * fc.d.S;
-  DeviceBuffer<double> d_U, d_loo;                       // outlive the walk, which drains the stream before it returns
-  hipError_t e = d_U.alloc(6 * (size_t)n);
-  if (e == hipSuccess) e = d_loo.alloc(ncells * kLooFields);
+  hipError_t e = U.alloc(6 * (size_t)n);
+  if (e == hipSuccess) e = loo.alloc((size_t)fc.n_genes * fc.d.S * kLooFields);
   if (e == hipSuccess) {
-    hipLaunchKernelGGL(ppcx_loo_mm_hyper_kernel, dim3((unsigned)((6 * n + 255) / 256)), dim3(256), 0, st, fc.draws, n, fc.d, d_U.p);
+    hipLaunchKernelGGL(ppcx_loo_mm_hyper_kernel, dim3((unsigned)((6 * n + 255) / 256)), dim3(256), 0, st, fc.draws, n, fc.d, U.p);
     e = hipGetLastError();
   }
+  return e;
+}
+LooMmArgs LooMmWalk::args(const FitCells& fc, const LooArgs& a, const int* genes, int n_cells, double k_threshold, int max_iters,
+                          double* out) {
+  LooMmArgs p;
+  p.l = a; p.genes = genes; p.U = U.p; p.loo = loo.p + done * kLooFields; p.K = fc.d.K; p.lambda_mu_mu = fc.d.lambda_mu_mu;
+  p.k_threshold = k_threshold; p.max_iters = max_iters; p.out = out;
+  p.l.out = loo.p + done * kLooFields;
+  done += (size_t)n_cells;
+  return p;
+}
+hipError_t launch_loo_mm_kernels(const LooMmArgs& q, const CellLaunch& c, hipStream_t st) {
+  const hipError_t e1 = launch_loo_kernel(q.l, kLooFields, c.n_blocks, st);
+  return e1 == hipSuccess ? launch_cell_kernel(pick_kernel<ppcx_loo_mm_kernel_of>(c.lds), q, c, q.l.sel_pad, loo_mm_slice(q.l.n), st) : e1;
+}
+
+hipError_t loo_mm_fit_cells(const FitCells& fc, double k_threshold, int max_iters, double* out, size_t scratch_bytes, hipStream_t st) {
+  LooMmWalk walk;                                        // outlives the walk, which drains the stream before it returns
+  const hipError_t e = walk.prepare(fc, st);
   if (e != hipSuccess) return finish(e, st);
-  size_t done = 0;                                       // cells of the earlier gene batches
   return for_gene_batches(fc, loo_mm_fields(fc.d.C), out, scratch_bytes, st,
                           [&](const LooArgs& a, const int* genes, int n_cells, DeviceBuffer<double>& scratch) {
-    LooMmArgs p;
-    p.l = a; p.genes = genes; p.U = d_U.p; p.loo = d_loo.p + done * kLooFields; p.K = fc.d.K; p.lambda_mu_mu = fc.d.lambda_mu_mu;
-    p.k_threshold = k_threshold; p.max_iters = max_iters; p.out = a.out;
-    p.l.out = d_loo.p + done * kLooFields;
-    done += (size_t)n_cells;
-    // per batch of cells: plain PSIS-LOO by its own kernel (its slices of the scratch lie within ours), then the matching
-    return cells_in_batches(p, loo_mm_slice(n), n_cells, scratch_bytes, scratch, [&](const LooMmArgs& q, const CellLaunch& c) {
-      const hipError_t e1 = launch_loo_kernel(q.l, kLooFields, c.n_blocks, st);
-      return e1 == hipSuccess ? launch_cell_kernel(pick_kernel<ppcx_loo_mm_kernel_of>(c.lds), q, c, q.l.sel_pad, loo_mm_slice(n), st) : e1;
+    const LooMmArgs p = walk.args(fc, a, genes, n_cells, k_threshold, max_iters, a.out);
+    // per batch of cells: plain PSIS-LOO, then the matching
+    return cells_in_batches(p, loo_mm_slice(fc.n), n_cells, scratch_bytes, scratch, [&](const LooMmArgs& q, const CellLaunch& c) {
+      return launch_loo_mm_kernels(q, c, st);
     });
   });
 }

@@ -227,6 +227,7 @@ class CheckContext:
     loo_mcse: bool = False
     pooled: bool = False         # a fit over the pooled draws of several fits' chains (pooled_summary): it holds no lp__
     loo_moment_match: bool = False   # check_loo reads Fit.loo_moment_match in place of Fit.loo
+    exact_loo_moment_match: bool = False   # exact_loo_intervals reads Fit.loo_predict_exact_moment_match in place of Fit.loo_predict_exact
 
 
 @dataclass(frozen=True)
@@ -263,6 +264,13 @@ def _read_loo(fit, ctx):
     return fit.loo(np.arange(ctx.K), r_eff=ctx.loo_r_eff, mcse=bool(ctx.loo_mcse))
 
 
+def _read_exact_loo(fit, ctx):
+    """exact_loo_intervals' read: Fit.loo_predict_exact(r_eff, the pass's interval), or with exact_loo_moment_match
+    Fit.loo_predict_exact_moment_match with the same keywords (its khat is the final one)"""
+    read = fit.loo_predict_exact_moment_match if ctx.exact_loo_moment_match else fit.loo_predict_exact
+    return read(np.arange(ctx.K), r_eff=ctx.loo_r_eff, **_interval(ctx))
+
+
 CHECKS = (          # in the order of the reads
     Check("check_approximation", "approximation", 2, "advi", False, False,
           "check_approximation needs an ADVI pass (approximate_posterior_inference = True): the Pareto k diagnostic judges the "
@@ -297,7 +305,7 @@ CHECKS = (          # in the order of the reads
     Check("exact_loo_intervals", "exact_loo_intervals", 8, "nuts", True, False,
           "exact_loo_intervals needs a NUTS pass: the exact leave-one-out intervals of an ADVI fit (loo_approximate_posterior) are "
           "exact_approximation_loo_intervals",
-          lambda fit, ctx: fit.loo_predict_exact(np.arange(ctx.K), r_eff=ctx.loo_r_eff, **_interval(ctx))),
+          _read_exact_loo),
 )
 
 MODIFIERS = (       # (option, the options of which it needs one, what it is told without one)
@@ -307,6 +315,8 @@ MODIFIERS = (       # (option, the options of which it needs one, what it is tol
      "loo_mcse needs check_loo: it adds the Monte-Carlo standard error and n_eff to its PSIS-LOO"),
     ("loo_moment_match", ("check_loo",),
      "loo_moment_match needs check_loo: it matches the moments of the cells whose k-hat its PSIS-LOO finds too high"),
+    ("exact_loo_moment_match", ("exact_loo_intervals",),
+     "exact_loo_moment_match needs exact_loo_intervals: it matches the moments of the cells whose k-hat their PSIS finds too high"),
 )
 LOO_MOMENT_MATCH_MCSE = ("loo_mcse cannot be combined with loo_moment_match: the Monte-Carlo standard error and n_eff are those of "
                          "plain PSIS weights and are not given for a matched cell")
@@ -377,7 +387,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                  check_approximation_loo_intervals=False,
                  exact_intervals=False,
                  exact_loo_intervals=False,
-                 exact_approximation_loo_intervals=False):
+                 exact_approximation_loo_intervals=False,
+                 exact_loo_moment_match=False):
     """One inference pass (discovery or test) of ppcseq on the GPU.
 
     counts            G x S integer matrix, genes ordered with the `how_many_to_check` checked genes first
@@ -443,6 +454,12 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
     exact_approximation_loo_intervals  exact_loo_intervals for an ADVI pass, under the weights of check_approximation_loo
                       (Fit.loo_predict_exact_approximate_posterior), kept as `res.exact_approximation_loo_intervals`. No
                       warning, no flag changes. Not for a NUTS pass.
+    exact_loo_moment_match  True: `res.exact_loo_intervals` comes from Fit.loo_predict_exact_moment_match: the cells whose k-hat
+                      exceeds loo_threshold -- the outliers the check exists to find -- are matched as loo_moment_match matches
+                      them and their interval and tail probabilities are taken under the matched weights at the matched draws;
+                      the result then also carries `khat_before`, `iterations`, `scale`, `shift` and `k_threshold`, and `khat` is
+                      the final one. Flags and frame are those of the call without it. devices=[...]: over the pooled chains.
+                      Needs exact_loo_intervals. loo_moment_match itself affects `res.loo` only.
     Returns an InferenceResult.
     """
     counts = np.asarray(counts)
@@ -503,7 +520,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
         msgs = [] if approximate_posterior_inference else hmc_warnings(res.diagnostics, warmup)
         msgs += read_checks(fit, CheckContext(K, p, seed, truncation_compensation, checks.get("loo_r_eff"),
                                               checks.get("loo_mcse", False),
-                                              loo_moment_match=bool(checks.get("loo_moment_match", False))), checks, res)
+                                              loo_moment_match=bool(checks.get("loo_moment_match", False)),
+                                              exact_loo_moment_match=bool(checks.get("exact_loo_moment_match", False))), checks, res)
         for msg in msgs:
             warnings.warn(msg, RuntimeWarning, stacklevel=2)
         res.counts_rng = rng
@@ -589,7 +607,8 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
             res.total_draws = counts.shape[1] * K * int(how_many_posterior_draws)
             msgs = read_checks(fit, CheckContext(K, p, seed, truncation_compensation, checks.get("loo_r_eff"),
                                                  checks.get("loo_mcse", False), pooled=True,
-                                                 loo_moment_match=bool(checks.get("loo_moment_match", False))), checks, res)
+                                                 loo_moment_match=bool(checks.get("loo_moment_match", False)),
+                                              exact_loo_moment_match=bool(checks.get("exact_loo_moment_match", False))), checks, res)
         finally:
             fit.close()
     finally:

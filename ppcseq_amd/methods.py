@@ -128,7 +128,7 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                       check_convergence=False, check_approximation=False, check_loo=False,
                       check_loo_intervals=False, loo_r_eff=None, loo_mcse=False, loo_moment_match=False,
                       check_approximation_loo=False, check_approximation_loo_intervals=False, exact_intervals=False,
-                      exact_loo_intervals=False, exact_approximation_loo_intervals=False):
+                      exact_loo_intervals=False, exact_approximation_loo_intervals=False, exact_loo_moment_match=False):
     """Mirror of ppcseq::identify_outliers (R/methods.R:74-367): same arguments, same defaults.
 
     data is a tidy pandas DataFrame (one row per transcript x sample); column arguments are strings. As in the
@@ -159,6 +159,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
     `exact_intervals` (NUTS and ADVI)             -> attrs["exact_intervals_discovery"], ["exact_intervals_test"]
     `exact_loo_intervals` (NUTS)                  -> attrs["exact_loo_intervals_discovery"], ["exact_loo_intervals_test"]
     `exact_approximation_loo_intervals` (ADVI)    -> attrs["exact_approximation_loo_intervals_discovery"], [..."_test"]
+    `exact_loo_moment_match` = True               -> exact_loo_intervals' results come from Fit.loo_predict_exact_moment_match; in
+                                                     the same attrs
     """
     import os
     import pandas as pd

@@ -1,0 +1,207 @@
+"""An independent restatement of the exact leave-one-out predictive under moment-matched weights
+(ppcseq_amd/csrc/ppcx_loo_mm_exact.h) with numpy and scipy: the state (scale, shift), the local density and the PSIS of
+tests/loo_mm_restate.py (point / local_density / psis), scipy.stats.nbinom.cdf / sf for the tails, and quantiles as the smallest
+integer k with F(k) >= p found by bisection. Nothing here is shared with the header. It also holds the loader of the CPU build
+of the header (tests/loo_mm_exact_host) and the truth of the one-gene case of tests/loo_mm_cases.py by quadrature
+(truth_predictive). Shared by tests/test_loo_mm_exact_host.py (CPU) and tests/test_gpu_loo_mm_exact.py (device).
+
+A gene is the dict of tests/loo_mm_restate.py.
+
+MEASURED: the largest error of the CPU build against this restatement in mean, sd, p_le, p_ge, khat, scale and shift over
+tests/loo_mm_cases.designed(), in units of max(1, |ref|), and of p_le / p_ge relatively where they are below 1e-3
+(test_header_matches_restatement prints it: 4.64e-11). GPU_MEASURED: that of the device against the CPU build over the designed
+cells (9.3e-12) and the draw counts of tests/test_gpu_loo_mm_exact.py (6.67e-11 at n = 257), which prints both. The bound of either comparison is ten times the measured
+value and never above BOUND."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+from tests import loo_mm_restate as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEAD = ("mean", "sd", "p_le", "p_ge", "lower", "upper", "y", "excluded", "outside", "khat", "khat_before", "iterations")
+INTEGERS = ("lower", "upper", "y", "excluded", "outside", "iterations")
+REALS = ("mean", "sd", "p_le", "p_ge", "khat", "khat_before")
+BOUND = 1e-9
+MEASURED = 4.7e-11
+GPU_MEASURED = 6.7e-11
+
+
+def fields(Cc):
+    return len(HEAD) + 2 * (Cc + 1)
+
+
+# ---- the statistic
+
+def mixture_cdf(k, w, mu, phi):
+    from scipy.stats import nbinom
+    return float(np.sum(w * nbinom.cdf(k, phi, phi / (phi + mu))))
+
+
+def quantile(p, w, mu, phi):
+    """the smallest integer k >= 0 with F(k) >= p, by bisection"""
+    if mixture_cdf(0, w, mu, phi) >= p:
+        return 0
+    lo, hi = 0, 1
+    while mixture_cdf(hi, w, mu, phi) < p:
+        lo, hi = hi, 2 * hi
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if mixture_cdf(mid, w, mu, phi) >= p:
+            hi = mid
+        else:
+            lo = mid
+    return hi
+
+
+def predictive(w, mu, phi, y, p_lo, p_hi):
+    """mean, sd, p_le, p_ge, lower, upper, outside of the mixture of negative binomials (mu_i, phi_i) under the weights w"""
+    from scipy.stats import nbinom
+    pr = phi / (phi + mu)
+    mean = float(np.sum(w * mu))
+    sd = float(np.sqrt(np.sum(w * (mu + mu * mu / phi)) + np.sum(w * (mu - mean) ** 2)))
+    lower, upper = quantile(p_lo, w, mu, phi), quantile(p_hi, w, mu, phi)
+    return dict(mean=mean, sd=sd, p_le=float(np.sum(w * nbinom.cdf(y, phi, pr))), p_ge=float(np.sum(w * nbinom.sf(y - 1, phi, pr))),
+                lower=lower, upper=upper, outside=bool(y < lower or y > upper))
+
+
+def point(gene, s, r_eff=1.0, k_threshold=0.7, max_iters=30, tc=1.0, p_lo=0.025, p_hi=0.975):
+    """dict of the cell's fields, `scale`, `shift` [C + 1], `kinds` (loo_mm_restate.point's) and, for a cell that is a number,
+    what the interval's allowance needs: w, mu, phi, p_lo, p_hi"""
+    Cc = gene["X"].shape[1]
+    n = gene["T"].shape[1]
+    mm = R.point(gene, s, r_eff, k_threshold, max_iters)
+    y, excluded = int(gene["y"][s]), bool(gene["excl"][s])
+    out = {k: np.nan for k in HEAD}
+    out.update(y=y, excluded=excluded, khat_before=mm["khat_before"], iterations=mm["iterations"], scale=np.asarray(mm["scale"], float),
+               shift=np.asarray(mm["shift"], float), kinds=mm["kinds"])
+    A, B = out["scale"], out["shift"]
+    q, ll_all = R.local_density(gene, A, B)
+    ll = ll_all[s]
+    if mm["iterations"] == 0:
+        if np.isnan(ll).any() or (not excluded and (ll == -np.inf).any()):
+            return out
+        if excluded:
+            w, khat = np.full(n, 1.0 / n), np.nan
+        else:
+            if not (ll != np.inf).any():
+                return out
+            lw, khat = R.psis(np.where(ll == np.inf, -np.inf, -ll), r_eff)
+            w = np.exp(lw - R.L.logsumexp(lw))
+    else:
+        Q0, _ = R.local_density(gene, np.ones(Cc + 1), np.zeros(Cc + 1))
+        with np.errstate(invalid="ignore"):
+            r = q - Q0 - ll
+        lw, khat = R.psis(np.where(np.isfinite(r), r, -np.inf), r_eff)
+        if not np.isfinite(lw).any():
+            return out
+        w = np.exp(lw - R.L.logsumexp(lw))
+    t = R.transformed(gene, A, B)
+    eta = gene["expo"][s] + np.asarray(gene["X"], float)[s] @ t[:Cc]
+    phi = tc * np.exp(-t[Cc])
+    with np.errstate(over="ignore", invalid="ignore"):
+        mu = np.exp(eta)
+    if not (np.all(np.isfinite(eta)) and np.all(np.isfinite(phi)) and np.all(phi > 0) and np.all(np.isfinite(mu))):
+        return out
+    out.update(predictive(w, mu, phi, y, p_lo, p_hi), khat=khat, w=w, mu=mu, phi=phi, p_lo=p_lo, p_hi=p_hi)
+    return out
+
+
+def errors(got, ref):
+    """the largest error of mean, sd, p_le, p_ge, khat, khat_before, scale and shift in units of max(1, |ref|), p_le and p_ge also
+    relatively where the reference is below 1e-3; values that are not finite must be equal (error 0 or Inf)"""
+    Cc = (len(got) - len(HEAD)) // 2 - 1
+    pairs = [(got[HEAD.index(k)], ref[k], k in ("p_le", "p_ge")) for k in REALS]
+    pairs += [(got[len(HEAD) + c], ref["scale"][c], False) for c in range(Cc + 1)]
+    pairs += [(got[len(HEAD) + Cc + 1 + c], ref["shift"][c], False) for c in range(Cc + 1)]
+    worst = 0.0
+    for g, r, tail in pairs:
+        g, r = float(g), float(r)
+        if not np.isfinite(r):
+            worst = max(worst, 0.0 if (np.isnan(r) and np.isnan(g)) or g == r else np.inf)
+            continue
+        worst = max(worst, abs(g - r) / max(1.0, abs(r)))
+        if tail and 0.0 < r < 1e-3:
+            worst = max(worst, abs(g - r) / r)
+    return worst
+
+
+def check_integers(got, ref, bound, what=""):
+    """the integer fields of got against point(): equal, but lower / upper may be one count apart where the restatement's own F
+    at the count between them is within `bound` of p. Returns how many ends used that allowance."""
+    if np.isnan(ref["mean"]):
+        assert all(np.isnan(got[HEAD.index(k)]) for k in ("mean", "sd", "p_le", "p_ge", "lower", "upper", "outside", "khat")), (what, got)
+    used = 0
+    for k, p in (("lower", ref.get("p_lo")), ("upper", ref.get("p_hi"))):
+        g, r = got[HEAD.index(k)], ref[k]
+        if np.isnan(r) or g == r:
+            assert np.isnan(g) == np.isnan(r), (what, k, g, r)
+            continue
+        assert abs(g - r) == 1, (what, k, g, r)
+        f = mixture_cdf(int(min(g, r)), ref["w"], ref["mu"], ref["phi"])
+        assert abs(f - p) <= bound, (what, k, g, r, f, p)
+        used += 1
+    for k in ("y", "excluded", "iterations") + (() if used else ("outside",)):
+        g, r = got[HEAD.index(k)], ref[k]
+        assert (np.isnan(g) and np.isnan(r)) if isinstance(r, float) and np.isnan(r) else g == r, (what, k, g, r)
+    return used
+
+
+def truth_predictive():
+    """the held-out predictive distribution of the last cell of the truth case by quadrature on TRUTH_GRID, under the posterior
+    of the other five cells: dict of mean, lower, upper (2.5 % / 97.5 %) and p_ge = P(X >= y)"""
+    from scipy.stats import nbinom
+    from tests import loo_mm_cases as cases
+    y = cases.TRUTH_COUNTS[0]
+    excl = np.zeros(6, bool)
+    excl[cases.TRUTH_CELL] = True
+    lp, _ = cases._grid_log_post(y, excl, np.zeros(6), np.ones((6, 1)), False, cases.TRUTH_GRID)
+    w = np.exp(lp - lp.max()).ravel()
+    keep = w > 1e-18 * w.max()                     # the rest of the grid carries nothing at double precision
+    w = w[keep] / w[keep].sum()
+    mesh = np.meshgrid(*cases.TRUTH_GRID, indexing="ij")
+    mu, phi = np.exp(mesh[0].ravel()[keep]), np.exp(-mesh[1].ravel()[keep])
+    yc = int(y[cases.TRUTH_CELL])
+    return dict(mean=float(np.sum(w * mu)), lower=quantile(0.025, w, mu, phi), upper=quantile(0.975, w, mu, phi),
+                p_ge=float(np.sum(w * nbinom.sf(yc - 1, phi, phi / (phi + mu)))))
+
+
+# ---- the CPU build of the header
+
+def host_lib():
+    here = os.path.join(ROOT, "tests", "loo_mm_exact_host")
+    src = os.path.join(here, "loo_mm_exact_host.cpp")
+    hdrs = [os.path.join(ROOT, "ppcseq_amd", "csrc", h) for h in ("ppcx_math.h", "ppcx_disp.h", "ppcx_model.h", "ppcx_psis.h", "ppcx_loo.h",
+                                                                  "ppcx_loo_predict.h", "ppcx_loo_ap.h", "ppcx_nbcdf.h", "ppcx_ppc_exact.h",
+                                                                  "ppcx_loo_exact.h", "ppcx_loo_mm.h", "ppcx_loo_mm_exact.h")]
+    lib = os.path.join(here, "libloo_mm_exact_host.so")
+    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in [src] + hdrs):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-o", lib, src])
+    h = C.CDLL(lib)
+    dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+    gene = [dp, dp, C.c_long, C.c_int, C.c_int, C.c_int, ip, dp, dp, C.c_double]
+    h.loo_mm_exact_host_cell.argtypes = gene + [C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, dp]
+    h.loo_mm_exact_host_cell.restype = None
+    h.loo_mm_exact_host_columns.argtypes = gene + [C.c_int, dp, dp, dp]
+    h.loo_mm_exact_host_columns.restype = None
+    return h
+
+
+def host_cell(h, gene, s, r_eff=1.0, k_threshold=0.7, max_iters=30, tc=1.0, p_lo=0.025, p_hi=0.975):
+    """the cell's record [12 + 2 (C + 1)] of the CPU build"""
+    keep, args = R._gene_args(gene)
+    out = np.zeros(fields(gene["X"].shape[1]))
+    h.loo_mm_exact_host_cell(*args, int(s), float(r_eff), float(k_threshold), int(max_iters), float(tc), float(p_lo), float(p_hi),
+                             R._dp(out))
+    return out
+
+
+def host_columns(h, gene, s):
+    """(eta, sigma_raw, ll) [n] of the cell at the original draws, as the CPU build forms them for a cell that is not matched"""
+    keep, args = R._gene_args(gene)
+    n = gene["T"].shape[1]
+    eta, sg, ll = np.zeros(n), np.zeros(n), np.zeros(n)
+    h.loo_mm_exact_host_columns(*args, int(s), R._dp(eta), R._dp(sg), R._dp(ll))
+    return eta, sg, ll
