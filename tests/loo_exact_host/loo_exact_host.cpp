@@ -1,6 +1,6 @@
 // CPU build of the exact leave-one-out predictive tails and interval per cell (ppcseq_amd/csrc/ppcx_loo_exact.h) for
 // tests/test_loo_exact_host.py: the same header the gfx950 kernel includes, compiled with g++ and called through ctypes. With
-// -DLOO_EXACT_HOST_MAIN it is a stand-alone program (a fixed set of cells, for a run under -fsanitize=address,undefined).
+// -DPPCX_HOST_MAIN it is a stand-alone program (a fixed set of cells, for a run under -fsanitize=address,undefined).
 #include "../../ppcseq_amd/csrc/ppcx_loo_exact.h"
 
 #define LOO_EXACT_EXPORT extern "C" __attribute__((visibility("default")))
@@ -22,7 +22,7 @@ LOO_EXACT_EXPORT void loo_exact_host_log_pmf(const double* eta, const double* si
   for (long i = 0; i < n; ++i) ll[i] = ppcx::loo_ll(y, eta[i], sigma_raw[i]);
 }
 
-#ifdef LOO_EXACT_HOST_MAIN
+#ifdef PPCX_HOST_MAIN
 #include <stdio.h>
 #include <vector>
 int main() {

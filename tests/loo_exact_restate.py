@@ -9,16 +9,14 @@ WEIGHTED_MEASURED: the largest error of the CPU build against this restatement i
 tests/loo_exact_cases.designed(), in units of max(1, |ref|). It stays below the 1e-12 of loo_predict_restate.check's rule for
 weighted sums, so that rule is the bound (WEIGHTED_BOUND) and no 4 x allowance is taken."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from tests import host_build
 from tests import loo_ap_restate as AP
 from tests import loo_predict_restate as LP
 from tests import ppc_exact_restate as E
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIELDS = E.FIELDS + ("khat",)                 # kLooExactFields, in order
 P2, TC = E.P2, E.TC
 TAILS_BOUND, TAILS_ABS = E.TAILS_BOUND, E.TAILS_ABS
@@ -27,22 +25,11 @@ WEIGHTED_BOUND = 1e-12
 
 
 def host_lib():
-    here = os.path.join(ROOT, "tests", "loo_exact_host")
-    src = os.path.join(here, "loo_exact_host.cpp")
-    hdrs = [os.path.join(ROOT, "ppcseq_amd", "csrc", h) for h in ("ppcx_math.h", "ppcx_disp.h", "ppcx_psis.h", "ppcx_loo.h", "ppcx_loo_predict.h",
-                                                                  "ppcx_loo_ap.h", "ppcx_nbcdf.h", "ppcx_ppc_exact.h", "ppcx_loo_exact.h")]
-    lib = os.path.join(here, "libloo_exact_host.so")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-o", lib, src])
-    h = C.CDLL(lib)
     dp = C.POINTER(C.c_double)
-    h.loo_exact_host_cell.argtypes = [dp, dp, dp, dp, C.c_long, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, dp]
-    h.loo_exact_host_cell.restype = C.c_int
-    h.loo_exact_host_ppc_cell.argtypes = [dp, dp, C.c_long, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, dp]
-    h.loo_exact_host_ppc_cell.restype = None
-    h.loo_exact_host_log_pmf.argtypes = [dp, dp, C.c_long, C.c_int, dp]
-    h.loo_exact_host_log_pmf.restype = None
-    return h
+    return host_build.host_lib("loo_exact", {
+        "loo_exact_host_cell": ([dp, dp, dp, dp, C.c_long, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, dp], C.c_int),
+        "loo_exact_host_ppc_cell": ([dp, dp, C.c_long, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, dp], None),
+        "loo_exact_host_log_pmf": ([dp, dp, C.c_long, C.c_int, dp], None)})
 
 
 def _col(a):

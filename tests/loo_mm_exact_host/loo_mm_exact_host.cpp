@@ -1,6 +1,6 @@
 // CPU build of the exact leave-one-out predictive under moment-matched weights (ppcseq_amd/csrc/ppcx_loo_mm_exact.h) for
 // tests/test_loo_mm_exact_host.py: the same header the gfx950 kernel includes, compiled with g++ and called through ctypes. With
-// -DLOO_MM_EXACT_HOST_MAIN it is a stand-alone program (a fixed gene, for a run under -fsanitize=address,undefined).
+// -DPPCX_HOST_MAIN it is a stand-alone program (a fixed gene, for a run under -fsanitize=address,undefined).
 #include "../../ppcseq_amd/csrc/ppcx_loo_mm_exact.h"
 
 #define LOO_MM_EXACT_EXPORT extern "C" __attribute__((visibility("default")))
@@ -34,7 +34,7 @@ LOO_MM_EXACT_EXPORT void loo_mm_exact_host_columns(const double* T, const double
   }
 }
 
-#ifdef LOO_MM_EXACT_HOST_MAIN
+#ifdef PPCX_HOST_MAIN
 #include <stdio.h>
 int main() {
   const int C = 2, S = 5;

@@ -13,14 +13,12 @@ tests/loo_mm_cases.designed(), in units of max(1, |ref|), and of p_le / p_ge rel
 cells (9.3e-12) and the draw counts of tests/test_gpu_loo_mm_exact.py (6.67e-11 at n = 257), which prints both. The bound of either comparison is ten times the measured
 value and never above BOUND."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from tests import host_build
 from tests import loo_mm_restate as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEAD = ("mean", "sd", "p_le", "p_ge", "lower", "upper", "y", "excluded", "outside", "khat", "khat_before", "iterations")
 INTEGERS = ("lower", "upper", "y", "excluded", "outside", "iterations")
 REALS = ("mean", "sd", "p_le", "p_ge", "khat", "khat_before")
@@ -171,22 +169,11 @@ def truth_predictive():
 # ---- the CPU build of the header
 
 def host_lib():
-    here = os.path.join(ROOT, "tests", "loo_mm_exact_host")
-    src = os.path.join(here, "loo_mm_exact_host.cpp")
-    hdrs = [os.path.join(ROOT, "ppcseq_amd", "csrc", h) for h in ("ppcx_math.h", "ppcx_disp.h", "ppcx_model.h", "ppcx_psis.h", "ppcx_loo.h",
-                                                                  "ppcx_loo_predict.h", "ppcx_loo_ap.h", "ppcx_nbcdf.h", "ppcx_ppc_exact.h",
-                                                                  "ppcx_loo_exact.h", "ppcx_loo_mm.h", "ppcx_loo_mm_exact.h")]
-    lib = os.path.join(here, "libloo_mm_exact_host.so")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-o", lib, src])
-    h = C.CDLL(lib)
     dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
     gene = [dp, dp, C.c_long, C.c_int, C.c_int, C.c_int, ip, dp, dp, C.c_double]
-    h.loo_mm_exact_host_cell.argtypes = gene + [C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, dp]
-    h.loo_mm_exact_host_cell.restype = None
-    h.loo_mm_exact_host_columns.argtypes = gene + [C.c_int, dp, dp, dp]
-    h.loo_mm_exact_host_columns.restype = None
-    return h
+    return host_build.host_lib("loo_mm_exact", {
+        "loo_mm_exact_host_cell": (gene + [C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, dp], None),
+        "loo_mm_exact_host_columns": (gene + [C.c_int, dp, dp, dp], None)})
 
 
 def host_cell(h, gene, s, r_eff=1.0, k_threshold=0.7, max_iters=30, tc=1.0, p_lo=0.025, p_hi=0.975):

@@ -1,5 +1,5 @@
 // CPU build of the gene-local moment matching of PSIS-LOO cells (ppcseq_amd/csrc/ppcx_loo_mm.h) for tests/test_loo_mm_host.py:
-// the same header the gfx950 kernel includes, compiled with g++ and called through ctypes. With -DLOO_MM_HOST_MAIN it is a
+// the same header the gfx950 kernel includes, compiled with g++ and called through ctypes. With -DPPCX_HOST_MAIN it is a
 // stand-alone program (a fixed gene, for a run under -fsanitize=address,undefined).
 #include "../../ppcseq_amd/csrc/ppcx_loo_mm.h"
 
@@ -36,7 +36,7 @@ LOO_MM_EXPORT void loo_mm_host_loo_cell(const double* ll, long n, double r_eff, 
   ppcx::loo_cell_host(ll, n, r_eff, excluded != 0, out);
 }
 
-#ifdef LOO_MM_HOST_MAIN
+#ifdef PPCX_HOST_MAIN
 #include <stdio.h>
 int main() {
   const int C = 2, S = 5;

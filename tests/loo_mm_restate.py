@@ -14,14 +14,12 @@ device against the CPU build over the designed cells (8.8e-12) and the draw coun
 n = 64), which prints both. The bound of either comparison is ten times the measured
 value and never above BOUND."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from tests import host_build
 from tests import loo_restate as L
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEAD = ("elpd_loo", "p_loo", "looic", "khat", "khat_before", "iterations")
 BOUND = 1e-9
 MEASURED = 1.8e-11
@@ -172,23 +170,12 @@ def errors(got, ref_row):
 # ---- the CPU build of the header
 
 def host_lib():
-    here = os.path.join(ROOT, "tests", "loo_mm_host")
-    src = os.path.join(here, "loo_mm_host.cpp")
-    hdrs = [os.path.join(ROOT, "ppcseq_amd", "csrc", h) for h in ("ppcx_math.h", "ppcx_disp.h", "ppcx_model.h", "ppcx_psis.h", "ppcx_loo.h",
-                                                                  "ppcx_loo_predict.h", "ppcx_loo_ap.h", "ppcx_loo_exact.h", "ppcx_loo_mm.h")]
-    lib = os.path.join(here, "libloo_mm_host.so")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-o", lib, src])
-    h = C.CDLL(lib)
     dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
     gene = [dp, dp, C.c_long, C.c_int, C.c_int, C.c_int, ip, dp, dp, C.c_double]
-    h.loo_mm_host_cell.argtypes = gene + [C.c_int, C.c_double, C.c_double, C.c_int, dp, ip]
-    h.loo_mm_host_cell.restype = C.c_int
-    h.loo_mm_host_density.argtypes = gene + [C.c_int, dp, dp, dp, dp]
-    h.loo_mm_host_density.restype = None
-    h.loo_mm_host_loo_cell.argtypes = [dp, C.c_long, C.c_double, C.c_int, dp]
-    h.loo_mm_host_loo_cell.restype = None
-    return h
+    return host_build.host_lib("loo_mm", {
+        "loo_mm_host_cell": (gene + [C.c_int, C.c_double, C.c_double, C.c_int, dp, ip], C.c_int),
+        "loo_mm_host_density": (gene + [C.c_int, dp, dp, dp, dp], None),
+        "loo_mm_host_loo_cell": ([dp, C.c_long, C.c_double, C.c_int, dp], None)})
 
 
 def _dp(a):

@@ -1,6 +1,6 @@
 // CPU build of the exact posterior-predictive tails and interval per cell (ppcseq_amd/csrc/ppcx_nbcdf.h, ppcx_ppc_exact.h) for
 // tests/test_nbcdf_host.py and tests/test_ppc_exact_host.py: the same headers the gfx950 kernel includes, compiled with g++ and
-// called through ctypes. With -DPPC_EXACT_HOST_MAIN it is a stand-alone program (a fixed set of points and cells, for a run under
+// called through ctypes. With -DPPCX_HOST_MAIN it is a stand-alone program (a fixed set of points and cells, for a run under
 // -fsanitize=address,undefined).
 #include "../../ppcseq_amd/csrc/ppcx_ppc_exact.h"
 
@@ -23,7 +23,7 @@ PPC_EXACT_EXPORT void ppc_exact_host_rng(int n, const double* eta, const double*
   for (int i = 0; i < n; ++i) out[i] = ppcx::nb2_log_rng(eta[i], phi[i], k0, cell, (uint32_t)i);
 }
 
-#ifdef PPC_EXACT_HOST_MAIN
+#ifdef PPCX_HOST_MAIN
 #include <stdio.h>
 #include <vector>
 int main() {

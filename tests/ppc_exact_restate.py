@@ -3,12 +3,11 @@ with scipy.stats.nbinom and numpy, the references of the negative-binomial tails
 headers (tests/ppc_exact_host) and the designed columns that the CPU and the device tests share. Nothing here is shared with
 the code under test: the mixture cdf is the mean of scipy's cdfs, the quantile the first integer of a numpy search."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests import host_build
+
 FIELDS = ("mean", "sd", "p_le", "p_ge", "lower", "upper", "y", "excluded", "outside")     # kPpcExactFields, in order
 P2 = 2.4e-4                                   # a pass-2 tail probability (the README case: 0.05 / 21 / 10 rounded)
 TC = 0.7352941                                # a pass-2 truncation compensation
@@ -22,21 +21,11 @@ TAILS_ABS = 1e-8                              # a condition, not a measurement: 
 
 
 def host_lib():
-    here = os.path.join(ROOT, "tests", "ppc_exact_host")
-    src = os.path.join(here, "ppc_exact_host.cpp")
-    hdrs = [os.path.join(ROOT, "ppcseq_amd", "csrc", h) for h in ("ppcx_math.h", "ppcx_disp.h", "ppcx_nbcdf.h", "ppcx_ppc_exact.h")]
-    lib = os.path.join(here, "libppc_exact_host.so")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-o", lib, src])
-    h = C.CDLL(lib)
     dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
-    h.ppc_exact_host_tails.argtypes = [C.c_int, ip, dp, dp, dp, dp, ip]
-    h.ppc_exact_host_tails.restype = None
-    h.ppc_exact_host_cell.argtypes = [dp, dp, C.c_long, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, dp]
-    h.ppc_exact_host_cell.restype = C.c_int
-    h.ppc_exact_host_rng.argtypes = [C.c_int, dp, dp, C.c_uint32, C.c_uint32, ip]
-    h.ppc_exact_host_rng.restype = None
-    return h
+    return host_build.host_lib("ppc_exact", {
+        "ppc_exact_host_tails": ([C.c_int, ip, dp, dp, dp, dp, ip], None),
+        "ppc_exact_host_cell": ([dp, dp, C.c_long, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, dp], C.c_int),
+        "ppc_exact_host_rng": ([C.c_int, dp, dp, C.c_uint32, C.c_uint32, ip], None)})
 
 
 def _dp(a):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from tests import loo_restate as L
+from tests.gpu_fixtures import small_fit, testing_library  # noqa: F401
 from tests.test_gpu_psis import _bundled_frame, designs
 
 pytestmark = pytest.mark.gpu
@@ -48,18 +49,6 @@ def _compare(got, ref, tol, what):
     assert np.array_equal(got[~fin & ~np.isnan(ref)], ref[~fin & ~np.isnan(ref)]), what
     err = np.abs(got[fin] - ref[fin]) / np.maximum(1.0, np.abs(ref[fin]))
     assert err.max(initial=0.0) <= tol, (what, err.max())
-
-
-@pytest.fixture(scope="module")
-def small_fit():
-    from ppcseq_amd import _lib
-    from ppcseq_amd.synth import synth
-    d = synth(30, 10, K=4, seed=5)
-    m = _lib.Model(d["counts"], d["X"], d["exposure"], 4, excl=np.array([3, 10 + 7], np.int32), device=0)
-    f = m.fit_nuts(chains=4, iter=400, warmup=150, seed=3)
-    yield m, f, d
-    f.close()
-    m.close()
 
 
 def test_log_lik_matches_scipy(bundled):
@@ -139,9 +128,7 @@ def test_loo_matches_restatement(small_fit):
 
 
 def test_kernel_on_designed_columns():
-    from ppcseq_amd import _lib, build
-    _lib.use_library(build.build_testing())
-    try:
+    with testing_library() as _lib:
         rng = np.random.default_rng(4)
         cols = [-L.P.normal_ratios(rng, s2, 3000) for s2 in (1.5, 3.0, 10.0)]
         cols.append(-np.log(L.P.gpd_sample(rng, 0.8, 3000)))
@@ -171,17 +158,13 @@ def test_kernel_on_designed_columns():
                 assert np.array_equal(_lib.testing_loo(ll), one, equal_nan=True), n
             finally:
                 _lib.testing_set("loo_scratch_bytes", 0)
-    finally:
-        _lib.use_library(None)
 
 
 def test_batches_of_the_fit_give_the_same_bits(small_fit):
-    from ppcseq_amd import _lib, build
     m, f, d = small_fit
     base, ll = f.loo(), f.log_lik()
     dr = f.draws()
-    _lib.use_library(build.build_testing())
-    try:
+    with testing_library() as _lib:
         mt = _lib.Model(d["counts"], d["X"], d["exposure"], 4, excl=np.array([3, 17], np.int32), device=0)
         try:
             ft = mt.fit_from_draws(dr)
@@ -195,8 +178,6 @@ def test_batches_of_the_fit_give_the_same_bits(small_fit):
                 ft.close()
         finally:
             mt.close()
-    finally:
-        _lib.use_library(None)
     for k in L.FIELDS:
         assert np.array_equal(got[k], base[k], equal_nan=True), k
     assert np.array_equal(gll, ll)
@@ -208,7 +189,6 @@ def test_gene_batches_over_scratch_batches_give_the_same_bits(small_fit):
     exact copy), the gene table in fifteen batches of two genes and each batch's 20 cells in several scratch launches that
     reuse one allocation. Every statistic gives the bits of the unbounded call, and the unbounded LOO is the restatement's on
     the fit's own log-likelihood, at the bound of test_loo_matches_restatement."""
-    from ppcseq_amd import _lib, build
     m, f, d = small_fit
     own = L.loo_columns(f.log_lik().reshape(-1, m.G * m.S), None, np.isin(np.arange(m.G * m.S), [3, 17]))
     dr = np.tile(f.draws(), (1, 6, 1))[:, :1300]
@@ -218,8 +198,7 @@ def test_gene_batches_over_scratch_batches_give_the_same_bits(small_fit):
     def calls(ft):
         return dict(loo=ft.loo(), mcse=ft.loo(mcse=True), predict=ft.loo_predict(), reff=dict(r_eff=ft.relative_eff()))
 
-    _lib.use_library(build.build_testing())
-    try:
+    with testing_library() as _lib:
         mt = _lib.Model(d["counts"], d["X"], d["exposure"], 4, excl=np.array([3, 17], np.int32), device=0)
         try:
             ft = mt.fit_from_draws(dr)
@@ -234,8 +213,6 @@ def test_gene_batches_over_scratch_batches_give_the_same_bits(small_fit):
                 ft.close()
         finally:
             mt.close()
-    finally:
-        _lib.use_library(None)
     for what, res in one.items():
         for k, v in res.items():
             if isinstance(v, np.ndarray):

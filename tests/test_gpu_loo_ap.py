@@ -16,6 +16,7 @@ from tests import loo_predict_restate as R
 from tests import loo_restate as L
 from tests import psis_restate as P
 from tests.test_gpu_loo import _compare
+from tests.gpu_fixtures import testing_library
 from tests.test_gpu_psis import _bundled_frame
 
 pytestmark = pytest.mark.gpu
@@ -72,11 +73,9 @@ def test_fit_matches_restatement(small_advi):
 
 def test_gene_batches_of_the_fit_give_the_same_bits():
     """the gene table of the walk in batches of one gene (testing build: the bound is a test hook) against one batch"""
-    from ppcseq_amd import _lib, build
     from ppcseq_amd.synth import synth
     d = synth(30, 10, K=4, seed=5)
-    _lib.use_library(build.build_testing())
-    try:
+    with testing_library() as _lib:
         mt = _lib.Model(d["counts"], d["X"], d["exposure"], 4, excl=np.array(EXCL, np.int32), device=0)
         try:
             ft = mt.fit_advi(output_samples=1000, iter=2000, seed=3)
@@ -91,8 +90,6 @@ def test_gene_batches_of_the_fit_give_the_same_bits():
                 ft.close()
         finally:
             mt.close()
-    finally:
-        _lib.use_library(None)
     assert np.all(np.isfinite(base["elpd_loo"]))
     for k in L.FIELDS:
         assert np.array_equal(got[k], base[k], equal_nan=True), k
@@ -101,9 +98,7 @@ def test_gene_batches_of_the_fit_give_the_same_bits():
 
 
 def test_kernel_on_designed_columns():
-    from ppcseq_amd import _lib, build
-    _lib.use_library(build.build_testing())
-    try:
+    with testing_library() as _lib:
         for name, ll, a, excl in cases.designed():
             got = _lib.testing_loo_approx(ll[:, None], a, [int(excl)])[0]
             ref = np.array(A.loo_point(ll, a, excl))
@@ -128,14 +123,10 @@ def test_kernel_on_designed_columns():
                 assert np.array_equal(_lib.testing_loo_approx(ll, a, excl), one, equal_nan=True), n
             finally:
                 _lib.testing_set("loo_scratch_bytes", 0)
-    finally:
-        _lib.use_library(None)
 
 
 def test_predictive_kernel_on_designed_columns():
-    from ppcseq_amd import _lib, build
-    _lib.use_library(build.build_testing())
-    try:
+    with testing_library() as _lib:
         for name, ll, a, x, y, excl, p_lo, p_hi in cases.predictive():
             ref = A.predict_point(ll, a, x, y, excl, p_lo, p_hi)
             got = _lib.testing_loo_predict_approx(ll[:, None], a, x[:, None], [y], [int(excl)], p_lo, p_hi)[0]
@@ -159,8 +150,6 @@ def test_predictive_kernel_on_designed_columns():
                 _lib.testing_set("loo_scratch_bytes", 0)
         with pytest.raises(_lib.PpcxError, match="p_lo"):
             _lib.testing_loo_predict_approx(np.zeros((30, 1)), np.zeros(30), np.ones((30, 1)), [1], p_lo=0.5, p_hi=0.5)
-    finally:
-        _lib.use_library(None)
 
 
 def test_predictive_fit_matches_restatement(small_advi):

@@ -16,6 +16,7 @@ from tests import loo_exact_cases as cases
 from tests import loo_exact_restate as R
 from tests import psis_restate as P
 from tests.conftest import bundled_test_config
+from tests.gpu_fixtures import testing_library
 from tests.test_gpu_psis import _bundled_frame
 
 pytestmark = pytest.mark.gpu
@@ -48,10 +49,8 @@ def _hook(_lib, ll, eta, sg, y, **kw):
 
 
 def test_kernel_on_designed_columns(host):
-    from ppcseq_amd import _lib, build
-    _lib.use_library(build.build_testing())
     worst = [0.0]
-    try:
+    with testing_library() as _lib:
         for c in cases.designed():
             kw = dict(excluded=[int(c["excluded"])], log_ratio=c["lr"], truncation_compensation=c["tc"], p_lo=c["p_lo"], p_hi=c["p_hi"])
             if c["lr"] is None:
@@ -71,17 +70,13 @@ def test_kernel_on_designed_columns(host):
         for lo, hi in ((0.0, 0.9), (0.5, 0.5), (0.6, 0.4), (0.1, 1.0), (np.nan, 0.9)):
             with pytest.raises(_lib.PpcxError, match="p_lo"):
                 _lib.testing_loo_exact(np.zeros((30, 1)), np.zeros((30, 1)), np.zeros((30, 1)), [1], p_lo=lo, p_hi=hi)
-    finally:
-        _lib.use_library(None)
 
 
 @pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 4096, 4097, 9000])
 def test_kernel_lengths(host, n):
     """the ends of the workgroup's stride, the LDS / scratch hand-over, and the scratch in batches of two cells; NUTS weights
     with r_eff and an excluded cell, then the ADVI weights"""
-    from ppcseq_amd import _lib, build
-    _lib.use_library(build.build_testing())
-    try:
+    with testing_library() as _lib:
         ll, eta, sg, y, excl, r_eff, lr = cases.long_columns(n)
         kw = dict(truncation_compensation=R.TC, p_lo=R.P2, p_hi=1 - R.P2)
         for form in (dict(r_eff=r_eff), dict(log_ratio=lr)):
@@ -100,8 +95,6 @@ def test_kernel_lengths(host, n):
                 finally:
                     _lib.testing_set("loo_scratch_bytes", 0)
                 assert np.array_equal(again, one, equal_nan=True), list(form)
-    finally:
-        _lib.use_library(None)
 
 
 EXCL = (0 * 21 + 3, 2 * 21 + 20)                     # the two cells the model holds out
@@ -214,7 +207,6 @@ def test_advi_fit_matches_restatement(fits):
 
 
 def test_determinism_subsets_and_batches(fits):
-    from ppcseq_amd import _lib, build
     f = fits
     fit = f["nuts"]
     full = fit.loo_predict_exact(r_eff="auto")
@@ -231,8 +223,7 @@ def test_determinism_subsets_and_batches(fits):
         assert np.array_equal(arev[k], afull[k][::-1], equal_nan=True), k
     draws = fit.draws()
     n = draws.shape[0] * draws.shape[1]
-    _lib.use_library(build.build_testing())
-    try:
+    with testing_library() as _lib:
         mt = _lib.Model(f["counts"], f["X"], f["expo"], f["K"], excl=np.array(EXCL, np.int32), device=0)
         try:
             ft = mt.fit_from_draws(draws)
@@ -248,8 +239,6 @@ def test_determinism_subsets_and_batches(fits):
                 ft.close()
         finally:
             mt.close()
-    finally:
-        _lib.use_library(None)
     for g in got:
         for k in KEYS:
             assert np.array_equal(g[k], full[k], equal_nan=True), k

@@ -14,29 +14,9 @@ from tests import loo_mcse_cases as K
 from tests import loo_mcse_restate as R
 from tests import loo_restate as L
 from tests.conftest import bundled_test_config
+from tests.gpu_fixtures import small_fit, testing_lib, testing_library  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture
-def testing_lib():
-    """The testing build for one test that holds no Model or Fit of the product library"""
-    from ppcseq_amd import _lib, build
-    _lib.use_library(build.build_testing())
-    yield _lib
-    _lib.use_library(None)
-
-
-@pytest.fixture(scope="module")
-def small_fit():
-    from ppcseq_amd import _lib
-    from ppcseq_amd.synth import synth
-    d = synth(30, 10, K=4, seed=5)
-    m = _lib.Model(d["counts"], d["X"], d["exposure"], 4, excl=np.array([3, 10 + 7], np.int32), device=0)
-    f = m.fit_nuts(chains=4, iter=400, warmup=150, seed=3)
-    yield m, f, d
-    f.close()
-    m.close()
 
 
 # ---- 1. the kernel on designed columns
@@ -146,11 +126,9 @@ def test_fit_determinism_and_subsets(small_fit):
 
 
 def test_fit_batches_give_the_same_bits(small_fit):
-    from ppcseq_amd import _lib, build
     m, f, d = small_fit
     base, dr = f.loo(mcse=True), f.draws()
-    _lib.use_library(build.build_testing())
-    try:
+    with testing_library() as _lib:
         mt = _lib.Model(d["counts"], d["X"], d["exposure"], 4, excl=np.array([3, 17], np.int32), device=0)
         try:
             ft = mt.fit_from_draws(dr)
@@ -164,8 +142,6 @@ def test_fit_batches_give_the_same_bits(small_fit):
                 ft.close()
         finally:
             mt.close()
-    finally:
-        _lib.use_library(None)
     for k in R.FIELDS:
         assert np.array_equal(got[k], base[k], equal_nan=True), k
 

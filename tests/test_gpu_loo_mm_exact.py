@@ -16,6 +16,7 @@ import pytest
 
 from tests import loo_mm_cases as cases
 from tests import loo_mm_exact_restate as X
+from tests.gpu_fixtures import testing_library
 from tests.test_gpu_psis import _bundled_frame
 
 pytestmark = pytest.mark.gpu
@@ -118,10 +119,8 @@ def test_designed_cells_against_the_cpu_build(host):
 def test_draw_counts(host, n):
     """the ends of the workgroup's stride and the LDS / scratch hand-over; the scratch bound set so that the scratch path runs
     in batches of two cells (and the gene table in batches of two genes)"""
-    from ppcseq_amd import _lib, build
     ds = cases.prefix(checked_all(cases.long_set()), n)
-    _lib.use_library(build.build_testing())
-    try:
+    with testing_library() as _lib:
         h = _Held(ds)
         try:
             one = h.fit.loo_predict_exact_moment_match(k_threshold=0.7)     # (loo_threshold is not defined at one draw)
@@ -134,8 +133,6 @@ def test_draw_counts(host, n):
                 _lib.testing_set("loo_scratch_bytes", 0)
         finally:
             h.close()
-    finally:
-        _lib.use_library(None)
     for k in KEYS:
         assert np.array_equal(res[k], one[k], equal_nan=True), k       # the same bits however the work is batched
     for k in MM_KEYS:

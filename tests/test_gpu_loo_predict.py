@@ -13,6 +13,7 @@ import pytest
 
 from tests import loo_predict_cases as cases
 from tests import loo_predict_restate as R
+from tests.gpu_fixtures import testing_library
 from tests.test_gpu_psis import _bundled_frame
 
 pytestmark = pytest.mark.gpu
@@ -23,9 +24,7 @@ def _slice_doubles(n):
 
 
 def test_kernel_on_designed_columns():
-    from ppcseq_amd import _lib, build
-    _lib.use_library(build.build_testing())
-    try:
+    with testing_library() as _lib:
         for c in cases.designed():
             kw = dict(r_eff=c["r_eff"], excluded=c["excluded"], p_lo=c["p_lo"], p_hi=c["p_hi"])
             ref = R.point(c["ll"], c["x"], c["y"], **kw)
@@ -61,8 +60,6 @@ def test_kernel_on_designed_columns():
                 _lib.testing_set("loo_scratch_bytes", 0)
         with pytest.raises(_lib.PpcxError, match="p_lo"):
             _lib.testing_loo_predict(np.zeros((30, 1)), np.ones((30, 1)), [1], p_lo=0.5, p_hi=0.5)
-    finally:
-        _lib.use_library(None)
 
 
 @pytest.fixture(scope="module")
@@ -130,7 +127,6 @@ def test_khat_is_loo_s_and_fields_are_ordered(oracle_fit):
 
 
 def test_determinism_subsets_and_batches(oracle_fit):
-    from ppcseq_amd import _lib, build
     m, fit, f = oracle_fit
     a, b = fit.loo_predict(seed=3), fit.loo_predict(seed=3)
     sub = np.array([7, 0, 29, 4])
@@ -146,8 +142,7 @@ def test_determinism_subsets_and_batches(oracle_fit):
         assert np.array_equal(c[k], a[k], equal_nan=True), k
     assert not np.array_equal(fit.loo_predict(seed=4)["mean"], a["mean"])
     d = f["d"]
-    _lib.use_library(build.build_testing())
-    try:
+    with testing_library() as _lib:
         mt = _lib.Model(d["counts"], d["X"], d["exposure"], 4, excl=f["excl"], device=0)
         try:
             ft = mt.fit_from_draws(f["draws"])
@@ -161,8 +156,6 @@ def test_determinism_subsets_and_batches(oracle_fit):
                 ft.close()
         finally:
             mt.close()
-    finally:
-        _lib.use_library(None)
     for k in R.FIELDS:
         assert np.array_equal(got[k], a[k], equal_nan=True), k
 

@@ -18,6 +18,7 @@ import pytest
 
 from tests import math_edges as me
 from tests.emul_util import P
+from tests.gpu_fixtures import testing_library
 from tests.test_disp_table import _exact, _rows
 
 pytestmark = pytest.mark.gpu
@@ -28,12 +29,10 @@ LP_TOL, G_TOL = 1e-12, 1e-11
 
 @pytest.fixture(scope="module")
 def L():
-    from ppcseq_amd import _lib, build
-    _lib.use_library(build.build_testing())
-    if _lib.device_count() < 1:
-        pytest.fail("no HIP device visible: the product has no CPU fallback")
-    yield _lib
-    _lib.use_library(None)
+    with testing_library() as _lib:
+        if _lib.device_count() < 1:
+            pytest.fail("no HIP device visible: the product has no CPU fallback")
+        yield _lib
 
 
 # ---- 1. the building blocks ----------------------------------------------------------------------------------------------

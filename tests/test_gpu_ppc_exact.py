@@ -12,6 +12,7 @@ import pytest
 
 from tests import ppc_exact_restate as R
 from tests.conftest import bundled_test_config
+from tests.gpu_fixtures import testing_library
 from tests.test_gpu_psis import _bundled_frame
 
 pytestmark = pytest.mark.gpu
@@ -33,16 +34,12 @@ def _against_host(got, ref, what):
 
 
 def test_device_tails_match_the_cpu_build(host):
-    from ppcseq_amd import _lib, build
     y, mu, phi = R.tails_points()
     eta = np.log(mu)
     le, ge, _ = R.host_tails(host, y, eta, phi)
-    _lib.use_library(build.build_testing())
-    try:
+    with testing_library() as _lib:
         dle, dge = _lib.testing_eval_math("nb2_tails", eta, phi, y)
         bad = _lib.testing_eval_math("nb2_tails", [np.nan, 1.0, 1.0, np.inf], [1.0, 0.0, np.inf, 1.0], [3, 3, 3, 3])
-    finally:
-        _lib.use_library(None)
     err, ab = R.tails_errors(dle, dge, le, ge)
     print("largest error of the device against the CPU build", err.max(), "absolute", ab.max())
     assert not np.isnan(dle).any() and not np.isnan(dge).any()
@@ -52,9 +49,7 @@ def test_device_tails_match_the_cpu_build(host):
 
 
 def test_kernel_on_designed_columns(host):
-    from ppcseq_amd import _lib, build
-    _lib.use_library(build.build_testing())
-    try:
+    with testing_library() as _lib:
         for c in R.designed():
             kw = dict(excluded=c["excluded"], tc=c["tc"], p_lo=c["p_lo"], p_hi=c["p_hi"])
             ref, _ = R.host_cell(host, c["eta"], c["sg"], c["y"], **kw)
@@ -83,8 +78,6 @@ def test_kernel_on_designed_columns(host):
         for lo, hi in ((0.0, 0.9), (0.5, 0.5), (0.6, 0.4), (0.1, 1.0), (np.nan, 0.9)):
             with pytest.raises(_lib.PpcxError, match="p_lo"):
                 _lib.testing_ppc_exact(np.zeros((30, 1)), np.zeros((30, 1)), [1], p_lo=lo, p_hi=hi)
-    finally:
-        _lib.use_library(None)
 
 
 @pytest.fixture(scope="module")

@@ -9,6 +9,7 @@ import pytest
 
 from tests import psis_restate as R
 from tests.conftest import bundled_test_config
+from tests.gpu_fixtures import testing_library
 
 pytestmark = pytest.mark.gpu
 
@@ -99,9 +100,7 @@ def test_psis_matches_restatement(small, n):
 
 def test_kernel_on_known_shapes():
     """the kernel itself (testing build) on GPD and normal-ratio samples, beside columns of the restatement's kind"""
-    from ppcseq_amd import _lib, build
-    _lib.use_library(build.build_testing())
-    try:
+    with testing_library() as _lib:
         rng = np.random.default_rng(0)
         for k in (0.3, 0.5, 0.9):
             r = np.log(R.gpd_sample(rng, k, 100_000))
@@ -133,8 +132,6 @@ def test_kernel_on_known_shapes():
         for n in (224, 225, 4096, 4097):                                      # tail rules, the LDS path's limit
             r = R.normal_ratios(rng, 2.5, n)
             compare_khat(_lib.testing_psis(r)[0], R.khat(r), n)
-    finally:
-        _lib.use_library(None)
 
 
 def test_refusals(small):

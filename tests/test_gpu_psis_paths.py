@@ -5,6 +5,8 @@ import numpy as np
 import pytest
 
 from tests import psis_restate as R
+from tests.gpu_fixtures import testing_library
+
 pytestmark = pytest.mark.gpu
 
 
@@ -17,14 +19,12 @@ def compare_khat(got, ref, what):
 
 @pytest.fixture
 def testing_lib():
-    from ppcseq_amd import _lib, build
-    _lib.use_library(build.build_testing())
-    try:
-        yield _lib
-    finally:
-        for key in ("psis_slots", "psis_scratch_bytes"):
-            _lib.testing_set(key, 0)
-        _lib.use_library(None)
+    with testing_library() as _lib:
+        try:
+            yield _lib
+        finally:
+            for key in ("psis_slots", "psis_scratch_bytes"):
+                _lib.testing_set(key, 0)
 
 
 @pytest.mark.parametrize("n", [1000, 5000])

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from tests import reff_restate as E
+from tests.gpu_fixtures import small_fit, testing_library  # noqa: F401
 from tests.test_gpu_psis import _bundled_frame
 
 pytestmark = pytest.mark.gpu
@@ -23,22 +24,8 @@ def _compare(got, ref, what):
     assert err.max(initial=0.0) <= TOL, (what, err.max())
 
 
-@pytest.fixture(scope="module")
-def small_fit():
-    from ppcseq_amd import _lib
-    from ppcseq_amd.synth import synth
-    d = synth(30, 10, K=4, seed=5)
-    m = _lib.Model(d["counts"], d["X"], d["exposure"], 4, excl=np.array([3, 10 + 7], np.int32), device=0)
-    f = m.fit_nuts(chains=4, iter=400, warmup=150, seed=3)
-    yield m, f, d
-    f.close()
-    m.close()
-
-
 def test_kernel_on_the_host_checks_columns():
-    from ppcseq_amd import _lib, build
-    _lib.use_library(build.build_testing())
-    try:
+    with testing_library() as _lib:
         by_shape = {}
         for name, ll in list(E.seeded_cases()) + [(n, x) for n, x, _ in E.rule_cases()]:
             by_shape.setdefault(ll.shape, []).append((name, ll))
@@ -56,14 +43,10 @@ def test_kernel_on_the_host_checks_columns():
             if "underflow" in names:
                 a, b = got[names.index("underflow")], got[names.index("underflow shifted")]
                 assert np.isfinite(a) and abs(a - b) <= 1e-12 * abs(b), (a, b)
-    finally:
-        _lib.use_library(None)
 
 
 def test_kernel_beyond_the_lds_path_and_in_batches():
-    from ppcseq_amd import _lib, build
-    _lib.use_library(build.build_testing())
-    try:
+    with testing_library() as _lib:
         M, n = 2, 2100                                                         # 4 200 draws: the split values in global scratch
         rng = np.random.default_rng(8)
         cols = [-3.0 + E.ar1(rng, phi, M, n, 0.7) for phi in (0.0, 0.5, 0.9, -0.5, 0.3, 0.7, 0.95)]
@@ -77,8 +60,6 @@ def test_kernel_beyond_the_lds_path_and_in_batches():
             assert np.array_equal(_lib.testing_relative_eff(ll, M), one, equal_nan=True)
         finally:
             _lib.testing_set("loo_scratch_bytes", 0)
-    finally:
-        _lib.use_library(None)
 
 
 def test_fit_matches_restatement_and_is_deterministic(small_fit):

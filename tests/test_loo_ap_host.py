@@ -3,8 +3,6 @@ tests/loo_ap_host) against the numpy restatement (tests/loo_ap_restate.py), the 
 the approximation is exact and against a conjugate model's analytic leave-one-out density, and the refusals of the two flags."""
 import ctypes as C
 import math
-import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,23 +11,12 @@ from tests import loo_ap_cases as cases
 from tests import loo_ap_restate as A
 from tests import loo_restate as L
 from tests import psis_restate as P
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.host_build import host_lib
 
 
 def _host_lib():
-    here = os.path.join(ROOT, "tests", "loo_ap_host")
-    src = os.path.join(here, "loo_ap_host.cpp")
-    hdrs = [os.path.join(ROOT, "ppcseq_amd", "csrc", h)
-            for h in ("ppcx_math.h", "ppcx_disp.h", "ppcx_psis.h", "ppcx_loo.h", "ppcx_loo_predict.h", "ppcx_loo_ap.h")]
-    lib = os.path.join(here, "libloo_ap_host.so")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-o", lib, src])
-    h = C.CDLL(lib)
     dp = C.POINTER(C.c_double)
-    h.loo_ap_host_cell.argtypes = [dp, dp, C.c_long, C.c_int, dp]
-    h.loo_ap_host_cell.restype = None
-    return h
+    return host_lib("loo_ap", {"loo_ap_host_cell": ([dp, dp, C.c_long, C.c_int, dp], None)})
 
 
 @pytest.fixture(scope="module")

@@ -1,28 +1,16 @@
 """PSIS-LOO per cell without a GPU: the CPU build of the kernel's header (ppcseq_amd/csrc/ppcx_loo.h, tests/loo_host) against
 the numpy restatement (tests/loo_restate.py), the decisions of inference.loo_warnings and the refusals of check_loo."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import loo_restate as L
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.host_build import host_lib
 
 
 def _host_lib():
-    here = os.path.join(ROOT, "tests", "loo_host")
-    src = os.path.join(here, "loo_host.cpp")
-    hdrs = [os.path.join(ROOT, "ppcseq_amd", "csrc", h) for h in ("ppcx_math.h", "ppcx_disp.h", "ppcx_psis.h", "ppcx_loo.h")]
-    lib = os.path.join(here, "libloo_host.so")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-o", lib, src])
-    h = C.CDLL(lib)
-    h.loo_host_cell.argtypes = [C.POINTER(C.c_double), C.c_long, C.c_double, C.c_int, C.POINTER(C.c_double)]
-    h.loo_host_cell.restype = None
-    return h
+    return host_lib("loo", {"loo_host_cell": ([C.POINTER(C.c_double), C.c_long, C.c_double, C.c_int, C.POINTER(C.c_double)], None)})
 
 
 @pytest.fixture(scope="module")

@@ -7,7 +7,6 @@ restatement on the designed columns is 1.65e-14 (tests/loo_mcse_cases.py MCSE_ME
 ten times that, 1.65e-13."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -15,22 +14,12 @@ import pytest
 from tests import loo_mcse_cases as K
 from tests import loo_mcse_restate as R
 from tests import loo_restate as L
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.host_build import ROOT, host_lib
 
 
 def _host_lib():
-    here = os.path.join(ROOT, "tests", "loo_mcse_host")
-    src = os.path.join(here, "loo_mcse_host.cpp")
-    hdrs = [os.path.join(ROOT, "ppcseq_amd", "csrc", h)
-            for h in ("ppcx_math.h", "ppcx_disp.h", "ppcx_psis.h", "ppcx_summary.h", "ppcx_loo.h")]
-    lib = os.path.join(here, "libloo_mcse_host.so")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-o", lib, src])
-    h = C.CDLL(lib)
-    h.loo_mcse_host_cell.argtypes = [C.POINTER(C.c_double), C.c_long, C.c_double, C.c_int, C.POINTER(C.c_double)]
-    h.loo_mcse_host_cell.restype = None
-    return h
+    return host_lib("loo_mcse", {"loo_mcse_host_cell": ([C.POINTER(C.c_double), C.c_long, C.c_double, C.c_int, C.POINTER(C.c_double)],
+                                                        None)})
 
 
 @pytest.fixture(scope="module")

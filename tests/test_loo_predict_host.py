@@ -7,32 +7,19 @@ Tolerances: sums of weights 1e-12 max(1, |ref|); a quantile must lie between the
 1e-12 max(1, |ref|) + 1e-12 (v* - v-) / (F(v*) - F(v-)). Cells that loo_predict_restate.borderline marks are skipped for lower /
 upper only, at most 1 cell in 1 000 per test."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import loo_predict_cases as cases
 from tests import loo_predict_restate as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.host_build import host_lib
 
 
 def _host_lib():
-    here = os.path.join(ROOT, "tests", "loo_predict_host")
-    src = os.path.join(here, "loo_predict_host.cpp")
-    hdrs = [os.path.join(ROOT, "ppcseq_amd", "csrc", h) for h in ("ppcx_math.h", "ppcx_disp.h", "ppcx_psis.h", "ppcx_loo.h",
-                                                                  "ppcx_loo_predict.h")]
-    lib = os.path.join(here, "libloo_predict_host.so")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-o", lib, src])
-    h = C.CDLL(lib)
     dp = C.POINTER(C.c_double)
-    h.loo_predict_host_cell.argtypes = [dp, C.POINTER(C.c_int32), C.c_long, C.c_int, C.c_double, C.c_int, C.c_double,
-                                        C.c_double, dp]
-    h.loo_predict_host_cell.restype = None
-    return h
+    return host_lib("loo_predict", {"loo_predict_host_cell": ([dp, C.POINTER(C.c_int32), C.c_long, C.c_int, C.c_double, C.c_int,
+                                                               C.c_double, C.c_double, dp], None)})
 
 
 @pytest.fixture(scope="module")

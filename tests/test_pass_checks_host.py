@@ -10,7 +10,9 @@ from types import SimpleNamespace
 import numpy as np
 import pytest
 
-G, S, K = 6, 4, 2
+from tests import pass_standin as standin
+from tests.pass_standin import COUNTS, G, K, S, X
+
 ar = np.arange
 
 # option -> (InferenceResult field and attrs prefix, the pass it needs, the one read of the fit, the warnings it adds with the
@@ -75,96 +77,16 @@ class Recorder:
 def rec(monkeypatch):
     """_lib.Model / Fit replaced by stand-ins that log every call and return arrays of the right shape, with k-hats and R-hats
     poor enough for every warning"""
-    from ppcseq_amd import _lib
-    log = Recorder()
+    poor = standin.cells(khat=0.9)
 
-    class Fit:
-        def __init__(self, model, chains, n_keep):
-            self.model, self.chains, self.n_keep, self.iter = model, chains, n_keep, n_keep + 150
+    def summary(fit, cols, kw):
+        n = len(cols) + bool(kw["lp"])
+        return dict(rhat=np.full(n, 2.0), ess_bulk=np.full(n, 5.0), ess_tail=np.full(n, 5.0))
 
-        def cells(self, genes):
-            return (len(genes), self.model.S)
-
-        def ppc(self, *a, **kw):
-            log("ppc", *a, **kw)
-            ci = np.zeros((self.model.K, self.model.S, 4))
-            ci[..., 0], ci[..., 1], ci[..., 3] = 3.0, 1.0, 2.0             # every count lies above the interval
-            return (ci, np.zeros((1, self.model.K, self.model.S), np.int32)) if kw.get("return_counts_rng") else ci
-
-        def columns(self, cols):
-            log("columns", cols)
-            return np.ones((self.chains, self.n_keep, len(cols)))
-
-        def summary(self, cols, lp=True):
-            log("summary", cols, lp=lp)
-            n = len(cols) + bool(lp)
-            return dict(rhat=np.full(n, 2.0), ess_bulk=np.full(n, 5.0), ess_tail=np.full(n, 5.0))
-
-        def psis(self, cols, overall=True):
-            log("psis", cols, overall=overall)
-            return dict(khat=np.full(len(cols) + bool(overall), 0.9))
-
-        def loo(self, genes, **kw):
-            log("loo", genes, **kw)
-            return dict(khat=np.full(self.cells(genes), 0.9))
-
-        def loo_predict(self, genes, **kw):
-            log("loo_predict", genes, **kw)
-            return dict(khat=np.full(self.cells(genes), 0.9))
-
-        def loo_approximate_posterior(self, genes):
-            log("loo_approximate_posterior", genes)
-            return dict(khat=np.full(self.cells(genes), 0.9))
-
-        def loo_predict_approximate_posterior(self, genes, **kw):
-            log("loo_predict_approximate_posterior", genes, **kw)
-            return dict(khat=np.full(self.cells(genes), 0.9))
-
-        def ppc_exact(self, genes, **kw):
-            log("ppc_exact", genes, **kw)
-            return dict(lower=np.zeros(self.cells(genes)))
-
-        def diagnostics(self):
-            log("diagnostics")
-            return dict(divergent=np.ones((self.chains, self.iter), np.int32), treedepth=np.full((self.chains, self.iter), 10))
-
-        def advi_info(self):
-            log("advi_info")
-            return dict(iterations=1, converged=True, elbo=0.0, eta=1.0)
-
-        def close(self):
-            log("fit.close")
-
-    class Model:
-        def __init__(self, counts, X, exposure_rate, K, **kw):
-            self.G, self.S = np.shape(counts)
-            self.K = int(K)
-            log("Model", (self.G, self.S), self.K, **kw)
-
-        def set_exclusions(self, excl):
-            log("set_exclusions", np.asarray(excl))
-
-        def set_launch(self, *a):
-            log("set_launch", *a)
-
-        def fit_nuts(self, **kw):
-            log("fit_nuts", **kw)
-            return Fit(self, kw["chains"], kw["iter"] - kw["warmup"])
-
-        def fit_advi(self, **kw):
-            log("fit_advi", **kw)
-            return Fit(self, 1, kw["output_samples"])
-
-        def fit_from_draws(self, draws):
-            log("fit_from_draws", np.shape(draws))
-            return Fit(self, draws.shape[0], draws.shape[1])
-
-        def close(self):
-            log("model.close")
-
-    monkeypatch.setattr(_lib, "Model", Model)
-    monkeypatch.setattr(_lib, "device_memory", lambda device=0: (1 << 40, 1 << 40))
-    return log
+    return standin.install(monkeypatch, log=Recorder(), poor_sampler=True, reads=dict(
+        summary=summary, psis=lambda fit, cols, kw: dict(khat=np.full(len(cols) + bool(kw["overall"]), 0.9)),
+        loo=poor, loo_predict=poor, loo_approximate_posterior=poor, loo_predict_approximate_posterior=poor,
+        ppc_exact=standin.cells(lower=0.0)))
 
 
 def reads(o, advi, **ctx):
@@ -190,18 +112,12 @@ def split(calls, first, last="fit.close"):
     return calls[:i], calls[i:j], calls[j:]
 
 
-COUNTS = np.random.default_rng(0).integers(5, 50, size=(G, S)).astype(np.int32)
-X = np.stack([np.ones(S), np.array([0.0, 1.0, 0.0, 1.0])], axis=1)
-PASS = dict(how_many_posterior_draws=300, cores=3, seed=7, launch=(8, 0), adj_prob_theshold=0.05, truncation_compensation=0.7,
-            to_exclude=np.array([1, 5, 20]))
+PASS = dict(standin.PASS, to_exclude=np.array([1, 5, 20]))
 
 
 def run_pass(rec, o, n_checked=K, **kw):
-    from ppcseq_amd.inference import do_inference
     del rec.calls[:]
-    with warnings.catch_warnings(record=True) as w:
-        warnings.simplefilter("always")
-        res = do_inference(COUNTS, X, np.zeros(S), n_checked, **PASS, **kw, **o)
+    res, w = standin.run_pass(n_checked, **PASS, **kw, **o)
     assert all(x.category is RuntimeWarning for x in w)
     return res, w
 

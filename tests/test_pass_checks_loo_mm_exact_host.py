@@ -9,85 +9,18 @@ import warnings
 import numpy as np
 import pytest
 
-G, S, K = 6, 4, 2
-COUNTS = np.random.default_rng(0).integers(5, 50, size=(G, S)).astype(np.int32)
-X = np.stack([np.ones(S), np.array([0.0, 1.0, 0.0, 1.0])], axis=1)
-PASS = dict(how_many_posterior_draws=300, cores=3, seed=7, launch=(8, 0), adj_prob_theshold=0.05, truncation_compensation=0.7)
+from tests import pass_standin as standin
+from tests.pass_standin import COUNTS, G, K, PASS, S, X, run_pass as _pass
+
 INTERVAL = dict(p_lo=0.05, p_hi=1 - 0.05, truncation_compensation=0.7)      # the pass's adj_prob_theshold and compensation
 
 
 @pytest.fixture
 def rec(monkeypatch):
     """_lib.Model / Fit replaced by stand-ins that log the reads of exact_loo_intervals and check_loo"""
-    from ppcseq_amd import _lib
-    log = []
-
-    class Fit:
-        def __init__(self, model, chains, n_keep):
-            self.model, self.chains, self.n_keep, self.iter = model, chains, n_keep, n_keep + 150
-
-        def ppc(self, *a, **kw):
-            ci = np.zeros((self.model.K, self.model.S, 4))
-            ci[..., 0], ci[..., 1], ci[..., 3] = 3.0, 1.0, 2.0
-            return ci
-
-        def columns(self, cols):
-            return np.ones((self.chains, self.n_keep, len(cols)))
-
-        def _read(self, name, genes, kw, **more):
-            log.append((name, np.asarray(genes).tolist(), kw))
-            return dict(khat=np.full((len(genes), self.model.S), 0.3), **more)
-
-        def loo(self, genes, **kw):
-            return self._read("loo", genes, kw)
-
-        def loo_moment_match(self, genes, **kw):
-            return self._read("loo_moment_match", genes, kw)
-
-        def loo_predict_exact(self, genes, **kw):
-            return self._read("loo_predict_exact", genes, kw)
-
-        def loo_predict_exact_moment_match(self, genes, **kw):
-            return self._read("loo_predict_exact_moment_match", genes, kw, khat_before=np.full((len(genes), self.model.S), 0.9))
-
-        def diagnostics(self):
-            return dict(divergent=np.zeros((self.chains, self.iter), np.int32), treedepth=np.full((self.chains, self.iter), 3))
-
-        def close(self):
-            pass
-
-    class Model:
-        def __init__(self, counts, X, exposure_rate, K, **kw):
-            self.G, self.S = np.shape(counts)
-            self.K = int(K)
-
-        def set_exclusions(self, excl):
-            pass
-
-        def set_launch(self, *a):
-            pass
-
-        def fit_nuts(self, **kw):
-            return Fit(self, kw["chains"], kw["iter"] - kw["warmup"])
-
-        def fit_from_draws(self, draws):
-            log.append(("fit_from_draws",))
-            return Fit(self, draws.shape[0], draws.shape[1])
-
-        def close(self):
-            pass
-
-    monkeypatch.setattr(_lib, "Model", Model)
-    monkeypatch.setattr(_lib, "device_memory", lambda device=0: (1 << 40, 1 << 40))
-    return log
-
-
-def _pass(**kw):
-    from ppcseq_amd.inference import do_inference
-    with warnings.catch_warnings(record=True) as w:
-        warnings.simplefilter("always")
-        res = do_inference(COUNTS, X, np.zeros(S), K, **PASS, **kw)
-    return res, w
+    good = standin.cells(khat=0.3)
+    return standin.install(monkeypatch, dict(loo=good, loo_moment_match=good, loo_predict_exact=good,
+                                             loo_predict_exact_moment_match=standin.cells(khat=0.3, khat_before=0.9)))
 
 
 def _same(log, expect):

@@ -2,28 +2,16 @@
 (ppcseq_amd/csrc/ppcx_psis.h, tests/psis_host) on cases with known answers, the header against the restatement, and the
 decisions of inference.approximation_warnings."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import psis_restate as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.host_build import host_lib
 
 
 def _host_lib():
-    here = os.path.join(ROOT, "tests", "psis_host")
-    src = os.path.join(here, "psis_host.cpp")
-    hdrs = [os.path.join(ROOT, "ppcseq_amd", "csrc", h) for h in ("ppcx_math.h", "ppcx_psis.h")]
-    lib = os.path.join(here, "libpsis_host.so")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-o", lib, src])
-    h = C.CDLL(lib)
-    h.psis_host_khat.argtypes = [C.POINTER(C.c_double), C.c_long]
-    h.psis_host_khat.restype = C.c_double
-    return h
+    return host_lib("psis", {"psis_host_khat": ([C.POINTER(C.c_double), C.c_long], C.c_double)})
 
 
 def host_khat(h, v):

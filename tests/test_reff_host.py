@@ -2,28 +2,16 @@
 tests/reff_host) against the numpy restatement (tests/reff_restate.py), the NaN rules, loose known answers, and the refusals of
 loo_r_eff."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import reff_restate as E
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.host_build import host_lib
 
 
 def _host_lib():
-    here = os.path.join(ROOT, "tests", "reff_host")
-    src = os.path.join(here, "reff_host.cpp")
-    hdrs = [os.path.join(ROOT, "ppcseq_amd", "csrc", h) for h in ("ppcx_math.h", "ppcx_summary.h", "ppcx_reff.h")]
-    lib = os.path.join(here, "libreff_host.so")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-o", lib, src])
-    h = C.CDLL(lib)
-    h.reff_host_cell.argtypes = [C.POINTER(C.c_double), C.c_int, C.c_int]
-    h.reff_host_cell.restype = C.c_double
-    return h
+    return host_lib("reff", {"reff_host_cell": ([C.POINTER(C.c_double), C.c_int, C.c_int], C.c_double)})
 
 
 @pytest.fixture(scope="module")

@@ -2,15 +2,12 @@
 the CPU build of the kernel's header (ppcseq_amd/csrc/ppcx_summary.h, tests/summary_host) against it, and the decisions of
 inference.convergence_warnings."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from tests import summary_restate as R
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.host_build import host_lib
 
 
 def ar1(rng, M, n, phi):
@@ -91,19 +88,9 @@ def impl(request):
 
 
 def _host_lib():
-    here = os.path.join(ROOT, "tests", "summary_host")
-    src = os.path.join(here, "summary_host.cpp")
-    hdrs = [os.path.join(ROOT, "ppcseq_amd", "csrc", h) for h in ("ppcx_math.h", "ppcx_summary.h")]
-    lib = os.path.join(here, "libsummary_host.so")
-    if not os.path.exists(lib) or os.path.getmtime(lib) < max(os.path.getmtime(p) for p in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden", "-o", lib, src])
-    h = C.CDLL(lib)
     dp = C.POINTER(C.c_double)
-    h.summary_host_column.argtypes = [dp, C.c_int, C.c_int, dp, dp]
-    h.summary_host_column.restype = None
-    h.summary_host_ndtri.argtypes = [C.c_double]
-    h.summary_host_ndtri.restype = C.c_double
-    return h
+    return host_lib("summary", {"summary_host_column": ([dp, C.c_int, C.c_int, dp, dp], None),
+                                "summary_host_ndtri": ([C.c_double], C.c_double)})
 
 
 def host_column(h, x):
