@@ -182,7 +182,8 @@ PPCX_API int ppcx_fit_loo_mcse(ppcx_fit* f, int n_genes, const int32_t* genes, c
  * the paper, not run against R. Per cell above the threshold, at most max_iters times: the draws of the gene are shifted to their
  * weighted mean, or, if that does not lower khat, shifted and scaled to their weighted mean and variance; a step is kept only if
  * the cell's PSIS khat on the new ratios is strictly lower. No covariance step (loo's default), no split transformation: a
- * matched khat is necessary, not sufficient, and no mcse / n_eff is given for a matched cell.
+ * matched khat is necessary, not sufficient (ppcx_fit_loo_moment_match_split below adds the split transformation), and no
+ * mcse / n_eff is given for a matched cell.
  * Fits, genes, r_eff, limits and refusals as ppcx_fit_loo (an ADVI fit: PPCX_ERR_ARG, moment matching under the weights of
  * loo_approximate_posterior is not available); also PPCX_ERR_ARG for a k_threshold that is not finite or max_iters < 0.
  * out [n_genes][S][PPCX_LOO_MM_FIELDS(C)]: elpd_loo, p_loo (lpd of the original draws - elpd_loo), looic, khat (the final one),
@@ -194,6 +195,25 @@ PPCX_API int ppcx_fit_loo_mcse(ppcx_fit* f, int n_genes, const int32_t* genes, c
 #define PPCX_LOO_MM_FIELDS(C) (6 + 2 * ((C) + 1))
 PPCX_API int ppcx_fit_loo_moment_match(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double k_threshold,
                                        int max_iters, double* out);
+/* ppcx_fit_loo_moment_match with the split transformation of Paananen et al. (2021, section 4; loo:::loo_moment_match_split, the
+ * default of loo::loo_moment_match) on the cells it has matched (iterations > 0). The matched draws are no longer a sample of a
+ * known density, so the matched estimate is biased; the split estimator transforms only the first h = n / 2 draws in the fit's
+ * order (whole leading chains, as loo takes them), keeps the others, and weights all of them against the two-component mixture
+ * they come from: draw i at its proposal point x_i (scale * draw_i + shift for i < h, draw_i from h on) has the log ratio
+ * q(x_i) - log_lik(x_i) - logaddexp(q(x_i), q(T^-1 x_i) - sum log scale), q the gene's local log density; the terms of the log
+ * posterior outside the gene are the same in both components and cancel, so a ppcx_fit_from_draws fit is served. PSIS runs on
+ * these ratios as on a candidate of the matching; elpd_loo, p_loo (lpd of the original draws - elpd_loo) and looic are taken
+ * under its weights. Restated from the paper and the published package; not run against R.
+ * Fits, genes, r_eff, k_threshold, max_iters, limits and refusals as ppcx_fit_loo_moment_match (an ADVI fit: PPCX_ERR_ARG).
+ * out [n_genes][S][PPCX_LOO_MM_SPLIT_FIELDS(C)]: ppcx_fit_loo_moment_match's record with elpd_loo, p_loo and looic the split
+ * ones -- khat stays the matching's final one, as loo reports it, and khat_before, iterations, scale and shift are that entry's
+ * bits -- then elpd_loo_matched (that entry's elpd_loo) and khat_split (the k-hat of the split ratios: a diagnostic, not a gate;
+ * NaN for a cell with iterations = 0). A cell with iterations = 0 holds ppcx_fit_loo_moment_match's record bit for bit. A cell
+ * none of whose split ratios is finite: elpd_loo, p_loo, looic and khat_split are NaN. No covariance step, no mcse / n_eff of a
+ * matched cell. The same bits on every call, for any gene subset.                                                              */
+#define PPCX_LOO_MM_SPLIT_FIELDS(C) (PPCX_LOO_MM_FIELDS(C) + 2)
+PPCX_API int ppcx_fit_loo_moment_match_split(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double k_threshold,
+                                             int max_iters, double* out);
 /* The relative efficiency of the importance ratios per observed cell of a NUTS fit: what rstan::loo(fit) passes to loo::loo as
  * r_eff, loo::relative_eff(exp(log_lik), chain_id), so that ppcx_fit_loo / ppcx_fit_loo_predict with it report what rstan::loo(fit)
  * does without the log-likelihood matrix ever leaving the device. Fits, genes and refusals as ppcx_fit_loo; more than 128 chains:
@@ -307,7 +327,7 @@ PPCX_API int ppcx_fit_loo_predict_exact_approx(ppcx_fit* f, int n_genes, const i
  * Genes (checked ones), r_eff, probabilities, truncation compensation, limits and refusals as ppcx_fit_loo_predict_exact;
  * k_threshold and max_iters as ppcx_fit_loo_moment_match (PPCX_ERR_ARG for a k_threshold that is not finite or max_iters < 0).
  * An ADVI fit: PPCX_ERR_ARG; a ppcx_fit_from_draws fit is served. No covariance step, no split transformation: a matched khat
- * is necessary, not sufficient. Synchronous on the model's stream; the same bits on every call, for any gene subset.
+ * is necessary, not sufficient (ppcx_fit_loo_predict_exact_moment_match_split below adds the split). Synchronous on the model's stream; the same bits on every call, for any gene subset.
  *   out [n_genes][S][PPCX_LOO_MM_EXACT_FIELDS(C)]: the ten fields of ppcx_fit_loo_predict_exact with khat the final one, then
  *   khat_before (plain PSIS's), iterations (accepted steps), scale[C + 1] and shift[C + 1] as ppcx_fit_loo_moment_match.
  *   A cell with iterations = 0 (excluded, NaN, at or below the threshold, max_iters = 0, or no step accepted) holds
@@ -318,6 +338,18 @@ PPCX_API int ppcx_fit_loo_predict_exact_approx(ppcx_fit* f, int n_genes, const i
 PPCX_API int ppcx_fit_loo_predict_exact_moment_match(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff,
                                                      double k_threshold, int max_iters, double truncation_compensation,
                                                      double p_lo, double p_hi, double* out);
+/* ppcx_fit_loo_predict_exact_moment_match with the split transformation (ppcx_fit_loo_moment_match_split) on the cells it has
+ * matched: the weights are the normalised PSIS weights of the split ratios, and eta_i, phi_i of the negative binomials are
+ * evaluated at the proposal points x_i -- scale * draw_i + shift for the first h = n / 2 draws in the fit's order, draw_i from h
+ * on. Arguments, limits and refusals as ppcx_fit_loo_predict_exact_moment_match.
+ *   out [n_genes][S][PPCX_LOO_MM_EXACT_SPLIT_FIELDS(C)]: that entry's record with the first nine fields under the split weights and
+ *   khat the matching's final one, then khat_split (NaN for a cell with iterations = 0, which holds that entry's record bit for
+ *   bit). A proposal point with invalid parameters, or no finite split ratio: every statistic of the cell is NaN, khat and
+ *   khat_split included. The same bits on every call, for any gene subset.                                                     */
+#define PPCX_LOO_MM_EXACT_SPLIT_FIELDS(C) (PPCX_LOO_MM_EXACT_FIELDS(C) + 1)
+PPCX_API int ppcx_fit_loo_predict_exact_moment_match_split(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff,
+                                                           double k_threshold, int max_iters, double truncation_compensation,
+                                                           double p_lo, double p_hi, double* out);
 /* lp: [chains][n_keep]; the rest [chains][iter] (warmup included); any pointer may be NULL */
 PPCX_API int ppcx_fit_get_diagnostics(ppcx_fit* f, double* lp, double* stepsize, int32_t* treedepth,
                              int32_t* n_leapfrog, int32_t* divergent, double* accept);

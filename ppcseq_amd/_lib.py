@@ -27,7 +27,7 @@ EXPORTS = [
     "ppcx_fit_get_approximation", "ppcx_fit_get_log_ratios", "ppcx_fit_psis", "ppcx_fit_get_log_lik", "ppcx_fit_loo",
     "ppcx_fit_loo_predict", "ppcx_fit_relative_eff", "ppcx_fit_loo_mcse", "ppcx_fit_loo_approx", "ppcx_fit_loo_predict_approx",
     "ppcx_fit_ppc_exact", "ppcx_fit_loo_predict_exact", "ppcx_fit_loo_predict_exact_approx", "ppcx_fit_loo_moment_match",
-    "ppcx_fit_loo_predict_exact_moment_match",
+    "ppcx_fit_loo_predict_exact_moment_match", "ppcx_fit_loo_moment_match_split", "ppcx_fit_loo_predict_exact_moment_match_split",
 ]
 ABI_VERSION = 400           # include/ppcx.h PPCX_VERSION this binding was written for
 SUMMARY_FIELDS = ("mean", "sd", "q05", "q50", "q95", "rhat", "ess_bulk", "ess_tail")   # PPCX_SUMMARY_FIELDS, in order
@@ -37,6 +37,7 @@ LOO_PREDICT_FIELDS = ("mean", "lower", "upper", "pit_lt", "pit_le", "khat")     
 PPC_EXACT_FIELDS = ("mean", "sd", "p_le", "p_ge", "lower", "upper", "y", "excluded", "outside")   # PPCX_PPC_EXACT_FIELDS, in order
 LOO_EXACT_FIELDS = PPC_EXACT_FIELDS + ("khat",)                                          # PPCX_LOO_EXACT_FIELDS, in order
 LOO_MM_HEAD = LOO_FIELDS + ("khat_before", "iterations")     # PPCX_LOO_MM_FIELDS(C): these, then scale[C + 1] and shift[C + 1]
+LOO_MM_SPLIT_TAIL = ("elpd_loo_matched", "khat_split")       # PPCX_LOO_MM_SPLIT_FIELDS(C): PPCX_LOO_MM_FIELDS(C), then these
 
 
 class PpcxError(RuntimeError):
@@ -111,6 +112,7 @@ def load() -> C.CDLL:
     lib.ppcx_fit_loo.argtypes = [C.c_void_p, C.c_int, ip, dp, dp]
     lib.ppcx_fit_loo_mcse.argtypes = [C.c_void_p, C.c_int, ip, dp, dp]
     lib.ppcx_fit_loo_moment_match.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_double, C.c_int, dp]
+    lib.ppcx_fit_loo_moment_match_split.argtypes = lib.ppcx_fit_loo_moment_match.argtypes
     lib.ppcx_fit_loo_predict.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_double, C.c_double, C.c_double, C.c_ulonglong, dp]
     lib.ppcx_fit_relative_eff.argtypes = [C.c_void_p, C.c_int, ip, dp]
     lib.ppcx_fit_loo_approx.argtypes = [C.c_void_p, C.c_int, ip, dp]
@@ -120,6 +122,7 @@ def load() -> C.CDLL:
     lib.ppcx_fit_loo_predict_exact_approx.argtypes = [C.c_void_p, C.c_int, ip, C.c_double, C.c_double, C.c_double, dp]
     lib.ppcx_fit_loo_predict_exact_moment_match.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_double, C.c_int, C.c_double, C.c_double,
                                                             C.c_double, dp]
+    lib.ppcx_fit_loo_predict_exact_moment_match_split.argtypes = lib.ppcx_fit_loo_predict_exact_moment_match.argtypes
     lib.ppcx_fit_get_diagnostics.argtypes = [C.c_void_p, dp, dp, ip, ip, ip, dp]
     lib.ppcx_fit_get_timing.argtypes = [C.c_void_p, dp, C.POINTER(C.c_longlong), dp, C.POINTER(C.c_longlong), dp]
     lib.ppcx_fit_get_kernel_times.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(C.c_longlong)]
@@ -819,7 +822,7 @@ class Fit:
             res["mcse_elpd_loo_total"] = loo_mcse_total(res)
         return res
 
-    def loo_moment_match(self, genes=None, r_eff=None, k_threshold=None, max_iters=30):
+    def loo_moment_match(self, genes=None, r_eff=None, k_threshold=None, max_iters=30, split=False):
         """Fit.loo with gene-local moment matching of the cells whose khat exceeds k_threshold (ppcx_fit_loo_moment_match; the
         importance-weighted moment matching of loo::loo_moment_match, applied to the coordinates of the cell's own gene only --
         a deliberate deviation, restated from the paper and not run against R): Fit.loo's dict with `estimates` over the new
@@ -827,14 +830,23 @@ class Fit:
         and `shift` [n_genes, S, C + 1] (the matched draws of the gene are scale * draw + shift, rows intercept, slopes,
         sigma_raw; 1 and 0 for a row the gene does not have) and `k_threshold`. A cell with iterations == 0 holds Fit.loo's
         bits. k_threshold=None: inference.loo_threshold(n_draws). There is no covariance step and no split transformation: a
-        matched khat is necessary, not sufficient; no mcse / n_eff. Not for an ADVI fit. r_eff as Fit.loo."""
+        matched khat is necessary, not sufficient; no mcse / n_eff. Not for an ADVI fit. r_eff as Fit.loo.
+        split=True (ppcx_fit_loo_moment_match_split): the split transformation of loo::loo_moment_match on the matched cells --
+        the first n_draws // 2 draws in the fit's order (whole leading chains) are transformed, the others kept, and all are
+        weighted against the mixture they come from, so elpd_loo, p_loo, looic and `estimates` no longer rest on the matched
+        draws being a sample of a known density. `khat`, `khat_before`, `iterations`, `scale` and `shift` stay the matching's
+        bits; added are `elpd_loo_matched` (the elpd_loo of split=False) and `khat_split` (the k-hat of the split ratios, a
+        diagnostic, NaN where iterations == 0)."""
         if k_threshold is None:
             from .inference import loo_threshold
             k_threshold = loo_threshold(self.chains * self.n_keep)
         k_threshold, max_iters = float(k_threshold), int(max_iters)
         nc = self.model.C + 1
         fields = LOO_MM_HEAD + tuple(f"scale{c}" for c in range(nc)) + tuple(f"shift{c}" for c in range(nc))
-        _, res, last = self._loo_cells(genes, r_eff, fields, lambda n, g, re, out: load().ppcx_fit_loo_moment_match(
+        if split:
+            fields = fields + LOO_MM_SPLIT_TAIL
+        entry = load().ppcx_fit_loo_moment_match_split if split else load().ppcx_fit_loo_moment_match
+        _, res, last = self._loo_cells(genes, r_eff, fields, lambda n, g, re, out: entry(
             self._h, n, g, re, k_threshold, max_iters, out))
         for name in ("scale", "shift"):
             res[name] = np.stack([res.pop(f"{name}{c}") for c in range(nc)], axis=-1)
@@ -933,7 +945,7 @@ class Fit:
             self._h, n, g, re, float(truncation_compensation), float(p_lo), float(p_hi), out))
 
     def loo_predict_exact_moment_match(self, genes=None, r_eff=None, k_threshold=None, max_iters=30, p_lo=0.025, p_hi=0.975,
-                                       truncation_compensation=1.0):
+                                       truncation_compensation=1.0, split=False):
         """Fit.loo_predict_exact with gene-local moment matching of the cells whose khat exceeds k_threshold
         (ppcx_fit_loo_predict_exact_moment_match): the outlying cells, whose plain PSIS weights are not to be trusted, are matched
         as Fit.loo_moment_match matches them, and their predictive is importance sampling with the matched draws as the proposal
@@ -941,7 +953,11 @@ class Fit:
         nothing is sampled. Fit.loo_predict_exact's dict (`khat` is the final one), plus Fit.loo_moment_match's `khat_before`,
         `iterations` (int64), `scale` and `shift` [n_genes, S, C + 1] (the same bits as that method's) and `k_threshold`. A cell
         with iterations == 0 holds Fit.loo_predict_exact's bits. k_threshold=None: inference.loo_threshold(n_draws). No covariance
-        step and no split transformation: a matched khat is necessary, not sufficient. Not for an ADVI fit."""
+        step and no split transformation: a matched khat is necessary, not sufficient. Not for an ADVI fit.
+        split=True (ppcx_fit_loo_predict_exact_moment_match_split): the split transformation as in Fit.loo_moment_match -- the
+        negative binomials are evaluated at the matched draws for the first n_draws // 2 draws in the fit's order and at the
+        original draws for the others, under the PSIS weights of the split ratios. `khat` and the matching's record stay its
+        bits; added is `khat_split` (NaN where iterations == 0)."""
         if k_threshold is None:
             from .inference import loo_threshold
             k_threshold = loo_threshold(self.chains * self.n_keep)
@@ -954,9 +970,12 @@ class Fit:
             res["scale"] = more[..., 2:2 + nc].copy()
             res["shift"] = more[..., 2 + nc:2 + 2 * nc].copy()
             res["k_threshold"] = k_threshold
-        return self._loo_exact(genes, r_eff, lambda n, g, re, out: load().ppcx_fit_loo_predict_exact_moment_match(
+            if split:
+                res["khat_split"] = more[..., 2 + 2 * nc].copy()
+        entry = load().ppcx_fit_loo_predict_exact_moment_match_split if split else load().ppcx_fit_loo_predict_exact_moment_match
+        return self._loo_exact(genes, r_eff, lambda n, g, re, out: entry(
             self._h, n, g, re, k_threshold, max_iters, float(truncation_compensation), float(p_lo), float(p_hi), out),
-            more=2 + 2 * nc, tail=tail)
+            more=2 + 2 * nc + (1 if split else 0), tail=tail)
 
     def loo_predict_exact_approximate_posterior(self, genes=None, p_lo=0.025, p_hi=0.975, truncation_compensation=1.0):
         """Fit.loo_predict_exact for an ADVI fit (ppcx_fit_loo_predict_exact_approx): the same dict (without r_eff) under the

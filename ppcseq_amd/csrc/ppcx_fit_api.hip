@@ -168,6 +168,21 @@ extern "C" int ppcx_fit_loo_moment_match(ppcx_fit* f, int n_genes, const int32_t
   if (rc != PPCX_OK) return rc;
   return hip_done(who, loo_mm_fit_cells(fc, k_threshold, max_iters, out, loo_scratch_bytes(), f->m->stream.s));
 }
+// ... with the split transformation of the matched cells (ppcx_loo_mm_split.h): the same checks, the matching's kernels, then the split
+extern "C" int ppcx_fit_loo_moment_match_split(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double k_threshold,
+                                               int max_iters, double* out) {
+  const char* who = "ppcx_fit_loo_moment_match_split";
+  if (f && f->advi)
+    return fail(PPCX_ERR_ARG, std::string(who) + " needs the draws of a NUTS fit: moment matching under the weights of an ADVI fit "
+                                                 "(loo_approximate_posterior) is not available");
+  if (!isfinite(k_threshold)) return fail(PPCX_ERR_ARG, std::string(who) + ": k_threshold must be finite");
+  if (max_iters < 0) return fail(PPCX_ERR_ARG, std::string(who) + ": max_iters must be >= 0");
+  std::vector<int> yenc; FitCells fc;
+  int rc = loo_prepare(f, n_genes, genes, out, yenc, fc);
+  if (rc == PPCX_OK) rc = loo_fit_reff(who, fc, r_eff);
+  if (rc != PPCX_OK) return rc;
+  return hip_done(who, loo_mm_split_fit_cells(fc, k_threshold, max_iters, false, 1.0, 0.0, 1.0, out, loo_scratch_bytes(), f->m->stream.s));
+}
 // ---- the leave-one-out predictive interval and LOO-PIT of the same cells (loo::E_loo / bayesplot::ppc_loo_intervals, ppc_loo_pit)
 static int loo_predict_check_probs(double p_lo, double p_hi) {
   if (!(p_lo >= 0.0 && p_lo < p_hi && p_hi <= 1.0)) return fail(PPCX_ERR_ARG, "need 0 <= p_lo < p_hi <= 1");
@@ -362,6 +377,24 @@ extern "C" int ppcx_fit_loo_predict_exact_moment_match(ppcx_fit* f, int n_genes,
   if ((rc = loo_fit_reff(who, fc, r_eff)) != PPCX_OK) return rc;
   return hip_done(who, loo_mm_exact_fit_cells(fc, k_threshold, max_iters, truncation_compensation, p_lo, p_hi, out, loo_scratch_bytes(),
                                               f->m->stream.s));
+}
+// ... and with the split transformation of the matched cells (ppcx_loo_mm_split.h step 8)
+extern "C" int ppcx_fit_loo_predict_exact_moment_match_split(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff,
+                                                             double k_threshold, int max_iters, double truncation_compensation,
+                                                             double p_lo, double p_hi, double* out) {
+  const char* who = "ppcx_fit_loo_predict_exact_moment_match_split";
+  if (!f) return fail(PPCX_ERR_ARG, "fit is NULL");
+  if (f->advi) return fail(PPCX_ERR_ARG, std::string(who) + " needs the draws of a NUTS fit: moment matching under the weights of an "
+                                                             "ADVI fit (loo_approximate_posterior) is not available");
+  if (!isfinite(k_threshold)) return fail(PPCX_ERR_ARG, std::string(who) + ": k_threshold must be finite");
+  if (max_iters < 0) return fail(PPCX_ERR_ARG, std::string(who) + ": max_iters must be >= 0");
+  int rc = loo_exact_check(f, n_genes, genes, truncation_compensation, p_lo, p_hi);
+  if (rc != PPCX_OK) return rc;
+  std::vector<int> yenc; FitCells fc;
+  if ((rc = loo_prepare_cells(f, n_genes, genes, out, yenc, fc)) != PPCX_OK) return rc;
+  if ((rc = loo_fit_reff(who, fc, r_eff)) != PPCX_OK) return rc;
+  return hip_done(who, loo_mm_split_fit_cells(fc, k_threshold, max_iters, true, truncation_compensation, p_lo, p_hi, out,
+                                              loo_scratch_bytes(), f->m->stream.s));
 }
 #ifdef PPCX_TESTING
 // testing build only (ppcx_testing.h): the kernel of the two above on host-given columns, on the current device

@@ -309,6 +309,12 @@ hipError_t loo_mm_fit_cells(const FitCells& fc, double k_threshold, int max_iter
 // (24 bytes per draw) in LDS up to kPsisLdsDraws draws, beyond that in the scratch. out [cells][loo_mm_exact_fields(C)]
 hipError_t loo_mm_exact_fit_cells(const FitCells& fc, double k_threshold, int max_iters, double tc, double p_lo, double p_hi, double* out,
                                   size_t scratch_bytes, hipStream_t st);
+// The split transformation of the matching (ppcx_loo_mm_split.hip, statistic in ppcx_loo_mm_split.h): per batch of cells the
+// matching's two kernels into a device record, then one workgroup per cell; ratio / eta, weight and ll_x / ln phi of the draws
+// (24 bytes per draw) in LDS up to kPsisLdsDraws draws, beyond that in the scratch. predictive false: the elpd form, out
+// [cells][loo_mm_split_fields(C)] (tc, p_lo, p_hi are not read); true: the exact predictive, out [cells][loo_mm_exact_split_fields(C)]
+hipError_t loo_mm_split_fit_cells(const FitCells& fc, double k_threshold, int max_iters, bool predictive, double tc, double p_lo,
+                                  double p_hi, double* out, size_t scratch_bytes, hipStream_t st);
 // The relative efficiency of the same cells (ppcx_reff.hip, statistic in ppcx_reff.h): one workgroup per cell; the split values
 // (8 bytes each) in LDS for fits of up to kPsisLdsDraws draws, beyond that in the scratch. Of `l` it uses T / y / expo / X / S / C
 // or cols, n = chains n_keep, cell0, n_cells, scratch ([launch's cells][2 chains (n_keep / 2)]) and out ([cells], one value

@@ -43,7 +43,8 @@
 //   5. Left out: the covariance step (loo's default leaves it off as well); the split transformation; mcse / n_eff of a matched
 //      cell. Without the split step repeated shifts can overshoot on a very fine posterior sample: khat falls below 0.7 while
 //      the error of elpd_loo stays at plain PSIS's size (seen on a 2-D grid posterior of 2500 x 2500 points at n = 4000; not at
-//      900 x 900). khat of a matched cell is therefore necessary, not sufficient.
+//      900 x 900). khat of a matched cell is therefore necessary, not sufficient. The split transformation is
+//      ppcx_loo_mm_split.h (ppcx_fit_loo_moment_match_split), which starts from this header's record.
 // The fields: elpd_loo, p_loo, looic, khat, khat_before, iterations, then scale[C + 1] and shift[C + 1] in the table's row order.
 // Every reduction runs in a fixed order with contraction off: a cell's fields depend on its own gene's data only.
 #pragma once

@@ -228,6 +228,8 @@ class CheckContext:
     pooled: bool = False         # a fit over the pooled draws of several fits' chains (pooled_summary): it holds no lp__
     loo_moment_match: bool = False   # check_loo reads Fit.loo_moment_match in place of Fit.loo
     exact_loo_moment_match: bool = False   # exact_loo_intervals reads Fit.loo_predict_exact_moment_match in place of Fit.loo_predict_exact
+    loo_moment_match_split: bool = False         # Fit.loo_moment_match is read with split=True
+    exact_loo_moment_match_split: bool = False   # Fit.loo_predict_exact_moment_match is read with split=True
 
 
 @dataclass(frozen=True)
@@ -258,17 +260,21 @@ def _loo_warnings(result, fit):
 
 
 def _read_loo(fit, ctx):
-    """check_loo's read: Fit.loo(r_eff, mcse), or with loo_moment_match Fit.loo_moment_match(r_eff) (its khat is the final one)"""
+    """check_loo's read: Fit.loo(r_eff, mcse), or with loo_moment_match Fit.loo_moment_match(r_eff) (its khat is the final one),
+    with loo_moment_match_split also split=True"""
     if ctx.loo_moment_match:
-        return fit.loo_moment_match(np.arange(ctx.K), r_eff=ctx.loo_r_eff)
+        split = dict(split=True) if ctx.loo_moment_match_split else {}
+        return fit.loo_moment_match(np.arange(ctx.K), r_eff=ctx.loo_r_eff, **split)
     return fit.loo(np.arange(ctx.K), r_eff=ctx.loo_r_eff, mcse=bool(ctx.loo_mcse))
 
 
 def _read_exact_loo(fit, ctx):
     """exact_loo_intervals' read: Fit.loo_predict_exact(r_eff, the pass's interval), or with exact_loo_moment_match
-    Fit.loo_predict_exact_moment_match with the same keywords (its khat is the final one)"""
+    Fit.loo_predict_exact_moment_match with the same keywords (its khat is the final one), with exact_loo_moment_match_split also
+    split=True"""
     read = fit.loo_predict_exact_moment_match if ctx.exact_loo_moment_match else fit.loo_predict_exact
-    return read(np.arange(ctx.K), r_eff=ctx.loo_r_eff, **_interval(ctx))
+    split = dict(split=True) if ctx.exact_loo_moment_match and ctx.exact_loo_moment_match_split else {}
+    return read(np.arange(ctx.K), r_eff=ctx.loo_r_eff, **_interval(ctx), **split)
 
 
 CHECKS = (          # in the order of the reads
@@ -317,6 +323,10 @@ MODIFIERS = (       # (option, the options of which it needs one, what it is tol
      "loo_moment_match needs check_loo: it matches the moments of the cells whose k-hat its PSIS-LOO finds too high"),
     ("exact_loo_moment_match", ("exact_loo_intervals",),
      "exact_loo_moment_match needs exact_loo_intervals: it matches the moments of the cells whose k-hat their PSIS finds too high"),
+    ("loo_moment_match_split", ("loo_moment_match",),
+     "loo_moment_match_split needs loo_moment_match: it is the split transformation of the cells that it has matched"),
+    ("exact_loo_moment_match_split", ("exact_loo_moment_match",),
+     "exact_loo_moment_match_split needs exact_loo_moment_match: it is the split transformation of the cells that it has matched"),
 )
 LOO_MOMENT_MATCH_MCSE = ("loo_mcse cannot be combined with loo_moment_match: the Monte-Carlo standard error and n_eff are those of "
                          "plain PSIS weights and are not given for a matched cell")
@@ -388,7 +398,9 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                  exact_intervals=False,
                  exact_loo_intervals=False,
                  exact_approximation_loo_intervals=False,
-                 exact_loo_moment_match=False):
+                 exact_loo_moment_match=False,
+                 loo_moment_match_split=False,
+                 exact_loo_moment_match_split=False):
     """One inference pass (discovery or test) of ppcseq on the GPU.
 
     counts            G x S integer matrix, genes ordered with the `how_many_to_check` checked genes first
@@ -460,6 +472,14 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                       the result then also carries `khat_before`, `iterations`, `scale`, `shift` and `k_threshold`, and `khat` is
                       the final one. Flags and frame are those of the call without it. devices=[...]: over the pooled chains.
                       Needs exact_loo_intervals. loo_moment_match itself affects `res.loo` only.
+    loo_moment_match_split  True: loo_moment_match reads Fit.loo_moment_match(split=True): the split transformation of
+                      loo::loo_moment_match on the matched cells (the first half of the draws in the fit's order is transformed,
+                      the rest kept, all weighted against the mixture they come from); `res.loo` then also carries
+                      `elpd_loo_matched` and `khat_split`, and the k-hat warning keeps reading `khat`, the matching's final one.
+                      Needs loo_moment_match.
+    exact_loo_moment_match_split  True: exact_loo_moment_match reads Fit.loo_predict_exact_moment_match(split=True), the same
+                      transformation for the predictive; `res.exact_loo_intervals` then also carries `khat_split`. Needs
+                      exact_loo_moment_match.
     Returns an InferenceResult.
     """
     counts = np.asarray(counts)
@@ -521,7 +541,10 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
         msgs += read_checks(fit, CheckContext(K, p, seed, truncation_compensation, checks.get("loo_r_eff"),
                                               checks.get("loo_mcse", False),
                                               loo_moment_match=bool(checks.get("loo_moment_match", False)),
-                                              exact_loo_moment_match=bool(checks.get("exact_loo_moment_match", False))), checks, res)
+                                              exact_loo_moment_match=bool(checks.get("exact_loo_moment_match", False)),
+                                              loo_moment_match_split=bool(checks.get("loo_moment_match_split", False)),
+                                              exact_loo_moment_match_split=bool(checks.get("exact_loo_moment_match_split", False))),
+                                  checks, res)
         for msg in msgs:
             warnings.warn(msg, RuntimeWarning, stacklevel=2)
         res.counts_rng = rng
@@ -608,7 +631,10 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
             msgs = read_checks(fit, CheckContext(K, p, seed, truncation_compensation, checks.get("loo_r_eff"),
                                                  checks.get("loo_mcse", False), pooled=True,
                                                  loo_moment_match=bool(checks.get("loo_moment_match", False)),
-                                              exact_loo_moment_match=bool(checks.get("exact_loo_moment_match", False))), checks, res)
+                                              exact_loo_moment_match=bool(checks.get("exact_loo_moment_match", False)),
+                                              loo_moment_match_split=bool(checks.get("loo_moment_match_split", False)),
+                                              exact_loo_moment_match_split=bool(checks.get("exact_loo_moment_match_split", False))),
+                                  checks, res)
         finally:
             fit.close()
     finally:

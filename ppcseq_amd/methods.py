@@ -128,7 +128,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                       check_convergence=False, check_approximation=False, check_loo=False,
                       check_loo_intervals=False, loo_r_eff=None, loo_mcse=False, loo_moment_match=False,
                       check_approximation_loo=False, check_approximation_loo_intervals=False, exact_intervals=False,
-                      exact_loo_intervals=False, exact_approximation_loo_intervals=False, exact_loo_moment_match=False):
+                      exact_loo_intervals=False, exact_approximation_loo_intervals=False, exact_loo_moment_match=False,
+                      loo_moment_match_split=False, exact_loo_moment_match_split=False):
     """Mirror of ppcseq::identify_outliers (R/methods.R:74-367): same arguments, same defaults.
 
     data is a tidy pandas DataFrame (one row per transcript x sample); column arguments are strings. As in the
@@ -161,6 +162,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
     `exact_approximation_loo_intervals` (ADVI)    -> attrs["exact_approximation_loo_intervals_discovery"], [..."_test"]
     `exact_loo_moment_match` = True               -> exact_loo_intervals' results come from Fit.loo_predict_exact_moment_match; in
                                                      the same attrs
+    `loo_moment_match_split`, `exact_loo_moment_match_split` = True -> the two above read their method with split=True (the
+                                                     split transformation of the matched cells); in the same attrs
     """
     import os
     import pandas as pd
