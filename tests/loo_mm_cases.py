@@ -5,7 +5,8 @@ the hyper-parameters, tabulated on a grid; and the one-gene truth case (C = 1, S
 quadrature on the same grid.
 
 A draw set is a dict: counts [G, S], X [S, C], expo [S], K, excl (flat cell ids), lambda_mu_mu, draws [n, D] in the model's
-unconstrained order. gene_of() cuts one gene out of it in the form tests/loo_mm_restate.py takes."""
+unconstrained order. gene_of() cuts one gene out of it in the form tests/loo_mm_restate.py takes, for any C (the draw sets with
+more than one slope are tests/wide_design_cases.py's)."""
 import numpy as np
 
 from tests import loo_restate as L
@@ -20,11 +21,18 @@ def dims(G, Cc, K):
     off_i, off_a1 = 3, 3 + G
     off_a2 = off_a1 + K
     off_sg = off_a2 + max(Cc - 2, 0) * K
-    return dict(D=off_sg + G + 3, intercept=off_i, alpha1=off_a1, sigma_raw=off_sg, tail=off_sg + G)
+    return dict(D=off_sg + G + 3, intercept=off_i, alpha1=off_a1, alpha2=off_a2, sigma_raw=off_sg, tail=off_sg + G)
+
+
+def slope_index(d, Cc, c, g):
+    """where slope c >= 1 of checked gene g lies in the unconstrained vector: alpha1 holds the K first slopes gene by gene, alpha2
+    the C - 2 further slopes of gene 0, then those of gene 1, ... (written out here, not taken from the header)"""
+    return d["alpha1"] + g if c == 1 else d["alpha2"] + (c - 2) + (Cc - 2) * g
 
 
 def gene_of(ds, g):
-    """gene g of a draw set as tests/loo_mm_restate.py takes it"""
+    """gene g of a draw set as tests/loo_mm_restate.py takes it. General in C: row c of a checked gene is its slope c for every
+    1 <= c < C (tests/wide_design_cases.py has C = 3 and 4); at C <= 2 the rows are what they were, bit for bit."""
     G, S = ds["counts"].shape
     Cc = ds["X"].shape[1]
     d = dims(G, Cc, ds["K"])
@@ -33,7 +41,8 @@ def gene_of(ds, g):
     T = np.zeros((Cc + 1, n))
     T[0] = u[:, d["intercept"] + g]
     if g < ds["K"] and Cc >= 2:
-        T[1] = u[:, d["alpha1"] + g]
+        for c in range(1, Cc):
+            T[c] = u[:, slope_index(d, Cc, c, g)]
     T[Cc] = u[:, d["sigma_raw"] + g]
     U = np.stack([u[:, 0], u[:, 1], u[:, 2], u[:, d["tail"]], u[:, d["tail"] + 1], u[:, d["tail"] + 2]])
     excl = np.zeros(G * S, bool)
