@@ -153,33 +153,38 @@ extern "C" int ppcx_fit_loo(ppcx_fit* f, int n_genes, const int32_t* genes, cons
 extern "C" int ppcx_fit_loo_mcse(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double* out) {
   return fit_loo("ppcx_fit_loo_mcse", f, n_genes, genes, r_eff, kLooMcseFields, out);
 }
+static int loo_exact_check(const ppcx_fit* f, int n_genes, const int32_t* genes, double truncation_compensation, double p_lo, double p_hi);
 // ---- gene-local moment matching of the cells with a high k-hat (loo::loo_moment_match restated per gene; ppcx_loo_mm.h)
+// The checks of the four moment-matching entries and the cells of the fit. probs: the predictive forms' truncation
+// compensation, p_lo and p_hi, which add loo_exact_check (checked genes only); null: the elpd forms, which leave a NULL fit to
+// loo_prepare.
+static int loo_mm_prepare(const char* who, ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double k_threshold,
+                          int max_iters, const double* probs, const void* out, std::vector<int>& yenc, FitCells& fc) {
+  if (probs && !f) return fail(PPCX_ERR_ARG, "fit is NULL");
+  if (f && f->advi)
+    return fail(PPCX_ERR_ARG, std::string(who) + " needs the draws of a NUTS fit: moment matching under the weights of an ADVI fit "
+                                                 "(loo_approximate_posterior) is not available");
+  if (!isfinite(k_threshold)) return fail(PPCX_ERR_ARG, std::string(who) + ": k_threshold must be finite");
+  if (max_iters < 0) return fail(PPCX_ERR_ARG, std::string(who) + ": max_iters must be >= 0");
+  int rc = probs ? loo_exact_check(f, n_genes, genes, probs[0], probs[1], probs[2]) : PPCX_OK;
+  if (rc == PPCX_OK) rc = probs ? loo_prepare_cells(f, n_genes, genes, out, yenc, fc) : loo_prepare(f, n_genes, genes, out, yenc, fc);
+  if (rc == PPCX_OK) rc = loo_fit_reff(who, fc, r_eff);
+  return rc;
+}
 extern "C" int ppcx_fit_loo_moment_match(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double k_threshold,
                                          int max_iters, double* out) {
   const char* who = "ppcx_fit_loo_moment_match";
-  if (f && f->advi)
-    return fail(PPCX_ERR_ARG, std::string(who) + " needs the draws of a NUTS fit: moment matching under the weights of an ADVI fit "
-                                                 "(loo_approximate_posterior) is not available");
-  if (!isfinite(k_threshold)) return fail(PPCX_ERR_ARG, std::string(who) + ": k_threshold must be finite");
-  if (max_iters < 0) return fail(PPCX_ERR_ARG, std::string(who) + ": max_iters must be >= 0");
   std::vector<int> yenc; FitCells fc;
-  int rc = loo_prepare(f, n_genes, genes, out, yenc, fc);
-  if (rc == PPCX_OK) rc = loo_fit_reff(who, fc, r_eff);
+  const int rc = loo_mm_prepare(who, f, n_genes, genes, r_eff, k_threshold, max_iters, nullptr, out, yenc, fc);
   if (rc != PPCX_OK) return rc;
   return hip_done(who, loo_mm_fit_cells(fc, k_threshold, max_iters, out, loo_scratch_bytes(), f->m->stream.s));
 }
-// ... with the split transformation of the matched cells (ppcx_loo_mm_split.h): the same checks, the matching's kernels, then the split
+// ... with the split transformation of the matched cells (ppcx_loo_mm_split.h): the matching's kernels, then the split
 extern "C" int ppcx_fit_loo_moment_match_split(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double k_threshold,
                                                int max_iters, double* out) {
   const char* who = "ppcx_fit_loo_moment_match_split";
-  if (f && f->advi)
-    return fail(PPCX_ERR_ARG, std::string(who) + " needs the draws of a NUTS fit: moment matching under the weights of an ADVI fit "
-                                                 "(loo_approximate_posterior) is not available");
-  if (!isfinite(k_threshold)) return fail(PPCX_ERR_ARG, std::string(who) + ": k_threshold must be finite");
-  if (max_iters < 0) return fail(PPCX_ERR_ARG, std::string(who) + ": max_iters must be >= 0");
   std::vector<int> yenc; FitCells fc;
-  int rc = loo_prepare(f, n_genes, genes, out, yenc, fc);
-  if (rc == PPCX_OK) rc = loo_fit_reff(who, fc, r_eff);
+  const int rc = loo_mm_prepare(who, f, n_genes, genes, r_eff, k_threshold, max_iters, nullptr, out, yenc, fc);
   if (rc != PPCX_OK) return rc;
   return hip_done(who, loo_mm_split_fit_cells(fc, k_threshold, max_iters, false, 1.0, 0.0, 1.0, out, loo_scratch_bytes(), f->m->stream.s));
 }
@@ -365,16 +370,10 @@ extern "C" int ppcx_fit_loo_predict_exact_moment_match(ppcx_fit* f, int n_genes,
                                                        double k_threshold, int max_iters, double truncation_compensation, double p_lo,
                                                        double p_hi, double* out) {
   const char* who = "ppcx_fit_loo_predict_exact_moment_match";
-  if (!f) return fail(PPCX_ERR_ARG, "fit is NULL");
-  if (f->advi) return fail(PPCX_ERR_ARG, std::string(who) + " needs the draws of a NUTS fit: moment matching under the weights of an "
-                                                             "ADVI fit (loo_approximate_posterior) is not available");
-  if (!isfinite(k_threshold)) return fail(PPCX_ERR_ARG, std::string(who) + ": k_threshold must be finite");
-  if (max_iters < 0) return fail(PPCX_ERR_ARG, std::string(who) + ": max_iters must be >= 0");
-  int rc = loo_exact_check(f, n_genes, genes, truncation_compensation, p_lo, p_hi);
-  if (rc != PPCX_OK) return rc;
+  const double probs[3] = {truncation_compensation, p_lo, p_hi};
   std::vector<int> yenc; FitCells fc;
-  if ((rc = loo_prepare_cells(f, n_genes, genes, out, yenc, fc)) != PPCX_OK) return rc;
-  if ((rc = loo_fit_reff(who, fc, r_eff)) != PPCX_OK) return rc;
+  const int rc = loo_mm_prepare(who, f, n_genes, genes, r_eff, k_threshold, max_iters, probs, out, yenc, fc);
+  if (rc != PPCX_OK) return rc;
   return hip_done(who, loo_mm_exact_fit_cells(fc, k_threshold, max_iters, truncation_compensation, p_lo, p_hi, out, loo_scratch_bytes(),
                                               f->m->stream.s));
 }
@@ -383,16 +382,10 @@ extern "C" int ppcx_fit_loo_predict_exact_moment_match_split(ppcx_fit* f, int n_
                                                              double k_threshold, int max_iters, double truncation_compensation,
                                                              double p_lo, double p_hi, double* out) {
   const char* who = "ppcx_fit_loo_predict_exact_moment_match_split";
-  if (!f) return fail(PPCX_ERR_ARG, "fit is NULL");
-  if (f->advi) return fail(PPCX_ERR_ARG, std::string(who) + " needs the draws of a NUTS fit: moment matching under the weights of an "
-                                                             "ADVI fit (loo_approximate_posterior) is not available");
-  if (!isfinite(k_threshold)) return fail(PPCX_ERR_ARG, std::string(who) + ": k_threshold must be finite");
-  if (max_iters < 0) return fail(PPCX_ERR_ARG, std::string(who) + ": max_iters must be >= 0");
-  int rc = loo_exact_check(f, n_genes, genes, truncation_compensation, p_lo, p_hi);
-  if (rc != PPCX_OK) return rc;
+  const double probs[3] = {truncation_compensation, p_lo, p_hi};
   std::vector<int> yenc; FitCells fc;
-  if ((rc = loo_prepare_cells(f, n_genes, genes, out, yenc, fc)) != PPCX_OK) return rc;
-  if ((rc = loo_fit_reff(who, fc, r_eff)) != PPCX_OK) return rc;
+  const int rc = loo_mm_prepare(who, f, n_genes, genes, r_eff, k_threshold, max_iters, probs, out, yenc, fc);
+  if (rc != PPCX_OK) return rc;
   return hip_done(who, loo_mm_split_fit_cells(fc, k_threshold, max_iters, true, truncation_compensation, p_lo, p_hi, out,
                                               loo_scratch_bytes(), f->m->stream.s));
 }

@@ -3,7 +3,8 @@
 // workgroup has and where its arrays live (cell_mem), the cell's linear predictor and log-likelihood from the transposed table,
 // its ratios r = -ll (an ADVI fit: (log_p - log_g) - ll, ppcx_loo_ap.h), the fitted tail with the copies of the cutoff, a draw's
 // log weight under the tie rule -- together the weights stage (loo_cell_verdict, loo_cell_weights) -- and the workgroup's sums
-// for the exact sweeps of ppcx_ppc_exact.h (ExactBlockSums).
+// for the exact sweeps of ppcx_ppc_exact.h (ExactBlockSums), the fill of (eta, ln phi) before them (loo_fill_eta_lnphi) and the
+// plain exact predictive of a cell from the verdict to khat (loo_exact_cell).
 // The table itself and a cell's read of it are ppcx_table.h's, shared with the posterior-predictive kernels.
 // On the host: the one walk over a fit's cells in gene batches (for_gene_batches), its counterpart for host-given columns
 // (for_given_columns) and the launch path: the batches of cells under the scratch bound (cells_in_batches), LDS against scratch
@@ -16,6 +17,7 @@
 #include "ppcx_loo.h"
 #include "ppcx_loo_ap.h"
 #include "ppcx_ppc_exact.h"
+#include "ppcx_loo_exact.h"
 #include "ppcx_columns.h"
 #include "ppcx_table.h"
 
@@ -191,6 +193,60 @@ struct ExactBlockSums {
     for (int k = 0; k < K; ++k) s[k] = block_sum(s[k], red);
   }
 };
+
+// (eta_i, ln phi_i) of every draw into E and LP, eta_i = src(i, &sigma_raw_i); returns whether a draw of the workgroup has
+// invalid parameters (ppc_exact_invalid). Every thread gets the same.
+template <class Src>
+__device__ __forceinline__ bool loo_fill_eta_lnphi(long n, double log_tc, double* E, double* LP, Src src) {
+  PPCX_NO_CONTRACT
+  bool inval = false;
+  for (long i = threadIdx.x; i < n; i += kBlockThreads) {
+    double sg = 0.0;
+    const double eta = src(i, &sg);
+    const double lp = ppc_exact_lnphi(sg, log_tc);
+    E[i] = eta; LP[i] = lp;
+    inval = inval || ppc_exact_invalid(eta, ppc_exact_phi(lp));
+  }
+  return block_any(inval);
+}
+
+// doubles per cell of the kernels that keep three arrays of n draws (ppcx_loo_exact_kernel and the moment-matched ones)
+__host__ __device__ inline long loo_slice3(long n) { return 3 * n; }
+
+// The exact predictive of cell c under plain PSIS weights (ppcx_loo_exact.h), from the verdict to khat: the ten fields into
+// o[kLooExactFields]. m.V holds the ratios, then eta; behind it the log weights, then the weights, and ln phi (loo_slice3).
+// ppcx_loo_exact_kernel is this function; the moment-matched kernels call it for a cell that was not matched, so their ten
+// fields are ppcx_fit_loo_predict_exact's bits by construction. etacols / sgcols: the given columns' (COLS).
+template <bool COLS, bool AP>
+__device__ __forceinline__ void loo_exact_cell(const LooArgs& a, const LooCell& c, const CellMem& m, const double* etacols,
+                                               const double* sgcols, double log_tc, double p_lo, double p_hi, double* o, PsisShared& sh) {
+  PPCX_NO_CONTRACT
+  const int tid = threadIdx.x;
+  const long n = a.n;
+  double* W = m.V + n;                                   // [n] log weights, then weights (m.V: [n] the ratios)
+  double* LP = W + n;                                    // [n] ln phi
+  double* E = m.V;                                       // [n] eta, once the ratios are dead
+  // ---- the ratios, the tail, the normalised weight of every draw
+  CellRatios cr;
+  const CellVerdict verdict = loo_cell_verdict<COLS, AP>(a, c, m, nullptr, sh, &cr);
+  if (verdict == CELL_NAN) { if (tid == 0) loo_exact_store_nan(o, c.y, c.excluded); return; }
+  const bool uniform = verdict == CELL_UNIFORM;          // already held out: w_i = 1, every sum over n
+  double khat = NAN;
+  if (uniform) for (long i = tid; i < n; i += kBlockThreads) W[i] = 1.0;
+  else khat = loo_cell_weights<true>(a, c, m, cr, W, sh);
+  __syncthreads();                                       // no thread reads a ratio any more: V becomes E
+  // ---- (eta, ln phi) of every draw
+  const double* Tg = COLS ? nullptr : a.T + (long)c.gi * (a.C + 1) * n;
+  const bool inval = loo_fill_eta_lnphi(n, log_tc, E, LP, [&](long i, double* sg) {
+    const double eta = COLS ? etacols[(long)c.cell * n + i] : loo_cell_eta(a, Tg, c.s, i, sg);
+    if (COLS) *sg = sgcols[(long)c.cell * n + i];
+    return eta;
+  });
+  if (inval) { if (tid == 0) loo_exact_store_nan(o, c.y, c.excluded); return; }
+  // ---- the moments, the two tails at y, the interval (ppc_exact_sweeps); khat beside its nine fields
+  const bool ok = ppc_exact_sweeps(ExactBlockSums<true>{W, E, LP, n, sh.red}, c.y, c.excluded, uniform ? n : 1, p_lo, p_hi, tid == 0, o);
+  if (tid == 0) o[kPpcExactFields] = ok ? khat : NAN;
+}
 
 // ---- the launch path (host)
 // A launch over cells: whether a cell's arrays live in LDS (up to kPsisLdsDraws draws) or in the scratch, whether the cells

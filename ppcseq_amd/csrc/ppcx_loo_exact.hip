@@ -1,7 +1,8 @@
 // ppcx_loo_exact.hip -- gfx950 kernel of the exact leave-one-out predictive tail probabilities and interval per cell
 // (ppcx_fit_loo_predict_exact, ppcx_fit_loo_predict_exact_approx, include/ppcx.h; the statistic: ppcx_loo_exact.h, the weights:
 // ppcx_loo_dev.h, the negative-binomial tails: ppcx_nbcdf.h). The walk over the cells is ppcx_loo_dev.h's (for_gene_batches,
-// for_given_columns); the drivers at the end of this file add the argument block and the kernel.
+// for_given_columns); the drivers at the end of this file add the argument block and the kernel. The kernel's body is
+// loo_exact_cell (ppcx_loo_dev.h), which the moment-matched kernels call for their unmatched cells.
 //
 //   ppcx_loo_exact_kernel  one workgroup of kBlockThreads per cell, a sibling of ppcx_loo_predict_kernel (the weights) and of
 //                          ppcx_ppc_exact_kernel (everything after them). The cell's ratios from the transposed table T
@@ -41,59 +42,23 @@ struct LooExactArgs {
   double log_tc = 0.0, p_lo = 0.025, p_hi = 0.975;
 };
 
-// doubles per cell, in LDS or in the scratch: ratio / eta [n], log weight / weight [n], ln phi [n]
-__host__ __device__ inline long loo_exact_slice(long n) { return 3 * n; }
-
-// AP: the weights of an ADVI fit (ppcx_loo_ap.h)
+// AP: the weights of an ADVI fit (ppcx_loo_ap.h). The stages are loo_exact_cell's (ppcx_loo_dev.h), which the moment-matched
+// kernels run on their unmatched cells.
 template <bool LDS, bool COLS, bool AP>
 __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_exact_kernel(LooExactArgs p) {
 #pragma clang fp contract(off)
   extern __shared__ uint64_t lds_u[];
   __shared__ PsisShared sh;
   const LooArgs& a = p.l;
-  const int tid = threadIdx.x;
-  const long n = a.n;
-  const CellMem m = cell_mem<LDS>(lds_u, a, loo_exact_slice(n));
-  double* W = m.V + n;                                   // [n] log weights, then weights (m.V: [n] the ratios)
-  double* LP = W + n;                                    // [n] ln phi
-  double* E = m.V;                                       // [n] eta, once the ratios are dead
   const LooCell c = loo_cell<COLS>(a, p.ycols);
-  const int cell = c.cell, gi = c.gi, s = c.s, y = c.y;
-  const bool excluded = c.excluded;
-  double* o = a.out + (long)cell * kLooExactFields;
-  auto all_nan = [&]() { if (tid == 0) loo_exact_store_nan(o, y, excluded); };
-  // ---- the ratios, the tail, the normalised weight of every draw
-  CellRatios cr;
-  const CellVerdict verdict = loo_cell_verdict<COLS, AP>(a, c, m, nullptr, sh, &cr);
-  if (verdict == CELL_NAN) { all_nan(); return; }
-  const bool uniform = verdict == CELL_UNIFORM;          // already held out: w_i = 1, every sum over n
-  double khat = NAN;
-  if (uniform) for (long i = tid; i < n; i += kBlockThreads) W[i] = 1.0;
-  else khat = loo_cell_weights<true>(a, c, m, cr, W, sh);
-  __syncthreads();                                       // no thread reads a ratio any more: V becomes E
-  // ---- (eta, ln phi) of every draw
-  bool inval = false;
-  {
-    const double* Tg = COLS ? nullptr : a.T + (long)gi * (a.C + 1) * n;
-    for (long i = tid; i < n; i += kBlockThreads) {
-      double sg = 0.0;
-      const double eta = COLS ? p.etacols[(long)cell * n + i] : loo_cell_eta(a, Tg, s, i, &sg);
-      if (COLS) sg = p.sgcols[(long)cell * n + i];
-      const double lp = ppc_exact_lnphi(sg, p.log_tc);
-      E[i] = eta; LP[i] = lp;
-      inval = inval || ppc_exact_invalid(eta, ppc_exact_phi(lp));
-    }
-  }
-  if (block_any(inval)) { all_nan(); return; }
-  // ---- the moments, the two tails at y, the interval (ppc_exact_sweeps); khat beside its nine fields
-  const bool ok = ppc_exact_sweeps(ExactBlockSums<true>{W, E, LP, n, sh.red}, y, excluded, uniform ? n : 1, p.p_lo, p.p_hi, tid == 0, o);
-  if (tid == 0) o[kPpcExactFields] = ok ? khat : NAN;
+  loo_exact_cell<COLS, AP>(a, c, cell_mem<LDS>(lds_u, a, loo_slice3(a.n)), p.etacols, p.sgcols, p.log_tc, p.p_lo, p.p_hi,
+                           a.out + (long)c.cell * kLooExactFields, sh);
 }
 
 // ---- launch helpers (host)
 PPCX_KERNEL_OF(ppcx_loo_exact_kernel);
 static hipError_t loo_exact_cells(const LooExactArgs& args, int n_cells, size_t scratch_bytes, DeviceBuffer<double>& scratch, hipStream_t st) {
-  const long slice = loo_exact_slice(args.l.n);
+  const long slice = loo_slice3(args.l.n);
   return cells_in_batches(args, slice, n_cells, scratch_bytes, scratch, [&](const LooExactArgs& p, const CellLaunch& c) {
     return launch_cell_kernel(pick_kernel<ppcx_loo_exact_kernel_of>(c.lds, c.cols, p.l.lr != nullptr), p, c, p.l.sel_pad, slice, st);
   });

@@ -177,6 +177,14 @@ inline double loo_mm_psis_host(const std::vector<double>& r, double r_eff, std::
   loo_exact_log_weights_host(r.data(), (long)r.size(), r_eff, lw, &khat);
   return khat;
 }
+// lpd of the original draws from the cell's log-likelihoods ll[0 .. n): log mean exp over the draws that take part (-ll is not
+// -Inf); false, and *lpd NaN, without one
+inline bool loo_mm_lpd_host(const std::vector<double>& ll, double* lpd) {
+  std::vector<double> part;
+  for (double l : ll) if (-l != -INFINITY) part.push_back(l);
+  *lpd = part.empty() ? NAN : loo_logsumexp_host(part) - log((double)part.size());
+  return !part.empty();
+}
 // the whole spec for one cell, sequentially, for the CPU check: out[loo_mm_fields(C)]. kinds (may be null): the accepted
 // candidates in order, 1 or 2.
 inline void loo_mm_cell_host(const LooMmGene& g, int s, double r_eff, double k_threshold, int max_iters, double* out,
@@ -193,10 +201,10 @@ inline void loo_mm_cell_host(const LooMmGene& g, int s, double r_eff, double k_t
   loo_cell_host(ll.data(), n, r_eff, excluded, out);
   loo_mm_store_state(out, C, out[3], 0, nullptr, nullptr);
   if (loo_mm_finished(excluded, out[3], k_threshold, max_iters)) return;
-  std::vector<double> r(n), lw, part;
-  for (long i = 0; i < n; ++i) { r[i] = -ll[i]; if (r[i] != -INFINITY) part.push_back(ll[i]); }
-  if (part.empty()) return;
-  const double lpd = loo_logsumexp_host(part) - log((double)part.size());
+  std::vector<double> r(n), lw;
+  for (long i = 0; i < n; ++i) r[i] = -ll[i];
+  double lpd;
+  if (!loo_mm_lpd_host(ll, &lpd)) return;
   double k = loo_mm_psis_host(r, r_eff, lw);
   // ---- step 1 at the original draws
   std::vector<double> Q0(n);

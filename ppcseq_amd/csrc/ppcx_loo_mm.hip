@@ -1,7 +1,9 @@
 // ppcx_loo_mm.hip -- gfx950 kernels of the gene-local moment matching of PSIS-LOO cells (ppcx_fit_loo_moment_match,
 // include/ppcx.h; the statistic: ppcx_loo_mm.h). The walk over the cells is ppcx_loo_dev.h's (for_gene_batches,
 // cells_in_batches); the driver at the end of this file adds the kernels. The argument block, the gene a workgroup reads and the
-// walk's own buffers are ppcx_loo_mm_dev.h's, shared with ppcx_loo_mm_exact.hip, which runs these kernels before its own.
+// walk's own buffers are ppcx_loo_mm_dev.h's, shared with ppcx_loo_mm_exact.hip and ppcx_loo_mm_split.hip, which run these kernels
+// before their own (loo_mm_then_fit_cells); so are the stages that those kernels run too: a candidate's counted ratio sweep
+// (loo_mm_count_ratios), lpd of the original draws (loo_mm_lpd) and step 4 (loo_mm_weighted_elpd).
 //
 //   ppcx_loo_mm_hyper_kernel  the draws' six unconstrained hyper-parameters, transposed: U[k][draw], once per call, so that a
 //                             wavefront's lanes read consecutive draws of one hyper-parameter as they do of the table T.
@@ -46,7 +48,7 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_kernel(LooMmArgs p)
   const int tid = threadIdx.x;
   const long n = a.n;
   const int C = a.C, nc = C + 1;
-  const CellMem m = cell_mem<LDS>(lds_u, a, loo_mm_slice(n));
+  const CellMem m = cell_mem<LDS>(lds_u, a, loo_slice3(n));
   uint64_t* K = m.K; double* X = m.X;
   double* V = m.V;                                       // [n] the ratios (of the last candidate)
   double* W = V + n;                                     // [n] the current log weights
@@ -64,16 +66,15 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_kernel(LooMmArgs p)
   if (loo_mm_finished(c.excluded, khat0, p.k_threshold, p.max_iters)) return;
   CellRatios cr;
   if (loo_cell_ratios<false, false>(a, c, false, V, nullptr, sh, &cr)) return;
-  const long N = cr.N; const double rmax = cr.rmax, lmax = cr.lmax;
+  const long N = cr.N;
   if (N == 0) return;
-  const double sl = draws_sum(n, sh.red, [&](long i) { const double r = V[i]; return r != -INFINITY ? exp(-r - lmax) : 0.0; });
-  const double lpd = (lmax == -INFINITY ? -INFINITY : lmax + log(sl)) - log((double)N);
+  const double lpd = loo_mm_lpd(V, n, cr, sh);
   const double re = a.r_eff ? a.r_eff[cell] : 1.0;
   double k;
   {
     const int M = psis_tail_len(N, re);
     const LooTail lt = loo_cell_tail(V, n, N, M, K, X, a.sel_pad, sh);
-    loo_cell_lw<false>(V, W, n, rmax, lt, M, K, sh);
+    loo_cell_lw<false>(V, W, n, cr.rmax, lt, M, K, sh);
     k = lt.khat;
   }
   // ---- the gene, the state, Q0
@@ -120,21 +121,16 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_kernel(LooMmArgs p)
       if (cand == 2 && !ok2) break;
       const double* Ac = cand == 1 ? ms.A1 : ms.A2;
       const double* Bc = cand == 1 ? ms.B1 : ms.B2;
-      double cnt = 0.0, rmx = -INFINITY;
-      for (long i = tid; i < n; i += kBlockThreads) {
+      const CountedRatios r2 = loo_mm_count_ratios(n, V, sh, [&](long i) {
         double l;
         const double q = loo_mm_density(g, i, Ac, Bc, s, &l);
-        const double r = loo_mm_ratio(q, Q0[i], l);
-        if (r != -INFINITY) { cnt += 1.0; rmx = fmax(rmx, r); }
-        V[i] = r;
-      }
-      const long N2 = (long)block_sum(cnt, sh.red);
-      rmx = block_max(rmx, sh.red);
-      const int M2 = psis_tail_len(N2, re);
-      const LooTail lt = loo_cell_tail(V, n, N2, M2, K, X, a.sel_pad, sh);
-      if (N2 > 0 && lt.khat < k) {
+        return loo_mm_ratio(q, Q0[i], l);
+      });
+      const int M2 = psis_tail_len(r2.N, re);
+      const LooTail lt = loo_cell_tail(V, n, r2.N, M2, K, X, a.sel_pad, sh);
+      if (r2.N > 0 && lt.khat < k) {
         kind = cand; k = lt.khat;
-        loo_cell_lw<false>(V, W, n, rmx, lt, M2, K, sh);
+        loo_cell_lw<false>(V, W, n, r2.rmax, lt, M2, K, sh);
         __syncthreads();
         if (tid < nc) { ms.A[tid] = Ac[tid]; ms.B[tid] = Bc[tid]; }
         __syncthreads();
@@ -145,23 +141,7 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_kernel(LooMmArgs p)
   }
   if (iters == 0) return;
   // ---- step 4
-  double ma = -INFINITY, mb = -INFINITY;
-  for (long i = tid; i < n; i += kBlockThreads) {
-    const double lw = W[i];
-    if (lw == -INFINITY) continue;
-    ma = fmax(ma, lw + loo_mm_cell_ll(g, i, ms.A, ms.B, s)); mb = fmax(mb, lw);
-  }
-  ma = block_max(ma, sh.red);
-  mb = block_max(mb, sh.red);
-  double sa = 0.0, sb = 0.0;
-  for (long i = tid; i < n; i += kBlockThreads) {
-    const double lw = W[i];
-    if (lw == -INFINITY) continue;
-    sa += exp(lw + loo_mm_cell_ll(g, i, ms.A, ms.B, s) - ma); sb += exp(lw - mb);
-  }
-  sa = block_sum(sa, sh.red);
-  sb = block_sum(sb, sh.red);
-  const double elpd = loo_ap_lse(ma, sa) - loo_ap_lse(mb, sb);
+  const double elpd = loo_mm_weighted_elpd(W, n, sh, [&](long i) { return loo_mm_cell_ll(g, i, ms.A, ms.B, s); });
   if (tid == 0) {
     o[0] = elpd; o[1] = lpd - elpd; o[2] = -2.0 * elpd; o[3] = k;
     loo_mm_store_state(o, C, khat0, iters, ms.A, ms.B);
@@ -192,7 +172,7 @@ LooMmArgs LooMmWalk::args(const FitCells& fc, const LooArgs& a, const int* genes
 }
 hipError_t launch_loo_mm_kernels(const LooMmArgs& q, const CellLaunch& c, hipStream_t st) {
   const hipError_t e1 = launch_loo_kernel(q.l, kLooFields, c.n_blocks, st);
-  return e1 == hipSuccess ? launch_cell_kernel(pick_kernel<ppcx_loo_mm_kernel_of>(c.lds), q, c, q.l.sel_pad, loo_mm_slice(q.l.n), st) : e1;
+  return e1 == hipSuccess ? launch_cell_kernel(pick_kernel<ppcx_loo_mm_kernel_of>(c.lds), q, c, q.l.sel_pad, loo_slice3(q.l.n), st) : e1;
 }
 
 hipError_t loo_mm_fit_cells(const FitCells& fc, double k_threshold, int max_iters, double* out, size_t scratch_bytes, hipStream_t st) {
@@ -203,7 +183,7 @@ hipError_t loo_mm_fit_cells(const FitCells& fc, double k_threshold, int max_iter
                           [&](const LooArgs& a, const int* genes, int n_cells, DeviceBuffer<double>& scratch) {
     const LooMmArgs p = walk.args(fc, a, genes, n_cells, k_threshold, max_iters, a.out);
     // per batch of cells: plain PSIS-LOO, then the matching
-    return cells_in_batches(p, loo_mm_slice(fc.n), n_cells, scratch_bytes, scratch, [&](const LooMmArgs& q, const CellLaunch& c) {
+    return cells_in_batches(p, loo_slice3(fc.n), n_cells, scratch_bytes, scratch, [&](const LooMmArgs& q, const CellLaunch& c) {
       return launch_loo_mm_kernels(q, c, st);
     });
   });

@@ -62,10 +62,53 @@ PPCX_HD void loo_mm_exact_store_state(double* o, int C, const double* rec) {
 #if !defined(__HIP_DEVICE_COMPILE__)
 #include <vector>
 namespace ppcx {
+// step 1: ppcx_loo_exact.h itself on the original draws of the cell, the ten fields into out
+inline void loo_mm_exact_unmatched_host(const LooMmGene& g, int s, double r_eff, double tc, double p_lo, double p_hi, double* out) {
+  const long n = g.n;
+  const bool excluded = g.yrow[s] < 0;
+  const int y = excluded ? -g.yrow[s] - 1 : g.yrow[s];
+  const std::vector<double> one((size_t)g.C + 1, 1.0), zero((size_t)g.C + 1, 0.0);
+  std::vector<double> eta((size_t)n), sg((size_t)n), ll((size_t)n);
+  for (long i = 0; i < n; ++i) {
+    eta[i] = loo_mm_exact_eta(g, s, i, one.data(), zero.data(), &sg[i]);
+    ll[i] = loo_ll(y, eta[i], sg[i]);
+  }
+  loo_exact_cell_host(ll.data(), eta.data(), sg.data(), nullptr, n, y, excluded, r_eff, tc, p_lo, p_hi, out);
+}
+// the log weights w[0 .. n) into the normalised weights exp(w - max) / sum (ppcx_loo_exact.h step 1); false, and w untouched,
+// where no draw has a log weight above -Inf
+inline bool loo_mm_normalise_host(std::vector<double>& w) {
+  PPCX_NO_CONTRACT
+  double mxw = -INFINITY, sw = 0.0;
+  for (double x : w) mxw = x > mxw ? x : mxw;
+  if (mxw == -INFINITY) return false;
+  for (double& x : w) { x = exp(x - mxw); sw += x; }
+  for (double& x : w) x = x / sw;
+  return true;
+}
+// step 3: the predictive under the normalised weights w at the states state(i) -> (A, B) of every draw: the nine fields of
+// ppc_exact_sweeps into out and true, or the cell's NaN record and false (an invalid draw, a failed sweep)
+template <class F>
+inline bool loo_mm_predictive_host(const LooMmGene& g, int s, const std::vector<double>& w, double tc, double p_lo, double p_hi, double* out,
+                                   F state) {
+  PPCX_NO_CONTRACT
+  const long n = g.n;
+  const bool excluded = g.yrow[s] < 0;
+  const int y = excluded ? -g.yrow[s] - 1 : g.yrow[s];
+  const double log_tc = log(tc);
+  std::vector<double> eta((size_t)n), sg((size_t)n);
+  for (long i = 0; i < n; ++i) {
+    const double *A, *B;
+    state(i, &A, &B);
+    eta[i] = loo_mm_exact_eta(g, s, i, A, B, &sg[i]);
+    if (ppc_exact_invalid(eta[i], ppc_exact_phi(ppc_exact_lnphi(sg[i], log_tc)))) { loo_exact_store_nan(out, y, excluded); return false; }
+  }
+  int mx = 0;
+  return ppc_exact_sweeps(ExactHostSums{w.data(), eta.data(), sg.data(), log_tc, n, &mx}, y, excluded, 1, p_lo, p_hi, true, out);
+}
 // the whole spec for one cell, sequentially, for the CPU check: out[loo_mm_exact_fields(C)]
 inline void loo_mm_exact_cell_host(const LooMmGene& g, int s, double r_eff, double k_threshold, int max_iters, double tc, double p_lo,
                                    double p_hi, double* out) {
-  PPCX_NO_CONTRACT
   const long n = g.n;
   const int C = g.C, nc = C + 1;
   const bool excluded = g.yrow[s] < 0;
@@ -73,37 +116,17 @@ inline void loo_mm_exact_cell_host(const LooMmGene& g, int s, double r_eff, doub
   std::vector<double> rec((size_t)loo_mm_fields(C));
   loo_mm_cell_host(g, s, r_eff, k_threshold, max_iters, rec.data());
   loo_mm_exact_store_state(out, C, rec.data());
+  if ((int)rec[5] == 0) { loo_mm_exact_unmatched_host(g, s, r_eff, tc, p_lo, p_hi, out); return; }
+  // ---- step 2
   const std::vector<double> one((size_t)nc, 1.0), zero((size_t)nc, 0.0);
   const double* A = rec.data() + kLooMmHead;
   const double* B = A + nc;
-  std::vector<double> eta((size_t)n), sg((size_t)n);
-  // ---- step 1
-  if ((int)rec[5] == 0) {
-    std::vector<double> ll((size_t)n);
-    for (long i = 0; i < n; ++i) {
-      eta[i] = loo_mm_exact_eta(g, s, i, one.data(), zero.data(), &sg[i]);
-      ll[i] = loo_ll(y, eta[i], sg[i]);
-    }
-    loo_exact_cell_host(ll.data(), eta.data(), sg.data(), nullptr, n, y, excluded, r_eff, tc, p_lo, p_hi, out);
-    return;
-  }
-  // ---- step 2
   std::vector<double> r((size_t)n), w;
   for (long i = 0; i < n; ++i) r[i] = loo_mm_exact_ratio(g, i, A, B, one.data(), zero.data(), s);
   const double khat = loo_mm_psis_host(r, r_eff, w);
-  double mxw = -INFINITY, sw = 0.0;
-  for (long i = 0; i < n; ++i) mxw = w[i] > mxw ? w[i] : mxw;
-  if (mxw == -INFINITY) { loo_exact_store_nan(out, y, excluded); return; }
-  for (long i = 0; i < n; ++i) { w[i] = exp(w[i] - mxw); sw += w[i]; }
-  for (long i = 0; i < n; ++i) w[i] = w[i] / sw;
+  if (!loo_mm_normalise_host(w)) { loo_exact_store_nan(out, y, excluded); return; }
   // ---- step 3
-  const double log_tc = log(tc);
-  for (long i = 0; i < n; ++i) {
-    eta[i] = loo_mm_exact_eta(g, s, i, A, B, &sg[i]);
-    if (ppc_exact_invalid(eta[i], ppc_exact_phi(ppc_exact_lnphi(sg[i], log_tc)))) { loo_exact_store_nan(out, y, excluded); return; }
-  }
-  int mx = 0;
-  const bool ok = ppc_exact_sweeps(ExactHostSums{w.data(), eta.data(), sg.data(), log_tc, n, &mx}, y, excluded, 1, p_lo, p_hi, true, out);
+  const bool ok = loo_mm_predictive_host(g, s, w, tc, p_lo, p_hi, out, [&](long, const double** a, const double** b) { *a = A; *b = B; });
   out[kPpcExactFields] = ok ? khat : NAN;
 }
 }  // namespace ppcx

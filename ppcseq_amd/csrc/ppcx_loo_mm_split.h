@@ -131,12 +131,10 @@ inline void loo_mm_split_from_record_host(const LooMmGene& g, int s, double r_ef
   const double* B = A + nc;
   // lpd of the original draws, as loo_mm_cell_host forms it
   const std::vector<double> one((size_t)nc, 1.0), zero((size_t)nc, 0.0);
-  std::vector<double> part;
-  for (long i = 0; i < n; ++i) {
-    const double l = loo_mm_cell_ll(g, i, one.data(), zero.data(), s);
-    if (-l != -INFINITY) part.push_back(l);
-  }
-  const double lpd = part.empty() ? NAN : loo_logsumexp_host(part) - log((double)part.size());
+  std::vector<double> ll((size_t)n);
+  for (long i = 0; i < n; ++i) ll[i] = loo_mm_cell_ll(g, i, one.data(), zero.data(), s);
+  double lpd;
+  loo_mm_lpd_host(ll, &lpd);
   std::vector<double> lw, lx;
   bool any;
   const double khat_split = loo_mm_split_weights_host(g, s, r_eff, A, B, lw, lx, &any);
@@ -148,27 +146,17 @@ inline void loo_mm_split_from_record_host(const LooMmGene& g, int s, double r_ef
 // the predictive form from the same record: out[loo_mm_exact_split_fields(C)]
 inline void loo_mm_exact_split_from_record_host(const LooMmGene& g, int s, double r_eff, double tc, double p_lo, double p_hi,
                                                 const double* rec, double* out) {
-  PPCX_NO_CONTRACT
-  const long n = g.n, h = loo_mm_split_half(n);
+  const long h = loo_mm_split_half(g.n);
   const int C = g.C, nc = C + 1;
   const bool excluded = g.yrow[s] < 0;
   const int y = excluded ? -g.yrow[s] - 1 : g.yrow[s];
   double* ks = out + loo_mm_exact_fields(C);
   loo_mm_exact_store_state(out, C, rec);
   *ks = NAN;
-  const std::vector<double> one((size_t)nc, 1.0), zero((size_t)nc, 0.0);
-  std::vector<double> eta((size_t)n), sg((size_t)n);
   // ---- step 1
-  if (!(rec[5] > 0.0)) {
-    std::vector<double> ll((size_t)n);
-    for (long i = 0; i < n; ++i) {
-      eta[i] = loo_mm_exact_eta(g, s, i, one.data(), zero.data(), &sg[i]);
-      ll[i] = loo_ll(y, eta[i], sg[i]);
-    }
-    loo_exact_cell_host(ll.data(), eta.data(), sg.data(), nullptr, n, y, excluded, r_eff, tc, p_lo, p_hi, out);
-    return;
-  }
+  if (!(rec[5] > 0.0)) { loo_mm_exact_unmatched_host(g, s, r_eff, tc, p_lo, p_hi, out); return; }
   // ---- steps 2 - 6
+  const std::vector<double> one((size_t)nc, 1.0), zero((size_t)nc, 0.0);
   const double* A = rec + kLooMmHead;
   const double* B = A + nc;
   std::vector<double> w, lx;
@@ -176,18 +164,10 @@ inline void loo_mm_exact_split_from_record_host(const LooMmGene& g, int s, doubl
   const double khat_split = loo_mm_split_weights_host(g, s, r_eff, A, B, w, lx, &any);
   if (!any) { loo_exact_store_nan(out, y, excluded); return; }
   // ---- step 8
-  double mxw = -INFINITY, sw = 0.0;
-  for (long i = 0; i < n; ++i) mxw = w[i] > mxw ? w[i] : mxw;
-  for (long i = 0; i < n; ++i) { w[i] = exp(w[i] - mxw); sw += w[i]; }
-  for (long i = 0; i < n; ++i) w[i] = w[i] / sw;
-  const double log_tc = log(tc);
-  for (long i = 0; i < n; ++i) {
-    const bool first = i < h;
-    eta[i] = loo_mm_exact_eta(g, s, i, first ? A : one.data(), first ? B : zero.data(), &sg[i]);
-    if (ppc_exact_invalid(eta[i], ppc_exact_phi(ppc_exact_lnphi(sg[i], log_tc)))) { loo_exact_store_nan(out, y, excluded); return; }
-  }
-  int mx = 0;
-  const bool ok = ppc_exact_sweeps(ExactHostSums{w.data(), eta.data(), sg.data(), log_tc, n, &mx}, y, excluded, 1, p_lo, p_hi, true, out);
+  loo_mm_normalise_host(w);
+  const bool ok = loo_mm_predictive_host(g, s, w, tc, p_lo, p_hi, out, [&](long i, const double** a, const double** b) {
+    *a = i < h ? A : one.data(); *b = i < h ? B : zero.data();
+  });
   out[kPpcExactFields] = ok ? rec[3] : NAN;
   *ks = ok ? khat_split : NAN;
 }
