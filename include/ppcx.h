@@ -181,9 +181,9 @@ PPCX_API int ppcx_fit_loo_mcse(ppcx_fit* f, int n_genes, const int32_t* genes, c
  * needed (a ppcx_fit_from_draws fit is served). A deliberate deviation from loo, which transforms every coordinate; restated from
  * the paper, not run against R. Per cell above the threshold, at most max_iters times: the draws of the gene are shifted to their
  * weighted mean, or, if that does not lower khat, shifted and scaled to their weighted mean and variance; a step is kept only if
- * the cell's PSIS khat on the new ratios is strictly lower. No covariance step (loo's default), no split transformation: a
- * matched khat is necessary, not sufficient (ppcx_fit_loo_moment_match_split below adds the split transformation), and no
- * mcse / n_eff is given for a matched cell.
+ * the cell's PSIS khat on the new ratios is strictly lower. No covariance step (ppcx_fit_loo_moment_match_cov below adds it as a
+ * third candidate), no split transformation: a matched khat is necessary, not sufficient (ppcx_fit_loo_moment_match_split below
+ * adds the split transformation), and no mcse / n_eff is given for a matched cell.
  * Fits, genes, r_eff, limits and refusals as ppcx_fit_loo (an ADVI fit: PPCX_ERR_ARG, moment matching under the weights of
  * loo_approximate_posterior is not available); also PPCX_ERR_ARG for a k_threshold that is not finite or max_iters < 0.
  * out [n_genes][S][PPCX_LOO_MM_FIELDS(C)]: elpd_loo, p_loo (lpd of the original draws - elpd_loo), looic, khat (the final one),
@@ -209,11 +209,34 @@ PPCX_API int ppcx_fit_loo_moment_match(ppcx_fit* f, int n_genes, const int32_t* 
  * ones -- khat stays the matching's final one, as loo reports it, and khat_before, iterations, scale and shift are that entry's
  * bits -- then elpd_loo_matched (that entry's elpd_loo) and khat_split (the k-hat of the split ratios: a diagnostic, not a gate;
  * NaN for a cell with iterations = 0). A cell with iterations = 0 holds ppcx_fit_loo_moment_match's record bit for bit. A cell
- * none of whose split ratios is finite: elpd_loo, p_loo, looic and khat_split are NaN. No covariance step, no mcse / n_eff of a
- * matched cell. The same bits on every call, for any gene subset.                                                              */
+ * none of whose split ratios is finite: elpd_loo, p_loo, looic and khat_split are NaN. No covariance step (that is
+ * ppcx_fit_loo_moment_match_cov, which takes the split as an argument), no mcse / n_eff of a matched cell. The same bits on every
+ * call, for any gene subset.                                                                                                   */
 #define PPCX_LOO_MM_SPLIT_FIELDS(C) (PPCX_LOO_MM_FIELDS(C) + 2)
 PPCX_API int ppcx_fit_loo_moment_match_split(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double k_threshold,
                                              int max_iters, double* out);
+/* ppcx_fit_loo_moment_match with the covariance step as a third candidate (ppcx_loo_mm_cov.h; loo's shift_and_cov restated for
+ * one gene; restated from the paper and the published package; not run against R). A gene's coordinates are correlated by
+ * construction, and an outlying cell can move the posterior along a direction that no per-coordinate scale follows. The state
+ * is an affine map (transform, shift) of the gene's coordinates, initially the identity; candidates 1 and 2 are the shift and
+ * the shift with a per-coordinate scale on that state; candidate 3, tried when 1 is refused and 2 is refused or invalid, maps
+ * the draws' mean and covariance over the gene's d coordinates onto their weighted mean and weighted covariance (the unbiased
+ * form of stats::cov.wt) through the Cholesky factors of the two matrices. It is invalid, and so refused, when n <= d, when
+ * 1 - sum w^2 is not positive, or when a pivot of either factor is not finite or <= 0. Gates, tail length, tie rule and r_eff as
+ * ppcx_fit_loo_moment_match. split != 0: the split transformation of ppcx_fit_loo_moment_match_split on the matched cells with
+ * the map, the identity and the map's inverse (carried along the accepted steps on the device) as its three states.
+ * Fits, genes, r_eff, limits and refusals as ppcx_fit_loo_moment_match (an ADVI fit: PPCX_ERR_ARG; a ppcx_fit_from_draws fit is
+ * served).
+ * out [n_genes][S][PPCX_LOO_MM_COV_FIELDS(C)]: elpd_loo, p_loo, looic, khat (the matching's final one), khat_before, iterations
+ * (accepted steps), cov_iterations (those of the third kind), elpd_loo_matched (the unsplit estimate; elpd_loo itself without
+ * split), khat_split (NaN without split or with iterations = 0), transform [C + 1][C + 1] row-major and shift [C + 1] in the
+ * order intercept, slopes, sigma_raw: the matched draws are transform * draw + shift (a row or column the gene does not have
+ * is the identity's, its shift 0). A cell with iterations = 0 holds ppcx_fit_loo's four fields bit for bit, the identity and
+ * zeros. Still left out: the exact predictive under these weights, mcse / n_eff of a matched cell, ADVI fits. The same bits
+ * on every call, for any gene subset.                                                                                          */
+#define PPCX_LOO_MM_COV_FIELDS(C) (9 + ((C) + 1) * ((C) + 1) + ((C) + 1))
+PPCX_API int ppcx_fit_loo_moment_match_cov(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double k_threshold,
+                                           int max_iters, int split, double* out);
 /* The relative efficiency of the importance ratios per observed cell of a NUTS fit: what rstan::loo(fit) passes to loo::loo as
  * r_eff, loo::relative_eff(exp(log_lik), chain_id), so that ppcx_fit_loo / ppcx_fit_loo_predict with it report what rstan::loo(fit)
  * does without the log-likelihood matrix ever leaving the device. Fits, genes and refusals as ppcx_fit_loo; more than 128 chains:

@@ -28,6 +28,7 @@ EXPORTS = [
     "ppcx_fit_loo_predict", "ppcx_fit_relative_eff", "ppcx_fit_loo_mcse", "ppcx_fit_loo_approx", "ppcx_fit_loo_predict_approx",
     "ppcx_fit_ppc_exact", "ppcx_fit_loo_predict_exact", "ppcx_fit_loo_predict_exact_approx", "ppcx_fit_loo_moment_match",
     "ppcx_fit_loo_predict_exact_moment_match", "ppcx_fit_loo_moment_match_split", "ppcx_fit_loo_predict_exact_moment_match_split",
+    "ppcx_fit_loo_moment_match_cov",
 ]
 ABI_VERSION = 400           # include/ppcx.h PPCX_VERSION this binding was written for
 SUMMARY_FIELDS = ("mean", "sd", "q05", "q50", "q95", "rhat", "ess_bulk", "ess_tail")   # PPCX_SUMMARY_FIELDS, in order
@@ -38,6 +39,8 @@ PPC_EXACT_FIELDS = ("mean", "sd", "p_le", "p_ge", "lower", "upper", "y", "exclud
 LOO_EXACT_FIELDS = PPC_EXACT_FIELDS + ("khat",)                                          # PPCX_LOO_EXACT_FIELDS, in order
 LOO_MM_HEAD = LOO_FIELDS + ("khat_before", "iterations")     # PPCX_LOO_MM_FIELDS(C): these, then scale[C + 1] and shift[C + 1]
 LOO_MM_SPLIT_TAIL = ("elpd_loo_matched", "khat_split")       # PPCX_LOO_MM_SPLIT_FIELDS(C): PPCX_LOO_MM_FIELDS(C), then these
+# PPCX_LOO_MM_COV_FIELDS(C): these, then transform[C + 1][C + 1] and shift[C + 1]
+LOO_MM_COV_HEAD = LOO_MM_HEAD + ("cov_iterations",) + LOO_MM_SPLIT_TAIL
 
 
 class PpcxError(RuntimeError):
@@ -113,6 +116,7 @@ def load() -> C.CDLL:
     lib.ppcx_fit_loo_mcse.argtypes = [C.c_void_p, C.c_int, ip, dp, dp]
     lib.ppcx_fit_loo_moment_match.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_double, C.c_int, dp]
     lib.ppcx_fit_loo_moment_match_split.argtypes = lib.ppcx_fit_loo_moment_match.argtypes
+    lib.ppcx_fit_loo_moment_match_cov.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_double, C.c_int, C.c_int, dp]
     lib.ppcx_fit_loo_predict.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_double, C.c_double, C.c_double, C.c_ulonglong, dp]
     lib.ppcx_fit_relative_eff.argtypes = [C.c_void_p, C.c_int, ip, dp]
     lib.ppcx_fit_loo_approx.argtypes = [C.c_void_p, C.c_int, ip, dp]
@@ -822,26 +826,48 @@ class Fit:
             res["mcse_elpd_loo_total"] = loo_mcse_total(res)
         return res
 
-    def loo_moment_match(self, genes=None, r_eff=None, k_threshold=None, max_iters=30, split=False):
+    def loo_moment_match(self, genes=None, r_eff=None, k_threshold=None, max_iters=30, split=False, cov=False):
         """Fit.loo with gene-local moment matching of the cells whose khat exceeds k_threshold (ppcx_fit_loo_moment_match; the
         importance-weighted moment matching of loo::loo_moment_match, applied to the coordinates of the cell's own gene only --
         a deliberate deviation, restated from the paper and not run against R): Fit.loo's dict with `estimates` over the new
         values, plus `khat_before` (plain PSIS's khat; `khat` is the final one), `iterations` (accepted steps, int64), `scale`
         and `shift` [n_genes, S, C + 1] (the matched draws of the gene are scale * draw + shift, rows intercept, slopes,
         sigma_raw; 1 and 0 for a row the gene does not have) and `k_threshold`. A cell with iterations == 0 holds Fit.loo's
-        bits. k_threshold=None: inference.loo_threshold(n_draws). There is no covariance step and no split transformation: a
-        matched khat is necessary, not sufficient; no mcse / n_eff. Not for an ADVI fit. r_eff as Fit.loo.
+        bits. k_threshold=None: inference.loo_threshold(n_draws). Without the keywords below there is no covariance step and no
+        split transformation: a matched khat is necessary, not sufficient; no mcse / n_eff. Not for an ADVI fit. r_eff as Fit.loo.
         split=True (ppcx_fit_loo_moment_match_split): the split transformation of loo::loo_moment_match on the matched cells --
         the first n_draws // 2 draws in the fit's order (whole leading chains) are transformed, the others kept, and all are
         weighted against the mixture they come from, so elpd_loo, p_loo, looic and `estimates` no longer rest on the matched
         draws being a sample of a known density. `khat`, `khat_before`, `iterations`, `scale` and `shift` stay the matching's
         bits; added are `elpd_loo_matched` (the elpd_loo of split=False) and `khat_split` (the k-hat of the split ratios, a
-        diagnostic, NaN where iterations == 0)."""
+        diagnostic, NaN where iterations == 0).
+        cov=True (ppcx_fit_loo_moment_match_cov; restated from the paper and the published package, not run against R): the
+        covariance step as a third candidate, tried when the shift is refused and the scale is refused or invalid -- the gene's
+        draws are mapped so that their mean and covariance over its coordinates become the weighted ones. The state is then an
+        affine map: in place of `scale` the dict has `transform` [n_genes, S, C + 1, C + 1] (the matched draws are
+        transform @ draw + shift; a row or column the gene does not have is the identity's) and `cov_iterations` (the accepted
+        steps of that kind, int64); with split=True also `elpd_loo_matched` and `khat_split` as above."""
         if k_threshold is None:
             from .inference import loo_threshold
             k_threshold = loo_threshold(self.chains * self.n_keep)
         k_threshold, max_iters = float(k_threshold), int(max_iters)
         nc = self.model.C + 1
+        if cov:
+            fields = LOO_MM_COV_HEAD + tuple(f"transform{c}" for c in range(nc * nc)) + tuple(f"shift{c}" for c in range(nc))
+            _, res, last = self._loo_cells(genes, r_eff, fields, lambda n, g, re, out: load().ppcx_fit_loo_moment_match_cov(
+                self._h, n, g, re, k_threshold, max_iters, int(bool(split)), out))
+            tr = np.stack([res.pop(f"transform{c}") for c in range(nc * nc)], axis=-1)
+            res["transform"] = tr.reshape(tr.shape[:-1] + (nc, nc))
+            res["shift"] = np.stack([res.pop(f"shift{c}") for c in range(nc)], axis=-1)
+            for name in ("iterations", "cov_iterations"):
+                res[name] = res[name].astype(np.int64)
+            if not split:
+                for name in LOO_MM_SPLIT_TAIL:
+                    del res[name]
+            res["k_threshold"] = k_threshold
+            res.update(last)
+            res["estimates"] = loo_estimates(res, res["excluded"])
+            return res
         fields = LOO_MM_HEAD + tuple(f"scale{c}" for c in range(nc)) + tuple(f"shift{c}" for c in range(nc))
         if split:
             fields = fields + LOO_MM_SPLIT_TAIL

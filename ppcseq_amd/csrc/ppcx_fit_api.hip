@@ -188,6 +188,16 @@ extern "C" int ppcx_fit_loo_moment_match_split(ppcx_fit* f, int n_genes, const i
   if (rc != PPCX_OK) return rc;
   return hip_done(who, loo_mm_split_fit_cells(fc, k_threshold, max_iters, false, 1.0, 0.0, 1.0, out, loo_scratch_bytes(), f->m->stream.s));
 }
+// ... with the covariance step as the third candidate (ppcx_loo_mm_cov.h); split != 0: the split transformation of the matched
+// cells under the affine map, in the same kernel
+extern "C" int ppcx_fit_loo_moment_match_cov(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double k_threshold,
+                                             int max_iters, int split, double* out) {
+  const char* who = "ppcx_fit_loo_moment_match_cov";
+  std::vector<int> yenc; FitCells fc;
+  const int rc = loo_mm_prepare(who, f, n_genes, genes, r_eff, k_threshold, max_iters, nullptr, out, yenc, fc);
+  if (rc != PPCX_OK) return rc;
+  return hip_done(who, loo_mm_cov_fit_cells(fc, k_threshold, max_iters, split != 0, out, loo_scratch_bytes(), f->m->stream.s));
+}
 // ---- the leave-one-out predictive interval and LOO-PIT of the same cells (loo::E_loo / bayesplot::ppc_loo_intervals, ppc_loo_pit)
 static int loo_predict_check_probs(double p_lo, double p_hi) {
   if (!(p_lo >= 0.0 && p_lo < p_hi && p_hi <= 1.0)) return fail(PPCX_ERR_ARG, "need 0 <= p_lo < p_hi <= 1");

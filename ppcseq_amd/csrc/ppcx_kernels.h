@@ -315,6 +315,11 @@ hipError_t loo_mm_exact_fit_cells(const FitCells& fc, double k_threshold, int ma
 // [cells][loo_mm_split_fields(C)] (tc, p_lo, p_hi are not read); true: the exact predictive, out [cells][loo_mm_exact_split_fields(C)]
 hipError_t loo_mm_split_fit_cells(const FitCells& fc, double k_threshold, int max_iters, bool predictive, double tc, double p_lo,
                                   double p_hi, double* out, size_t scratch_bytes, hipStream_t st);
+// The matching with the covariance step as its third candidate (ppcx_loo_mm_cov.hip, statistic in ppcx_loo_mm_cov.h):
+// ppcx_loo_kernel over the cells, then one workgroup per cell with the affine state in static LDS; the same three arrays of n
+// doubles as loo_mm_fit_cells. split: the split transformation follows in the same workgroup. out [cells][loo_mm_cov_fields(C)]
+hipError_t loo_mm_cov_fit_cells(const FitCells& fc, double k_threshold, int max_iters, bool split, double* out, size_t scratch_bytes,
+                                hipStream_t st);
 // The relative efficiency of the same cells (ppcx_reff.hip, statistic in ppcx_reff.h): one workgroup per cell; the split values
 // (8 bytes each) in LDS for fits of up to kPsisLdsDraws draws, beyond that in the scratch. Of `l` it uses T / y / expo / X / S / C
 // or cols, n = chains n_keep, cell0, n_cells, scratch ([launch's cells][2 chains (n_keep / 2)]) and out ([cells], one value

@@ -40,8 +40,8 @@
 //      if neither is accepted the loop ends. The Jacobian of the transform is the same for every draw and cancels.
 //   4. elpd_loo = logsumexp(lw + ll_gs(t)) - logsumexp(lw) under the final state; lpd that of the original draws;
 //      p_loo = lpd - elpd_loo, looic = -2 elpd_loo, khat the final k, khat_before that of plain PSIS.
-//   5. Left out: the covariance step (loo's default leaves it off as well); the split transformation; mcse / n_eff of a matched
-//      cell. Without the split step repeated shifts can overshoot on a very fine posterior sample: khat falls below 0.7 while
+//   5. Left out here: the covariance step (it is ppcx_loo_mm_cov.h, ppcx_fit_loo_moment_match_cov, which restates this header's
+//      candidates on an affine state and adds the third); the split transformation; mcse / n_eff of a matched cell. Without the split step repeated shifts can overshoot on a very fine posterior sample: khat falls below 0.7 while
 //      the error of elpd_loo stays at plain PSIS's size (seen on a 2-D grid posterior of 2500 x 2500 points at n = 4000; not at
 //      900 x 900). khat of a matched cell is therefore necessary, not sufficient. The split transformation is
 //      ppcx_loo_mm_split.h (ppcx_fit_loo_moment_match_split), which starts from this header's record.

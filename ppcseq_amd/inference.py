@@ -230,6 +230,7 @@ class CheckContext:
     exact_loo_moment_match: bool = False   # exact_loo_intervals reads Fit.loo_predict_exact_moment_match in place of Fit.loo_predict_exact
     loo_moment_match_split: bool = False         # Fit.loo_moment_match is read with split=True
     exact_loo_moment_match_split: bool = False   # Fit.loo_predict_exact_moment_match is read with split=True
+    loo_moment_match_cov: bool = False           # Fit.loo_moment_match is read with cov=True
 
 
 @dataclass(frozen=True)
@@ -261,10 +262,11 @@ def _loo_warnings(result, fit):
 
 def _read_loo(fit, ctx):
     """check_loo's read: Fit.loo(r_eff, mcse), or with loo_moment_match Fit.loo_moment_match(r_eff) (its khat is the final one),
-    with loo_moment_match_split also split=True"""
+    with loo_moment_match_split also split=True, with loo_moment_match_cov also cov=True"""
     if ctx.loo_moment_match:
         split = dict(split=True) if ctx.loo_moment_match_split else {}
-        return fit.loo_moment_match(np.arange(ctx.K), r_eff=ctx.loo_r_eff, **split)
+        cov = dict(cov=True) if ctx.loo_moment_match_cov else {}
+        return fit.loo_moment_match(np.arange(ctx.K), r_eff=ctx.loo_r_eff, **split, **cov)
     return fit.loo(np.arange(ctx.K), r_eff=ctx.loo_r_eff, mcse=bool(ctx.loo_mcse))
 
 
@@ -327,6 +329,8 @@ MODIFIERS = (       # (option, the options of which it needs one, what it is tol
      "loo_moment_match_split needs loo_moment_match: it is the split transformation of the cells that it has matched"),
     ("exact_loo_moment_match_split", ("exact_loo_moment_match",),
      "exact_loo_moment_match_split needs exact_loo_moment_match: it is the split transformation of the cells that it has matched"),
+    ("loo_moment_match_cov", ("loo_moment_match",),
+     "loo_moment_match_cov needs loo_moment_match: it is the covariance step of the matching of its cells"),
 )
 LOO_MOMENT_MATCH_MCSE = ("loo_mcse cannot be combined with loo_moment_match: the Monte-Carlo standard error and n_eff are those of "
                          "plain PSIS weights and are not given for a matched cell")
@@ -400,7 +404,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                  exact_approximation_loo_intervals=False,
                  exact_loo_moment_match=False,
                  loo_moment_match_split=False,
-                 exact_loo_moment_match_split=False):
+                 exact_loo_moment_match_split=False,
+                 loo_moment_match_cov=False):
     """One inference pass (discovery or test) of ppcseq on the GPU.
 
     counts            G x S integer matrix, genes ordered with the `how_many_to_check` checked genes first
@@ -441,8 +446,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                       `mcse_elpd_loo_total` (Fit.loo(mcse=True); pareto_k_table reads it). It raises no further warning.
                       devices=[...]: over the pooled chains. Needs check_loo.
     loo_moment_match  True: `res.loo` comes from Fit.loo_moment_match: the cells whose k-hat exceeds loo_threshold get gene-local
-                      moment matching (a restatement of loo::loo_moment_match on the cell's own gene, without its split and
-                      covariance steps); `res.loo` then also carries `khat_before`, `iterations`, `scale`, `shift` and
+                      moment matching (a restatement of loo::loo_moment_match on the cell's own gene; its split and
+                      covariance steps are loo_moment_match_split and loo_moment_match_cov); `res.loo` then also carries `khat_before`, `iterations`, `scale`, `shift` and
                       `k_threshold`, and the k-hat warning reads the final `khat`. Flags and frame are those of the call
                       without it. devices=[...]: over the pooled chains (no lp__ is needed). Needs check_loo; not with loo_mcse
                       (a matched cell has no mcse / n_eff).
@@ -480,6 +485,10 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
     exact_loo_moment_match_split  True: exact_loo_moment_match reads Fit.loo_predict_exact_moment_match(split=True), the same
                       transformation for the predictive; `res.exact_loo_intervals` then also carries `khat_split`. Needs
                       exact_loo_moment_match.
+    loo_moment_match_cov  True: loo_moment_match reads Fit.loo_moment_match(cov=True): the covariance step as a third candidate of
+                      the matching (restated from the paper and the published package; not run against R); `res.loo` then carries
+                      `transform` in place of `scale`, and `cov_iterations`. Free to combine with loo_moment_match_split; refused
+                      with loo_mcse as loo_moment_match is. Needs loo_moment_match. The exact predictive takes no such flag.
     Returns an InferenceResult.
     """
     counts = np.asarray(counts)
@@ -543,7 +552,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                                               loo_moment_match=bool(checks.get("loo_moment_match", False)),
                                               exact_loo_moment_match=bool(checks.get("exact_loo_moment_match", False)),
                                               loo_moment_match_split=bool(checks.get("loo_moment_match_split", False)),
-                                              exact_loo_moment_match_split=bool(checks.get("exact_loo_moment_match_split", False))),
+                                              exact_loo_moment_match_split=bool(checks.get("exact_loo_moment_match_split", False)),
+                                              loo_moment_match_cov=bool(checks.get("loo_moment_match_cov", False))),
                                   checks, res)
         for msg in msgs:
             warnings.warn(msg, RuntimeWarning, stacklevel=2)
@@ -633,7 +643,8 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
                                                  loo_moment_match=bool(checks.get("loo_moment_match", False)),
                                               exact_loo_moment_match=bool(checks.get("exact_loo_moment_match", False)),
                                               loo_moment_match_split=bool(checks.get("loo_moment_match_split", False)),
-                                              exact_loo_moment_match_split=bool(checks.get("exact_loo_moment_match_split", False))),
+                                              exact_loo_moment_match_split=bool(checks.get("exact_loo_moment_match_split", False)),
+                                              loo_moment_match_cov=bool(checks.get("loo_moment_match_cov", False))),
                                   checks, res)
         finally:
             fit.close()
