@@ -28,7 +28,7 @@ LOO_MM_COV_EXPORT int loo_mm_cov_twin_cell(const double* T, const double* U, lon
 #ifdef PPCX_HOST_MAIN
 #include <stdio.h>
 // fixed columns: n = 1, n = d, n = d + 1, longer ones; a checked gene (d = 4), an unchecked one (d = 2) and a gene whose two slope
-// rows are the same column (a singular Sigma and Sigma_w)
+// rows are the same column (a singular Sigma and Sigma_w); then 17 coordinates
 int main() {
   const int C = 3, S = 5, nc = C + 1;
   const int yrow[S] = {120, 180, -96, 160, 2500};
@@ -67,6 +67,38 @@ int main() {
     }
   }
   printf("matched cells: %d, with a covariance step: %d\n", matched, cov);
-  return matched > 0 && cov > 0 ? 0 : 1;
+  // the widest design, C = kMaxC = 16 (nc = 17): ones and fifteen indicators, sample s in level s % 16; n = d - 1, d, d + 1, longer
+  const int CW = 16, SW = 20, nw = CW + 1;
+  int yw[SW];
+  double ew[SW], XW[CW * SW] = {0.0};
+  for (int s = 0; s < SW; ++s) { yw[s] = 150 + 37 * (s % 5); ew[s] = 0.01 * s; XW[s] = 1.0; if (s % CW) XW[(s % CW) * SW + s] = 1.0; }
+  yw[5] = 1500; yw[3] = -201;
+  int wide_cov = 0;
+  for (long n : {16L, 17L, 18L, 300L}) {
+    std::vector<double> T(nw * n), U(6 * n);
+    for (long i = 0; i < n; ++i) {
+      const double x = (double)i;
+      T[i] = 5.0 + 0.2 * sin(x) + 0.1 * cos(3.0 * x);
+      for (int c = 1; c < CW; ++c) T[c * n + i] = 0.1 * sin((2.0 + 0.7 * c) * x + c) + (0.3 - 0.04 * c) * (T[i] - 5.0);
+      T[CW * n + i] = -1.0 + 0.3 * sin(5.0 * x) - 0.4 * (T[i] - 5.0);
+      const double u[6] = {0.5, 0.6, -1.0, -1.2, 0.0, -0.9};
+      for (int k = 0; k < 6; ++k) U[k * n + i] = u[k] + 0.01 * sin((double)(i + k));
+    }
+    for (int checked = 0; checked < 2; ++checked)
+      for (int s : {3, 5, 19})
+        for (int split = 0; split < 2; ++split) {
+          const ppcx::LooMmGene g = gene_of(T.data(), U.data(), n, CW, SW, checked, yw, ew, XW, 5.6);
+          double out[9 + nw * nw + nw], inv[nw * nw + nw + 1];
+          std::vector<int> kinds;
+          ppcx::loo_mm_cov_cell_host(g, s, 0.8, 0.1, 6, split != 0, out, &kinds, inv);
+          printf("C=16 n=%ld checked=%d s=%d split=%d elpd_loo=%.6f khat=%g iterations=%g cov=%g\n", n, checked, s, split, out[0], out[3],
+                 out[5], out[6]);
+          wide_cov += checked && out[6] > 0.0;
+          if (n <= (checked ? nw : 2) && out[6] != 0.0) return 1;
+          for (int j = 0; j < nw * nw + nw; ++j) if (out[5] > 0.0 && !(out[9 + j] == out[9 + j])) return 1;
+        }
+  }
+  printf("C = 16: checked-gene cells with a covariance step: %d\n", wide_cov);
+  return matched > 0 && cov > 0 && wide_cov > 0 ? 0 : 1;
 }
 #endif

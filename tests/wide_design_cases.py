@@ -5,7 +5,13 @@ of two genes side by side and a wrong stride reads the other gene's) on
     "covariate"  C = 3, S = 6: ones, a 0/1 group and a centred continuous covariate; one excluded cell in gene 0's row
     "factor4"    C = 4, S = 8: ones and three indicators; one excluded cell in gene 1's row
 
-The product grid of tests/loo_mm_cases.py does not reach d = 4 or 5 coordinates, so a gene's draws come from n independent
+and, for tests/test_widest_designs_host.py and tests/test_gpu_widest_designs.py, on the widest designs the library takes
+
+    "columns8"   C = 8, S = 12: ones, six indicators and a centred continuous covariate; one excluded cell in gene 1's row
+    "columns16"  C = 16, S = 20: ones and fifteen indicators, the first levels twice; one excluded cell in gene 1's row
+    "columns15"  "columns16" cut down to its first 15 columns: (C + 1)^2 = 256
+
+The product grid of tests/loo_mm_cases.py does not reach d = 4 or more coordinates, so a gene's draws come from n independent
 random-walk Metropolis chains, one per draw, on the restatement's own density (tests/loo_mm_restate.local_density) at HYPER; the
 draws' hyper-parameters carry the jitter of loo_mm_cases.tiny_set. A draw set is the dict of tests/loo_mm_cases.py and
 loo_mm_cases.gene_of() cuts a gene out of it."""
@@ -22,6 +28,18 @@ BOUND = 1e-9
 WIDE_MEASURED = dict(mm=3.0e-11, exact=3.0e-11, split=5.1e-11, density=1.4e-11)     # 2.95e-11, 2.95e-11, 5.01e-11, 1.37e-11
 WIDE_GPU_MEASURED = dict(mm=1.4e-11, split=2.7e-11, exact=1.4e-11, exact_split=2.7e-11,         # 1.38e-11, 2.68e-11, twice
                          counts=1.8e-11)                                                      # 1.75e-11 at n = 1000
+# The same on the cells of "columns8", "columns16" and "columns15" (designed(widest=True), loo_mm_cov_cases.designed(widest=True)),
+# one value per statistic and width. WIDEST_MEASURED: tests/test_widest_designs_host.py prints them (`cov`: the covariance form on
+# its designed cells, split both ways; `counts`: on the draw-count cells); WIDEST_GPU_MEASURED: tests/test_gpu_widest_designs.py.
+WIDEST_MEASURED = dict(columns8=dict(mm=5.2e-11, exact=8.1e-11, split=5.7e-11, cov=9.0e-11, counts=8.7e-12),     # 5.12e-11, 8.02e-11, 5.62e-11, 8.95e-11, 8.66e-12 (n = 257)
+                       columns16=dict(mm=2.8e-11, exact=2.8e-11, split=3.7e-11, cov=2.2e-10, counts=4.3e-11),    # 2.76e-11, 2.76e-11, 3.67e-11, 2.197e-10, 4.29e-11 (n = 255)
+                       columns15=dict(cov=2.2e-11))                                                              # 2.194e-11
+WIDEST_GPU_MEASURED = dict(
+    columns8=dict(mm=1.6e-11, split=1.6e-11, exact=2.6e-11, exact_split=1.5e-11, cov=5.5e-11, diag=1.4e-13,      # 1.599e-11 twice, 2.506e-11, 1.442e-11, 5.43e-11, 1.34e-13
+                  counts=1.4e-11),                                                                               # 1.32e-11 at n = 257
+    columns16=dict(mm=2.6e-11, split=3.0e-11, exact=2.6e-11, exact_split=2.6e-11, cov=4.9e-11, diag=4.8e-13,     # 2.513e-11, 2.995e-11, 2.513e-11 twice, 4.88e-11, 4.74e-13
+                   counts=2.1e-11),                                                                              # 2.08e-11 at n = 257
+    columns15=dict(cov=9.2e-12, diag=3.1e-14))                                                                   # 9.19e-12, 3.03e-14
 
 
 def metropolis(rng, n, y, excl, expo, X, checked, steps=300, sd=0.25):
@@ -62,6 +80,36 @@ SPECS = {
 }
 
 
+# ---- the widest designs (tests/test_widest_designs_host.py, tests/test_gpu_widest_designs.py): C = 8 with a continuous covariate
+# (the generic constants path; the widest design that may hold one) and C = 16 (kMaxC: ones and fifteen indicators). Sample s sits
+# in level s % C (level 0: the ones alone), so with S > C + 1 samples the first levels occur twice and a slope is not determined by
+# a single cell. Counts from 80..400, on them the outliers of the narrower sets: 2 500 in gene 0, 2 200 in gene 1, 2 in gene 2.
+COV8 = (-1.35, 0.15, 0.65, -0.65, 1.25, -0.05, 0.85, -0.95, 0.45, -0.25, 1.05, -1.15)      # centred, no integer among them
+
+
+def indicator_design(S, Cc):
+    X = np.zeros((S, Cc))
+    X[:, 0] = 1.0
+    for s in range(S):
+        if s % Cc:
+            X[s, s % Cc] = 1.0
+    return X
+
+
+def _widest_counts(seed, S):
+    y = np.random.default_rng(seed).integers(80, 401, (G, S))
+    y[0, 5], y[1, 2], y[2, 1] = 2500, 2200, 2
+    return y.tolist()
+
+
+X8 = indicator_design(12, 8)
+X8[:, 7] = COV8
+X16 = indicator_design(20, 16)
+SPECS["columns8"] = dict(X=X8, seed=24, excl=((1, 3),), counts=_widest_counts(124, 12))
+SPECS["columns16"] = dict(X=X16, seed=25, excl=((1, 3),), counts=_widest_counts(128, 20))
+WIDEST = ("columns8", "columns16")
+
+
 def wide_set(name, n=1000, seed=None, hyper_jitter=0.02):
     spec = SPECS[name]
     seed = spec["seed"] if seed is None else seed
@@ -87,24 +135,73 @@ def wide_set(name, n=1000, seed=None, hyper_jitter=0.02):
                 draws=u)
 
 
+def cut_columns(ds, Cc):
+    """the draw set on the first Cc columns of its design: the same counts, hyper-parameters, intercepts, first Cc - 1 slopes and
+    sigma_raw, laid out as a Cc-column model has them. An indicator design stays one: a sample of a level that is cut joins
+    level 0. The draws are not a posterior sample of the narrower model; the statistics take any draws."""
+    n_genes, k = ds["counts"].shape[0], ds["K"]
+    C0 = ds["X"].shape[1]
+    assert 2 <= Cc <= C0
+    d0, d1 = dims(n_genes, C0, k), dims(n_genes, Cc, k)
+    u0 = ds["draws"]
+    u = np.zeros((u0.shape[0], d1["D"]))
+    u[:, 0:3], u[:, d1["tail"]:d1["tail"] + 3] = u0[:, 0:3], u0[:, d0["tail"]:d0["tail"] + 3]
+    for g in range(n_genes):
+        u[:, d1["intercept"] + g], u[:, d1["sigma_raw"] + g] = u0[:, d0["intercept"] + g], u0[:, d0["sigma_raw"] + g]
+        if g < k:
+            for c in range(1, Cc):
+                u[:, slope_index(d1, Cc, c, g)] = u0[:, slope_index(d0, C0, c, g)]
+    return dict(ds, X=np.ascontiguousarray(ds["X"][:, :Cc]), draws=u)
+
+
 _SETS = {}
 
 
 def draw_set(name):
-    """ "covariate" and "factor4" at 1 000 draws; "long": "factor4" at 4 097 draws (its prefixes are the draw counts of the
-    device test). Built once."""
+    """ "covariate", "factor4", "columns8" and "columns16" at 1 000 draws; "long": "factor4" at 4 097 draws (its prefixes are the
+    draw counts of the device test); "columns15": "columns16" cut down to its first 15 columns ((C + 1)^2 = 256, the workgroup's
+    size). Built once."""
     if name not in _SETS:
-        _SETS[name] = wide_set("factor4", n=4097, seed=23) if name == "long" else wide_set(name)
+        if name == "columns15":
+            _SETS[name] = cut_columns(draw_set("columns16"), 15)
+        else:
+            _SETS[name] = wide_set("factor4", n=4097, seed=23) if name == "long" else wide_set(name)
     return _SETS[name]
 
 
-def designed():
-    """dicts of name, set, g, s, r_eff, k_threshold, max_iters and `kinds`, as tests/loo_mm_cases.designed() gives them"""
+def designed(widest=False):
+    """dicts of name, set, g, s, r_eff, k_threshold, max_iters and `kinds`, as tests/loo_mm_cases.designed() gives them.
+    widest: the cells of "columns8" and "columns16" instead (a list of their own: the cells of C = 3 and 4 stay the list they
+    were, with the constants recorded for them)"""
     cs = []
 
     def add(name, set_, g, s, kinds, r_eff=1.0, k_threshold=0.7, max_iters=30):
         cs.append(dict(name=name, set=set_, g=g, s=s, kinds=kinds, r_eff=r_eff, k_threshold=k_threshold, max_iters=max_iters))
 
+    if widest:
+        add("columns8: one shift (d = 9)", "columns8", 0, 0, [1], k_threshold=0.5)
+        add("columns8: one shift in gene 1", "columns8", 1, 10, [1])
+        add("columns8: shift, then shift and scale", "columns8", 1, 4, [1, 2])
+        add("columns8: shift and scale first at gene 1's outlier", "columns8", 1, 2, [2, 1, 2], k_threshold=0.5)
+        add("columns8: r_eff = 0.4", "columns8", 0, 6, [1, 2, 2], r_eff=0.4)
+        add("columns8: outlier in the unchecked gene", "columns8", 2, 1, [1])
+        add("columns8: four steps in the unchecked gene", "columns8", 2, 1, [1, 1, 1, 2], k_threshold=0.1)
+        add("columns8: excluded cell", "columns8", 1, 3, [])
+        add("columns8: below the threshold", "columns8", 0, 7, [])
+        add("columns8: stops at max_iters", "columns8", 1, 6, [1, 2], max_iters=2)
+        add("columns16: one shift (d = 17)", "columns16", 0, 1, [1])
+        add("columns16: one shift at a level that occurs once", "columns16", 0, 7, [1])
+        add("columns16: shift, shift and scale, shift", "columns16", 0, 15, [1, 2, 1])
+        add("columns16: shift, then two shifts and scales in gene 1", "columns16", 1, 7, [1, 2, 2])
+        add("columns16: shift and scale alone", "columns16", 0, 8, [2])
+        add("columns16: r_eff = 0.4", "columns16", 1, 9, [2, 1], r_eff=0.4, k_threshold=0.5)
+        add("columns16: outlier in the unchecked gene", "columns16", 2, 1, [1])
+        add("columns16: three steps in the unchecked gene", "columns16", 2, 1, [1, 1, 2], k_threshold=0.1)
+        add("columns16: excluded cell", "columns16", 1, 3, [])
+        add("columns16: below the threshold", "columns16", 0, 3, [])
+        add("columns16: stops at max_iters", "columns16", 1, 2, [1, 1], max_iters=2)
+        add("columns16: stops at max_iters after a scale", "columns16", 0, 14, [1, 1, 2], max_iters=3)
+        return cs
     add("covariate: repeated shifts at the outlier (d = 4)", "covariate", 0, 5, [1, 1, 1])
     add("covariate: shift, then shift and scale (d = 4)", "covariate", 0, 4, [1, 2], k_threshold=0.5)
     add("covariate: gene 1, shifts, then shift and scale", "covariate", 1, 0, [1, 1, 2], k_threshold=0.5)
