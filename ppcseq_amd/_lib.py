@@ -858,25 +858,20 @@ class Fit:
                 self._h, n, g, re, k_threshold, max_iters, int(bool(split)), out))
             tr = np.stack([res.pop(f"transform{c}") for c in range(nc * nc)], axis=-1)
             res["transform"] = tr.reshape(tr.shape[:-1] + (nc, nc))
-            res["shift"] = np.stack([res.pop(f"shift{c}") for c in range(nc)], axis=-1)
-            for name in ("iterations", "cov_iterations"):
-                res[name] = res[name].astype(np.int64)
             if not split:
                 for name in LOO_MM_SPLIT_TAIL:
                     del res[name]
-            res["k_threshold"] = k_threshold
-            res.update(last)
-            res["estimates"] = loo_estimates(res, res["excluded"])
-            return res
-        fields = LOO_MM_HEAD + tuple(f"scale{c}" for c in range(nc)) + tuple(f"shift{c}" for c in range(nc))
-        if split:
-            fields = fields + LOO_MM_SPLIT_TAIL
-        entry = load().ppcx_fit_loo_moment_match_split if split else load().ppcx_fit_loo_moment_match
-        _, res, last = self._loo_cells(genes, r_eff, fields, lambda n, g, re, out: entry(
-            self._h, n, g, re, k_threshold, max_iters, out))
-        for name in ("scale", "shift"):
-            res[name] = np.stack([res.pop(f"{name}{c}") for c in range(nc)], axis=-1)
-        res["iterations"] = res["iterations"].astype(np.int64)
+        else:
+            fields = LOO_MM_HEAD + tuple(f"scale{c}" for c in range(nc)) + tuple(f"shift{c}" for c in range(nc))
+            if split:
+                fields = fields + LOO_MM_SPLIT_TAIL
+            entry = load().ppcx_fit_loo_moment_match_split if split else load().ppcx_fit_loo_moment_match
+            _, res, last = self._loo_cells(genes, r_eff, fields, lambda n, g, re, out: entry(
+                self._h, n, g, re, k_threshold, max_iters, out))
+            res["scale"] = np.stack([res.pop(f"scale{c}") for c in range(nc)], axis=-1)
+        res["shift"] = np.stack([res.pop(f"shift{c}") for c in range(nc)], axis=-1)
+        for name in ("iterations", "cov_iterations") if cov else ("iterations",):
+            res[name] = res[name].astype(np.int64)
         res["k_threshold"] = k_threshold
         res.update(last)
         res["estimates"] = loo_estimates(res, res["excluded"])

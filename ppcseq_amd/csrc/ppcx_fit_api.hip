@@ -171,32 +171,36 @@ static int loo_mm_prepare(const char* who, ppcx_fit* f, int n_genes, const int32
   if (rc == PPCX_OK) rc = loo_fit_reff(who, fc, r_eff);
   return rc;
 }
-extern "C" int ppcx_fit_loo_moment_match(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double k_threshold,
-                                         int max_iters, double* out) {
-  const char* who = "ppcx_fit_loo_moment_match";
+// The elpd forms: the checks, the cells, then walk(fc, scratch_bytes, stream) -- the entry's driver over them
+template <class Walk>
+static int loo_mm_elpd_entry(const char* who, ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double k_threshold,
+                             int max_iters, double* out, Walk walk) {
   std::vector<int> yenc; FitCells fc;
   const int rc = loo_mm_prepare(who, f, n_genes, genes, r_eff, k_threshold, max_iters, nullptr, out, yenc, fc);
   if (rc != PPCX_OK) return rc;
-  return hip_done(who, loo_mm_fit_cells(fc, k_threshold, max_iters, out, loo_scratch_bytes(), f->m->stream.s));
+  return hip_done(who, walk(fc, loo_scratch_bytes(), f->m->stream.s));
+}
+extern "C" int ppcx_fit_loo_moment_match(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double k_threshold,
+                                         int max_iters, double* out) {
+  return loo_mm_elpd_entry("ppcx_fit_loo_moment_match", f, n_genes, genes, r_eff, k_threshold, max_iters, out,
+                           [&](const FitCells& fc, size_t bytes, hipStream_t st) { return loo_mm_fit_cells(fc, k_threshold, max_iters, out, bytes, st); });
 }
 // ... with the split transformation of the matched cells (ppcx_loo_mm_split.h): the matching's kernels, then the split
 extern "C" int ppcx_fit_loo_moment_match_split(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double k_threshold,
                                                int max_iters, double* out) {
-  const char* who = "ppcx_fit_loo_moment_match_split";
-  std::vector<int> yenc; FitCells fc;
-  const int rc = loo_mm_prepare(who, f, n_genes, genes, r_eff, k_threshold, max_iters, nullptr, out, yenc, fc);
-  if (rc != PPCX_OK) return rc;
-  return hip_done(who, loo_mm_split_fit_cells(fc, k_threshold, max_iters, false, 1.0, 0.0, 1.0, out, loo_scratch_bytes(), f->m->stream.s));
+  return loo_mm_elpd_entry("ppcx_fit_loo_moment_match_split", f, n_genes, genes, r_eff, k_threshold, max_iters, out,
+                           [&](const FitCells& fc, size_t bytes, hipStream_t st) {
+    return loo_mm_split_fit_cells(fc, k_threshold, max_iters, false, 1.0, 0.0, 1.0, out, bytes, st);
+  });
 }
 // ... with the covariance step as the third candidate (ppcx_loo_mm_cov.h); split != 0: the split transformation of the matched
 // cells under the affine map, in the same kernel
 extern "C" int ppcx_fit_loo_moment_match_cov(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double k_threshold,
                                              int max_iters, int split, double* out) {
-  const char* who = "ppcx_fit_loo_moment_match_cov";
-  std::vector<int> yenc; FitCells fc;
-  const int rc = loo_mm_prepare(who, f, n_genes, genes, r_eff, k_threshold, max_iters, nullptr, out, yenc, fc);
-  if (rc != PPCX_OK) return rc;
-  return hip_done(who, loo_mm_cov_fit_cells(fc, k_threshold, max_iters, split != 0, out, loo_scratch_bytes(), f->m->stream.s));
+  return loo_mm_elpd_entry("ppcx_fit_loo_moment_match_cov", f, n_genes, genes, r_eff, k_threshold, max_iters, out,
+                           [&](const FitCells& fc, size_t bytes, hipStream_t st) {
+    return loo_mm_cov_fit_cells(fc, k_threshold, max_iters, split != 0, out, bytes, st);
+  });
 }
 // ---- the leave-one-out predictive interval and LOO-PIT of the same cells (loo::E_loo / bayesplot::ppc_loo_intervals, ppc_loo_pit)
 static int loo_predict_check_probs(double p_lo, double p_hi) {

@@ -13,7 +13,10 @@
 // deliberate deviation from loo.
 //
 // Shared by the gfx950 kernel (ppcx_loo_mm.hip) and the CPU check (tests/loo_mm_host): the blocks below are
-// `__host__ __device__`; loo_mm_cell_host at the end is their sequential composition.
+// `__host__ __device__`; loo_mm_cell_host at the end is their sequential composition. The local density (the prior, eta, q and
+// the cell's log-likelihood), the moment sweeps and the sequential cell are stated here once, over a state's point and a policy:
+// ppcx_loo_mm_cov.h instantiates them with its affine state. The two kernels keep a body each over the one density
+// (ppcx_loo_mm.hip, ppcx_loo_mm_cov.hip).
 //
 // One cell (g, s) from the gene's rows of the transposed table T[c][draw] (c = 0 intercept, 1 .. C - 1 slopes, C sigma_raw), the
 // draws' six unconstrained hyper-parameters U[k][draw], the gene's encoded counts, r_eff, k_threshold and max_iters:
@@ -40,8 +43,8 @@
 //      if neither is accepted the loop ends. The Jacobian of the transform is the same for every draw and cancels.
 //   4. elpd_loo = logsumexp(lw + ll_gs(t)) - logsumexp(lw) under the final state; lpd that of the original draws;
 //      p_loo = lpd - elpd_loo, looic = -2 elpd_loo, khat the final k, khat_before that of plain PSIS.
-//   5. Left out here: the covariance step (it is ppcx_loo_mm_cov.h, ppcx_fit_loo_moment_match_cov, which restates this header's
-//      candidates on an affine state and adds the third); the split transformation; mcse / n_eff of a matched cell. Without the split step repeated shifts can overshoot on a very fine posterior sample: khat falls below 0.7 while
+//   5. Left out here: the covariance step (it is ppcx_loo_mm_cov.h, ppcx_fit_loo_moment_match_cov, which runs this header's
+//      cell on an affine state and adds the third candidate); the split transformation; mcse / n_eff of a matched cell. Without the split step repeated shifts can overshoot on a very fine posterior sample: khat falls below 0.7 while
 //      the error of elpd_loo stays at plain PSIS's size (seen on a 2-D grid posterior of 2500 x 2500 points at n = 4000; not at
 //      900 x 900). khat of a matched cell is therefore necessary, not sufficient. The split transformation is
 //      ppcx_loo_mm_split.h (ppcx_fit_loo_moment_match_split), which starts from this header's record.
@@ -77,13 +80,18 @@ PPCX_HD double loo_mm_coord(const LooMmGene& g, int c, long i, const double* A, 
   PPCX_NO_CONTRACT
   return A[c] * g.Tg[(long)c * g.n + i] + B[c];
 }
-// linear predictor of sample s at draw i under the state, t0 the transformed intercept
-PPCX_HD double loo_mm_eta(const LooMmGene& g, int s, long i, double t0, const double* A, const double* B) {
-  PPCX_NO_CONTRACT
-  double eta = g.expo[s] + g.X[s] * t0;
-  for (int c = 1; c < g.C; ++c) eta += g.X[(long)c * g.S + s] * loo_mm_coord(g, c, i, A, B);
-  return eta;
-}
+// A state maps draw i of the table to a point t: t(c) is row c of the draw under the state. The local density below reads a
+// point and nothing else of a state; the moment sweeps read one coordinate at a time (coord). The diagonal state (A, B) forms a
+// coordinate where it is read and keeps no array; the affine state is ppcx_loo_mm_cov.h's LooMmAffine.
+struct LooMmDiag {
+  const double* A; const double* B;
+  struct Point {
+    const LooMmGene& g; long i; const double* A; const double* B;
+    PPCX_HD double operator()(int c) const { return loo_mm_coord(g, c, i, A, B); }
+  };
+  PPCX_HD double coord(const LooMmGene& g, int c, long i) const { return loo_mm_coord(g, c, i, A, B); }
+  PPCX_HD Point point(const LooMmGene& g, long i) const { return Point{g, i, A, B}; }
+};
 // loo_ll with the dispersion's point formed by the caller (once per draw)
 PPCX_HD double loo_mm_ll(int y, double eta, double sigma_raw, const DispPoint& p) {
   PPCX_NO_CONTRACT
@@ -93,8 +101,17 @@ PPCX_HD double loo_mm_ll(int y, double eta, double sigma_raw, const DispPoint& p
   const double lw = loo_log1pexp(eta + sigma_raw);
   return yd * eta - yd - (yd + p.phi) * lw + F - lgamma_int1(yd);
 }
-// the gene's prior terms at draw i under the state (step 1), t0 / sg the transformed intercept and sigma_raw
-PPCX_HD double loo_mm_prior(const LooMmGene& g, long i, double t0, double sg, const double* A, const double* B) {
+// linear predictor of sample s at the point t, t0 = t(0)
+template <class Point>
+PPCX_HD double loo_mm_eta_at(const LooMmGene& g, int s, double t0, const Point& t) {
+  PPCX_NO_CONTRACT
+  double eta = g.expo[s] + g.X[s] * t0;
+  for (int c = 1; c < g.C; ++c) eta += g.X[(long)c * g.S + s] * t(c);
+  return eta;
+}
+// the gene's prior terms at draw i's hyper-parameters and the point t (step 1), t0 = t(0), sg = t(C)
+template <class Point>
+PPCX_HD double loo_mm_prior_at(const LooMmGene& g, long i, double t0, double sg, const Point& t) {
   PPCX_NO_CONTRACT
   double u6[6];
   for (int k = 0; k < 6; ++k) u6[k] = g.U[(long)k * g.n + i];
@@ -107,33 +124,47 @@ PPCX_HD double loo_mm_prior(const LooMmGene& g, long i, double t0, double sg, co
   lp += -0.5 * r * (r * h.inv_ss2);
   if (g.checked) {
     for (int c = 1; c < g.C; ++c) {
-      const double al = loo_mm_coord(g, c, i, A, B);
+      const double al = t(c);
       lp += c == 1 ? -fabs(al) : -(al * al) / 12.5;
     }
   }
   return lp;
 }
 // q(t_i; h_i) of step 1 under the state, and the log-likelihood of the cell of sample s_cell itself (whether excluded or not)
-PPCX_HD double loo_mm_density(const LooMmGene& g, long i, const double* A, const double* B, int s_cell, double* ll_cell) {
+template <class State>
+PPCX_HD double loo_mm_density(const LooMmGene& g, long i, const State& st, int s_cell, double* ll_cell) {
   PPCX_NO_CONTRACT
-  const double t0 = loo_mm_coord(g, 0, i, A, B), sg = loo_mm_coord(g, g.C, i, A, B);
+  const auto t = st.point(g, i);
+  const double t0 = t(0), sg = t(g.C);
   const DispPoint p = disp_point(sg);
   double q = 0.0;
   for (int s = 0; s < g.S; ++s) {
     const int ye = g.yrow[s];
     if (ye < 0 && s != s_cell) continue;
-    const double ll = loo_mm_ll(ye < 0 ? -ye - 1 : ye, loo_mm_eta(g, s, i, t0, A, B), sg, p);
+    const double ll = loo_mm_ll(ye < 0 ? -ye - 1 : ye, loo_mm_eta_at(g, s, t0, t), sg, p);
     if (ye >= 0) q += ll;
     if (s == s_cell) *ll_cell = ll;
   }
-  return q + loo_mm_prior(g, i, t0, sg, A, B);
+  return q + loo_mm_prior_at(g, i, t0, sg, t);
 }
 // the log-likelihood of the cell of sample s alone, under the state (step 4)
-PPCX_HD double loo_mm_cell_ll(const LooMmGene& g, long i, const double* A, const double* B, int s) {
+template <class State>
+PPCX_HD double loo_mm_cell_ll(const LooMmGene& g, long i, const State& st, int s) {
   PPCX_NO_CONTRACT
-  const double t0 = loo_mm_coord(g, 0, i, A, B), sg = loo_mm_coord(g, g.C, i, A, B);
+  const auto t = st.point(g, i);
+  const double t0 = t(0), sg = t(g.C);
   const int ye = g.yrow[s];
-  return loo_mm_ll(ye < 0 ? -ye - 1 : ye, loo_mm_eta(g, s, i, t0, A, B), sg, disp_point(sg));
+  return loo_mm_ll(ye < 0 ? -ye - 1 : ye, loo_mm_eta_at(g, s, t0, t), sg, disp_point(sg));
+}
+// the same under the diagonal state given by its arrays (ppcx_loo_mm_exact.h, ppcx_loo_mm_split.h, tests/loo_mm_host)
+PPCX_HD double loo_mm_eta(const LooMmGene& g, int s, long i, double t0, const double* A, const double* B) {
+  return loo_mm_eta_at(g, s, t0, LooMmDiag{A, B}.point(g, i));
+}
+PPCX_HD double loo_mm_density(const LooMmGene& g, long i, const double* A, const double* B, int s_cell, double* ll_cell) {
+  return loo_mm_density(g, i, LooMmDiag{A, B}, s_cell, ll_cell);
+}
+PPCX_HD double loo_mm_cell_ll(const LooMmGene& g, long i, const double* A, const double* B, int s) {
+  return loo_mm_cell_ll(g, i, LooMmDiag{A, B}, s);
 }
 // a candidate's ratio at one draw (step 3)
 PPCX_HD double loo_mm_ratio(double q, double q0, double ll) {
@@ -161,6 +192,61 @@ PPCX_HD void loo_mm_store_state(double* o, int C, double khat_before, int iterat
   for (int c = 0; c <= C; ++c) { o[kLooMmHead + c] = A ? A[c] : 1.0; o[kLooMmHead + C + 1 + c] = B ? B[c] : 0.0; }
 }
 
+// ---- what the sequential cells of both states share beside the density.
+// Step 3's moments of coordinate c under the state `cur` and the weights exp(W[i] - lse), two sweeps over the draws: m, mw and
+// the scale sc = sqrt(vw / v). The kernels state the same two sweeps over their workgroup (ppcx_loo_mm.hip, ppcx_loo_mm_cov.hip).
+struct LooMmMoments { double m, mw, sc; };
+template <class State>
+inline LooMmMoments loo_mm_coord_moments(const LooMmGene& g, const State& cur, int c, long n, const double* W, double lse) {
+  PPCX_NO_CONTRACT
+  double st = 0.0, swt = 0.0, swt2 = 0.0, sd2 = 0.0;
+  for (long i = 0; i < n; ++i) {
+    const double t = cur.coord(g, c, i), w = exp(W[i] - lse);
+    st += t; swt += w * t; swt2 += w * (t * t);
+  }
+  const double m = loo_mm_mean(st, n);
+  for (long i = 0; i < n; ++i) { const double d = cur.coord(g, c, i) - m; sd2 += d * d; }
+  const double v = loo_mm_var(sd2, n), vw = loo_mm_wvar(swt2, swt);
+  return LooMmMoments{m, swt, loo_mm_scale(vw, v)};
+}
+
+// The sequential cell (loo_mm_cell_host_as below) runs under a policy that owns what differs between the states: the record
+// (fields, store), the identity, the state and candidate 1 .. kCandidates as a point's source (state(cand), 0 the current one),
+// what is kept of a coordinate's moments (keep; coord false: a row that is no coordinate keeps its state in every candidate) and
+// how the candidates are formed from them (form_candidates), what a candidate needs before its density sweep (prepare: false
+// refuses it and ends the iteration) and what an accepted step does (accept). LooMmDiagCell is the per-coordinate state of this
+// header, ppcx_loo_mm_cov.h's LooMmCovCell the affine one.
+// ok2: unused; keeps the static LDS of ppcx_loo_mm_kernel at 3 712 bytes
+struct LooMmShared { double A[kMaxC + 1], B[kMaxC + 1], A1[kMaxC + 1], B1[kMaxC + 1], A2[kMaxC + 1], B2[kMaxC + 1]; int ok2; };
+struct LooMmDiagCell {
+  using Shared = LooMmShared;
+  static constexpr int kCandidates = 2;
+  const LooMmGene& g;
+  Shared& ms;
+  static int fields(int C) { return loo_mm_fields(C); }
+  // ms null: an unmatched cell, scales 1 and shifts 0
+  static void store(double* o, int C, double elpd, double p_loo, double looic, double khat, double khat_before, int iterations, int,
+                    const Shared* ms) {
+    o[0] = elpd; o[1] = p_loo; o[2] = looic; o[3] = khat;
+    loo_mm_store_state(o, C, khat_before, iterations, ms ? ms->A : nullptr, ms ? ms->B : nullptr);
+  }
+  void identity() { for (int c = 0; c <= g.C; ++c) { ms.A[c] = 1.0; ms.B[c] = 0.0; } }
+  LooMmDiag state(int cand) const {
+    return cand == 0 ? LooMmDiag{ms.A, ms.B} : cand == 1 ? LooMmDiag{ms.A1, ms.B1} : LooMmDiag{ms.A2, ms.B2};
+  }
+  void keep(int c, bool coord, const LooMmMoments& mo) {
+    ms.A1[c] = ms.A[c]; ms.B1[c] = coord ? loo_mm_shift(ms.B[c], mo.m, mo.mw) : ms.B[c];
+    ms.A2[c] = coord ? loo_mm_scaled_A(mo.sc, ms.A[c]) : ms.A[c];
+    ms.B2[c] = coord ? loo_mm_scaled_B(mo.sc, ms.B[c], mo.m, mo.mw) : ms.B[c];
+  }
+  void form_candidates() {}
+  bool prepare(int, long, const double*, double) { return true; }
+  void accept(int cand) {
+    const LooMmDiag c = state(cand);
+    for (int j = 0; j <= g.C; ++j) { ms.A[j] = c.A[j]; ms.B[j] = c.B[j]; }
+  }
+};
+
 }  // namespace ppcx
 
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -185,74 +271,75 @@ inline bool loo_mm_lpd_host(const std::vector<double>& ll, double* lpd) {
   *lpd = part.empty() ? NAN : loo_logsumexp_host(part) - log((double)part.size());
   return !part.empty();
 }
-// the whole spec for one cell, sequentially, for the CPU check: out[loo_mm_fields(C)]. kinds (may be null): the accepted
-// candidates in order, 1 or 2.
-inline void loo_mm_cell_host(const LooMmGene& g, int s, double r_eff, double k_threshold, int max_iters, double* out,
-                             std::vector<int>* kinds = nullptr) {
+// The whole spec for one cell, sequentially, for the CPU checks, under the policy `cell` at its identity: out[Cell::fields(C)].
+// kinds (may be null): the accepted candidates in order. Returns whether the cell was matched (iterations > 0); then *lpd is
+// that of the original draws and the final state is cell.ms's.
+template <class Cell>
+inline bool loo_mm_cell_host_as(Cell& cell, int s, double r_eff, double k_threshold, int max_iters, double* out, std::vector<int>* kinds,
+                                double* lpd) {
   PPCX_NO_CONTRACT
+  const LooMmGene& g = cell.g;
   const long n = g.n;
-  const int C = g.C, nc = C + 1;
-  std::vector<double> A(nc, 1.0), B(nc, 0.0);
+  const int C = g.C;
   const bool excluded = g.yrow[s] < 0;
   if (kinds) kinds->clear();
   // ---- step 0
   std::vector<double> ll(n);
-  for (long i = 0; i < n; ++i) ll[i] = loo_mm_cell_ll(g, i, A.data(), B.data(), s);
-  loo_cell_host(ll.data(), n, r_eff, excluded, out);
-  loo_mm_store_state(out, C, out[3], 0, nullptr, nullptr);
-  if (loo_mm_finished(excluded, out[3], k_threshold, max_iters)) return;
-  std::vector<double> r(n), lw;
+  for (long i = 0; i < n; ++i) ll[i] = loo_mm_cell_ll(g, i, cell.state(0), s);
+  double loo4[kLooFields];
+  loo_cell_host(ll.data(), n, r_eff, excluded, loo4);
+  Cell::store(out, C, loo4[0], loo4[1], loo4[2], loo4[3], loo4[3], 0, 0, nullptr);
+  if (loo_mm_finished(excluded, loo4[3], k_threshold, max_iters)) return false;
+  std::vector<double> r(n), lw, lw2;
   for (long i = 0; i < n; ++i) r[i] = -ll[i];
-  double lpd;
-  if (!loo_mm_lpd_host(ll, &lpd)) return;
+  if (!loo_mm_lpd_host(ll, lpd)) return false;
   double k = loo_mm_psis_host(r, r_eff, lw);
   // ---- step 1 at the original draws
   std::vector<double> Q0(n);
-  for (long i = 0; i < n; ++i) { double l; Q0[i] = loo_mm_density(g, i, A.data(), B.data(), s, &l); }
+  for (long i = 0; i < n; ++i) { double l; Q0[i] = loo_mm_density(g, i, cell.state(0), s, &l); }
   // ---- step 3
-  int iters = 0;
-  std::vector<double> A1(nc), B1(nc), A2(nc), B2(nc), lw2;
+  int iters = 0, cov_iters = 0;
   while (k > k_threshold && iters < max_iters) {
     const double lse = loo_logsumexp_host(lw);
     bool ok2 = true;
-    A1 = A; B1 = B; A2 = A; B2 = B;
-    for (int c = 0; c < nc; ++c) {
-      if (!loo_mm_is_coord(g, c)) continue;
-      double st = 0.0, swt = 0.0, swt2 = 0.0, sd2 = 0.0;
-      for (long i = 0; i < n; ++i) {
-        const double t = loo_mm_coord(g, c, i, A.data(), B.data()), w = exp(lw[i] - lse);
-        st += t; swt += w * t; swt2 += w * (t * t);
-      }
-      const double m = loo_mm_mean(st, n);
-      for (long i = 0; i < n; ++i) { const double d = loo_mm_coord(g, c, i, A.data(), B.data()) - m; sd2 += d * d; }
-      const double v = loo_mm_var(sd2, n), vw = loo_mm_wvar(swt2, swt);
-      B1[c] = loo_mm_shift(B[c], m, swt);
-      const double sc = loo_mm_scale(vw, v);
-      ok2 = ok2 && loo_mm_scale_ok(sc);
-      A2[c] = loo_mm_scaled_A(sc, A[c]); B2[c] = loo_mm_scaled_B(sc, B[c], m, swt);
+    for (int c = 0; c <= C; ++c) {
+      const bool coord = loo_mm_is_coord(g, c);
+      LooMmMoments mo{0.0, 0.0, 1.0};
+      if (coord) { mo = loo_mm_coord_moments(g, cell.state(0), c, n, lw.data(), lse); ok2 = ok2 && loo_mm_scale_ok(mo.sc); }
+      cell.keep(c, coord, mo);
     }
+    cell.form_candidates();
     int kind = 0;
-    for (int cand = 1; cand <= 2 && !kind; ++cand) {
-      if (cand == 2 && !ok2) break;
-      const double* Ac = cand == 1 ? A1.data() : A2.data();
-      const double* Bc = cand == 1 ? B1.data() : B2.data();
-      for (long i = 0; i < n; ++i) { double l; const double q = loo_mm_density(g, i, Ac, Bc, s, &l); r[i] = loo_mm_ratio(q, Q0[i], l); }
+    for (int cand = 1; cand <= Cell::kCandidates && !kind; ++cand) {
+      if (cand == 2 && !ok2) continue;
+      if (!cell.prepare(cand, n, lw.data(), lse)) break;
+      const auto st = cell.state(cand);
+      for (long i = 0; i < n; ++i) { double l; const double q = loo_mm_density(g, i, st, s, &l); r[i] = loo_mm_ratio(q, Q0[i], l); }
       const double k2 = loo_mm_psis_host(r, r_eff, lw2);
-      if (k2 < k) { kind = cand; k = k2; lw = lw2; A.assign(Ac, Ac + nc); B.assign(Bc, Bc + nc); }
+      if (k2 < k) { kind = cand; k = k2; lw = lw2; cell.accept(cand); }
     }
     if (!kind) break;
     ++iters;
+    cov_iters += kind == 3;
     if (kinds) kinds->push_back(kind);
   }
-  if (iters == 0) return;
+  if (iters == 0) return false;
   // ---- step 4
   std::vector<double> a, b;
   for (long i = 0; i < n; ++i)
-    if (lw[i] != -INFINITY) { a.push_back(lw[i] + loo_mm_cell_ll(g, i, A.data(), B.data(), s)); b.push_back(lw[i]); }
-  const double khat_before = out[3];
+    if (lw[i] != -INFINITY) { a.push_back(lw[i] + loo_mm_cell_ll(g, i, cell.state(0), s)); b.push_back(lw[i]); }
   const double elpd = loo_logsumexp_host(a) - loo_logsumexp_host(b);
-  out[0] = elpd; out[1] = lpd - elpd; out[2] = -2.0 * elpd; out[3] = k;
-  loo_mm_store_state(out, C, khat_before, iters, A.data(), B.data());
+  Cell::store(out, C, elpd, *lpd - elpd, -2.0 * elpd, k, loo4[3], iters, cov_iters, &cell.ms);
+  return true;
+}
+// the per-coordinate state's: out[loo_mm_fields(C)], kinds 1 or 2
+inline void loo_mm_cell_host(const LooMmGene& g, int s, double r_eff, double k_threshold, int max_iters, double* out,
+                             std::vector<int>* kinds = nullptr) {
+  LooMmShared ms;
+  LooMmDiagCell cell{g, ms};
+  cell.identity();
+  double lpd;
+  loo_mm_cell_host_as(cell, s, r_eff, k_threshold, max_iters, out, kinds, &lpd);
 }
 }  // namespace ppcx
 #endif

@@ -1,6 +1,6 @@
 // ppcx_loo_mm.hip -- gfx950 kernels of the gene-local moment matching of PSIS-LOO cells (ppcx_fit_loo_moment_match,
 // include/ppcx.h; the statistic: ppcx_loo_mm.h). The walk over the cells is ppcx_loo_dev.h's (for_gene_batches,
-// cells_in_batches); the driver at the end of this file adds the kernels. The argument block, the gene a workgroup reads and the
+// cells_in_batches); the driver is ppcx_loo_mm_dev.h's loo_mm_match_cells. The argument block, the gene a workgroup reads and the
 // walk's own buffers are ppcx_loo_mm_dev.h's, shared with ppcx_loo_mm_exact.hip and ppcx_loo_mm_split.hip, which run these kernels
 // before their own (loo_mm_then_fit_cells); so are the stages that those kernels run too: a candidate's counted ratio sweep
 // (loo_mm_count_ratios), lpd of the original draws (loo_mm_lpd) and step 4 (loo_mm_weighted_elpd).
@@ -11,17 +11,16 @@
 //                             and left their four fields (ppcx_fit_loo's bits, by the same kernel); a cell that is finished in
 //                             step 0 copies them, writes khat_before = khat, iterations 0, scales 1, shifts 0 and leaves at
 //                             once, before a ratio is formed. A cell above the threshold forms its ratios, tail and the log
-//                             weight of every draw by loo_cell_ratios, loo_cell_tail and loo_cell_lw (ppcx_loo_dev.h: the parts of
-//                             the other per-cell kernels' weights stage), then Q0, and iterates: per coordinate two sweeps over the draws
-//                             for the four moments (t formed from the table on the fly), per candidate one sweep that forms
-//                             q(t'; h) - Q0 - ll per draw (disp_point once per draw, disp_cell per sample of the gene) and
-//                             the cell's PSIS on it. The state (A, B) and the candidate's live in LDS, written by thread 0.
-//                             Every thread holds the same sums and the same k: the control flow is uniform per workgroup.
-//                             Three arrays of n doubles -- a candidate's ratios, the current log weights, Q0 -- in LDS up to
-//                             kPsisLdsDraws draws beside the two selection arrays (96 KB + 4 KB at 4 096 draws: one workgroup
-//                             per CU; 1 000 draws take 24 KB + 2 KB), in the workgroup's slice of the bounded scratch beyond.
-//                             A candidate's ratios overwrite the last candidate's: the current weights are enough for the
-//                             moments and for step 4. Timed at the entry only (profiles/README.md, cell_entries_ab.json).
+//                             weight of every draw by loo_cell_ratios, loo_cell_tail and loo_cell_lw (ppcx_loo_dev.h), then
+//                             Q0, and iterates: the normaliser (loo_mm_lse), per coordinate two sweeps over the draws for the
+//                             four moments (t formed from the table on the fly), per candidate one sweep that forms
+//                             q(t'; h) - Q0 - ll per draw (ppcx_loo_mm.h's one density under LooMmDiag) and the cell's PSIS on
+//                             it. The state (A, B) and the candidate's live in LDS, written by thread 0. Every thread holds
+//                             the same sums and the same k: the control flow is uniform per workgroup. Three arrays of n
+//                             doubles -- a candidate's ratios, the current log weights, Q0 -- in LDS up to kPsisLdsDraws draws
+//                             beside the two selection arrays (96 KB + 4 KB at 4 096 draws: one workgroup per CU; 1 000 draws
+//                             take 24 KB + 2 KB), in the workgroup's slice of the bounded scratch beyond. Kept apart from
+//                             ppcx_loo_mm_cov_kernel's body: as one function it was 1.6 - 2.1 % slower (profiles/README.md).
 // Every reduction runs in a fixed order and a cell reads nothing of another gene: its fields are the same bits whatever else is
 // requested and however the work is batched.
 #include <hip/hip_runtime.h>
@@ -35,8 +34,6 @@ __global__ __launch_bounds__(256) void ppcx_loo_mm_hyper_kernel(const double* dr
   const long j = t / 6; const int k = (int)(t - j * 6);
   U[(long)k * n_draws + j] = draws[j * (long)d.D + hyper_index(d, k)];
 }
-
-struct LooMmShared { double A[kMaxC + 1], B[kMaxC + 1], A1[kMaxC + 1], B1[kMaxC + 1], A2[kMaxC + 1], B2[kMaxC + 1]; int ok2; };
 
 template <bool LDS>
 __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_kernel(LooMmArgs p) {
@@ -86,9 +83,7 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_kernel(LooMmArgs p)
   int iters = 0;
   while (k > p.k_threshold && iters < p.max_iters) {
     // the normaliser of the current weights
-    const double mb = draws_max(n, sh.red, [&](long i) { return W[i]; });
-    const double sb = draws_sum(n, sh.red, [&](long i) { return exp(W[i] - mb); });
-    const double lse = mb + log(sb);
+    const double lse = loo_mm_lse(W, n, sh);
     // the moments of every coordinate, the two candidates
     bool ok2 = true;
     for (int cc = 0; cc < nc; ++cc) {
@@ -176,17 +171,8 @@ hipError_t launch_loo_mm_kernels(const LooMmArgs& q, const CellLaunch& c, hipStr
 }
 
 hipError_t loo_mm_fit_cells(const FitCells& fc, double k_threshold, int max_iters, double* out, size_t scratch_bytes, hipStream_t st) {
-  LooMmWalk walk;                                        // outlives the walk, which drains the stream before it returns
-  const hipError_t e = walk.prepare(fc, st);
-  if (e != hipSuccess) return finish(e, st);
-  return for_gene_batches(fc, loo_mm_fields(fc.d.C), out, scratch_bytes, st,
-                          [&](const LooArgs& a, const int* genes, int n_cells, DeviceBuffer<double>& scratch) {
-    const LooMmArgs p = walk.args(fc, a, genes, n_cells, k_threshold, max_iters, a.out);
-    // per batch of cells: plain PSIS-LOO, then the matching
-    return cells_in_batches(p, loo_slice3(fc.n), n_cells, scratch_bytes, scratch, [&](const LooMmArgs& q, const CellLaunch& c) {
-      return launch_loo_mm_kernels(q, c, st);
-    });
-  });
+  return loo_mm_match_cells(fc, k_threshold, max_iters, loo_mm_fields(fc.d.C), out, scratch_bytes, st,
+                            [&](const LooMmArgs& q, const CellLaunch& c) { return launch_loo_mm_kernels(q, c, st); });
 }
 
 }  // namespace ppcx

@@ -9,8 +9,9 @@
 // here the matrix is d x d with d = 2 .. C + 1 <= 17, estimated from all n draws and factorised by one thread.
 //
 // Shared by the gfx950 kernel (ppcx_loo_mm_cov.hip) and the CPU check (tests/loo_mm_cov_twin): the blocks below are
-// `__host__ __device__`; loo_mm_cov_cell_host at the end is their sequential composition. The local density, the prior, eta and
-// the cell's log-likelihood of ppcx_loo_mm.h are restated here against the general state; ppcx_loo_mm.h's own are untouched.
+// `__host__ __device__`; loo_mm_cov_cell_host at the end is their sequential composition. The local density, the moment sweeps and
+// the sequential cell (steps 0 - 4, the gates, the accepts) are ppcx_loo_mm.h's, stated there once; this header gives them the affine state
+// (LooMmAffine, whose point is loo_mm_cov_point's array) and its policy (LooMmCovCell: the candidates, step 5, the inverse).
 //
 // One cell (g, s) from what ppcx_loo_mm.h reads:
 //   1. The state: an affine map (M [nc][nc] row-major, b [nc]), nc = C + 1, initially the identity. The current draws are
@@ -89,59 +90,16 @@ PPCX_HD void loo_mm_cov_point(const LooMmGene& g, long i, const double* M, const
     t[c] = x + b[c];
   }
 }
-// linear predictor of sample s at the point t
-PPCX_HD double loo_mm_cov_eta(const LooMmGene& g, int s, const double* t) {
-  PPCX_NO_CONTRACT
-  double eta = g.expo[s] + g.X[s] * t[0];
-  for (int c = 1; c < g.C; ++c) eta += g.X[(long)c * g.S + s] * t[c];
-  return eta;
-}
-// the gene's prior terms at draw i's hyper-parameters and the point t (ppcx_loo_mm.h step 1)
-PPCX_HD double loo_mm_cov_prior(const LooMmGene& g, long i, const double* t) {
-  PPCX_NO_CONTRACT
-  double u6[6];
-  for (int k = 0; k < 6; ++k) u6[k] = g.U[(long)k * g.n + i];
-  const Hyper h = make_hyper(u6, g.lambda_mu_mu);
-  const double t0 = t[0], sg = t[g.C];
-  const double z = (t0 - h.xi) * h.inv_om;
-  double lerfc, ratio;
-  log_erfc_and_ratio(-h.lambda_skew * z * 0.70710678118654752440, &lerfc, &ratio);
-  double lp = -0.5 * z * z + lerfc;
-  const double r = sg - (h.sigma_slope * t0 + h.sigma_intercept);
-  lp += -0.5 * r * (r * h.inv_ss2);
-  if (g.checked) {
-    for (int c = 1; c < g.C; ++c) {
-      const double al = t[c];
-      lp += c == 1 ? -fabs(al) : -(al * al) / 12.5;
-    }
-  }
-  return lp;
-}
-// q(t_i; h_i) under the state, and the log-likelihood of the cell of sample s_cell itself (whether excluded or not)
-PPCX_HD double loo_mm_cov_density(const LooMmGene& g, long i, const double* M, const double* b, int s_cell, double* ll_cell) {
-  PPCX_NO_CONTRACT
-  double t[kLooMmCovNc];
-  loo_mm_cov_point(g, i, M, b, t);
-  const double sg = t[g.C];
-  const DispPoint p = disp_point(sg);
-  double q = 0.0;
-  for (int s = 0; s < g.S; ++s) {
-    const int ye = g.yrow[s];
-    if (ye < 0 && s != s_cell) continue;
-    const double ll = loo_mm_ll(ye < 0 ? -ye - 1 : ye, loo_mm_cov_eta(g, s, t), sg, p);
-    if (ye >= 0) q += ll;
-    if (s == s_cell) *ll_cell = ll;
-  }
-  return q + loo_mm_cov_prior(g, i, t);
-}
-// the log-likelihood of the cell of sample s alone, under the state
-PPCX_HD double loo_mm_cov_cell_ll(const LooMmGene& g, long i, const double* M, const double* b, int s) {
-  PPCX_NO_CONTRACT
-  double t[kLooMmCovNc];
-  loo_mm_cov_point(g, i, M, b, t);
-  const int ye = g.yrow[s];
-  return loo_mm_ll(ye < 0 ? -ye - 1 : ye, loo_mm_cov_eta(g, s, t), t[g.C], disp_point(t[g.C]));
-}
+// The affine state as ppcx_loo_mm.h's density and moment sweeps read one: a point is a private array filled once per draw
+struct LooMmAffine {
+  const double* M; const double* b;
+  struct Point {
+    double t[kLooMmCovNc];
+    PPCX_HD double operator()(int c) const { return t[c]; }
+  };
+  PPCX_HD double coord(const LooMmGene& g, int c, long i) const { return loo_mm_cov_coord(g, c, i, M, b); }
+  PPCX_HD Point point(const LooMmGene& g, long i) const { Point p; loo_mm_cov_point(g, i, M, b, p.t); return p; }
+};
 
 // step 4: candidates 1 and 2 from the moments m, mw and the scales sc (rows of the table; read at the gene's coordinates only)
 PPCX_HD void loo_mm_cov_cand12(const LooMmGene& g, const double* M, const double* b, const double* m, const double* mw, const double* sc,
@@ -262,18 +220,6 @@ PPCX_HD void loo_mm_cov_binv(const LooMmGene& g, const double* Minv, const doubl
     binv[ra] = -x;
   }
 }
-// step 7: the split's ratio of draw i (ppcx_loo_mm_split.h steps 3 - 5) under general states
-PPCX_HD double loo_mm_cov_split_ratio(const LooMmGene& g, long i, const double* Mx, const double* bx, const double* Mi, const double* bi,
-                                      double logJ, int s, double* ll_x) {
-  PPCX_NO_CONTRACT
-  double l, li;
-  const double qx = loo_mm_cov_density(g, i, Mx, bx, s, &l);
-  const double qinv = loo_mm_cov_density(g, i, Mi, bi, s, &li);
-  const double dd = qinv - logJ;
-  const double r = qx - l - loo_mm_split_logaddexp(qx, dd);
-  *ll_x = l;
-  return isfinite(r) ? r : -INFINITY;
-}
 // step 8: the record. M null: the identity and zeros. elpd_loo_matched = elpd_loo and khat_split = NaN until a cell is split.
 PPCX_HD void loo_mm_cov_store(double* o, int C, double elpd, double p_loo, double looic, double khat, double khat_before, int iterations,
                               int cov_iterations, const double* M, const double* b) {
@@ -291,129 +237,110 @@ PPCX_HD void loo_mm_cov_store_split(double* o, double elpd, double lpd, double k
 }
 PPCX_HD void loo_mm_cov_store_split_nan(double* o) { o[0] = o[1] = o[2] = NAN; o[8] = NAN; }
 
+// ---- the affine state as the policy of ppcx_loo_mm.h's sequential cell. What a cell keeps beside the draws' arrays: the state (M, b), the
+// three candidates, the accumulated inverse, the factors and the moments (the kernel's static LDS; eight (C + 1)^2 matrices at kMaxC)
+constexpr int kCovNN = kLooMmCovNc * kLooMmCovNc;
+struct LooMmCovShared {
+  double M[kCovNN], M2[kCovNN], M3[kCovNN], Minv[kCovNN], Tinv[kCovNN], SA[kCovNN], SB[kCovNN], Tm[kCovNN];
+  double b[kLooMmCovNc], b1[kLooMmCovNc], b2[kLooMmCovNc], b3[kLooMmCovNc], binv[kLooMmCovNc];
+  double m[kLooMmCovNc], mw[kLooMmCovNc], sc[kLooMmCovNc];
+  double logJ, dlogJ;
+  int ok3;
+};
+struct LooMmCovCell {
+  using Shared = LooMmCovShared;
+  static constexpr int kCandidates = 3;
+  const LooMmGene& g;
+  Shared& ms;
+  static int fields(int C) { return loo_mm_cov_fields(C); }
+  // ms null: an unmatched cell, the identity and zeros
+  static void store(double* o, int C, double elpd, double p_loo, double looic, double khat, double khat_before, int iterations,
+                    int cov_iterations, const Shared* ms) {
+    loo_mm_cov_store(o, C, elpd, p_loo, looic, khat, khat_before, iterations, cov_iterations, ms ? ms->M : nullptr, ms ? ms->b : nullptr);
+  }
+  void identity() {
+    loo_mm_cov_identity(ms.M, ms.b, g.C + 1);
+    loo_mm_cov_identity(ms.Minv, nullptr, g.C + 1);
+    ms.logJ = 0.0;
+  }
+  LooMmAffine state(int cand) const {
+    return cand == 0 ? LooMmAffine{ms.M, ms.b} : cand == 1 ? LooMmAffine{ms.M, ms.b1} : cand == 2 ? LooMmAffine{ms.M2, ms.b2}
+                                                                                                   : LooMmAffine{ms.M3, ms.b3};
+  }
+  void keep(int c, bool coord, const LooMmMoments& mo) { if (coord) { ms.m[c] = mo.m; ms.mw[c] = mo.mw; ms.sc[c] = mo.sc; } }
+  void form_candidates() { loo_mm_cov_cand12(g, ms.M, ms.b, ms.m, ms.mw, ms.sc, ms.b1, ms.M2, ms.b2); }
+  // step 5 before candidate 3: sum w^2, per pair (a <= b) one sweep for the two centred sums, the factorisation and the candidate
+  bool prepare(int cand, long n, const double* W, double lse) {
+    PPCX_NO_CONTRACT
+    if (cand != 3) return true;
+    const int nc = g.C + 1, d = loo_mm_cov_dim(g);
+    const LooMmAffine cur = state(0);
+    double sw2 = 0.0;
+    for (long i = 0; i < n; ++i) { const double w = exp(W[i] - lse); sw2 += w * w; }
+    for (int ia = 0; ia < d; ++ia)
+      for (int ib = ia; ib < d; ++ib) {
+        const int ra = loo_mm_cov_row(g, ia), rb = loo_mm_cov_row(g, ib);
+        const double ma = ms.m[ra], mb = ms.m[rb], mwa = ms.mw[ra], mwb = ms.mw[rb];
+        double sa = 0.0, sw = 0.0;
+        for (long i = 0; i < n; ++i) {
+          const double ta = cur.coord(g, ra, i), tb = cur.coord(g, rb, i);
+          const double w = exp(W[i] - lse);
+          sa += (ta - ma) * (tb - mb);
+          sw += w * ((ta - mwa) * (tb - mwb));
+        }
+        ms.SA[ib * nc + ia] = sa; ms.SB[ib * nc + ia] = sw;
+      }
+    ms.dlogJ = 0.0;
+    return loo_mm_cov_cand3(g, sw2, ms.m, ms.mw, ms.SA, ms.SB, ms.M, ms.b, ms.Tm, ms.Tinv, ms.M3, ms.b3, &ms.dlogJ);
+  }
+  void accept(int cand) {
+    const int nc = g.C + 1;
+    const LooMmAffine c = state(cand);
+    loo_mm_cov_accept_inverse(g, cand, ms.sc, ms.Tinv, ms.dlogJ, ms.Minv, &ms.logJ);
+    if (cand != 1) for (int j = 0; j < nc * nc; ++j) ms.M[j] = c.M[j];
+    for (int j = 0; j < nc; ++j) ms.b[j] = c.b[j];
+  }
+};
+
 }  // namespace ppcx
 
 #if !defined(__HIP_DEVICE_COMPILE__)
+#include <memory>
 #include <vector>
 namespace ppcx {
-// the whole spec for one cell, sequentially, for the CPU check: out[loo_mm_cov_fields(C)]. kinds (may be null): the accepted
-// candidates in order, 1, 2 or 3. inv (may be null): Minv [nc][nc], binv [nc] and logJ of the final state, nc nc + nc + 1 doubles.
+// the whole spec for one cell, sequentially, for the CPU check: ppcx_loo_mm.h's cell under the affine state, then step 7:
+// out[loo_mm_cov_fields(C)]. kinds (may be null): the accepted candidates in order, 1, 2 or 3. inv (may be null): Minv [nc][nc],
+// binv [nc] and logJ of the final state, nc nc + nc + 1 doubles.
 inline void loo_mm_cov_cell_host(const LooMmGene& g, int s, double r_eff, double k_threshold, int max_iters, bool split, double* out,
                                  std::vector<int>* kinds = nullptr, double* inv = nullptr) {
   PPCX_NO_CONTRACT
   const long n = g.n;
-  const int C = g.C, nc = C + 1, d = loo_mm_cov_dim(g);
-  std::vector<double> M(nc * nc), b(nc), Minv(nc * nc), binv(nc, 0.0), I(nc * nc), zero(nc, 0.0);
-  loo_mm_cov_identity(M.data(), b.data(), nc);
-  loo_mm_cov_identity(Minv.data(), nullptr, nc);
-  loo_mm_cov_identity(I.data(), nullptr, nc);
-  double logJ = 0.0;
-  auto give_inverse = [&]() {
-    if (!inv) return;
-    for (int j = 0; j < nc * nc; ++j) inv[j] = Minv[j];
-    for (int c = 0; c < nc; ++c) inv[nc * nc + c] = binv[c];
-    inv[nc * nc + nc] = logJ;
-  };
-  const bool excluded = g.yrow[s] < 0;
-  if (kinds) kinds->clear();
-  give_inverse();
-  // ---- step 0 of ppcx_loo_mm.h
-  std::vector<double> ll(n);
-  for (long i = 0; i < n; ++i) ll[i] = loo_mm_cov_cell_ll(g, i, M.data(), b.data(), s);
-  double loo4[kLooFields];
-  loo_cell_host(ll.data(), n, r_eff, excluded, loo4);
-  loo_mm_cov_store(out, C, loo4[0], loo4[1], loo4[2], loo4[3], loo4[3], 0, 0, nullptr, nullptr);
-  if (loo_mm_finished(excluded, loo4[3], k_threshold, max_iters)) return;
-  std::vector<double> r(n), lw;
-  for (long i = 0; i < n; ++i) r[i] = -ll[i];
+  const int nc = g.C + 1;
+  const std::unique_ptr<LooMmCovShared> held(new LooMmCovShared());   // value-initialised: inv's binv of an unmatched cell is zeros
+  LooMmCovShared& cs = *held;
+  LooMmCovCell cell{g, cs};
+  cell.identity();
   double lpd;
-  if (!loo_mm_lpd_host(ll, &lpd)) return;
-  double k = loo_mm_psis_host(r, r_eff, lw);
-  // ---- Q0 at the original draws
-  std::vector<double> Q0(n);
-  for (long i = 0; i < n; ++i) { double l; Q0[i] = loo_mm_cov_density(g, i, M.data(), b.data(), s, &l); }
-  // ---- the loop
-  int iters = 0, cov_iters = 0;
-  std::vector<double> m(nc, 0.0), mw(nc, 0.0), sc(nc, 1.0), b1(nc), M2(nc * nc), b2(nc), M3(nc * nc), b3(nc), SA(nc * nc), SB(nc * nc),
-      Tm(nc * nc), Tinv(nc * nc), lw2, w(n);
-  while (k > k_threshold && iters < max_iters) {
-    const double lse = loo_logsumexp_host(lw);
-    bool ok2 = true;
-    for (int c = 0; c < nc; ++c) {
-      if (!loo_mm_is_coord(g, c)) continue;
-      double st = 0.0, swt = 0.0, swt2 = 0.0, sd2 = 0.0;
-      for (long i = 0; i < n; ++i) {
-        const double t = loo_mm_cov_coord(g, c, i, M.data(), b.data()), wi = exp(lw[i] - lse);
-        st += t; swt += wi * t; swt2 += wi * (t * t);
-      }
-      m[c] = loo_mm_mean(st, n);
-      for (long i = 0; i < n; ++i) { const double dd = loo_mm_cov_coord(g, c, i, M.data(), b.data()) - m[c]; sd2 += dd * dd; }
-      mw[c] = swt;
-      sc[c] = loo_mm_scale(loo_mm_wvar(swt2, swt), loo_mm_var(sd2, n));
-      ok2 = ok2 && loo_mm_scale_ok(sc[c]);
-    }
-    loo_mm_cov_cand12(g, M.data(), b.data(), m.data(), mw.data(), sc.data(), b1.data(), M2.data(), b2.data());
-    int kind = 0;
-    double dlogJ = 0.0;
-    for (int cand = 1; cand <= 3 && !kind; ++cand) {
-      if (cand == 2 && !ok2) continue;
-      if (cand == 3) {
-        double sw2 = 0.0;
-        for (long i = 0; i < n; ++i) { w[i] = exp(lw[i] - lse); sw2 += w[i] * w[i]; }
-        for (int a = 0; a < d; ++a)
-          for (int c2 = a; c2 < d; ++c2) {
-            const int ra = loo_mm_cov_row(g, a), rb = loo_mm_cov_row(g, c2);
-            double sa = 0.0, sb = 0.0;
-            for (long i = 0; i < n; ++i) {
-              const double ta = loo_mm_cov_coord(g, ra, i, M.data(), b.data()), tb = loo_mm_cov_coord(g, rb, i, M.data(), b.data());
-              sa += (ta - m[ra]) * (tb - m[rb]);
-              sb += w[i] * ((ta - mw[ra]) * (tb - mw[rb]));
-            }
-            SA[c2 * nc + a] = sa; SB[c2 * nc + a] = sb;
-          }
-        if (!loo_mm_cov_cand3(g, sw2, m.data(), mw.data(), SA.data(), SB.data(), M.data(), b.data(), Tm.data(), Tinv.data(), M3.data(),
-                              b3.data(), &dlogJ))
-          break;
-      }
-      const double* Mc = cand == 1 ? M.data() : cand == 2 ? M2.data() : M3.data();
-      const double* bc = cand == 1 ? b1.data() : cand == 2 ? b2.data() : b3.data();
-      for (long i = 0; i < n; ++i) { double l; const double q = loo_mm_cov_density(g, i, Mc, bc, s, &l); r[i] = loo_mm_ratio(q, Q0[i], l); }
-      const double k2 = loo_mm_psis_host(r, r_eff, lw2);
-      if (k2 < k) {
-        kind = cand; k = k2; lw = lw2;
-        loo_mm_cov_accept_inverse(g, kind, sc.data(), Tinv.data(), dlogJ, Minv.data(), &logJ);
-        const std::vector<double> Mn(Mc, Mc + nc * nc), bn(bc, bc + nc);
-        M = Mn; b = bn;
-      }
-    }
-    if (!kind) break;
-    ++iters;
-    cov_iters += kind == 3;
-    if (kinds) kinds->push_back(kind);
+  const bool matched = loo_mm_cell_host_as(cell, s, r_eff, k_threshold, max_iters, out, kinds, &lpd);
+  if (matched) loo_mm_cov_binv(g, cs.Minv, cs.b, cs.binv);
+  if (inv) {
+    for (int j = 0; j < nc * nc; ++j) inv[j] = cs.Minv[j];
+    for (int c = 0; c < nc; ++c) inv[nc * nc + c] = cs.binv[c];
+    inv[nc * nc + nc] = cs.logJ;
   }
-  if (iters == 0) return;
-  // ---- step 4 of ppcx_loo_mm.h
-  std::vector<double> a1, a2;
-  for (long i = 0; i < n; ++i)
-    if (lw[i] != -INFINITY) { a1.push_back(lw[i] + loo_mm_cov_cell_ll(g, i, M.data(), b.data(), s)); a2.push_back(lw[i]); }
-  const double elpd = loo_logsumexp_host(a1) - loo_logsumexp_host(a2);
-  loo_mm_cov_store(out, C, elpd, lpd - elpd, -2.0 * elpd, k, loo4[3], iters, cov_iters, M.data(), b.data());
-  loo_mm_cov_binv(g, Minv.data(), b.data(), binv.data());
-  give_inverse();
-  if (!split) return;
-  // ---- step 7
+  if (!matched || !split) return;
+  // ---- step 7: candidate 2's place becomes the identity state, as in the kernel
+  loo_mm_cov_identity(cs.M2, cs.b2, nc);
   const long h = loo_mm_split_half(n);
-  std::vector<double> lx(n);
+  const LooMmAffine fwd{cs.M, cs.b}, id{cs.M2, cs.b2}, back{cs.Minv, cs.binv};
+  std::vector<double> r(n), lx(n), lw, a1, a2;
   bool any = false;
   for (long i = 0; i < n; ++i) {
-    const bool first = i < h;
-    r[i] = loo_mm_cov_split_ratio(g, i, first ? M.data() : I.data(), first ? b.data() : zero.data(), first ? I.data() : Minv.data(),
-                                  first ? zero.data() : binv.data(), logJ, s, &lx[i]);
+    r[i] = i < h ? loo_mm_split_ratio(g, i, fwd, id, cs.logJ, s, &lx[i]) : loo_mm_split_ratio(g, i, id, back, cs.logJ, s, &lx[i]);
     any = any || r[i] != -INFINITY;
   }
   const double khat_split = loo_mm_psis_host(r, r_eff, lw);
   if (!any) { loo_mm_cov_store_split_nan(out); return; }
-  a1.clear(); a2.clear();
   for (long i = 0; i < n; ++i) if (lw[i] != -INFINITY) { a1.push_back(lw[i] + lx[i]); a2.push_back(lw[i]); }
   loo_mm_cov_store_split(out, loo_logsumexp_host(a1) - loo_logsumexp_host(a2), lpd, khat_split);
 }

@@ -1,44 +1,29 @@
 // ppcx_loo_mm_cov.hip -- gfx950 kernel of gene-local moment matching with the covariance step (ppcx_fit_loo_moment_match_cov,
 // include/ppcx.h; the statistic: ppcx_loo_mm_cov.h). The walk over the cells is ppcx_loo_dev.h's (for_gene_batches,
-// cells_in_batches) with ppcx_loo_mm_dev.h's LooMmWalk; the stages it shares with the other moment-matched kernels are that
-// header's: a candidate's counted ratio sweep (loo_mm_count_ratios), lpd of the original draws (loo_mm_lpd) and the weighted elpd
-// (loo_mm_weighted_elpd). ppcx_loo_mm_kernel and its entries are untouched.
+// cells_in_batches) with ppcx_loo_mm_dev.h's LooMmWalk and loo_mm_match_cells. The density is ppcx_loo_mm.h's, under the affine
+// state (LooMmAffine); the normaliser, the counted ratio sweep, lpd and the weighted elpd are ppcx_loo_mm_dev.h's, shared with
+// ppcx_loo_mm_kernel, whose body this one follows step for step (kept apart: ppcx_loo_mm.hip says why).
 //
 //   ppcx_loo_mm_cov_kernel  one workgroup of kBlockThreads per cell, after ppcx_loo_kernel over the same cells; SPLIT: the split
 //                           transformation follows in the same workgroup, from the state it has just built. A cell that is
 //                           finished in step 0 copies ppcx_loo_kernel's four fields, writes the identity and leaves at once.
-//                           Otherwise as ppcx_loo_mm_kernel: ratios, tail, log weights, Q0, then per iteration two sweeps per
-//                           coordinate for the four moments (t formed from the table and the state on the fly) and one density
-//                           sweep and one PSIS per candidate. Candidate 3, reached only when 1 is refused and 2 is refused or
-//                           invalid: sum w^2, then per pair (a <= b) one sweep for the two centred sums; thread 0 scales them,
-//                           factorises both matrices, forms L_w L^-1, L L_w^-1 and the candidate, and writes its validity to LDS;
-//                           every thread reads that word behind a barrier, so the control flow is uniform per workgroup.
-//                           The state (M, b), the three candidates, the accumulated inverse and the factors live in static LDS
-//                           (LooMmCovShared: eight (C + 1)^2 matrices at kMaxC; 22 496 bytes with PsisShared) beside the dynamic
-//                           LDS of three arrays of n doubles and the two selection arrays (96 KB + 4 KB at 4 096 draws: 124 896 of
-//                           the CU's 163 840 bytes, one workgroup per CU as ppcx_loo_mm_kernel), in the workgroup's slice of the
-//                           bounded scratch beyond.
-//                           SPLIT, a cell with iterations > 0: binv by thread 0, candidate 2's place becomes the identity; per
-//                           draw the lane selects two state pointers as ppcx_loo_mm_split_kernel does, and the ratios, ll_x and
-//                           the split's log weights take the places of the matching's ratios, Q0 and log weights, which are dead.
-//                           The inverse and logJ never leave the device.
-// A thread reads only log weights that it wrote itself or that a barrier has published. Every reduction runs in a fixed order
-// and a cell reads nothing of another gene: its fields are the same bits whatever else is requested and however the work is
-// batched.
+//                           Candidate 3, reached only when 1 is refused and 2 is refused or invalid: sum w^2, then per pair
+//                           (a <= b) one sweep for the two centred sums; thread
+//                           0 scales them, factorises both matrices, forms L_w L^-1, L L_w^-1 and the candidate, and writes
+//                           its validity to LDS; every thread reads that word behind a barrier, so the control flow is uniform
+//                           per workgroup. The state (M, b), the three candidates, the accumulated inverse and the factors
+//                           live in static LDS (LooMmCovShared: eight (C + 1)^2 matrices at kMaxC; 22 496 bytes with
+//                           PsisShared) beside the dynamic LDS of three arrays of n doubles and the two selection arrays
+//                           (96 KB + 4 KB at 4 096 draws: 124 896 of the CU's 163 840 bytes, one workgroup per CU as
+//                           ppcx_loo_mm_kernel), in the workgroup's slice of the bounded scratch beyond. The inverse and logJ
+//                           never leave the device.
+// Every reduction runs in a fixed order and a cell reads nothing of another gene: its fields are the same bits whatever else is
+// requested and however the work is batched.
 #include <hip/hip_runtime.h>
 #include "ppcx_loo_mm_dev.h"
 #include "ppcx_loo_mm_cov.h"
 
 namespace ppcx {
-
-constexpr int kCovNN = kLooMmCovNc * kLooMmCovNc;
-struct LooMmCovShared {
-  double M[kCovNN], M2[kCovNN], M3[kCovNN], Minv[kCovNN], Tinv[kCovNN], SA[kCovNN], SB[kCovNN], Tm[kCovNN];
-  double b[kLooMmCovNc], b1[kLooMmCovNc], b2[kLooMmCovNc], b3[kLooMmCovNc], binv[kLooMmCovNc];
-  double m[kLooMmCovNc], mw[kLooMmCovNc], sc[kLooMmCovNc];
-  double logJ, dlogJ;
-  int ok3;
-};
 
 template <bool LDS, bool SPLIT>
 __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_cov_kernel(LooMmArgs p) {
@@ -83,14 +68,12 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_cov_kernel(LooMmArg
   if (tid < nc) cs.b[tid] = 0.0;
   if (tid == 0) cs.logJ = 0.0;
   __syncthreads();
-  for (long i = tid; i < n; i += kBlockThreads) { double l; Q0[i] = loo_mm_cov_density(g, i, cs.M, cs.b, s, &l); }
+  for (long i = tid; i < n; i += kBlockThreads) { double l; Q0[i] = loo_mm_density(g, i, LooMmAffine{cs.M, cs.b}, s, &l); }
   // ---- the loop
   int iters = 0, cov_iters = 0;
   while (k > p.k_threshold && iters < p.max_iters) {
     // the normaliser of the current weights
-    const double mb = draws_max(n, sh.red, [&](long i) { return W[i]; });
-    const double sb = draws_sum(n, sh.red, [&](long i) { return exp(W[i] - mb); });
-    const double lse = mb + log(sb);
+    const double lse = loo_mm_lse(W, n, sh);
     // the moments of every coordinate
     bool ok2 = true;
     for (int cc = 0; cc < nc; ++cc) {
@@ -147,7 +130,7 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_cov_kernel(LooMmArg
       const double* bc = cand == 1 ? cs.b1 : cand == 2 ? cs.b2 : cs.b3;
       const CountedRatios r2 = loo_mm_count_ratios(n, V, sh, [&](long i) {
         double l;
-        const double q = loo_mm_cov_density(g, i, Mc, bc, s, &l);
+        const double q = loo_mm_density(g, i, LooMmAffine{Mc, bc}, s, &l);
         return loo_mm_ratio(q, Q0[i], l);
       });
       const int M2 = psis_tail_len(r2.N, re);
@@ -168,7 +151,7 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_cov_kernel(LooMmArg
   }
   if (iters == 0) return;
   // ---- step 4 of ppcx_loo_mm.h
-  const double elpd = loo_mm_weighted_elpd(W, n, sh, [&](long i) { return loo_mm_cov_cell_ll(g, i, cs.M, cs.b, s); });
+  const double elpd = loo_mm_weighted_elpd(W, n, sh, [&](long i) { return loo_mm_cell_ll(g, i, LooMmAffine{cs.M, cs.b}, s); });
   if (tid == 0) loo_mm_cov_store(o, C, elpd, lpd - elpd, -2.0 * elpd, k, khat0, iters, cov_iters, cs.M, cs.b);
   if constexpr (SPLIT) {
     // ---- step 7: binv; candidate 2's place becomes the identity state
@@ -187,7 +170,7 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_cov_kernel(LooMmArg
       const double* Mi = first ? cs.M2 : cs.Minv;
       const double* bi = first ? cs.b2 : cs.binv;
       double lx;
-      const double r = loo_mm_cov_split_ratio(g, i, Mx, bx, Mi, bi, logJ, s, &lx);
+      const double r = loo_mm_split_ratio(g, i, LooMmAffine{Mx, bx}, LooMmAffine{Mi, bi}, logJ, s, &lx);
       LP[i] = lx;
       return r;
     });
@@ -205,18 +188,10 @@ PPCX_KERNEL_OF(ppcx_loo_mm_cov_kernel);
 
 hipError_t loo_mm_cov_fit_cells(const FitCells& fc, double k_threshold, int max_iters, bool split, double* out, size_t scratch_bytes,
                                 hipStream_t st) {
-  LooMmWalk walk;                                        // outlives the walk, which drains the stream before it returns
-  const hipError_t e = walk.prepare(fc, st);
-  if (e != hipSuccess) return finish(e, st);
-  const long slice = loo_slice3(fc.n);
-  return for_gene_batches(fc, loo_mm_cov_fields(fc.d.C), out, scratch_bytes, st,
-                          [&](const LooArgs& a, const int* genes, int n_cells, DeviceBuffer<double>& scratch) {
-    const LooMmArgs p = walk.args(fc, a, genes, n_cells, k_threshold, max_iters, a.out);
-    // per batch of cells: plain PSIS-LOO, then the matching with the covariance step
-    return cells_in_batches(p, slice, n_cells, scratch_bytes, scratch, [&](const LooMmArgs& q, const CellLaunch& c) {
-      const hipError_t e1 = launch_loo_kernel(q.l, kLooFields, c.n_blocks, st);
-      return e1 == hipSuccess ? launch_cell_kernel(pick_kernel<ppcx_loo_mm_cov_kernel_of>(c.lds, split), q, c, q.l.sel_pad, slice, st) : e1;
-    });
+  return loo_mm_match_cells(fc, k_threshold, max_iters, loo_mm_cov_fields(fc.d.C), out, scratch_bytes, st,
+                            [&](const LooMmArgs& q, const CellLaunch& c) {
+    const hipError_t e1 = launch_loo_kernel(q.l, kLooFields, c.n_blocks, st);
+    return e1 == hipSuccess ? launch_cell_kernel(pick_kernel<ppcx_loo_mm_cov_kernel_of>(c.lds, split), q, c, q.l.sel_pad, loo_slice3(q.l.n), st) : e1;
   });
 }
 

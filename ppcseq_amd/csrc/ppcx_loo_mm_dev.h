@@ -2,7 +2,8 @@
 // ppcx_loo_mm_exact.hip: the exact predictive under the matched weights; ppcx_loo_mm_split.hip: the split transformation, both
 // forms). On the device: the argument block of the matching and the one of a kernel that runs after it (LooMmThenArgs), the gene
 // a workgroup reads, and the stages that more than one of the kernels runs -- the counted sweep of a state's ratios
-// (loo_mm_count_ratios), lpd of the original draws (loo_mm_lpd) and the weighted elpd (loo_mm_weighted_elpd). The unmatched
+// (loo_mm_count_ratios), lpd of the original draws (loo_mm_lpd), the weighted elpd (loo_mm_weighted_elpd) and the normaliser of
+// the current weights (loo_mm_lse). The unmatched
 // predictive cell and the fill of (eta, ln phi) are ppcx_loo_dev.h's (loo_exact_cell, loo_fill_eta_lnphi), shared with
 // ppcx_loo_exact_kernel. On the host: what a walk of the matching keeps on the device beside for_gene_batches' own buffers, the
 // launch of plain PSIS-LOO and the matching over a batch of cells, and the one driver of the entries that launch a kernel
@@ -96,6 +97,13 @@ __device__ __forceinline__ double loo_mm_weighted_elpd(const double* W, long n, 
   return loo_ap_lse(ma, sa) - loo_ap_lse(mb, sb);
 }
 
+// The normaliser of the current weights: logsumexp of the log weights W[0 .. n). Every thread gets the same.
+__device__ __forceinline__ double loo_mm_lse(const double* W, long n, PsisShared& sh) {
+  const double mb = draws_max(n, sh.red, [&](long i) { return W[i]; });
+  const double sb = draws_sum(n, sh.red, [&](long i) { return exp(W[i] - mb); });
+  return mb + log(sb);
+}
+
 // ---- host (ppcx_loo_mm.hip)
 // What a walk of the matching keeps for all of its gene batches: the draws' transposed hyper-parameters and ppcx_loo_kernel's
 // fields of every cell. prepare() before for_gene_batches; args() once per gene batch, in the walk's order (it counts the cells
@@ -108,6 +116,21 @@ struct LooMmWalk {
 };
 // plain PSIS-LOO by its own kernel (its slices of the scratch lie within the matching's), then the matching, over the launch c
 hipError_t launch_loo_mm_kernels(const LooMmArgs& q, const CellLaunch& c, hipStream_t st);
+
+// The driver of an entry that is the matching itself, with either state: per batch of cells launch(q, c) -- plain PSIS-LOO, then
+// the matching's kernel -- with `fields` doubles per cell into out (host)
+template <class Launch>
+hipError_t loo_mm_match_cells(const FitCells& fc, double k_threshold, int max_iters, int fields, double* out, size_t scratch_bytes,
+                              hipStream_t st, Launch launch) {
+  LooMmWalk walk;                                        // outlives the walk, which drains the stream before it returns
+  const hipError_t e = walk.prepare(fc, st);
+  if (e != hipSuccess) return finish(e, st);
+  return for_gene_batches(fc, fields, out, scratch_bytes, st,
+                          [&](const LooArgs& a, const int* genes, int n_cells, DeviceBuffer<double>& scratch) {
+    const LooMmArgs p = walk.args(fc, a, genes, n_cells, k_threshold, max_iters, a.out);
+    return cells_in_batches(p, loo_slice3(fc.n), n_cells, scratch_bytes, scratch, launch);
+  });
+}
 
 // The driver of an entry that runs a kernel after the matching: per batch of cells plain PSIS-LOO and the matching into a device
 // record that never leaves the device, then then(c.lds) -- the kernel's instantiation for cells in LDS or in the scratch -- with

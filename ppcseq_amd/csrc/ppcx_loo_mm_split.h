@@ -70,18 +70,23 @@ PPCX_HD double loo_mm_split_logaddexp(double a, double b) {
   const double mx = a > b ? a : b;
   return mx + log1p(exp(-fabs(a - b)));
 }
-// steps 3 - 5: the ratio of draw i, whose proposal point lies under the state (Ax, Bx) and whose other mixture component is
-// evaluated under (Ai, Bi); *ll_x the log-likelihood of the cell of sample s at the proposal point
-PPCX_HD double loo_mm_split_ratio(const LooMmGene& g, long i, const double* Ax, const double* Bx, const double* Ai, const double* Bi,
-                                  double logJ, int s, double* ll_x) {
+// steps 3 - 5: the ratio of draw i, whose proposal point lies under the state x and whose other mixture component is
+// evaluated under the state inv; *ll_x the log-likelihood of the cell of sample s at the proposal point
+template <class State>
+PPCX_HD double loo_mm_split_ratio(const LooMmGene& g, long i, const State& x, const State& inv, double logJ, int s, double* ll_x) {
   PPCX_NO_CONTRACT
   double l, li;
-  const double qx = loo_mm_density(g, i, Ax, Bx, s, &l);
-  const double qinv = loo_mm_density(g, i, Ai, Bi, s, &li);
+  const double qx = loo_mm_density(g, i, x, s, &l);
+  const double qinv = loo_mm_density(g, i, inv, s, &li);
   const double d = qinv - logJ;
   const double r = qx - l - loo_mm_split_logaddexp(qx, d);
   *ll_x = l;
   return isfinite(r) ? r : -INFINITY;
+}
+// the same under diagonal states (Ax, Bx) and (Ai, Bi) given by their arrays
+PPCX_HD double loo_mm_split_ratio(const LooMmGene& g, long i, const double* Ax, const double* Bx, const double* Ai, const double* Bi,
+                                  double logJ, int s, double* ll_x) {
+  return loo_mm_split_ratio(g, i, LooMmDiag{Ax, Bx}, LooMmDiag{Ai, Bi}, logJ, s, ll_x);
 }
 // step 7: the record of ppcx_loo_mm.h, then elpd_loo_matched and khat_split (NaN until a cell is split)
 PPCX_HD void loo_mm_split_store_record(double* o, int C, const double* rec) {

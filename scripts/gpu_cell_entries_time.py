@@ -52,6 +52,8 @@ def one_round(path, counts, X, expo, draws):
                  loo_moment_match_split=lambda: f.loo_moment_match(r_eff=re, k_threshold=0.5, max_iters=4, split=True),
                  loo_predict_exact_moment_match_split=lambda: f.loo_predict_exact_moment_match(r_eff=re[:K], k_threshold=0.5, max_iters=4,
                                                                                                split=True),
+                 loo_moment_match_cov=lambda: f.loo_moment_match(r_eff=re, k_threshold=0.5, max_iters=4, cov=True),
+                 loo_moment_match_cov_split=lambda: f.loo_moment_match(r_eff=re, k_threshold=0.5, max_iters=4, cov=True, split=True),
                  loo_approx=lambda: a.loo_approximate_posterior(), loo_predict_approx=lambda: a.loo_predict_approximate_posterior(seed=3),
                  loo_predict_exact_approx=lambda: a.loo_predict_exact_approximate_posterior())
     out = {}

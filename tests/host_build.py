@@ -1,6 +1,7 @@
-"""The one recipe for the CPU builds of the kernel headers: tests/<name>_host/<name>_host.cpp includes the header the gfx950
-kernel includes and is compiled with g++, as a library that the tests call through ctypes (host_lib) and, with -DPPCX_HOST_MAIN,
-as a stand-alone program with fixed inputs for a run under the host sanitizers:
+"""The one recipe for the CPU builds of the kernel headers: tests/<name>_host/<name>_host.cpp (a name that ends in _twin:
+tests/<name>/<name>.cpp) includes the header the gfx950 kernel includes and is compiled with g++, as a library that the tests
+call through ctypes (host_lib) and, with -DPPCX_HOST_MAIN, as a stand-alone program with fixed inputs for a run under the host
+sanitizers:
 
     python -m tests.host_build --sanitize [name ...]
 
@@ -18,14 +19,20 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NAMES = ("psis", "summary", "reff", "loo", "loo_mcse", "loo_predict", "loo_ap", "ppc_exact", "loo_exact", "loo_mm", "loo_mm_exact")
+NAMES = ("psis", "summary", "reff", "loo", "loo_mcse", "loo_predict", "loo_ap", "ppc_exact", "loo_exact", "loo_mm", "loo_mm_exact",
+         "loo_mm_split_twin", "loo_mm_cov_twin")
 FLAGS = ["-O2", "-std=c++17", "-fPIC", "-shared", "-fvisibility=hidden"]
 SANITIZE = ["-O1", "-g", "-std=c++17", "-DPPCX_HOST_MAIN", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"]
 RUN_SECONDS = 120                                     # a program's time limit under the sanitizers; each runs in well under 1 s
 
 
+def program(name):
+    """the program's, its directory's and its source's name"""
+    return name if name.endswith("_twin") else name + "_host"
+
+
 def source(name, root=ROOT):
-    return os.path.join(root, "tests", name + "_host", name + "_host.cpp")
+    return os.path.join(root, "tests", program(name), program(name) + ".cpp")
 
 
 def dependencies(src):
@@ -44,9 +51,9 @@ def build(src, lib):
 
 
 def host_lib(name, signatures, root=ROOT):
-    """the ctypes.CDLL of tests/<name>_host/<name>_host.cpp under root, built or reused; signatures: {function: (argtypes, restype)}"""
+    """the ctypes.CDLL of source(name, root), built or reused; signatures: {function: (argtypes, restype)}"""
     src = source(name, root)
-    lib = os.path.join(os.path.dirname(src), "lib" + name + "_host.so")
+    lib = os.path.join(os.path.dirname(src), "lib" + program(name) + ".so")
     build(src, lib)
     h = ctypes.CDLL(lib)
     for fn, (argtypes, restype) in signatures.items():
@@ -58,15 +65,15 @@ def sanitize(names):
     """build and run the stand-alone programs under the sanitizers; the exit status of the first that fails, or 0"""
     with tempfile.TemporaryDirectory() as tmp:
         for name in names:
-            exe = os.path.join(tmp, name + "_host")
+            exe = os.path.join(tmp, program(name))
             subprocess.check_call(["g++"] + SANITIZE + ["-o", exe, source(name)])
-            print("---- " + name + "_host", flush=True)
+            print("---- " + program(name), flush=True)
             try:
                 status = subprocess.run([exe], timeout=RUN_SECONDS).returncode
             except subprocess.TimeoutExpired:
                 status = 124
             if status:
-                print(f"{name}_host failed under the sanitizers: exit status {status}", flush=True)
+                print(f"{program(name)} failed under the sanitizers: exit status {status}", flush=True)
                 return status
     print(f"{len(names)} programs clean under -fsanitize=address,undefined: " + " ".join(names))
     return 0

@@ -21,10 +21,7 @@ n = 4096). GPU_MEASURED: that of the device against the CPU build over the desig
 (3.99e-11) and the draw counts (3.0e-11 at n = 4097) of tests/test_gpu_loo_mm_cov.py, which prints them. The bound of either comparison is ten times the measured
 value and never above BOUND."""
 import ctypes as C
-import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
@@ -242,20 +239,11 @@ def errors(got, ref_row):
 
 # ---- the CPU build of the header
 
-def twin_source():
-    return os.path.join(host_build.ROOT, "tests", "loo_mm_cov_twin", "loo_mm_cov_twin.cpp")
-
-
 def host_lib():
-    src = twin_source()
-    lib = os.path.join(os.path.dirname(src), "libloo_mm_cov_twin.so")
-    host_build.build(src, lib)
-    h = C.CDLL(lib)
     dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
     gene = [dp, dp, C.c_long, C.c_int, C.c_int, C.c_int, ip, dp, dp, C.c_double]
-    h.loo_mm_cov_twin_cell.argtypes = gene + [C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, dp, ip, dp]
-    h.loo_mm_cov_twin_cell.restype = C.c_int
-    return h
+    return host_build.host_lib("loo_mm_cov_twin", {
+        "loo_mm_cov_twin_cell": (gene + [C.c_int, C.c_double, C.c_double, C.c_int, C.c_int, dp, ip, dp], C.c_int)})
 
 
 def host_cell(h, gene, s, r_eff=1.0, k_threshold=0.7, max_iters=30, split=False):
@@ -271,17 +259,8 @@ def host_cell(h, gene, s, r_eff=1.0, k_threshold=0.7, max_iters=30, split=False)
 
 
 def sanitize():
-    """build the twin's stand-alone program with host_build.SANITIZE and run it as a child process under a time limit; its exit
-    status (124: the time limit)"""
-    with tempfile.TemporaryDirectory() as tmp:
-        exe = os.path.join(tmp, "loo_mm_cov_twin")
-        subprocess.check_call(["g++"] + host_build.SANITIZE + ["-o", exe, twin_source()])
-        try:
-            status = subprocess.run([exe], timeout=host_build.RUN_SECONDS).returncode
-        except subprocess.TimeoutExpired:
-            status = 124
-    print("loo_mm_cov_twin under -fsanitize=address,undefined: " + ("clean" if status == 0 else f"exit status {status}"), flush=True)
-    return status
+    """the twin's stand-alone program under the host sanitizers (python -m tests.host_build --sanitize loo_mm_cov_twin); its exit status"""
+    return host_build.sanitize(["loo_mm_cov_twin"])
 
 
 def factor4():

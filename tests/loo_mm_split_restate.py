@@ -20,10 +20,7 @@ it: 1.75e-11). GPU_MEASURED: that of the device against the CPU build over the d
 (4.78e-11 at n = 1000) and the truth case (1.9e-12) of tests/test_gpu_loo_mm_split.py, which prints them. The bound of either comparison is ten times the measured value and
 never above BOUND."""
 import ctypes as C
-import os
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 
@@ -142,24 +139,14 @@ def exact_errors(got, ref):
 
 # ---- the CPU build of the header
 
-def twin_source():
-    return os.path.join(host_build.ROOT, "tests", "loo_mm_split_twin", "loo_mm_split_twin.cpp")
-
-
 def host_lib():
-    src = twin_source()
-    lib = os.path.join(os.path.dirname(src), "libloo_mm_split_twin.so")
-    host_build.build(src, lib)
-    h = C.CDLL(lib)
     dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
     gene = [dp, dp, C.c_long, C.c_int, C.c_int, C.c_int, ip, dp, dp, C.c_double]
-    for fn, argtypes in {
-            "loo_mm_split_twin_cell": gene + [C.c_int, C.c_double, C.c_double, C.c_int, dp],
-            "loo_mm_split_twin_from_record": gene + [C.c_int, C.c_double, dp, dp],
-            "loo_mm_split_twin_exact_cell": gene + [C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, dp],
-            "loo_mm_split_twin_exact_from_record": gene + [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, dp, dp]}.items():
-        getattr(h, fn).argtypes, getattr(h, fn).restype = argtypes, None
-    return h
+    return host_build.host_lib("loo_mm_split_twin", {
+        "loo_mm_split_twin_cell": (gene + [C.c_int, C.c_double, C.c_double, C.c_int, dp], None),
+        "loo_mm_split_twin_from_record": (gene + [C.c_int, C.c_double, dp, dp], None),
+        "loo_mm_split_twin_exact_cell": (gene + [C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_double, dp], None),
+        "loo_mm_split_twin_exact_from_record": (gene + [C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, dp, dp], None)})
 
 
 def host_cell(h, gene, s, r_eff=1.0, k_threshold=0.7, max_iters=30):
@@ -225,17 +212,8 @@ def fine_grid(points=2500, n=4000):
 
 
 def sanitize():
-    """build the twin's stand-alone program with host_build.SANITIZE and run it as a child process under a time limit; its exit
-    status (124: the time limit)"""
-    with tempfile.TemporaryDirectory() as tmp:
-        exe = os.path.join(tmp, "loo_mm_split_twin")
-        subprocess.check_call(["g++"] + host_build.SANITIZE + ["-o", exe, twin_source()])
-        try:
-            status = subprocess.run([exe], timeout=host_build.RUN_SECONDS).returncode
-        except subprocess.TimeoutExpired:
-            status = 124
-    print("loo_mm_split_twin under -fsanitize=address,undefined: " + ("clean" if status == 0 else f"exit status {status}"), flush=True)
-    return status
+    """the twin's stand-alone program under the host sanitizers (python -m tests.host_build --sanitize loo_mm_split_twin); its exit status"""
+    return host_build.sanitize(["loo_mm_split_twin"])
 
 
 if __name__ == "__main__":

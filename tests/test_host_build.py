@@ -21,13 +21,15 @@ EXPECT = {
     "loo_exact": ("ppcx_summary.h", "ppcx_ppc.h", "ppcx_nbcdf.h", "ppcx_ppc_exact.h", "ppcx_loo_exact.h"),
     "loo_mm": ("ppcx_summary.h", "ppcx_ppc.h", "ppcx_ppc_exact.h", "ppcx_nbcdf.h", "ppcx_model.h", "ppcx_loo_mm.h"),
     "loo_mm_exact": ("ppcx_summary.h", "ppcx_ppc.h", "ppcx_loo_mm.h", "ppcx_loo_mm_exact.h"),
+    "loo_mm_split_twin": ("ppcx_summary.h", "ppcx_ppc.h", "ppcx_loo_mm.h", "ppcx_loo_mm_exact.h", "ppcx_loo_mm_split.h"),
+    "loo_mm_cov_twin": ("ppcx_summary.h", "ppcx_ppc.h", "ppcx_loo_mm.h", "ppcx_loo_mm_split.h", "ppcx_loo_mm_cov.h"),
 }
 
 
 def test_every_program_is_listed():
     assert sorted(EXPECT) == sorted(host_build.NAMES)
-    on_disk = sorted(d[:-len("_host")] for d in os.listdir(os.path.join(host_build.ROOT, "tests"))
-                     if d.endswith("_host") and d != "c_host" and os.path.isdir(os.path.join(host_build.ROOT, "tests", d)))
+    on_disk = sorted(d[:-len("_host")] if d.endswith("_host") else d for d in os.listdir(os.path.join(host_build.ROOT, "tests"))
+                     if d.endswith(("_host", "_twin")) and d != "c_host" and os.path.isdir(os.path.join(host_build.ROOT, "tests", d)))
     assert on_disk == sorted(host_build.NAMES)
 
 

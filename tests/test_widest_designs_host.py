@@ -327,7 +327,9 @@ def test_too_few_draws_and_a_duplicated_coordinate_are_refusals(cov_host, mm_hos
     """tests/test_loo_mm_cov_host.test_invalid_candidate_is_a_refusal at d = 17 and d = 9: prefixes of n = d - 1, d, d + 1 draws of
     the outlier cell of gene 0, and the 17-coordinate gene with slope 2 a copy of slope 1 (a singular Sigma and Sigma_w): no
     covariance step, a finite state, and the record is loo_mm_cell_host's. Every one of them ends above the threshold before
-    max_iters: candidate 3 was reached."""
+    max_iters: candidate 3 was reached.
+    Known limit: the record is held to the other twin, and both twins read the one density, prior and eta of ppcx_loo_mm.h, so
+    an error there moves both alike and is not seen here; the tests against the restatement are the ones that see it."""
     todo = []
     for name, d in (("columns16", 17), ("columns8", 9)):
         for n in (d - 1, d, d + 1):
@@ -359,7 +361,10 @@ def test_too_few_draws_and_a_duplicated_coordinate_are_refusals(cov_host, mm_hos
 
 
 def test_cells_without_a_covariance_step_are_the_diagonal_records(cov_host, mm_host):
-    """every plain designed cell on whose path no kind 3 is accepted gives loo_mm_cell_host's record from loo_mm_cov_cell_host"""
+    """every plain designed cell on whose path no kind 3 is accepted gives loo_mm_cell_host's record from loo_mm_cov_cell_host.
+    Known limit: one twin is held to the other, and both read the one density, prior and eta of ppcx_loo_mm.h: this test sees what
+    the affine state adds (the point, the candidates, the record), not an error in what the twins share, which the tests against
+    the restatement see."""
     seen = unmatched = 0
     for c in DESIGNED:
         gene = _gene(c)
