@@ -232,8 +232,8 @@ PPCX_API int ppcx_fit_loo_moment_match_split(ppcx_fit* f, int n_genes, const int
  * split), khat_split (NaN without split or with iterations = 0), transform [C + 1][C + 1] row-major and shift [C + 1] in the
  * order intercept, slopes, sigma_raw: the matched draws are transform * draw + shift (a row or column the gene does not have
  * is the identity's, its shift 0). A cell with iterations = 0 holds ppcx_fit_loo's four fields bit for bit, the identity and
- * zeros. Still left out: the exact predictive under these weights, mcse / n_eff of a matched cell, ADVI fits. The same bits
- * on every call, for any gene subset.                                                                                          */
+ * zeros. The exact predictive under these weights is ppcx_fit_loo_predict_exact_moment_match_cov. Still left out: mcse / n_eff
+ * of a matched cell, ADVI fits. The same bits on every call, for any gene subset.                                              */
 #define PPCX_LOO_MM_COV_FIELDS(C) (9 + ((C) + 1) * ((C) + 1) + ((C) + 1))
 PPCX_API int ppcx_fit_loo_moment_match_cov(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double k_threshold,
                                            int max_iters, int split, double* out);
@@ -350,7 +350,8 @@ PPCX_API int ppcx_fit_loo_predict_exact_approx(ppcx_fit* f, int n_genes, const i
  * Genes (checked ones), r_eff, probabilities, truncation compensation, limits and refusals as ppcx_fit_loo_predict_exact;
  * k_threshold and max_iters as ppcx_fit_loo_moment_match (PPCX_ERR_ARG for a k_threshold that is not finite or max_iters < 0).
  * An ADVI fit: PPCX_ERR_ARG; a ppcx_fit_from_draws fit is served. No covariance step, no split transformation: a matched khat
- * is necessary, not sufficient (ppcx_fit_loo_predict_exact_moment_match_split below adds the split). Synchronous on the model's stream; the same bits on every call, for any gene subset.
+ * is necessary, not sufficient (ppcx_fit_loo_predict_exact_moment_match_split below adds the split,
+ * ppcx_fit_loo_predict_exact_moment_match_cov the covariance step). Synchronous on the model's stream; the same bits on every call, for any gene subset.
  *   out [n_genes][S][PPCX_LOO_MM_EXACT_FIELDS(C)]: the ten fields of ppcx_fit_loo_predict_exact with khat the final one, then
  *   khat_before (plain PSIS's), iterations (accepted steps), scale[C + 1] and shift[C + 1] as ppcx_fit_loo_moment_match.
  *   A cell with iterations = 0 (excluded, NaN, at or below the threshold, max_iters = 0, or no step accepted) holds
@@ -373,6 +374,23 @@ PPCX_API int ppcx_fit_loo_predict_exact_moment_match(ppcx_fit* f, int n_genes, c
 PPCX_API int ppcx_fit_loo_predict_exact_moment_match_split(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff,
                                                            double k_threshold, int max_iters, double truncation_compensation,
                                                            double p_lo, double p_hi, double* out);
+/* ppcx_fit_loo_predict_exact with the cells above k_threshold matched first as ppcx_fit_loo_moment_match_cov matches them (the same
+ * kernels, so khat, khat_before, iterations, cov_iterations, transform and shift are that entry's bits), then the predictive
+ * under those weights at the affinely matched draws transform * draw_i + shift (ppcx_loo_mm_cov_exact.h). split != 0: the
+ * weights are the normalised PSIS weights of the split ratios of ppcx_fit_loo_moment_match_cov(split), formed on the transform,
+ * the identity and the inverse accumulated along the accepted steps; eta_i, phi_i are evaluated at the proposal points --
+ * transform * draw_i + shift for the first h = n / 2 draws in the fit's order, draw_i from h on. Nothing is sampled.
+ * Arguments, limits and refusals as ppcx_fit_loo_predict_exact_moment_match: checked genes only, an ADVI fit is PPCX_ERR_ARG, a
+ * ppcx_fit_from_draws fit and pooled chains are served.
+ *   out [n_genes][S][PPCX_LOO_MM_COV_EXACT_FIELDS(C)]: the ten fields of ppcx_fit_loo_predict_exact with khat the matching's final
+ *   one, then khat_before, iterations, cov_iterations, khat_split (NaN without split or with iterations = 0), transform
+ *   [C + 1][C + 1] row-major and shift [C + 1]. A cell with iterations = 0 holds ppcx_fit_loo_predict_exact's ten fields bit for
+ *   bit. A proposal point with invalid parameters, or no finite ratio: every statistic of the cell is NaN, khat and khat_split
+ *   included. Left out: mcse / n_eff of a matched cell, ADVI fits. The same bits on every call, for any gene subset.          */
+#define PPCX_LOO_MM_COV_EXACT_FIELDS(C) (14 + ((C) + 1) * ((C) + 1) + ((C) + 1))
+PPCX_API int ppcx_fit_loo_predict_exact_moment_match_cov(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff,
+                                                         double k_threshold, int max_iters, int split,
+                                                         double truncation_compensation, double p_lo, double p_hi, double* out);
 /* lp: [chains][n_keep]; the rest [chains][iter] (warmup included); any pointer may be NULL */
 PPCX_API int ppcx_fit_get_diagnostics(ppcx_fit* f, double* lp, double* stepsize, int32_t* treedepth,
                              int32_t* n_leapfrog, int32_t* divergent, double* accept);

@@ -28,7 +28,7 @@ EXPORTS = [
     "ppcx_fit_loo_predict", "ppcx_fit_relative_eff", "ppcx_fit_loo_mcse", "ppcx_fit_loo_approx", "ppcx_fit_loo_predict_approx",
     "ppcx_fit_ppc_exact", "ppcx_fit_loo_predict_exact", "ppcx_fit_loo_predict_exact_approx", "ppcx_fit_loo_moment_match",
     "ppcx_fit_loo_predict_exact_moment_match", "ppcx_fit_loo_moment_match_split", "ppcx_fit_loo_predict_exact_moment_match_split",
-    "ppcx_fit_loo_moment_match_cov",
+    "ppcx_fit_loo_moment_match_cov", "ppcx_fit_loo_predict_exact_moment_match_cov",
 ]
 ABI_VERSION = 400           # include/ppcx.h PPCX_VERSION this binding was written for
 SUMMARY_FIELDS = ("mean", "sd", "q05", "q50", "q95", "rhat", "ess_bulk", "ess_tail")   # PPCX_SUMMARY_FIELDS, in order
@@ -62,14 +62,18 @@ class AdviConfig(C.Structure):
 
 PROGRESS_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_double)
 _lib = None
+_LACKING = ()
 
 
-def use_library(path=None):
+def use_library(path=None, lacking=()):
     """Bind another build of the library from now on (None: back to the product build). For the tests that need the
     testing build (tests/libppcx_testing.so: fault injection, forced cell paths, kernel-level timing); every Model / Fit /
-    Comm of the previous library must have been closed."""
-    global _lib, LIB_PATH
+    Comm of the previous library must have been closed. lacking: the entries of EXPORTS that the caller states the build at
+    `path` does not have (an older build, scripts/gpu_cell_entries_time.py's parent); they are left unbound and calling one
+    raises AttributeError. load() refuses a library that lacks any other entry."""
+    global _lib, LIB_PATH, _LACKING
     _lib = None
+    _LACKING = tuple(lacking) if path else ()
     LIB_PATH = path if path else os.environ.get("PPCX_LIB", os.path.join(_HERE, "libppcx.so"))
 
 
@@ -86,6 +90,9 @@ def load() -> C.CDLL:
     if lib.ppcx_version() != ABI_VERSION:
         raise PpcxError(f"{LIB_PATH} has ABI version {lib.ppcx_version()}, this binding needs {ABI_VERSION}: rebuild it "
                         "(`python -m ppcseq_amd.build --force`)")
+    missing = [name for name in EXPORTS if name not in _LACKING and not hasattr(lib, name)]
+    if missing:
+        raise PpcxError(f"{LIB_PATH} lacks {', '.join(missing)}: rebuild it (`python -m ppcseq_amd.build --force`)")
     dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int32)
     lib.ppcx_guard_decision.argtypes = [dp, C.c_int]
     lib.ppcx_device_memory.argtypes = [C.c_int, C.POINTER(C.c_ulonglong), C.POINTER(C.c_ulonglong)]
@@ -127,6 +134,9 @@ def load() -> C.CDLL:
     lib.ppcx_fit_loo_predict_exact_moment_match.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_double, C.c_int, C.c_double, C.c_double,
                                                             C.c_double, dp]
     lib.ppcx_fit_loo_predict_exact_moment_match_split.argtypes = lib.ppcx_fit_loo_predict_exact_moment_match.argtypes
+    if "ppcx_fit_loo_predict_exact_moment_match_cov" not in _LACKING:
+        lib.ppcx_fit_loo_predict_exact_moment_match_cov.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_double, C.c_int, C.c_int, C.c_double,
+                                                                    C.c_double, C.c_double, dp]
     lib.ppcx_fit_get_diagnostics.argtypes = [C.c_void_p, dp, dp, ip, ip, ip, dp]
     lib.ppcx_fit_get_timing.argtypes = [C.c_void_p, dp, C.POINTER(C.c_longlong), dp, C.POINTER(C.c_longlong), dp]
     lib.ppcx_fit_get_kernel_times.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(C.c_longlong)]
@@ -846,7 +856,8 @@ class Fit:
         draws are mapped so that their mean and covariance over its coordinates become the weighted ones. The state is then an
         affine map: in place of `scale` the dict has `transform` [n_genes, S, C + 1, C + 1] (the matched draws are
         transform @ draw + shift; a row or column the gene does not have is the identity's) and `cov_iterations` (the accepted
-        steps of that kind, int64); with split=True also `elpd_loo_matched` and `khat_split` as above."""
+        steps of that kind, int64); with split=True also `elpd_loo_matched` and `khat_split` as above. The predictive under these
+        weights is Fit.loo_predict_exact_moment_match_cov. Still left out: mcse / n_eff of a matched cell, ADVI fits."""
         if k_threshold is None:
             from .inference import loo_threshold
             k_threshold = loo_threshold(self.chains * self.n_keep)
@@ -974,7 +985,8 @@ class Fit:
         nothing is sampled. Fit.loo_predict_exact's dict (`khat` is the final one), plus Fit.loo_moment_match's `khat_before`,
         `iterations` (int64), `scale` and `shift` [n_genes, S, C + 1] (the same bits as that method's) and `k_threshold`. A cell
         with iterations == 0 holds Fit.loo_predict_exact's bits. k_threshold=None: inference.loo_threshold(n_draws). No covariance
-        step and no split transformation: a matched khat is necessary, not sufficient. Not for an ADVI fit.
+        step (Fit.loo_predict_exact_moment_match_cov has it) and no split transformation: a matched khat is necessary, not
+        sufficient. Not for an ADVI fit.
         split=True (ppcx_fit_loo_predict_exact_moment_match_split): the split transformation as in Fit.loo_moment_match -- the
         negative binomials are evaluated at the matched draws for the first n_draws // 2 draws in the fit's order and at the
         original draws for the others, under the PSIS weights of the split ratios. `khat` and the matching's record stay its
@@ -997,6 +1009,39 @@ class Fit:
         return self._loo_exact(genes, r_eff, lambda n, g, re, out: entry(
             self._h, n, g, re, k_threshold, max_iters, float(truncation_compensation), float(p_lo), float(p_hi), out),
             more=2 + 2 * nc + (1 if split else 0), tail=tail)
+
+    def loo_predict_exact_moment_match_cov(self, genes=None, r_eff=None, k_threshold=None, max_iters=30, p_lo=0.025, p_hi=0.975,
+                                           truncation_compensation=1.0, split=False):
+        """Fit.loo_predict_exact with the cells whose khat exceeds k_threshold matched first as Fit.loo_moment_match(cov=True)
+        matches them (ppcx_fit_loo_predict_exact_moment_match_cov; restated from the paper and the published package, not run
+        against R): the predictive is taken under those weights at the affinely matched draws transform @ draw + shift; nothing
+        is sampled. Fit.loo_predict_exact's dict (`khat` is the final one), plus `khat_before`, `iterations` and
+        `cov_iterations` (int64), `transform` [n_genes, S, C + 1, C + 1], `shift` [n_genes, S, C + 1] (the same bits as
+        Fit.loo_moment_match(cov=True)'s) and `k_threshold`; there is no `scale`. A cell with iterations == 0 holds
+        Fit.loo_predict_exact's bits. k_threshold=None: inference.loo_threshold(n_draws). Not for an ADVI fit; no mcse / n_eff of
+        a matched cell.
+        split=True: the split transformation on the affine map -- the negative binomials are evaluated at the matched draws for
+        the first n_draws // 2 draws in the fit's order and at the original draws for the others, under the PSIS weights of the
+        split ratios of Fit.loo_moment_match(cov=True, split=True). `khat` and the matching's record stay its bits; added is
+        `khat_split` (NaN where iterations == 0)."""
+        if k_threshold is None:
+            from .inference import loo_threshold
+            k_threshold = loo_threshold(self.chains * self.n_keep)
+        k_threshold, max_iters = float(k_threshold), int(max_iters)
+        nc = self.model.C + 1
+
+        def tail(res, more):
+            res["khat_before"] = more[..., 0].copy()
+            res["iterations"] = more[..., 1].astype(np.int64)
+            res["cov_iterations"] = more[..., 2].astype(np.int64)
+            res["transform"] = more[..., 4:4 + nc * nc].reshape(more.shape[:-1] + (nc, nc)).copy()
+            res["shift"] = more[..., 4 + nc * nc:4 + nc * nc + nc].copy()
+            res["k_threshold"] = k_threshold
+            if split:
+                res["khat_split"] = more[..., 3].copy()
+        return self._loo_exact(genes, r_eff, lambda n, g, re, out: load().ppcx_fit_loo_predict_exact_moment_match_cov(
+            self._h, n, g, re, k_threshold, max_iters, int(bool(split)), float(truncation_compensation), float(p_lo), float(p_hi), out),
+            more=4 + nc * nc + nc, tail=tail)
 
     def loo_predict_exact_approximate_posterior(self, genes=None, p_lo=0.025, p_hi=0.975, truncation_compensation=1.0):
         """Fit.loo_predict_exact for an ADVI fit (ppcx_fit_loo_predict_exact_approx): the same dict (without r_eff) under the

@@ -403,6 +403,19 @@ extern "C" int ppcx_fit_loo_predict_exact_moment_match_split(ppcx_fit* f, int n_
   return hip_done(who, loo_mm_split_fit_cells(fc, k_threshold, max_iters, true, truncation_compensation, p_lo, p_hi, out,
                                               loo_scratch_bytes(), f->m->stream.s));
 }
+// ... with the cells matched by the matching with the covariance step (ppcx_loo_mm_cov_exact.h): ppcx_fit_loo_moment_match_cov's
+// kernels, then the predictive under their weights at the affinely matched draws; split != 0: under the split weights
+extern "C" int ppcx_fit_loo_predict_exact_moment_match_cov(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff,
+                                                           double k_threshold, int max_iters, int split,
+                                                           double truncation_compensation, double p_lo, double p_hi, double* out) {
+  const char* who = "ppcx_fit_loo_predict_exact_moment_match_cov";
+  const double probs[3] = {truncation_compensation, p_lo, p_hi};
+  std::vector<int> yenc; FitCells fc;
+  const int rc = loo_mm_prepare(who, f, n_genes, genes, r_eff, k_threshold, max_iters, probs, out, yenc, fc);
+  if (rc != PPCX_OK) return rc;
+  return hip_done(who, loo_mm_cov_exact_fit_cells(fc, k_threshold, max_iters, split != 0, truncation_compensation, p_lo, p_hi, out,
+                                                  loo_scratch_bytes(), f->m->stream.s));
+}
 #ifdef PPCX_TESTING
 // testing build only (ppcx_testing.h): the kernel of the two above on host-given columns, on the current device
 extern "C" int ppcx_testing_loo_exact(int n, int n_cols, const double* ll, const double* eta, const double* sigma_raw, const int32_t* y,

@@ -320,6 +320,12 @@ hipError_t loo_mm_split_fit_cells(const FitCells& fc, double k_threshold, int ma
 // doubles as loo_mm_fit_cells. split: the split transformation follows in the same workgroup. out [cells][loo_mm_cov_fields(C)]
 hipError_t loo_mm_cov_fit_cells(const FitCells& fc, double k_threshold, int max_iters, bool split, double* out, size_t scratch_bytes,
                                 hipStream_t st);
+// The exact predictive under the weights of that matching (ppcx_loo_mm_cov_exact.hip, statistic in ppcx_loo_mm_cov_exact.h): per
+// batch of cells ppcx_loo_kernel and the non-split ppcx_loo_mm_cov_kernel into a device record and the accumulated inverse beside
+// it, then one workgroup per cell with the states in static LDS; the same three arrays of n doubles. split: under the split
+// weights. out [cells][loo_mm_cov_exact_fields(C)]
+hipError_t loo_mm_cov_exact_fit_cells(const FitCells& fc, double k_threshold, int max_iters, bool split, double tc, double p_lo, double p_hi,
+                                      double* out, size_t scratch_bytes, hipStream_t st);
 // The relative efficiency of the same cells (ppcx_reff.hip, statistic in ppcx_reff.h): one workgroup per cell; the split values
 // (8 bytes each) in LDS for fits of up to kPsisLdsDraws draws, beyond that in the scratch. Of `l` it uses T / y / expo / X / S / C
 // or cols, n = chains n_keep, cell0, n_cells, scratch ([launch's cells][2 chains (n_keep / 2)]) and out ([cells], one value

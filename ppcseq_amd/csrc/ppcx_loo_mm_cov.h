@@ -43,7 +43,8 @@
 //      cov_iterations (the accepted steps of kind 3), elpd_loo_matched (the unsplit estimate; elpd_loo without split),
 //      khat_split (NaN without split or with iterations == 0), transform [C + 1][C + 1] row-major, shift [C + 1]. A cell with
 //      iterations == 0 holds ppcx_fit_loo's four fields bit for bit, the identity and zeros.
-// Still left out: the exact predictive under covariance-matched weights, mcse / n_eff of a matched cell, ADVI fits.
+// The exact predictive under these weights is ppcx_loo_mm_cov_exact.h, which reads this record and the accumulated inverse.
+// Still left out: mcse / n_eff of a matched cell, ADVI fits.
 // Every reduction runs in a fixed order with contraction off: a cell's fields depend on its own gene's data only.
 #pragma once
 #include <stdint.h>
@@ -310,7 +311,7 @@ struct LooMmCovCell {
 namespace ppcx {
 // the whole spec for one cell, sequentially, for the CPU check: ppcx_loo_mm.h's cell under the affine state, then step 7:
 // out[loo_mm_cov_fields(C)]. kinds (may be null): the accepted candidates in order, 1, 2 or 3. inv (may be null): Minv [nc][nc],
-// binv [nc] and logJ of the final state, nc nc + nc + 1 doubles.
+// binv [nc] and logJ of the final state, nc nc + nc + 1 doubles (ppcx_loo_mm_cov_exact.h's loo_mm_cov_inv_fields).
 inline void loo_mm_cov_cell_host(const LooMmGene& g, int s, double r_eff, double k_threshold, int max_iters, bool split, double* out,
                                  std::vector<int>* kinds = nullptr, double* inv = nullptr) {
   PPCX_NO_CONTRACT

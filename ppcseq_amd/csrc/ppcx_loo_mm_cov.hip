@@ -16,7 +16,11 @@
 //                           PsisShared) beside the dynamic LDS of three arrays of n doubles and the two selection arrays
 //                           (96 KB + 4 KB at 4 096 draws: 124 896 of the CU's 163 840 bytes, one workgroup per CU as
 //                           ppcx_loo_mm_kernel), in the workgroup's slice of the bounded scratch beyond. The inverse and logJ
-//                           never leave the device.
+//                           never leave the device. INV (ppcx_loo_mm_cov_exact.hip's driver; launched where LooMmArgs::inv
+//                           is given, without SPLIT): thread 0 writes Minv, binv and logJ of a matched cell there after the
+//                           loop. It is an instantiation of its own, so that the kernels of a launch without the pointer are
+//                           the code they were: a run-time check of the pointer cost loo_moment_match(cov=True) 2.7 % of its time
+//                           (profiles/cell_entries_ab.json, mm_cov_exact / first_version).
 // Every reduction runs in a fixed order and a cell reads nothing of another gene: its fields are the same bits whatever else is
 // requested and however the work is batched.
 #include <hip/hip_runtime.h>
@@ -25,7 +29,14 @@
 
 namespace ppcx {
 
-template <bool LDS, bool SPLIT>
+// the accumulated inverse of a matched cell for the kernel that runs after this one: Minv, binv, logJ (thread 0; binv formed)
+__device__ __forceinline__ void loo_mm_cov_store_inverse(double* v, int nc, const LooMmCovShared& cs) {
+  for (int j = 0; j < nc * nc; ++j) v[j] = cs.Minv[j];
+  for (int j = 0; j < nc; ++j) v[nc * nc + j] = cs.binv[j];
+  v[nc * nc + nc] = cs.logJ;
+}
+
+template <bool LDS, bool SPLIT, bool INV = false>
 __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_cov_kernel(LooMmArgs p) {
 #pragma clang fp contract(off)
   extern __shared__ uint64_t lds_u[];
@@ -153,6 +164,14 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_cov_kernel(LooMmArg
   // ---- step 4 of ppcx_loo_mm.h
   const double elpd = loo_mm_weighted_elpd(W, n, sh, [&](long i) { return loo_mm_cell_ll(g, i, LooMmAffine{cs.M, cs.b}, s); });
   if (tid == 0) loo_mm_cov_store(o, C, elpd, lpd - elpd, -2.0 * elpd, k, khat0, iters, cov_iters, cs.M, cs.b);
+  static_assert(!(INV && SPLIT), "the inverse is handed on by the non-split instantiation");
+  if constexpr (INV) {
+    // ---- the accumulated inverse for the kernel that runs after this one: thread 0 alone wrote Minv and logJ; binv is formed here
+    if (tid == 0) {
+      loo_mm_cov_binv(g, cs.Minv, cs.b, cs.binv);
+      loo_mm_cov_store_inverse(p.inv + (long)cell * (nc * nc + nc + 1), nc, cs);
+    }
+  }
   if constexpr (SPLIT) {
     // ---- step 7: binv; candidate 2's place becomes the identity state
     __syncthreads();                                       // step 4's reads of the state and of W are over
@@ -186,13 +205,20 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_cov_kernel(LooMmArg
 // ---- launch helpers (host)
 PPCX_KERNEL_OF(ppcx_loo_mm_cov_kernel);
 
+// q.inv given: the non-split instantiation that leaves the accumulated inverse there (split is then not served)
+hipError_t launch_loo_mm_cov_kernels(const LooMmArgs& q, const CellLaunch& c, bool split, hipStream_t st) {
+  if (q.inv && split) return hipErrorInvalidValue;
+  const hipError_t e1 = launch_loo_kernel(q.l, kLooFields, c.n_blocks, st);
+  if (e1 != hipSuccess) return e1;
+  const auto kernel = q.inv ? (c.lds ? &ppcx_loo_mm_cov_kernel<true, false, true> : &ppcx_loo_mm_cov_kernel<false, false, true>)
+                            : pick_kernel<ppcx_loo_mm_cov_kernel_of>(c.lds, split);
+  return launch_cell_kernel(kernel, q, c, q.l.sel_pad, loo_slice3(q.l.n), st);
+}
+
 hipError_t loo_mm_cov_fit_cells(const FitCells& fc, double k_threshold, int max_iters, bool split, double* out, size_t scratch_bytes,
                                 hipStream_t st) {
   return loo_mm_match_cells(fc, k_threshold, max_iters, loo_mm_cov_fields(fc.d.C), out, scratch_bytes, st,
-                            [&](const LooMmArgs& q, const CellLaunch& c) {
-    const hipError_t e1 = launch_loo_kernel(q.l, kLooFields, c.n_blocks, st);
-    return e1 == hipSuccess ? launch_cell_kernel(pick_kernel<ppcx_loo_mm_cov_kernel_of>(c.lds, split), q, c, q.l.sel_pad, loo_slice3(q.l.n), st) : e1;
-  });
+                            [&](const LooMmArgs& q, const CellLaunch& c) { return launch_loo_mm_cov_kernels(q, c, split, st); });
 }
 
 }  // namespace ppcx

@@ -23,13 +23,14 @@ struct LooMmArgs {
   int K = 0;                       // checked genes of the model
   double lambda_mu_mu = 0.0, k_threshold = 0.7;
   int max_iters = 0;
-  double* out = nullptr;           // [cells][loo_mm_fields(C)]
+  double* out = nullptr;           // [cells][loo_mm_fields(C)]; ppcx_loo_mm_cov_kernel: [cells][loo_mm_cov_fields(C)]
+  double* inv = nullptr;           // ppcx_loo_mm_cov_kernel<.., INV>, optional: [cells][(C + 1)^2 + (C + 1) + 1] Minv, binv, logJ of a matched cell
 };
 
 // The argument block of a kernel that runs after the matching over the same cells (ppcx_loo_mm_exact_kernel,
-// ppcx_loo_mm_split_kernel)
+// ppcx_loo_mm_split_kernel, ppcx_loo_mm_cov_exact_kernel)
 struct LooMmThenArgs {
-  LooMmArgs m;                     // the matching's block: m.l the table and the cells, m.out its record [cells][loo_mm_fields(C)] (device)
+  LooMmArgs m;                     // the matching's block: m.l the table and the cells, m.out its record (device), m.inv its second one
   double log_tc = 0.0, p_lo = 0.025, p_hi = 0.975;   // the predictive forms'
   double* out = nullptr;           // [cells][the entry's fields]
 };
@@ -116,6 +117,16 @@ struct LooMmWalk {
 };
 // plain PSIS-LOO by its own kernel (its slices of the scratch lie within the matching's), then the matching, over the launch c
 hipError_t launch_loo_mm_kernels(const LooMmArgs& q, const CellLaunch& c, hipStream_t st);
+// the same with the matching of ppcx_loo_mm_cov.hip (split: its split instantiation)
+hipError_t launch_loo_mm_cov_kernels(const LooMmArgs& q, const CellLaunch& c, bool split, hipStream_t st);
+
+// The matching that runs ahead of a kernel, as loo_mm_then_fit_cells takes it: its launch over a batch of cells, the width of
+// its record and of an optional second device record per cell (0: none; LooMmArgs::inv). The per-coordinate matching:
+struct LooMmDiagMatching {
+  int fields(int C) const { return loo_mm_fields(C); }
+  int second(int) const { return 0; }
+  hipError_t launch(const LooMmArgs& q, const CellLaunch& c, hipStream_t st) const { return launch_loo_mm_kernels(q, c, st); }
+};
 
 // The driver of an entry that is the matching itself, with either state: per batch of cells launch(q, c) -- plain PSIS-LOO, then
 // the matching's kernel -- with `fields` doubles per cell into out (host)
@@ -132,16 +143,18 @@ hipError_t loo_mm_match_cells(const FitCells& fc, double k_threshold, int max_it
   });
 }
 
-// The driver of an entry that runs a kernel after the matching: per batch of cells plain PSIS-LOO and the matching into a device
-// record that never leaves the device, then then(c.lds) -- the kernel's instantiation for cells in LDS or in the scratch -- with
-// `fields` doubles per cell into out (host). Every kernel takes its slice of loo_slice3 doubles from the same scratch.
-template <class Then>
-hipError_t loo_mm_then_fit_cells(const FitCells& fc, double k_threshold, int max_iters, double tc, double p_lo, double p_hi, int fields,
-                                 double* out, size_t scratch_bytes, hipStream_t st, Then then) {
-  const int mm_fields = loo_mm_fields(fc.d.C);
-  LooMmWalk walk; DeviceBuffer<double> d_rec;            // outlive the walk, which drains the stream before it returns
+// The driver of an entry that runs a kernel after a matching `mt` (LooMmDiagMatching, ppcx_loo_mm_cov_exact.hip's): per batch of
+// cells plain PSIS-LOO and the matching into a device record (and its optional second one) that never leaves the device, then
+// then(c.lds) -- the kernel's instantiation for cells in LDS or in the scratch -- with `fields` doubles per cell into out (host).
+// Every kernel takes its slice of loo_slice3 doubles from the same scratch.
+template <class Matching, class Then>
+hipError_t loo_mm_then_fit_cells(const FitCells& fc, const Matching& mt, double k_threshold, int max_iters, double tc, double p_lo,
+                                 double p_hi, int fields, double* out, size_t scratch_bytes, hipStream_t st, Then then) {
+  const int mm_fields = mt.fields(fc.d.C), inv_fields = mt.second(fc.d.C);
+  LooMmWalk walk; DeviceBuffer<double> d_rec, d_inv;     // outlive the walk, which drains the stream before it returns
   hipError_t e = walk.prepare(fc, st);
   if (e == hipSuccess) e = d_rec.alloc((size_t)fc.n_genes * fc.d.S * mm_fields);
+  if (e == hipSuccess && inv_fields > 0) e = d_inv.alloc((size_t)fc.n_genes * fc.d.S * inv_fields);
   if (e != hipSuccess) return finish(e, st);
   const double log_tc = log(tc);
   const long slice = loo_slice3(fc.n);
@@ -150,9 +163,10 @@ hipError_t loo_mm_then_fit_cells(const FitCells& fc, double k_threshold, int max
     LooMmThenArgs p;
     const size_t done = walk.done;
     p.m = walk.args(fc, a, genes, n_cells, k_threshold, max_iters, d_rec.p + done * mm_fields);
+    if (inv_fields > 0) p.m.inv = d_inv.p + done * inv_fields;
     p.log_tc = log_tc; p.p_lo = p_lo; p.p_hi = p_hi; p.out = a.out;
     return cells_in_batches(p, slice, n_cells, scratch_bytes, scratch, [&](const LooMmThenArgs& q, const CellLaunch& c) {
-      const hipError_t e1 = launch_loo_mm_kernels(q.m, c, st);
+      const hipError_t e1 = mt.launch(q.m, c, st);
       return e1 == hipSuccess ? launch_cell_kernel(then(c.lds), q, c, q.m.l.sel_pad, slice, st) : e1;
     });
   });

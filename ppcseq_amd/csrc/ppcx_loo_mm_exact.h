@@ -26,7 +26,8 @@
 //      in the table's row order.
 //   5. Left out, as in ppcx_loo_mm.h: the split transformation and the covariance step. A matched khat therefore stays
 //      necessary, not sufficient; mcse / n_eff of a matched cell are not estimated. The split transformation is
-//      ppcx_loo_mm_split.h (ppcx_fit_loo_predict_exact_moment_match_split).
+//      ppcx_loo_mm_split.h (ppcx_fit_loo_predict_exact_moment_match_split); the covariance step is ppcx_loo_mm_cov_exact.h
+//      (ppcx_fit_loo_predict_exact_moment_match_cov).
 // Every sum runs in a fixed order with contraction off: a cell's fields depend on its own gene's data only.
 #pragma once
 #include <stdint.h>

@@ -74,8 +74,8 @@ PPCX_KERNEL_OF(ppcx_loo_mm_exact_kernel);
 
 hipError_t loo_mm_exact_fit_cells(const FitCells& fc, double k_threshold, int max_iters, double tc, double p_lo, double p_hi, double* out,
                                   size_t scratch_bytes, hipStream_t st) {
-  return loo_mm_then_fit_cells(fc, k_threshold, max_iters, tc, p_lo, p_hi, loo_mm_exact_fields(fc.d.C), out, scratch_bytes, st,
-                               [](bool lds) { return pick_kernel<ppcx_loo_mm_exact_kernel_of>(lds); });
+  return loo_mm_then_fit_cells(fc, LooMmDiagMatching{}, k_threshold, max_iters, tc, p_lo, p_hi, loo_mm_exact_fields(fc.d.C), out,
+                               scratch_bytes, st, [](bool lds) { return pick_kernel<ppcx_loo_mm_exact_kernel_of>(lds); });
 }
 
 }  // namespace ppcx

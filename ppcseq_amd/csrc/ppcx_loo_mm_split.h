@@ -40,7 +40,8 @@
 //   9. The first half is the first h draws in the fit's order, i.e. whole leading chains (and the leading part of the middle one
 //      when the chain count is odd), as loo takes them.
 //  10. Every sum runs in a fixed order with contraction off: a cell's fields depend on its own gene's data only.
-// Left out: the covariance step (ppcx_loo_mm_cov.h runs these steps on its affine map), mcse / n_eff of a matched cell, ADVI fits. khat_split is a diagnostic of the split ratios, not
+// Left out: the covariance step (ppcx_loo_mm_cov.h runs steps 2 - 7 on its affine map, ppcx_loo_mm_cov_exact.h step 8), mcse / n_eff of a
+// matched cell, ADVI fits. khat_split is a diagnostic of the split ratios, not
 // a gate: nothing is refused or repeated on its account.
 #pragma once
 #include <stdint.h>

@@ -131,8 +131,8 @@ PPCX_KERNEL_OF(ppcx_loo_mm_split_kernel);
 hipError_t loo_mm_split_fit_cells(const FitCells& fc, double k_threshold, int max_iters, bool predictive, double tc, double p_lo,
                                   double p_hi, double* out, size_t scratch_bytes, hipStream_t st) {
   const int fields = predictive ? loo_mm_exact_split_fields(fc.d.C) : loo_mm_split_fields(fc.d.C);
-  return loo_mm_then_fit_cells(fc, k_threshold, max_iters, predictive ? tc : 1.0, p_lo, p_hi, fields, out, scratch_bytes, st,
-                               [=](bool lds) { return pick_kernel<ppcx_loo_mm_split_kernel_of>(lds, predictive); });
+  return loo_mm_then_fit_cells(fc, LooMmDiagMatching{}, k_threshold, max_iters, predictive ? tc : 1.0, p_lo, p_hi, fields, out, scratch_bytes,
+                               st, [=](bool lds) { return pick_kernel<ppcx_loo_mm_split_kernel_of>(lds, predictive); });
 }
 
 }  // namespace ppcx

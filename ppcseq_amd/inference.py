@@ -231,6 +231,7 @@ class CheckContext:
     loo_moment_match_split: bool = False         # Fit.loo_moment_match is read with split=True
     exact_loo_moment_match_split: bool = False   # Fit.loo_predict_exact_moment_match is read with split=True
     loo_moment_match_cov: bool = False           # Fit.loo_moment_match is read with cov=True
+    exact_loo_moment_match_cov: bool = False     # exact_loo_moment_match reads Fit.loo_predict_exact_moment_match_cov
 
 
 @dataclass(frozen=True)
@@ -273,8 +274,10 @@ def _read_loo(fit, ctx):
 def _read_exact_loo(fit, ctx):
     """exact_loo_intervals' read: Fit.loo_predict_exact(r_eff, the pass's interval), or with exact_loo_moment_match
     Fit.loo_predict_exact_moment_match with the same keywords (its khat is the final one), with exact_loo_moment_match_split also
-    split=True"""
+    split=True; with exact_loo_moment_match_cov the method is Fit.loo_predict_exact_moment_match_cov, its keywords the same"""
     read = fit.loo_predict_exact_moment_match if ctx.exact_loo_moment_match else fit.loo_predict_exact
+    if ctx.exact_loo_moment_match and ctx.exact_loo_moment_match_cov:
+        read = fit.loo_predict_exact_moment_match_cov
     split = dict(split=True) if ctx.exact_loo_moment_match and ctx.exact_loo_moment_match_split else {}
     return read(np.arange(ctx.K), r_eff=ctx.loo_r_eff, **_interval(ctx), **split)
 
@@ -331,6 +334,8 @@ MODIFIERS = (       # (option, the options of which it needs one, what it is tol
      "exact_loo_moment_match_split needs exact_loo_moment_match: it is the split transformation of the cells that it has matched"),
     ("loo_moment_match_cov", ("loo_moment_match",),
      "loo_moment_match_cov needs loo_moment_match: it is the covariance step of the matching of its cells"),
+    ("exact_loo_moment_match_cov", ("exact_loo_moment_match",),
+     "exact_loo_moment_match_cov needs exact_loo_moment_match: it is the covariance step of the matching of its cells"),
 )
 LOO_MOMENT_MATCH_MCSE = ("loo_mcse cannot be combined with loo_moment_match: the Monte-Carlo standard error and n_eff are those of "
                          "plain PSIS weights and are not given for a matched cell")
@@ -405,7 +410,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                  exact_loo_moment_match=False,
                  loo_moment_match_split=False,
                  exact_loo_moment_match_split=False,
-                 loo_moment_match_cov=False):
+                 loo_moment_match_cov=False,
+                 exact_loo_moment_match_cov=False):
     """One inference pass (discovery or test) of ppcseq on the GPU.
 
     counts            G x S integer matrix, genes ordered with the `how_many_to_check` checked genes first
@@ -488,7 +494,12 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
     loo_moment_match_cov  True: loo_moment_match reads Fit.loo_moment_match(cov=True): the covariance step as a third candidate of
                       the matching (restated from the paper and the published package; not run against R); `res.loo` then carries
                       `transform` in place of `scale`, and `cov_iterations`. Free to combine with loo_moment_match_split; refused
-                      with loo_mcse as loo_moment_match is. Needs loo_moment_match. The exact predictive takes no such flag.
+                      with loo_mcse as loo_moment_match is. Needs loo_moment_match. It affects `res.loo` only.
+    exact_loo_moment_match_cov  True: exact_loo_moment_match reads Fit.loo_predict_exact_moment_match_cov, the predictive under the
+                      weights of the matching with the covariance step at the affinely matched draws;
+                      `res.exact_loo_intervals` then carries `transform` in place of `scale`, and `cov_iterations`. Free to
+                      combine with exact_loo_moment_match_split. devices=[...]: over the pooled chains. Needs
+                      exact_loo_moment_match.
     Returns an InferenceResult.
     """
     counts = np.asarray(counts)
@@ -553,7 +564,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                                               exact_loo_moment_match=bool(checks.get("exact_loo_moment_match", False)),
                                               loo_moment_match_split=bool(checks.get("loo_moment_match_split", False)),
                                               exact_loo_moment_match_split=bool(checks.get("exact_loo_moment_match_split", False)),
-                                              loo_moment_match_cov=bool(checks.get("loo_moment_match_cov", False))),
+                                              loo_moment_match_cov=bool(checks.get("loo_moment_match_cov", False)),
+                                              exact_loo_moment_match_cov=bool(checks.get("exact_loo_moment_match_cov", False))),
                                   checks, res)
         for msg in msgs:
             warnings.warn(msg, RuntimeWarning, stacklevel=2)
@@ -644,7 +656,8 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
                                               exact_loo_moment_match=bool(checks.get("exact_loo_moment_match", False)),
                                               loo_moment_match_split=bool(checks.get("loo_moment_match_split", False)),
                                               exact_loo_moment_match_split=bool(checks.get("exact_loo_moment_match_split", False)),
-                                              loo_moment_match_cov=bool(checks.get("loo_moment_match_cov", False))),
+                                              loo_moment_match_cov=bool(checks.get("loo_moment_match_cov", False)),
+                                              exact_loo_moment_match_cov=bool(checks.get("exact_loo_moment_match_cov", False))),
                                   checks, res)
         finally:
             fit.close()

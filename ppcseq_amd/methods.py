@@ -129,7 +129,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                       check_loo_intervals=False, loo_r_eff=None, loo_mcse=False, loo_moment_match=False,
                       check_approximation_loo=False, check_approximation_loo_intervals=False, exact_intervals=False,
                       exact_loo_intervals=False, exact_approximation_loo_intervals=False, exact_loo_moment_match=False,
-                      loo_moment_match_split=False, exact_loo_moment_match_split=False, loo_moment_match_cov=False):
+                      loo_moment_match_split=False, exact_loo_moment_match_split=False, loo_moment_match_cov=False,
+                      exact_loo_moment_match_cov=False):
     """Mirror of ppcseq::identify_outliers (R/methods.R:74-367): same arguments, same defaults.
 
     data is a tidy pandas DataFrame (one row per transcript x sample); column arguments are strings. As in the
@@ -166,6 +167,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                                                      split transformation of the matched cells); in the same attrs
     `loo_moment_match_cov` = True                 -> loo_moment_match reads its method with cov=True (the covariance step); in
                                                      the same attrs
+    `exact_loo_moment_match_cov` = True           -> exact_loo_moment_match reads Fit.loo_predict_exact_moment_match_cov (the
+                                                     covariance step); in the same attrs
     """
     import os
     import pandas as pd

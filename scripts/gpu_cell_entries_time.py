@@ -2,10 +2,12 @@
 model of 1 000 genes (500 checked) x 100 samples with two excluded cells, 4 x 500 draws around the data's own parameters loaded with
 Model.fit_from_draws, and an ADVI fit of the same model (2 000 draws) for the three ADVI entries. The two libraries alternate
 in one process, PAIRS pairs after a warm-up pair; each entry is one synchronous call. A record, not a gate: an entry counts as
-slower where the new median exceeds the parent's by more than twice the larger same-build spread (max - min) of the visit.
+slower where the new median exceeds the parent's by more than twice the larger same-build spread (max - min) of the visit. An
+entry that the parent build lacks is recorded with its new times only.
 
     git worktree add ../parent <commit> && (cd ../parent && python -m ppcseq_amd.build)
     python scripts/gpu_cell_entries_time.py ../parent/ppcseq_amd/libppcx.so [out.json]"""
+import ctypes
 import json
 import os
 import statistics
@@ -38,8 +40,13 @@ def inputs():
 
 
 def one_round(path, counts, X, expo, draws):
-    """{entry: seconds} of one call each under the library at path (None: this tree's)"""
-    L.use_library(path)
+    """{entry: seconds} of one call each under the library at path (None: this tree's); an entry whose export the library at
+    path lacks is left out"""
+    lacking = ()
+    if path:
+        probe = ctypes.CDLL(path)
+        lacking = tuple(name for name in L.EXPORTS if not hasattr(probe, name))
+    L.use_library(path, lacking=lacking)
     m = L.Model(counts, X, expo, K, lambda_mu_mu=loo_mm_cases.LAMBDA_MU_MU, excl=np.array([3, 7 * S + 1], np.int32))
     f = m.fit_from_draws(draws)
     a = m.fit_advi(output_samples=CHAINS * KEEP, iter=400, eval_elbo=50, seed=4)
@@ -54,11 +61,16 @@ def one_round(path, counts, X, expo, draws):
                                                                                                split=True),
                  loo_moment_match_cov=lambda: f.loo_moment_match(r_eff=re, k_threshold=0.5, max_iters=4, cov=True),
                  loo_moment_match_cov_split=lambda: f.loo_moment_match(r_eff=re, k_threshold=0.5, max_iters=4, cov=True, split=True),
+                 loo_predict_exact_moment_match_cov=lambda: f.loo_predict_exact_moment_match_cov(r_eff=re[:K], k_threshold=0.5, max_iters=4),
+                 loo_predict_exact_moment_match_cov_split=lambda: f.loo_predict_exact_moment_match_cov(r_eff=re[:K], k_threshold=0.5,
+                                                                                                       max_iters=4, split=True),
                  loo_approx=lambda: a.loo_approximate_posterior(), loo_predict_approx=lambda: a.loo_predict_approximate_posterior(seed=3),
                  loo_predict_exact_approx=lambda: a.loo_predict_exact_approximate_posterior())
     out = {}
     try:
         for name, call in calls.items():
+            if "ppcx_fit_" + name.removesuffix("_split") in lacking:   # the two forms of the one export the parent build may lack
+                continue
             t0 = time.perf_counter()
             call()
             out[name] = time.perf_counter() - t0
@@ -82,7 +94,11 @@ def main():
     rec = dict(what="seconds per synchronous call, parent build against this tree's, alternating in one process; %d genes x %d samples, "
                     "%d checked, %d draws; %d pairs after a warm-up pair" % (G, S, K, CHAINS * KEEP, PAIRS), entries={})
     for name in times["new"]:
-        p, n = times["parent"][name], times["new"][name]
+        n = times["new"][name]
+        if name not in times["parent"]:                                # new with this tree: nothing to compare with
+            rec["entries"][name] = dict(new=[round(t, 5) for t in n], new_median=round(statistics.median(n), 5))
+            continue
+        p = times["parent"][name]
         spread = max(max(p) - min(p), max(n) - min(n))
         rec["entries"][name] = dict(parent=[round(t, 5) for t in p], new=[round(t, 5) for t in n],
                                     parent_median=round(statistics.median(p), 5), new_median=round(statistics.median(n), 5),
