@@ -62,6 +62,24 @@ PPCX_API const char* ppcx_last_error(void);
 PPCX_API int ppcx_model_create(int device, int G, int S, int C, int K, const int32_t* counts, const double* X,
                       const double* exposure_rate, double lambda_mu_mu, int n_excl, const int32_t* excl,
                       ppcx_model** out);
+/* ... with a choice of where the log-likelihood kernel keeps the per-sample constants (exp(exposure_s) and the design's slope
+ * columns: S * C doubles; S * (2 + C) for a design without the column of ones). In LDS they share a compute unit's 160 KB with
+ * 20 KB of tables, which bounds S (8 704 at C = 2, 2 176 at C = 8, 1 088 at C = 16); streamed, the kernel reads them from global
+ * memory and the bound is the dispersion-table kernel's row of counts, S <= 39 552 (PPCX_ERR_LIMIT beyond).
+ *   PPCX_PER_SAMPLE_LDS    exactly ppcx_model_create, its refusals included
+ *   PPCX_PER_SAMPLE_STREAM always streamed
+ *   PPCX_PER_SAMPLE_AUTO   LDS where ppcx_model_create accepts the model (the same model, bit for bit), streamed where it
+ *                          refuses it for LDS
+ * A streamed model runs the three-launch round (ppcx_model_get_rounds says so; ppcx_fit_nuts_xchg refuses it); the gene-shard
+ * constructors stay on LDS. The refusals of more than 16 columns, and of a continuous covariate or a missing column of ones
+ * among more than 8, hold for every value.                                                                                  */
+#define PPCX_PER_SAMPLE_LDS 0
+#define PPCX_PER_SAMPLE_STREAM 1
+#define PPCX_PER_SAMPLE_AUTO 2
+PPCX_API int ppcx_model_create_ex(int device, int G, int S, int C, int K, const int32_t* counts, const double* X,
+                      const double* exposure_rate, double lambda_mu_mu, int n_excl, const int32_t* excl,
+                      int per_sample, ppcx_model** out);
+PPCX_API int ppcx_model_get_per_sample(const ppcx_model* m, int* streamed);   /* 1: the model streams them, 0: LDS */
 PPCX_API int ppcx_model_set_exclusions(ppcx_model* m, int n_excl, const int32_t* excl);   /* pass 2 of R/methods.R:320-342 */
 PPCX_API int ppcx_model_set_launch(ppcx_model* m, int lanes_per_gene, int workgroups); /* 0 = automatic; lanes: power of two <= 64 */
 PPCX_API int ppcx_model_get_launch(const ppcx_model* m, int* lanes_per_gene, int* nblocks);

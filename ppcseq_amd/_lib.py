@@ -29,7 +29,9 @@ EXPORTS = [
     "ppcx_fit_ppc_exact", "ppcx_fit_loo_predict_exact", "ppcx_fit_loo_predict_exact_approx", "ppcx_fit_loo_moment_match",
     "ppcx_fit_loo_predict_exact_moment_match", "ppcx_fit_loo_moment_match_split", "ppcx_fit_loo_predict_exact_moment_match_split",
     "ppcx_fit_loo_moment_match_cov", "ppcx_fit_loo_predict_exact_moment_match_cov",
+    "ppcx_model_create_ex", "ppcx_model_get_per_sample",
 ]
+PER_SAMPLE = {"lds": 0, "stream": 1, "auto": 2}     # PPCX_PER_SAMPLE_*
 ABI_VERSION = 400           # include/ppcx.h PPCX_VERSION this binding was written for
 SUMMARY_FIELDS = ("mean", "sd", "q05", "q50", "q95", "rhat", "ess_bulk", "ess_tail")   # PPCX_SUMMARY_FIELDS, in order
 LOO_FIELDS = ("elpd_loo", "p_loo", "looic", "khat")                                      # PPCX_LOO_FIELDS, in order
@@ -99,6 +101,9 @@ def load() -> C.CDLL:
     lib.ppcx_fit_get_ppc_timing.argtypes = [C.c_void_p, dp, C.POINTER(C.c_longlong)]
     lib.ppcx_last_error.restype = C.c_char_p
     lib.ppcx_model_create.argtypes = [C.c_int] * 5 + [ip, dp, dp, C.c_double, C.c_int, ip, C.POINTER(C.c_void_p)]
+    if "ppcx_model_create_ex" not in _LACKING:
+        lib.ppcx_model_create_ex.argtypes = [C.c_int] * 5 + [ip, dp, dp, C.c_double, C.c_int, ip, C.c_int, C.POINTER(C.c_void_p)]
+        lib.ppcx_model_get_per_sample.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
     lib.ppcx_model_set_exclusions.argtypes = [C.c_void_p, C.c_int, ip]
     lib.ppcx_model_set_launch.argtypes = [C.c_void_p, C.c_int, C.c_int]
     lib.ppcx_model_get_launch.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -457,11 +462,18 @@ def shard_genes(G_total, g0, stride):
 class Model:
     """Device-resident model inputs (Stan data block in logical form, include/ppcx.h)."""
 
-    def __init__(self, counts, X, exposure_rate, K, lambda_mu_mu=5.612671, excl=None, device=0, shard=None):
-        """shard = (G_total, K_total, g0, g1): `counts` then holds only genes [g0, g1) of the whole problem and K is
+    def __init__(self, counts, X, exposure_rate, K, lambda_mu_mu=5.612671, excl=None, device=0, shard=None, per_sample="lds"):
+        """per_sample: where the log-likelihood kernel keeps the per-sample constants (include/ppcx.h ppcx_model_create_ex) --
+        "lds" (S * C doubles must fit LDS beside the tables: PpcxError beyond), "stream" (read from global memory), "auto" (LDS
+        where it fits, streamed beyond); Model.per_sample says which of the two the model runs. Gene shards stay on "lds".
+        shard = (G_total, K_total, g0, g1): `counts` then holds only genes [g0, g1) of the whole problem and K is
         ignored (the shard's checked genes are those of the first K_total that fall in its range). shard = (G_total, K_total,
         g0, None, stride): the genes g0, g0 + stride, ... of the whole problem -- rank r of N with (r, None, N) is the
         reference's round-robin deal of genes to shards (R/utilities.R:125-136; shard_genes() picks the rows)."""
+        if per_sample not in PER_SAMPLE:
+            raise ValueError('per_sample must be "lds", "stream" or "auto"')
+        if shard is not None and per_sample != "lds":
+            raise ValueError('a gene shard keeps the per-sample constants in LDS: per_sample must be "lds" with shard=')
         lib = load()
         counts = np.ascontiguousarray(counts, dtype=np.int32)
         if counts.ndim != 2:
@@ -479,7 +491,11 @@ class Model:
         self.counts = counts                     # the observed counts (Fit.loo_predict reports them beside the intervals)
         h = C.c_void_p()
         self.shard = shard
-        if shard is None:
+        if shard is None and per_sample != "lds":
+            _check(lib.ppcx_model_create_ex(int(device), self.G, self.S, self.C, self.K, _p(counts, C.c_int32),
+                                            _p(X, C.c_double), _p(exposure_rate, C.c_double), float(lambda_mu_mu),
+                                            int(excl.size), _p(excl, C.c_int32), PER_SAMPLE[per_sample], C.byref(h)))
+        elif shard is None:
             _check(lib.ppcx_model_create(int(device), self.G, self.S, self.C, self.K, _p(counts, C.c_int32),
                                          _p(X, C.c_double), _p(exposure_rate, C.c_double), float(lambda_mu_mu),
                                          int(excl.size), _p(excl, C.c_int32), C.byref(h)))
@@ -502,6 +518,13 @@ class Model:
                                                    int(excl.size), _p(excl, C.c_int32), C.byref(h)))
         self._h = h
         self.D = int(lib.ppcx_model_dim(h))
+
+    @property
+    def per_sample(self):
+        """"lds" or "stream": where this model's log-likelihood kernel reads the per-sample constants."""
+        v = C.c_int()
+        _check(load().ppcx_model_get_per_sample(self._h, C.byref(v)))
+        return "stream" if v.value else "lds"
 
     def set_exclusions(self, excl):
         excl = np.ascontiguousarray(excl if excl is not None else np.zeros(0), dtype=np.int32)

@@ -45,6 +45,8 @@ extern "C" int ppcx_device_memory(int device, unsigned long long* free_bytes, un
 //   L: minimise passes x pass cost for the full chain count (chosen once per fit: a gene's sums depend on L).
 //   bounds: contiguous ranges of whole passes of (nearly) equal cost -- the boundary of wavefront j is where the running
 //   cost crosses j / (wavefronts per chain) of the total; recomputed when chains finish and the others get their slots.
+// (A streamed model -- ppcx_model::streamed -- is planned by the same costs: nobody has measured what its passes cost relative to
+// one another, and its sums depend on the lanes per gene only, as everyone's.)
 static double pass_cost(const ppcx_model* m, int L, int p, int n) {
   const int S = m->d.S;
   bool slope = false;
@@ -287,11 +289,13 @@ static int upload_counts(ppcx_model* m, int n_excl, const int32_t* excl) {
   return PPCX_OK;
 }
 
-extern "C" int ppcx_model_create(int device, int G, int S, int C, int K, const int32_t* counts, const double* X,
-                                 const double* exposure, double lambda_mu_mu, int n_excl, const int32_t* excl,
-                                 ppcx_model** out) {
+// per_sample: where the log-likelihood kernel keeps the per-sample constants (ppcx.h PPCX_PER_SAMPLE_*)
+static int model_create(int device, int G, int S, int C, int K, const int32_t* counts, const double* X, const double* exposure,
+                        double lambda_mu_mu, int n_excl, const int32_t* excl, int per_sample, ppcx_model** out) {
   if (!out) return fail(PPCX_ERR_ARG, "out is NULL");
   *out = nullptr;
+  if (per_sample != PPCX_PER_SAMPLE_LDS && per_sample != PPCX_PER_SAMPLE_STREAM && per_sample != PPCX_PER_SAMPLE_AUTO)
+    return fail(PPCX_ERR_ARG, "per_sample must be PPCX_PER_SAMPLE_LDS, PPCX_PER_SAMPLE_STREAM or PPCX_PER_SAMPLE_AUTO");
   if (G < 1 || S < 1 || C < 1 || K < 0 || K > G) return fail(PPCX_ERR_ARG, "need G>=1, S>=1, C>=1, 0<=K<=G");
   if (C > kMaxC) return fail(PPCX_ERR_LIMIT, "C exceeds the 16 design columns this build supports");
   if ((long long)G * S > 2000000000LL) return fail(PPCX_ERR_LIMIT, "G*S exceeds int32 cell ids");
@@ -333,20 +337,30 @@ extern "C" int ppcx_model_create(int device, int G, int S, int C, int K, const i
   if (const char* e = getenv("PPCX_PIPELINE")) if (atoi(e) == 0) m->opt_pipelined = 0;
   if (const char* e = getenv("PPCX_STREAM_GROUPS")) { const int v = atoi(e); if (v >= 1) m->opt_stream_groups = v; }
   // the log-likelihood kernel stages its tables (20 KB) and the per-sample constants in LDS: exp(exposure) and the design's slope
-  // columns -- S * C doubles; S * (2 + C) without the column of ones
-  if (loglik_lds_bytes(m->d) > 160u * 1024u)
+  // columns -- S * C doubles; S * (2 + C) without the column of ones. Beyond that a model streams them from global memory if it was
+  // asked to (ppcx_model_create_ex): the same sweep on the model's own arrays, in the three-launch round only -- the merged launch
+  // of a pipelined round has no streamed form, so such a model reports no resident workgroups for it (model_pipelines)
+  const bool fits_lds = loglik_lds_bytes(m->d, false) <= 160u * 1024u;
+  m->streamed = per_sample == PPCX_PER_SAMPLE_STREAM || (per_sample == PPCX_PER_SAMPLE_AUTO && !fits_lds);
+  if (!m->streamed && !fits_lds)
     return fail(PPCX_ERR_LIMIT, "the per-sample constants (S * C doubles; S * (2 + C) for a design without a column of ones) do not fit the 160 KB of LDS of a compute unit beside the 20 KB of tables");
-  m->wgs_per_cu = loglik_resident_workgroups_per_cu(m->CM, m->d);      // of the instantiation this model runs
+  // ... and then the next bound is the dispersion-table kernel's, which keeps a gene's row of S counts in LDS
+  if (m->streamed && disp_build_lds_bytes(S) > 160u * 1024u)
+    return fail(PPCX_ERR_LIMIT, "the dispersion-table kernel (ppcx_disp_build_kernel) keeps a gene's row of S counts in LDS beside 5.5 KB of node values: S may not exceed 39 552");
+  m->wgs_per_cu = loglik_resident_workgroups_per_cu(m->CM, m->d, m->streamed);      // of the instantiation this model runs
   if (m->wgs_per_cu < 1) return fail(PPCX_ERR_LIMIT, "the log-likelihood kernel cannot be resident with S * (2 + C) doubles of per-sample constants in LDS");
-  m->ls_wgs_per_cu = ls_resident_workgroups_per_cu(m->CM, m->d);
+  m->ls_wgs_per_cu = m->streamed ? 0 : ls_resident_workgroups_per_cu(m->CM, m->d);
   std::vector<double> E(S);
   for (int s = 0; s < S; ++s) E[s] = exp(exposure[s]);
   HIPCHK(m->stream.create());
   HIPCHK(m->d_counts.alloc(((size_t)G * S + 512)));   // + 512: the row sweep requests counts up to two trips of 4 x 64 lanes past the end
   HIPCHK(hipMemset(m->d_counts.p, 0, sizeof(int32_t) * ((size_t)G * S + 512)));
-  HIPCHK(m->d_E.alloc(S));
-  HIPCHK(m->d_expo.alloc(S));
-  HIPCHK(m->d_X.alloc((size_t)S * C));
+  // a streamed model's sweep reads exp(exposure) and the last column of X up to kLdsPad entries past their ends (sweep_cells: the
+  // partial last trip, the trip requested ahead), as the LDS route reads its copies: padded with finite values that no cell uses
+  const size_t pad = m->streamed ? (size_t)kLdsPad : 0;
+  HIPCHK(m->d_E.alloc(S + pad));
+  HIPCHK(m->d_expo.alloc(S + pad));
+  HIPCHK(m->d_X.alloc((size_t)S * C + pad));
   HIPCHK(m->d_Sy.alloc(G));
   HIPCHK(m->d_SyE.alloc(G));
   HIPCHK(m->d_SyX.alloc((size_t)C * G));
@@ -366,10 +380,30 @@ extern "C" int ppcx_model_create(int device, int G, int S, int C, int K, const i
   HIPCHK(hipMemcpy(m->d_E.p, E.data(), sizeof(double) * S, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(m->d_expo.p, exposure, sizeof(double) * S, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(m->d_X.p, X, sizeof(double) * (size_t)S * C, hipMemcpyHostToDevice));
+  if (pad) {
+    HIPCHK(hipMemset(m->d_E.p + S, 0, sizeof(double) * pad));
+    HIPCHK(hipMemset(m->d_expo.p + S, 0, sizeof(double) * pad));
+    HIPCHK(hipMemset(m->d_X.p + (size_t)S * C, 0, sizeof(double) * pad));
+  }
   const int rc = upload_counts(m, n_excl, excl);
   if (rc != PPCX_OK) return rc;
   choose_launch(m, 1);
   *out = owner.release();
+  return PPCX_OK;
+}
+extern "C" int ppcx_model_create(int device, int G, int S, int C, int K, const int32_t* counts, const double* X,
+                                 const double* exposure, double lambda_mu_mu, int n_excl, const int32_t* excl,
+                                 ppcx_model** out) {
+  return model_create(device, G, S, C, K, counts, X, exposure, lambda_mu_mu, n_excl, excl, PPCX_PER_SAMPLE_LDS, out);
+}
+extern "C" int ppcx_model_create_ex(int device, int G, int S, int C, int K, const int32_t* counts, const double* X,
+                                    const double* exposure, double lambda_mu_mu, int n_excl, const int32_t* excl,
+                                    int per_sample, ppcx_model** out) {
+  return model_create(device, G, S, C, K, counts, X, exposure, lambda_mu_mu, n_excl, excl, per_sample, out);
+}
+extern "C" int ppcx_model_get_per_sample(const ppcx_model* m, int* streamed) {
+  if (!m || !streamed) return fail(PPCX_ERR_ARG, "bad arguments");
+  *streamed = m->streamed ? 1 : 0;
   return PPCX_OK;
 }
 // ---- gene shards (second mode; the reference's map_rect over gene shards, .stan:226-240) ---------
@@ -419,7 +453,7 @@ extern "C" int ppcx_model_set_rounds(ppcx_model* m, int pipelined, int stream_gr
 }
 bool model_pipelines(const ppcx_model* m) {
   // the pipelined round needs cells that read the anticipated constants only: every design since round 5 (a per-cell linear
-  // predictor reads the coefficients kept among the constants: Dims::raw_consts)
+  // predictor reads the coefficients kept among the constants: Dims::raw_consts); a streamed model has no merged launch
   return m->opt_pipelined != 0 && m->ls_wgs_per_cu >= 1;
 }
 extern "C" int ppcx_model_set_progress(ppcx_model* m, ppcx_progress_fn fn, void* user, double every_seconds) {

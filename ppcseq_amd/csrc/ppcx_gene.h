@@ -134,6 +134,11 @@ PPCX_HD void st32(PPCX_GLOBAL T* base, int i, T x) {
   base[i] = x;
 #endif
 }
+// `bytes` past a uniform global base: the scalar-base form again, for arrays walked alike that share one moving byte offset
+template <class T>
+PPCX_HD const PPCX_GLOBAL T* at32(const PPCX_GLOBAL T* base, unsigned bytes) {
+  return (const PPCX_GLOBAL T*)((const PPCX_GLOBAL char*)base + bytes);
+}
 // (called by the log-likelihood kernel only: its VecRef and its cell data lie in global memory)
 PPCX_HD GenePre gene_pre_load(const Dims& d, const VecRef& v, const CellData& m, int g) {
   GenePre r;
@@ -211,6 +216,10 @@ PPCX_HD void sweep_cells(int S, const int* row, const double* sE, const double* 
     double x0 = 0.0, x1 = 0.0, x2 = 0.0, x3 = 0.0;                                                                           \
     if (MODE != 0) { x0 = qx[(B)]; x1 = qx[(B) + L]; x2 = qx[(B) + 2 * L]; x3 = qx[(B) + 3 * L]; }                           \
     N0 = p[(B) + 4 * L]; N1 = p[(B) + 5 * L]; N2 = p[(B) + 6 * L]; N3 = p[(B) + 7 * L];                                      \
+    PPCX_SWEEP_FOUR(Y0, Y1, Y2, Y3, B)                                                                                       \
+  }
+  // the four cells of a trip: their counts in Y0 .. Y3, their constants in e0 .. e3 and x0 .. x3
+#define PPCX_SWEEP_FOUR(Y0, Y1, Y2, Y3, B)                                                                                   \
     if (MODE == 0 && !MASKED && WIN) {                                                                                       \
       /* the common trip: the four first halves, then the four second halves (cell_front_win / cell_back_win, ppcx_model.h) */ \
       CellMidWin c0, c1, c2, c3;                                                                                             \
@@ -233,8 +242,7 @@ PPCX_HD void sweep_cells(int S, const int* row, const double* sE, const double* 
       PPCX_SWEEP_CELL(Y1, e1, x1, (B) + L, true)                                                                             \
       PPCX_SWEEP_CELL(Y2, e2, x2, (B) + 2 * L, true)                                                                         \
       PPCX_SWEEP_CELL(Y3, e3, x3, (B) + 3 * L, true)                                                                         \
-    }                                                                                                                        \
-  }
+    }
   // Two trips per turn: the counts requested by the first are the second's and the other way round, so no register is copied to
   // carry them over, and the three pointers move once per eight cells. (Two design columns only: the wider accumulators of the
   // other instantiations leave no registers for a second trip's cells in flight -- their loop stays one trip per turn.)
@@ -269,16 +277,101 @@ PPCX_HD void sweep_cells(int S, const int* row, const double* sE, const double* 
     PPCX_SWEEP_CELL(y2, e2, x2, 2 * L, k + 2 < nlane)
     PPCX_SWEEP_CELL(y3, e3, x3, 3 * L, k + 3 < nlane)
   }
+}
+
+// The same sweep with the per-sample constants in GLOBAL memory (the streamed route, ppcx_loglik.h): gE = exp(exposure_s) and gX1 =
+// the first slope column of the model's own arrays, which the host pads to be readable 4 L entries past S like the copies in LDS.
+// Both are walked alike, so they share one moving byte offset on their uniform bases. The cells, the trips and their order are
+// sweep_cells' (its macros); what differs is when a trip's constants are requested: a trip AHEAD, with its counts -- a round
+// trip to L2 at the head of every trip would lie in the open, where the LDS round trip is short. That is eight (MODE 0: four)
+// more doubles in flight. The further columns of MODE 2 / 3, up to fifteen per cell and read by the checked genes only, stay at
+// the point of use: no registers are left to carry them.
+struct SweepVals { double e0, e1, e2, e3, x0, x1, x2, x3; };
+template <int CM, int L, int MODE, bool MASKED, bool WIN>
+PPCX_HD void sweep_cells_stream(int S, const int* row, const double* gE, const double* gX1, int sub, double A, double A1, double one,
+                                const GeneParams<CM>& gp, const double* tab, CellAcc<CM>& acc, const double* ec = nullptr, int C = 2) {
+  const int nmin = S / L;
+  const int nlane = nmin + (sub < S - nmin * L ? 1 : 0);
+  const PPCX_GLOBAL int* p = as_global(row + sub);
+  const PPCX_GLOBAL double* bE = as_global(gE);
+  const PPCX_GLOBAL double* bX = as_global(gX1);
+  unsigned ob = (unsigned)sub * (unsigned)sizeof(double);   // of the lane's next cell in both arrays
+  int y0 = p[0], y1 = p[L], y2 = p[2 * L], y3 = p[3 * L];
+  int k = 0;
+  double L4 = kCellL4;
+  PPCX_OPAQUE(L4);
+#define PPCX_STREAM_VALS(T, B)                                                                                               \
+  {                                                                                                                          \
+    const PPCX_GLOBAL double* q_ = at32(bE, ob);                                                                             \
+    T.e0 = q_[(B)]; T.e1 = q_[(B) + L]; T.e2 = q_[(B) + 2 * L]; T.e3 = q_[(B) + 3 * L];                                       \
+    T.x0 = T.x1 = T.x2 = T.x3 = 0.0;                                                                                         \
+    if (MODE != 0) { const PPCX_GLOBAL double* x_ = at32(bX, ob); T.x0 = x_[(B)]; T.x1 = x_[(B) + L]; T.x2 = x_[(B) + 2 * L]; T.x3 = x_[(B) + 3 * L]; } \
+  }
+  // one trip: its constants arrive in T; the next trip's are requested into TN, its counts into N0 .. N3
+#define PPCX_STREAM_TRIP(Y0, Y1, Y2, Y3, N0, N1, N2, N3, T, TN, B)                                                           \
+  {                                                                                                                          \
+    const PPCX_GLOBAL double* qx = at32(bX, ob); (void)qx;                                                                   \
+    PPCX_STREAM_VALS(TN, (B) + 4 * L)                                                                                        \
+    N0 = p[(B) + 4 * L]; N1 = p[(B) + 5 * L]; N2 = p[(B) + 6 * L]; N3 = p[(B) + 7 * L];                                      \
+    const double e0 = T.e0, e1 = T.e1, e2 = T.e2, e3 = T.e3, x0 = T.x0, x1 = T.x1, x2 = T.x2, x3 = T.x3;                     \
+    PPCX_SWEEP_FOUR(Y0, Y1, Y2, Y3, B)                                                                                       \
+  }
+  SweepVals t0, t1;
+  PPCX_STREAM_VALS(t0, 0)
+  if (CM <= 2) {
+    for (; k + 8 <= nmin; k += 8) {
+      int n0, n1, n2, n3;
+      PPCX_STREAM_TRIP(y0, y1, y2, y3, n0, n1, n2, n3, t0, t1, 0)
+      PPCX_STREAM_TRIP(n0, n1, n2, n3, y0, y1, y2, y3, t1, t0, 4 * L)
+      p += 8 * L; ob += 8 * L * (unsigned)sizeof(double);
+    }
+    if (k + 4 <= nmin) {
+      int n0, n1, n2, n3;
+      PPCX_STREAM_TRIP(y0, y1, y2, y3, n0, n1, n2, n3, t0, t1, 0)
+      p += 4 * L; ob += 4 * L * (unsigned)sizeof(double);
+      y0 = n0; y1 = n1; y2 = n2; y3 = n3; t0 = t1;
+      k += 4;
+    }
+  } else {
+    for (; k + 4 <= nmin; k += 4) {
+      int n0, n1, n2, n3;
+      PPCX_STREAM_TRIP(y0, y1, y2, y3, n0, n1, n2, n3, t0, t1, 0)
+      p += 4 * L; ob += 4 * L * (unsigned)sizeof(double);
+      y0 = n0; y1 = n1; y2 = n2; y3 = n3; t0 = t1;
+    }
+  }
+  if (k < nlane) {                                         // the last, partial trip: its constants are here already
+    const PPCX_GLOBAL double* qx = at32(bX, ob); (void)qx;
+    const double e0 = t0.e0, e1 = t0.e1, e2 = t0.e2, e3 = t0.e3, x0 = t0.x0, x1 = t0.x1, x2 = t0.x2, x3 = t0.x3;
+    PPCX_SWEEP_CELL(y0, e0, x0, 0, true)
+    PPCX_SWEEP_CELL(y1, e1, x1, L, k + 1 < nlane)
+    PPCX_SWEEP_CELL(y2, e2, x2, 2 * L, k + 2 < nlane)
+    PPCX_SWEEP_CELL(y3, e3, x3, 3 * L, k + 3 < nlane)
+  }
+#undef PPCX_STREAM_TRIP
+#undef PPCX_STREAM_VALS
+}
 #undef PPCX_SWEEP_TRIP
+#undef PPCX_SWEEP_FOUR
 #undef PPCX_SWEEP_HALVES
 #undef PPCX_SWEEP_CELL
+// the sweep on the route the kernel runs
+template <int CM, int L, int MODE, bool MASKED, bool WIN, bool STREAM>
+PPCX_HD void sweep_route(int S, const int* row, const double* sE, const double* sX1, int sub, double A, double A1, double one,
+                         const GeneParams<CM>& gp, const double* tab, CellAcc<CM>& acc, const double* ec = nullptr, int C = 2) {
+  if (STREAM) sweep_cells_stream<CM, L, MODE, MASKED, WIN>(S, row, sE, sX1, sub, A, A1, one, gp, tab, acc, ec, C);
+  else sweep_cells<CM, L, MODE, MASKED, WIN>(S, row, sE, sX1, sub, A, A1, one, gp, tab, acc, ec, C);
 }
 
 // a gene whose linear predictor has to be formed per cell: t = exposure_s + X_s . coef + sigma_raw, u = exp(t)
-template <int CM, int L>
+// (STREAM: sExpo / sX are the model's arrays in global memory, read at the point of use)
+template <bool STREAM> struct PerSample { typedef const double* ptr; };
+template <> struct PerSample<true> { typedef const PPCX_GLOBAL double* ptr; };
+template <int CM, int L, bool STREAM = false>
 PPCX_HD void generic_cells(const Dims& d, const Cmd& c, const VecRef& v, int g, bool has_slopes, const int* row,
-                           const double* sExpo, const double* sX, int sub, GeneParams<CM>& gp, const double* tab,
+                           const double* sExpo_, const double* sX_, int sub, GeneParams<CM>& gp, const double* tab,
                            CellAcc<CM>& acc) {
+  const typename PerSample<STREAM>::ptr sExpo = (typename PerSample<STREAM>::ptr)sExpo_, sX = (typename PerSample<STREAM>::ptr)sX_;
   const int S = d.S, C = d.C;
   // the position being evaluated, from the coordinates' constants (coord_consts; gp.sigma_raw is set by the caller from them)
   gp.coef[0] = v.at(V_C2, d.off_intercept + g);
@@ -304,7 +397,8 @@ PPCX_HD void generic_cells(const Dims& d, const Cmd& c, const VecRef& v, int g, 
 // sweep_cells MODE 3), bit 1: a design without the column of ones (generic_cells). 0: a model in which every gene factorises
 // (X[,1] == 1 and slopes only on indicator columns), which leaves the registers to the sweep; the kernels have one instantiation
 // per value (0, 1, 2), the host-side emulation compiles both routes (3)
-template <int CM, int L, int GEN = 3>
+// STREAM: sE / sExpo / sX are the model's arrays in global memory, not a workgroup's copies in LDS (sweep_cells_stream)
+template <int CM, int L, int GEN = 3, bool STREAM = false>
 PPCX_HD void lane_gene_sums(const Dims& d, const Cmd& c, const VecRef& v, const CellData& m, int g, const GenePre& pre, int sub,
                             const double* sE, const double* sExpo, const double* sX, const double* tab, const double* wtab,
                             GeneSumsV<CM>& o
@@ -354,7 +448,7 @@ PPCX_HD void lane_gene_sums(const Dims& d, const Cmd& c, const VecRef& v, const 
   PPCX_GSTAMP(5);
   if (GEN & 2) {
     if (PPCX_WAVE_ANY(generic)) {
-      if (generic) generic_cells<CM, L>(d, c, v, g, has_slopes, row, sExpo, sX, sub, gp, tab, acc);
+      if (generic) generic_cells<CM, L, STREAM>(d, c, v, g, has_slopes, row, sExpo, sX, sub, gp, tab, acc);
     }
   }
   GeneWindow gw; gw.k = 0; gw.ok = false; gw.scale = 1.0;
@@ -367,16 +461,16 @@ PPCX_HD void lane_gene_sums(const Dims& d, const Cmd& c, const VecRef& v, const 
 #define PPCX_SWEEP(MODE, A_LO, A_HI, A_, A1_, X1_, ...)                                                                  \
       gw = gene_window(fma(m.e_min, A_LO, 1.0), fma(m.e_max, A_HI, 1.0));                                                 \
       win = !any_masked && PPCX_WAVE_ALL(gw.ok);                                                                          \
-      if (any_masked) sweep_cells<CM, L, MODE, true, false>(S, row, sE, X1_, sub, A_, A1_, 1.0, gp, tab, acc, ##__VA_ARGS__);   \
-      else if (win) sweep_cells<CM, L, MODE, false, true>(S, row, sE, X1_, sub, (A_) * gw.scale, (A1_) * gw.scale, gw.scale, gp, wtab, acc, ##__VA_ARGS__); \
-      else sweep_cells<CM, L, MODE, false, false>(S, row, sE, X1_, sub, A_, A1_, 1.0, gp, tab, acc, ##__VA_ARGS__);
+      if (any_masked) sweep_route<CM, L, MODE, true, false, STREAM>(S, row, sE, X1_, sub, A_, A1_, 1.0, gp, tab, acc, ##__VA_ARGS__);   \
+      else if (win) sweep_route<CM, L, MODE, false, true, STREAM>(S, row, sE, X1_, sub, (A_) * gw.scale, (A1_) * gw.scale, gw.scale, gp, wtab, acc, ##__VA_ARGS__); \
+      else sweep_route<CM, L, MODE, false, false, STREAM>(S, row, sE, X1_, sub, A_, A1_, 1.0, gp, tab, acc, ##__VA_ARGS__);
       if ((GEN & 1) && PPCX_WAVE_ANY(lin)) {                     // a continuous covariate among the slope columns: exp(X_s . slopes) per
         double be[CM];                                     // cell; a plain gene of the same pass (the host puts genes with slopes
         be[0] = 0.0;                                       // first) runs it with slopes 0
 #pragma unroll
         for (int cc = 1; cc < CM; ++cc) be[cc] = (lin && cc < d.C) ? v.at(V_C2, coef_index(d, cc, g)) : 0.0;
-        if (any_masked) sweep_cells<CM, L, 3, true, false>(S, row, sE, sX + S, sub, A, A, 1.0, gp, tab, acc, be, d.C);
-        else sweep_cells<CM, L, 3, false, false>(S, row, sE, sX + S, sub, A, A, 1.0, gp, tab, acc, be, d.C);
+        if (any_masked) sweep_route<CM, L, 3, true, false, STREAM>(S, row, sE, sX + S, sub, A, A, 1.0, gp, tab, acc, be, d.C);
+        else sweep_route<CM, L, 3, false, false, STREAM>(S, row, sE, sX + S, sub, A, A, 1.0, gp, tab, acc, be, d.C);
       } else if (CM > 2 && d.C > 2 && PPCX_WAVE_ANY(two)) {       // indicator columns, C > 2 (factor designs): e^t = E_s A times the
         double ec[CM];                                     // exp(slope_c) of the sample's columns; a plain gene of the same
         ec[0] = 1.0;                                       // pass (the host puts genes with slopes first) runs it with ec = 1

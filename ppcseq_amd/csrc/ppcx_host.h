@@ -54,6 +54,8 @@ struct ppcx_model {
   int L_override = 0, wgs_override = 0;        // ppcx_model_set_launch
   int n_cu = 256, wgs_per_cu = 4;              // resident workgroups of the log-likelihood kernel = n_cu * wgs_per_cu
   int ls_wgs_per_cu = 0;                       // the same for the merged launch of a pipelined round (0: cannot run)
+  bool streamed = false;                       // the log-likelihood kernel reads the per-sample constants from global memory, not from
+                                               // LDS (ppcx_model_create_ex): d_E, d_expo, d_X carry kLdsPad entries more
   int nblocks_chosen = 0;                      // workgroups of the last planned launch (what ppcx_model_get_launch reports)
   // round structure of a NUTS fit (ppcx_model_set_rounds; initial values from PPCX_PIPELINE / PPCX_STREAM_GROUPS, read
   // once when the model is created): pipelined -1 = where it applies, 0 = never; stream_groups 0 = by the number of chains

@@ -6,7 +6,7 @@
 
 namespace ppcx {
 
-constexpr int kLdsPad = 256;     // entries the sweep may read past the per-sample arrays in LDS (4 x 64 lanes)
+constexpr int kLdsPad = 256;     // entries the sweep may read past the per-sample arrays (4 x 64 lanes), in LDS or in global memory
 struct LoglikArgs {
   Dims d;
   CellData cd;                  // counts, dispersion tables, gene flags (ppcx_gene.h)
@@ -137,9 +137,12 @@ struct PpcArgs {
   int* scratch;                 // null: a cell's draws in LDS (grid = n_cells); else [grid][n_gen] global scratch, cells in turn
 };
 
-hipError_t launch_loglik_kernel(int CM, const LoglikArgs& a, hipStream_t st);
-int loglik_resident_workgroups_per_cu(int CM, const Dims& d);   // 0: the kernel cannot be launched with this much LDS
-size_t loglik_lds_bytes(const Dims& d);
+// streamed: the form of the kernel that reads the per-sample constants from global memory (ppcx_loglik.h; sampleE and X must
+// then be readable kLdsPad entries past their ends) -- a property of the model (ppcx_model::streamed)
+hipError_t launch_loglik_kernel(int CM, const LoglikArgs& a, bool streamed, hipStream_t st);
+int loglik_resident_workgroups_per_cu(int CM, const Dims& d, bool streamed);   // 0: the kernel cannot be launched with this much LDS
+size_t loglik_lds_bytes(const Dims& d, bool streamed);
+size_t disp_build_lds_bytes(int S);            // LDS of a workgroup of the dispersion-table kernel: a row of S counts and the node values
 hipError_t launch_close_kernel(int CM, const CloseArgs& a, int nblocks, int nchains, hipStream_t st);
 // pipelined rounds: the merged launch (the state machines take position 7 of the first n_srun runs of 8 x chains
 // workgroups, log-likelihood range blocks everything else) and the gene kernel

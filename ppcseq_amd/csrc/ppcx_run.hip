@@ -118,7 +118,7 @@ int launch_loglik(ppcx_model* m, Work& w, int nchains) {
   LoglikArgs la;
   int rc = loglik_args(m, w, nchains, 0, &la);
   if (rc != PPCX_OK) return rc;
-  hipError_t e = launch_loglik_kernel(m->CM, la, w.stream);
+  hipError_t e = launch_loglik_kernel(m->CM, la, m->streamed, w.stream);
   if (e != hipSuccess) return fail(PPCX_ERR_HIP, std::string("loglik kernel: ") + hipGetErrorString(e));
   return PPCX_OK;
 }

@@ -86,17 +86,25 @@ def any_rank_failed(err: BaseException | None, device="cpu") -> bool:
     return max_over_ranks(1.0 if err is not None else 0.0, device=device) > 0.0
 
 
+def _refuse_per_sample(per_sample):
+    if per_sample != "lds":
+        raise ValueError('per_sample: passes over several ranks keep the per-sample constants in LDS ("lds")')
+
+
 def do_inference(counts, X, exposure_rate, how_many_to_check, *, device=0, coll_device="cpu", chains=None, cores=None,
                  approximate_posterior_analysis=False, lambda_mu_mu=5.612671, adj_prob_theshold=0.05,
-                 how_many_posterior_draws=1000, to_exclude=None, truncation_compensation=1.0, seed=1, launch=None):
+                 how_many_posterior_draws=1000, to_exclude=None, truncation_compensation=1.0, seed=1, launch=None,
+                 per_sample="lds"):
     """One inference pass of ppcseq (ppcseq_amd.inference.do_inference) with the chains partitioned over the ranks of the
     initialised torch.distributed job, one process per GPU. Every rank holds the inputs, fits its chains with the global
     chain ids (the Philox stream of chain c does not depend on the rank that runs it), the draws of the checked genes are
     all-gathered (a few MB) and rank 0 computes the credible intervals and flags from the POOLED draws; the result is
     broadcast, so every rank returns the same InferenceResult as one fit of all the chains would give.
     `launch` = (lanes_per_gene, workgroups) pins the log-likelihood launch (0 = automatic) (bit-identical results across rank counts need
-    the same geometry: the automatic choice depends on the chains per launch)."""
+    the same geometry: the automatic choice depends on the chains per launch).
+    `per_sample`: "lds" only -- passes over several ranks keep the per-sample constants in LDS (ValueError otherwise)."""
     import math
+    _refuse_per_sample(per_sample)
     from .inference import _to_cell_ids, checked_columns, fit_chain_block, pass_plan, pooled_summary
     dist = _dist()
     rank, world = dist.get_rank(), dist.get_world_size()
@@ -138,7 +146,7 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *, device=0, coll_
 def do_inference_shards(counts, X, exposure_rate, how_many_to_check, *, device=0, coll_device="cpu", chains=None, cores=None,
                         approximate_posterior_analysis=False, lambda_mu_mu=5.612671, adj_prob_theshold=0.05,
                         how_many_posterior_draws=1000, to_exclude=None, truncation_compensation=1.0, seed=1, launch=None,
-                        exchange="direct"):
+                        exchange="direct", per_sample="lds"):
     """One inference pass with the GENES partitioned over the ranks (the reference's map_rect over gene shards,
     inst/stan/negBinomial_MPI.stan:226-240; BASELINE cfg4): every rank holds every world-th gene (the reference's round-robin deal,
     R/utilities.R:125-136: an equal share of the checked genes and of the work on every rank) and runs ALL the chains on them, the six hyper-parameters and the chains' state machines are replicated, and the ranks' partial sums meet every leapfrog
@@ -157,6 +165,7 @@ def do_inference_shards(counts, X, exposure_rate, how_many_to_check, *, device=0
     from .inference import _to_cell_ids, checked_columns, pass_plan, pooled_summary
     if exchange not in ("direct", "rccl"):
         raise ValueError("exchange must be 'direct' or 'rccl'")
+    _refuse_per_sample(per_sample)                  # gene shards stay on LDS (include/ppcx.h ppcx_model_create_ex)
     dist = _dist()
     rank, world = dist.get_rank(), dist.get_world_size()
     counts = np.asarray(counts)

@@ -411,7 +411,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                  loo_moment_match_split=False,
                  exact_loo_moment_match_split=False,
                  loo_moment_match_cov=False,
-                 exact_loo_moment_match_cov=False):
+                 exact_loo_moment_match_cov=False,
+                 per_sample="lds"):
     """One inference pass (discovery or test) of ppcseq on the GPU.
 
     counts            G x S integer matrix, genes ordered with the `how_many_to_check` checked genes first
@@ -500,8 +501,13 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                       `res.exact_loo_intervals` then carries `transform` in place of `scale`, and `cov_iterations`. Free to
                       combine with exact_loo_moment_match_split. devices=[...]: over the pooled chains. Needs
                       exact_loo_moment_match.
+    per_sample        "lds" | "stream" | "auto": where the log-likelihood kernel keeps the per-sample constants, for every model
+                      this pass creates (_lib.Model). "lds" refuses a design whose S * C doubles do not fit LDS beside the
+                      tables (S <= 8 704 at two columns, 1 088 at sixteen); "auto" streams them from global memory there.
     Returns an InferenceResult.
     """
+    if per_sample not in _lib.PER_SAMPLE:
+        raise ValueError('per_sample must be "lds", "stream" or "auto"')
     counts = np.asarray(counts)
     if counts.ndim != 2:
         # R/utilities.R:1360-1361
@@ -522,12 +528,12 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
     if devices is not None and len(devices) > 1 and not approximate_posterior_inference:
         return _do_inference_devices(counts, X, exposure_rate, K, list(devices), chains, n_iter, warmup, excl,
                                      lambda_mu_mu, approximate_posterior_analysis, adj_prob_theshold,
-                                     how_many_posterior_draws, truncation_compensation, seed, launch, checks)
+                                     how_many_posterior_draws, truncation_compensation, seed, launch, checks, per_sample)
     if devices is not None and len(devices) >= 1 and model is None:
         device = devices[0]
     own_model = model is None
     if own_model:
-        model = _lib.Model(counts, X, exposure_rate, K, lambda_mu_mu=lambda_mu_mu, excl=excl, device=device)
+        model = _lib.Model(counts, X, exposure_rate, K, lambda_mu_mu=lambda_mu_mu, excl=excl, device=device, **_route(per_sample))
     else:
         model.set_exclusions(excl)
     if launch is not None:
@@ -619,8 +625,15 @@ def checked_columns(G, C, K):
                            off_sr + np.arange(K), off_sr + G + np.arange(3)]).astype(np.int32)
 
 
+def _route(per_sample):
+    """The keyword of _lib.Model for a pass's per_sample: nothing for the default, so that a default pass creates its models exactly
+    as before the keyword existed"""
+    return {} if per_sample == "lds" else {"per_sample": per_sample}
+
+
 def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, approximate_posterior_analysis,
-                   adj_prob_theshold, how_many_posterior_draws, truncation_compensation, seed, device=0, excl=None, checks=None):
+                   adj_prob_theshold, how_many_posterior_draws, truncation_compensation, seed, device=0, excl=None, checks=None,
+                   per_sample="lds"):
     """Credible intervals, slopes and flags from the pooled draws of all chains (rstan::summary over merged chains,
     R/utilities.R:685-703): `draws_checked` is [chains, n_keep, len(checked_columns)] in global chain order. The
     posterior-predictive kernel runs on a model that holds the K checked genes only -- cell ids g*S+s and draw indices are
@@ -638,7 +651,7 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
     if excl is not None and any(chk.cells for chk in CHECKS if checks.get(chk.keyword)):
         e = np.asarray(excl, dtype=np.int64).ravel()
         small_excl = e[e < K * counts.shape[1]].astype(np.int32)
-    small = _lib.Model(counts[:K], X, exposure_rate, K, lambda_mu_mu=lambda_mu_mu, device=device, excl=small_excl)
+    small = _lib.Model(counts[:K], X, exposure_rate, K, lambda_mu_mu=lambda_mu_mu, device=device, excl=small_excl, **_route(per_sample))
     try:
         fit = small.fit_from_draws(draws_checked)
         try:
@@ -669,11 +682,11 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
 
 
 def fit_chain_block(counts, X, exposure_rate, K, cols, *, device, chains, n_iter, warmup, seed, chain_id_offset, lambda_mu_mu,
-                    excl, launch):
+                    excl, launch, per_sample="lds"):
     """One device's share of a pass whose chains are dealt out (to the devices of this process, or to the ranks of a job): fits
     `chains` chains with the global ids chain_id_offset, ... on `device` and returns their columns `cols`,
     [chains, n_keep, len(cols)]."""
-    m = _lib.Model(counts, X, exposure_rate, K, lambda_mu_mu=lambda_mu_mu, excl=excl, device=device)
+    m = _lib.Model(counts, X, exposure_rate, K, lambda_mu_mu=lambda_mu_mu, excl=excl, device=device, **_route(per_sample))
     try:
         if launch is not None:
             m.set_launch(*launch)
@@ -688,7 +701,7 @@ def fit_chain_block(counts, X, exposure_rate, K, cols, *, device, chains, n_iter
 
 def _do_inference_devices(counts, X, exposure_rate, K, devices, chains, n_iter, warmup, excl, lambda_mu_mu,
                           approximate_posterior_analysis, adj_prob_theshold, how_many_posterior_draws,
-                          truncation_compensation, seed, launch, checks):
+                          truncation_compensation, seed, launch, checks, per_sample="lds"):
     """Chains split over several devices of this process (one host thread per device; the C ABI allows different handles
     on different threads), pooled summary on the first device."""
     import threading
@@ -704,7 +717,7 @@ def _do_inference_devices(counts, X, exposure_rate, K, devices, chains, n_iter, 
         try:
             parts[r] = fit_chain_block(counts, X, exposure_rate, K, cols, device=devices[r], chains=n, n_iter=n_iter,
                                        warmup=warmup, seed=seed, chain_id_offset=r * per, lambda_mu_mu=lambda_mu_mu,
-                                       excl=excl, launch=launch)
+                                       excl=excl, launch=launch, per_sample=per_sample)
         except Exception as e:          # re-raised on the calling thread
             errs[r] = e
 
@@ -720,6 +733,6 @@ def _do_inference_devices(counts, X, exposure_rate, K, devices, chains, n_iter, 
     res = pooled_summary(counts, X, exposure_rate, K, pooled, lambda_mu_mu=lambda_mu_mu,
                          approximate_posterior_analysis=approximate_posterior_analysis, adj_prob_theshold=adj_prob_theshold,
                          how_many_posterior_draws=how_many_posterior_draws, truncation_compensation=truncation_compensation,
-                         seed=seed, device=devices[0], excl=excl, checks=checks)
+                         seed=seed, device=devices[0], excl=excl, checks=checks, per_sample=per_sample)
     res.chains, res.iter = chains, n_iter
     return res

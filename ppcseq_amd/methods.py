@@ -130,7 +130,7 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                       check_approximation_loo=False, check_approximation_loo_intervals=False, exact_intervals=False,
                       exact_loo_intervals=False, exact_approximation_loo_intervals=False, exact_loo_moment_match=False,
                       loo_moment_match_split=False, exact_loo_moment_match_split=False, loo_moment_match_cov=False,
-                      exact_loo_moment_match_cov=False):
+                      exact_loo_moment_match_cov=False, per_sample="lds"):
     """Mirror of ppcseq::identify_outliers (R/methods.R:74-367): same arguments, same defaults.
 
     data is a tidy pandas DataFrame (one row per transcript x sample); column arguments are strings. As in the
@@ -169,8 +169,15 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                                                      the same attrs
     `exact_loo_moment_match_cov` = True           -> exact_loo_moment_match reads Fit.loo_predict_exact_moment_match_cov (the
                                                      covariance step); in the same attrs
+    `per_sample` = "lds" | "stream" | "auto": where the log-likelihood kernel keeps the per-sample constants, for every model of
+    both passes (inference.do_inference; "auto" lifts the bound that LDS puts on the number of samples). Passes over several ranks
+    (ppcseq_amd.distributed) take "lds" only.
     """
     import os
+    if per_sample not in ("lds", "stream", "auto"):
+        raise ValueError('per_sample must be "lds", "stream" or "auto"')
+    if _pass is not None and per_sample != "lds":
+        raise ValueError('per_sample: passes over several ranks keep the per-sample constants in LDS ("lds")')
     import pandas as pd
     if cores is None:
         cores = os.cpu_count() or 1                                        # detect_cores(), R/methods.R:91
@@ -262,10 +269,10 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
         raise ValueError("devices=[...] deals the chains to several devices and pools their draws: not with save_generated_quantities / pass_fit")
     if devices is not None and len(devices) >= 1:
         device = devices[0]
-    model = None if multi else _lib.Model(counts, X, exposure_rate, K, device=device)
+    model = None if multi else _lib.Model(counts, X, exposure_rate, K, device=device, **({} if per_sample == "lds" else {"per_sample": per_sample}))
     where = {} if _pass is not None else (dict(devices=list(devices)) if multi else dict(model=model))
     if _pass is None:
-        where.update(approximate_posterior_inference=approximate_posterior_inference, pass_fit=pass_fit, launch=launch, **checks)
+        where.update(approximate_posterior_inference=approximate_posterior_inference, pass_fit=pass_fit, launch=launch, **({} if per_sample == "lds" else {"per_sample": per_sample}), **checks)
     try:
         # ---- pass 1: discovery (R/methods.R:268-286); always the full posterior analysis
         res1 = run_pass(counts, X, exposure_rate, K,
