@@ -12,12 +12,14 @@ LIB = os.path.join(HERE, "libppcx.so")
 # the testing build (-DPPCX_TESTING: fault injection, forced cell paths, kernel-level timing; csrc/ppcx_testing.h) lives
 # with the tests, not in the package
 TESTING_LIB = os.path.join(os.path.dirname(HERE), "tests", "libppcx_testing.so")
-# ppcx_kernels.hip and ppcx_kernels_stream.hip first: they take minutes, the others seconds, and the compilers start in this order
-SOURCES = ["ppcx_kernels.hip", "ppcx_kernels_stream.hip", "ppcx_summary.hip", "ppcx_psis.hip", "ppcx_loo.hip", "ppcx_loo_predict.hip", "ppcx_reff.hip", "ppcx_ppc_exact.hip", "ppcx_loo_exact.hip", "ppcx_loo_mm.hip", "ppcx_loo_mm_exact.hip", "ppcx_loo_mm_split.hip", "ppcx_loo_mm_cov.hip", "ppcx_loo_mm_cov_exact.hip", "ppcx_ppc.hip",
+# the three translation units of the log-likelihood sweep first (LDS-staged, streamed, merged launch): they take minutes, the
+# others seconds, and the compilers start in this order
+SOURCES = ["ppcx_kernels.hip", "ppcx_kernels_stream.hip", "ppcx_kernels_ls.hip",
+           "ppcx_kernels_close.hip", "ppcx_kernels_model.hip", "ppcx_summary.hip", "ppcx_psis.hip", "ppcx_loo.hip", "ppcx_loo_predict.hip", "ppcx_reff.hip", "ppcx_ppc_exact.hip", "ppcx_loo_exact.hip", "ppcx_loo_mm.hip", "ppcx_loo_mm_exact.hip", "ppcx_loo_mm_split.hip", "ppcx_loo_mm_cov.hip", "ppcx_loo_mm_cov_exact.hip", "ppcx_ppc.hip",
            "ppcx_capi.hip", "ppcx_run.hip", "ppcx_fit_nuts.hip", "ppcx_fit_advi.hip", "ppcx_fit_api.hip"]
 TESTING_SOURCES = ["ppcx_testing_math.hip"]      # the device's building blocks one by one (csrc/ppcx_testing.h): testing build only
-HEADERS = ["ppcx_math.h", "ppcx_disp.h", "ppcx_model.h", "ppcx_nuts.h", "ppcx_gene.h", "ppcx_kernels.h", "ppcx_loglik.h", "ppcx_summary.h", "ppcx_summary_dev.h", "ppcx_psis.h", "ppcx_psis_dev.h", "ppcx_loo.h", "ppcx_loo_ap.h", "ppcx_loo_dev.h", "ppcx_loo_predict.h", "ppcx_reff.h", "ppcx_nbcdf.h", "ppcx_ppc_exact.h", "ppcx_loo_exact.h", "ppcx_loo_mm.h", "ppcx_loo_mm_dev.h", "ppcx_loo_mm_exact.h", "ppcx_loo_mm_split.h", "ppcx_loo_mm_cov.h", "ppcx_loo_mm_cov_exact.h", "ppcx_ppc.h", "ppcx_table.h", "ppcx_block.h", "ppcx_columns.h", "ppcx_host.h", "ppcx_testing.h",
-           os.path.join("..", "..", "include", "ppcx.h")]
+# every header present, so that a new one cannot be forgotten (a stale library that looks fresh)
+HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "ppcx.h")]
 
 
 # hipcc (ROCm 7.2) miscompiles the scalar state machine of ppcx_step_kernel when the SLP vectoriser has made <2 x i32> phis of
@@ -85,7 +87,7 @@ def build_testing(force: bool = False, verbose: bool = False) -> str:
 
 
 def build_all(force: bool = False, verbose: bool = False):
-    """The product and the testing build side by side (the kernels' translation unit takes minutes)."""
+    """The product and the testing build side by side (the sweep's translation units take minutes)."""
     jobs = []
     if force or _stale(LIB):
         jobs.append((LIB, []))

@@ -199,7 +199,7 @@ static int fit_nuts_impl(ppcx_model* m, const ppcx_nuts_config* cfg, ppcx_xchg* 
   const int nch = cfg->chains, D = m->d.D;
   choose_launch(m, (xg && xg->nranks > 1) ? nch : fit_launch_chains(m, nch));   // (between ranks: one group, below)
   // Round structure. Pipelined (default where it applies): two launches per leapfrog, the state machine beside the
-  // log-likelihood workgroups (ppcx_kernels.hip, "Pipelined rounds"). It needs a model whose cells read the anticipated
+  // log-likelihood workgroups (ppcx_kernels_ls.hip, "Pipelined rounds"). It needs a model whose cells read the anticipated
   // constants only (no per-cell linear predictor). The choice must not depend on the number of chains: the two round
   // structures sum the kinetic energy of fresh momenta in different orders, and a chain's draws may not depend on its
   // company. (With more chains than the chip holds workgroups the state machines simply run ahead of the log-likelihood

@@ -4,7 +4,7 @@
 //                           coord_top_dots); the gene kernel of a pipelined round closes a leaf by the same two
 //   update kernel         : coord_update (per coordinate: the command's coordinate work + coord_consts)
 //   step kernel           : chain_step (scalar state machine)
-// Shared by the gfx950 kernel (ppcx_kernels.hip) and the CPU emulation harness in tests/emul.
+// Shared by the gfx950 kernels (the ppcx_kernels*.hip translation units; index: ppcx_kernels.h) and the CPU emulation harness in tests/emul.
 #pragma once
 #include "ppcx_nuts.h"
 
@@ -101,7 +101,7 @@ struct CellData {                // the chain-independent inputs of the log-like
 };
 
 // What a pass needs of a gene before its sweep, all of it addressed by the gene alone: the log-likelihood kernel requests it a
-// whole pass ahead (ppcx_kernels.hip loglik_passes), so that a pass starts with its constants in registers. (Every wavefront of
+// whole pass ahead (ppcx_loglik.h loglik_passes), so that a pass starts with its constants in registers. (Every wavefront of
 // the launch starts and ends its passes at the same time -- equal costs since round 5 -- so a round trip at the start of a pass is
 // hidden by nobody; with the 17-instruction cell the sweep of 25 cells no longer dwarfs it.)
 struct GenePre { double phi, sigma, a0, Sy, n; int flags; };
@@ -110,7 +110,7 @@ struct GenePre { double phi, sigma, a0, Sy, n; int flags; };
 // scalar-base form of the global memory instructions: arrays indexed alike share one offset register, where base[i] costs
 // every array a sign extension, a shift and a 64-bit addition per lane. The address space is part of the parameter's type: a
 // caller says as_global(p) where it knows that p is global -- the log-likelihood kernel's arguments and what is derived from them
-// (ppcx_kernels.hip loglik_role: vecs, sums, order, the cell data); a VecRef in LDS (the state machine's hyper vectors) is not.
+// (ppcx_loglik.h loglik_role: vecs, sums, order, the cell data); a VecRef in LDS (the state machine's hyper vectors) is not.
 #if defined(__HIP_DEVICE_COMPILE__)
 #define PPCX_GLOBAL __attribute__((address_space(1)))
 #else

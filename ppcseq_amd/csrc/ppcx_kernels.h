@@ -1,10 +1,52 @@
-// ppcx_kernels.h -- argument blocks, launchers and drivers of the gfx950 kernels (ppcx_kernels.hip and the translation units of
-// the predictive kernels and the fit diagnostics).
+// ppcx_kernels.h -- argument blocks, launchers and drivers of the gfx950 kernels (the ppcx_kernels*.hip translation units of the
+// NB hierarchical NUTS / ADVI engine, one per kernel family, and the translation units of the predictive kernels and the fit
+// diagnostics).
+//
+// The engine's kernels and the translation unit that holds each, with its launch helpers:
+//   ppcx_loglik_kernel<CM,GEN>  ppcx_kernels.hip        streams the int32 count matrix once per gradient evaluation and reduces it
+//                           to a handful of sums per gene. Replaces lp_reduce + map_rect + X*alpha of
+//                           inst/stan/negBinomial_MPI.stan:58-120,:205,:226-240. CM = design columns (2, 4, 8, 16), GEN = the
+//                           route with an exp per cell that is compiled in (0 none, 1 continuous covariate, 2 no column of ones).
+//   ppcx_loglik_stream_kernel<CM,GEN>  ppcx_kernels_stream.hip   the same workgroup with the per-sample constants read from global memory.
+//   ppcx_ls_kernel<CM,GEN>  ppcx_kernels_ls.hip     the merged launch of a pipelined round: those workgroups beside the chains' state machines.
+//   ppcx_gene_kernel<CM>    ppcx_kernels_close.hip  the other launch of a pipelined round: everything per gene (command, close, anticipated constants).
+//   ppcx_close_kernel<CM>   ppcx_kernels_close.hip  per gene: priors (.stan:219-223), gradient, second half kick of the leapfrog, NUTS tree
+//                           bookkeeping of the gene's coordinates, block partial sums.
+//   ppcx_step_kernel        ppcx_kernels_ls.hip     reduction of the close kernel's block partials, hyper-parameters, NUTS / adaptation state
+//                           machine (ppcx_nuts.h) and, in the same launch, the per-coordinate work of the next command.
+//   ppcx_update_kernel      ppcx_kernels_ls.hip     that per-coordinate work as a launch of its own (initialisation, ADVI).
+//   ppcx_sum_shards_kernel  ppcx_kernels_ls.hip     in-process gene shards: the sum of the shards' sums.
+//   ppcx_xchg_abort_kernel  ppcx_kernels_ls.hip     a rank that leaves a gene-sharded fit says so to its peers.
+//   ppcx_advi_kernel        ppcx_kernels_ls.hip     the per-coordinate work of ADVI (draws, steps); ppcx_advi_elbo_kernel its ELBO.
+//   ppcx_disp_build_kernel  ppcx_kernels_model.hip  the genes' dispersion tables (ppcx_disp.h), once per model and per change of the exclusions.
+//   ppcx_gather_kernel      ppcx_kernels_model.hip  column gather of the retained draws.
+//   ppcx_fill_kernel        ppcx_kernels_model.hip  a constant into an array.
+// The log-likelihood workgroup itself is ppcx_loglik.h, the chain's state machine ppcx_step.h (device headers). The kernels of
+// ppcx_kernels_ls.hip stay together because their code depends on it (its header says how).
+//
+// Work decomposition of the log-likelihood kernel: a gene is owned by L lanes of one wavefront
+// (L in {1,2,4,...,64}); a wavefront walks a range of the host's gene order, 64 / L genes per pass; lanes stride over the
+// gene's samples four cells per trip, read the per-sample constants from LDS, and combine with an L-lane butterfly.
+// Per-block partial sums of the close kernel go to a slab that the step kernel reduces in a fixed order, so results are
+// bitwise reproducible for a fixed number of lanes per gene.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ppcx_gene.h"
 
 namespace ppcx {
+
+// ChainState / Cmd travel between global memory, registers and LDS word by word (one 4-byte word per thread). The word type
+// may alias any object: reading a struct with double members through a plain `int` lvalue is undefined under the strict
+// aliasing rule that -O3 applies, whatever the copy looks like in practice.
+typedef int __attribute__((may_alias)) word_t;
+// v of lane i moved by a DPP control word (data-parallel primitives: a VALU move, no LDS round trip); lanes the
+// control leaves without a source, or outside row_mask, receive 0
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ double dpp_take(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, true);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, true);
+  return __hiloint2double(hi, lo);
+}
 
 constexpr int kLdsPad = 256;     // entries the sweep may read past the per-sample arrays (4 x 64 lanes), in LDS or in global memory
 struct LoglikArgs {
@@ -142,6 +184,11 @@ struct PpcArgs {
 hipError_t launch_loglik_kernel(int CM, const LoglikArgs& a, bool streamed, hipStream_t st);
 int loglik_resident_workgroups_per_cu(int CM, const Dims& d, bool streamed);   // 0: the kernel cannot be launched with this much LDS
 size_t loglik_lds_bytes(const Dims& d, bool streamed);
+// defined in ppcx_kernels.hip, used by the merged launch's helpers (ppcx_kernels_ls.hip) as well: the route with an exp per cell
+// that the model's genes can need (GEN), and the workgroups of 256 threads of kernel f that a CU holds with lds_bytes of dynamic
+// LDS each (0: the query failed)
+int loglik_generic_possible(const Dims& d);
+int resident_workgroups_per_cu(const void* f, size_t lds_bytes);
 size_t disp_build_lds_bytes(int S);            // LDS of a workgroup of the dispersion-table kernel: a row of S counts and the node values
 hipError_t launch_close_kernel(int CM, const CloseArgs& a, int nblocks, int nchains, hipStream_t st);
 // pipelined rounds: the merged launch (the state machines take position 7 of the first n_srun runs of 8 x chains

@@ -1,7 +1,8 @@
 // ppcx_loglik.h -- the log-likelihood workgroup (device): the L-lane reduction, a wavefront's passes over its range of genes, the
 // workgroup's body, and the kernel in its two forms -- the per-sample constants staged in LDS (ppcx_kernels.hip) or read from
 // global memory (STREAM; ppcx_kernels_stream.hip, a translation unit of its own so that the two sets of instantiations compile
-// side by side).
+// side by side). ppcx_ls_kernel (ppcx_kernels_ls.hip) runs the same workgroup beside the chains' state machines (ppcx_step.h).
+// word_t and dpp_take, which the state machine and the close kernels use as well: ppcx_kernels.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ppcx_gene.h"
@@ -9,10 +10,6 @@
 
 namespace ppcx {
 
-// ChainState / Cmd travel between global memory, registers and LDS word by word (one 4-byte word per thread). The word type
-// may alias any object: reading a struct with double members through a plain `int` lvalue is undefined under the strict
-// aliasing rule that -O3 applies, whatever the copy looks like in practice.
-typedef int __attribute__((may_alias)) word_t;
 // 16-byte requests of arrays of doubles (LDS fills)
 typedef double2 __attribute__((may_alias)) dpair_t;
 
@@ -32,14 +29,6 @@ __device__ __forceinline__ double wave_xor_add_rt(double v, int lane_xor_mask) {
   const int lo = __builtin_amdgcn_ds_bpermute(src, __double2loint(v));
   const int hi = __builtin_amdgcn_ds_bpermute(src, __double2hiint(v));
   return v + __hiloint2double(hi, lo);
-}
-// v of lane i moved by a DPP control word (data-parallel primitives: a VALU move, no LDS round trip); lanes the
-// control leaves without a source, or outside row_mask, receive 0
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ double dpp_take(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, ROW_MASK, 0xf, true);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROW_MASK, 0xf, true);
-  return __hiloint2double(hi, lo);
 }
 // sum over the L lanes that share a gene, every lane ending with the total: inside a row of 16 lanes by DPP moves (neighbours,
 // pairs, the other quad by row_half_mirror, the other half-row by row_mirror -- vector-unit moves, no LDS round trips: nine

@@ -1,7 +1,7 @@
 // ppcx_math.h -- scalar building blocks of the MI355X NB hierarchical engine.
 //
 // Everything here is `__host__ __device__` so the *same* arithmetic is compiled into the gfx950
-// kernels (ppcx_kernels.hip) and into the CPU emulation harness that tests/ uses to check the host
+// kernels (ppcx_kernels*.hip) and into the CPU emulation harness that tests/ uses to check the host
 // logic without a GPU (tests/emul). Nothing here comes from the reference: Stan Math (third party,
 // not vendored) is where the reference's arithmetic lives; the formulas below are written from the
 // published definitions cited at each function.

@@ -296,7 +296,7 @@ struct ChainScalars {
   double lp_eval;                // CMD_EVAL result
   long long total_leapfrogs;
 };
-// gene shards with the direct exchange (ppcx_kernels.hip xchg_sums): exchanges this chain has taken part in -- the sequence
+// gene shards with the direct exchange (ppcx_step.h xchg_sums): exchanges this chain has taken part in -- the sequence
 // number its ranks stamp their contributions with -- and the wall-clock ticks (100 MHz) its state machine has waited for peers.
 // Kept apart from ChainScalars: those live in registers while a state machine runs, and ppcx_step_kernel has none to spare.
 struct XchgCount { unsigned count; unsigned pad_; long long ticks; };

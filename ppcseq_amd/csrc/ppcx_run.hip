@@ -60,7 +60,7 @@ int work_alloc(Work& w, ppcx_model* m, int nchains) {
 // The kinetic energy of freshly drawn momenta travels from the update of one round to the step of the next through the
 // T0 slab, double-buffered like the states: a step launched at generation g (= w.launches) reads buffer g & 1, the
 // update that belongs to the command it decides writes buffer (g + 1) & 1.
-// with_update: the per-coordinate work of the new command in the same launch (ppcx_kernels.hip, ppcx_step_kernel).
+// with_update: the per-coordinate work of the new command in the same launch (ppcx_kernels_ls.hip, ppcx_step_kernel).
 static void step_args(ppcx_model* m, Work& w, const RunIO& io, int phases, bool with_update, StepArgs* o) {
   const int in = (int)(w.launches & 1), out = in ^ 1;
   StepArgs& sa = *o;

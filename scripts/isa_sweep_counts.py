@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
-"""Count the vector instructions of the log-likelihood sweep in the gfx950 ISA of ppcx_kernels.hip (no GPU needed).
+"""Count the vector instructions of the log-likelihood sweep in the gfx950 ISA of its translation units (no GPU needed).
 
-    python scripts/isa_sweep_counts.py [--asm FILE] [--keep FILE] [--kernel NAME ...] [--label TEXT]
+    python scripts/isa_sweep_counts.py [--asm FILE ...] [--tu NAME ...] [--keep DIR] [--kernel NAME ...] [--label TEXT]
 
-Compiles ppcseq_amd/csrc/ppcx_kernels.hip to assembly with the flags of ppcseq_amd/build.py (--cuda-device-only -S; about four
-minutes) -- or reads an assembly file made that way (--asm) -- and prints one JSON object: for each requested kernel
+Compiles translation units of ppcseq_amd/csrc (--tu; by default ppcx_kernels_ls.hip and ppcx_kernels.hip, which hold the default
+kernels) to assembly with the flags of ppcseq_amd/build.py (--cuda-device-only -S; minutes each) -- or reads assembly files made
+that way (--asm) -- and prints one JSON object: for each requested kernel
 
   trips     every loop block (a basic block that branches back to its own label) holding a multiple of four v_rcp_f64: its label,
             its vector instructions, how many four-cell trips it holds (v_rcp_f64 / 4) and the vector instructions per trip;
@@ -25,6 +26,7 @@ from __future__ import annotations
 
 import argparse
 import collections
+import importlib.util
 import json
 import os
 import re
@@ -33,8 +35,8 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
 DEFAULT_KERNELS = ["ppcx_ls_kernelILi2ELi0EE", "ppcx_loglik_kernelILi2ELi0EE"]
+DEFAULT_TUS = ["ppcx_kernels_ls.hip", "ppcx_kernels.hip"]      # the translation units that hold them
 
 _LABEL = re.compile(r"^(\.LBB\d+_\d+):")
 _INSN = re.compile(r"^\s+([a-z][a-z0-9_]+)\b(.*)$")
@@ -42,11 +44,24 @@ _BRANCH = re.compile(r"^\s+s_c?branch\w*\s+(\.LBB\d+_\d+)")
 _COUNT_LOAD = re.compile(r"^\s+global_load_dword\s+v\d+, v\[\d+:\d+\], off(?: offset:(-?\d+))?\s*$")
 
 
-def compile_asm(out: str) -> None:
-    from ppcseq_amd import build as b                      # the library's own flags (nothing is built by importing it)
+def build_module(root: str = ROOT):
+    """ppcseq_amd/build.py of the source tree `root`, loaded by path (nothing is built, the package is not imported)"""
+    spec = importlib.util.spec_from_file_location("_ppcx_build_" + str(abs(hash(root))), os.path.join(root, "ppcseq_amd", "build.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def asm_command(out: str, tu: str, root: str = ROOT, extra=()):
+    """the compiler line that turns translation unit `tu` of the tree `root` into device assembly, with that tree's own flags"""
+    b = build_module(root)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    cmd = [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden", "-Wno-unused-result"] + b.CODEGEN_FLAGS + \
-          ["--cuda-device-only", "-S", "-o", out, os.path.join(b.CSRC, "ppcx_kernels.hip")]
+    return [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-fvisibility=hidden", "-Wno-unused-result"] + b.CODEGEN_FLAGS + \
+           list(extra) + ["--cuda-device-only", "-S", "-o", out, os.path.join(b.CSRC, tu)]
+
+
+def compile_asm(out: str, tu: str) -> None:
+    cmd = asm_command(out, tu)
     print(" ".join(cmd), file=sys.stderr)
     subprocess.check_call(cmd)
 
@@ -124,11 +139,12 @@ def metadata_of(lines, name):
     return out
 
 
-def count_kernel(lines, bodies, pattern):
-    names = [n for n in bodies if pattern in n]
-    if len(names) != 1:
-        raise SystemExit("kernel pattern %r matches %d functions: %s" % (pattern, len(names), names))
-    name = names[0]
+def count_kernel(files, pattern):
+    """files: [(lines, kernel_bodies(lines))], one entry per assembly file; the kernel is looked for in all of them"""
+    found = [(lines, bodies, n) for lines, bodies in files for n in bodies if pattern in n]
+    if len(found) != 1:
+        raise SystemExit("kernel pattern %r matches %d functions: %s" % (pattern, len(found), [n for _, _, n in found]))
+    lines, bodies, name = found[0]
     blocks = blocks_of(bodies[name])
     trips, idx = [], []
     for i, (label, ops, targets, offs) in enumerate(blocks):
@@ -179,28 +195,28 @@ def count_kernel(lines, bodies, pattern):
 
 def main() -> None:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("--asm", help="an assembly file of ppcx_kernels.hip made with the library's flags (default: compile it)")
-    ap.add_argument("--keep", help="where to leave the compiled assembly (default: a temporary file, removed)")
+    ap.add_argument("--asm", action="append", help="an assembly file of a translation unit made with the library's flags; may be "
+                    "repeated, the kernels are looked for in all of them (default: compile --tu)")
+    ap.add_argument("--tu", action="append", help="a translation unit of ppcseq_amd/csrc to compile; may be repeated (default: %s)" % ", ".join(DEFAULT_TUS))
+    ap.add_argument("--keep", help="a directory in which to leave the compiled assembly, <translation unit>.s (default: temporary files, removed)")
     ap.add_argument("--kernel", action="append", help="part of a kernel's mangled name; may be repeated (default: %s)" % ", ".join(DEFAULT_KERNELS))
     ap.add_argument("--label", default="", help="a note that travels with the output (the commit counted, for instance)")
     a = ap.parse_args()
-    tmp = None
-    path = a.asm
-    if path is None:
-        path = a.keep
-        if path is None:
-            fd, tmp = tempfile.mkstemp(suffix=".s")
-            os.close(fd)
-            path = tmp
-        compile_asm(path)
-    try:
-        with open(path) as f:
-            lines = f.read().splitlines()
-    finally:
-        if tmp:
-            os.remove(tmp)
-    bodies = kernel_bodies(lines)
-    out = {"label": a.label, "kernels": [count_kernel(lines, bodies, k) for k in (a.kernel or DEFAULT_KERNELS)]}
+    paths = a.asm
+    with tempfile.TemporaryDirectory() as tmp:
+        if paths is None:
+            where = a.keep or tmp
+            os.makedirs(where, exist_ok=True)
+            paths = []
+            for tu in a.tu or DEFAULT_TUS:          # one after the other: each takes minutes and a core
+                paths.append(os.path.join(where, os.path.splitext(tu)[0] + ".s"))
+                compile_asm(paths[-1], tu)
+        files = []
+        for path in paths:
+            with open(path) as f:
+                lines = f.read().splitlines()
+            files.append((lines, kernel_bodies(lines)))
+    out = {"label": a.label, "kernels": [count_kernel(files, k) for k in (a.kernel or DEFAULT_KERNELS)]}
     print(json.dumps(out, indent=1))
 
 

@@ -1,6 +1,6 @@
 """The log-likelihood sweep keeps its bits: lp and the whole gradient of Model.log_prob_grad at pinned lanes per gene, and a short
 two-chain NUTS fit, equal bit for bit to what the commit before the sweep's glue was trimmed (operand addressing, trip unrolling,
-uniform bases: ppcx_gene.h sweep_cells, ppcx_kernels.hip loglik_passes) returned on an MI355X. The recording is
+uniform bases: ppcx_gene.h sweep_cells, ppcx_loglik.h loglik_passes) returned on an MI355X. The recording is
 tests/golden/sweep_bits_parent.npz, written by scripts/gpu_record_sweep_bits.py from the cases below.
 
 Cases (the smallest shapes at which that code can go wrong): G = 70 genes, K = 3 of them with a slope, so that no pass is full and
