@@ -203,7 +203,7 @@ PPCX_API int ppcx_fit_loo_mcse(ppcx_fit* f, int n_genes, const int32_t* genes, c
  * third candidate), no split transformation: a matched khat is necessary, not sufficient (ppcx_fit_loo_moment_match_split below
  * adds the split transformation), and no mcse / n_eff is given for a matched cell.
  * Fits, genes, r_eff, limits and refusals as ppcx_fit_loo (an ADVI fit: PPCX_ERR_ARG, moment matching under the weights of
- * loo_approximate_posterior is not available); also PPCX_ERR_ARG for a k_threshold that is not finite or max_iters < 0.
+ * loo_approximate_posterior is ppcx_fit_loo_moment_match_approx); also PPCX_ERR_ARG for a k_threshold that is not finite or max_iters < 0.
  * out [n_genes][S][PPCX_LOO_MM_FIELDS(C)]: elpd_loo, p_loo (lpd of the original draws - elpd_loo), looic, khat (the final one),
  * khat_before (plain PSIS's), iterations (accepted steps), then scale[C + 1] and shift[C + 1] of the gene's coordinates in the
  * order intercept, slopes, sigma_raw: the matched draws are scale * draw + shift (a row the gene does not have: 1 and 0). A cell
@@ -251,7 +251,7 @@ PPCX_API int ppcx_fit_loo_moment_match_split(ppcx_fit* f, int n_genes, const int
  * order intercept, slopes, sigma_raw: the matched draws are transform * draw + shift (a row or column the gene does not have
  * is the identity's, its shift 0). A cell with iterations = 0 holds ppcx_fit_loo's four fields bit for bit, the identity and
  * zeros. The exact predictive under these weights is ppcx_fit_loo_predict_exact_moment_match_cov. Still left out: mcse / n_eff
- * of a matched cell, ADVI fits. The same bits on every call, for any gene subset.                                              */
+ * of a matched cell, the covariance step for ADVI fits. The same bits on every call, for any gene subset.                                              */
 #define PPCX_LOO_MM_COV_FIELDS(C) (9 + ((C) + 1) * ((C) + 1) + ((C) + 1))
 PPCX_API int ppcx_fit_loo_moment_match_cov(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff, double k_threshold,
                                            int max_iters, int split, double* out);
@@ -367,7 +367,7 @@ PPCX_API int ppcx_fit_loo_predict_exact_approx(ppcx_fit* f, int n_genes, const i
  * density; the constant Jacobian cancels), and eta_i, phi_i of the negative binomials are evaluated at t_i. Nothing is sampled.
  * Genes (checked ones), r_eff, probabilities, truncation compensation, limits and refusals as ppcx_fit_loo_predict_exact;
  * k_threshold and max_iters as ppcx_fit_loo_moment_match (PPCX_ERR_ARG for a k_threshold that is not finite or max_iters < 0).
- * An ADVI fit: PPCX_ERR_ARG; a ppcx_fit_from_draws fit is served. No covariance step, no split transformation: a matched khat
+ * An ADVI fit: PPCX_ERR_ARG (theirs is ppcx_fit_loo_predict_exact_moment_match_approx); a ppcx_fit_from_draws fit is served. No covariance step, no split transformation: a matched khat
  * is necessary, not sufficient (ppcx_fit_loo_predict_exact_moment_match_split below adds the split,
  * ppcx_fit_loo_predict_exact_moment_match_cov the covariance step). Synchronous on the model's stream; the same bits on every call, for any gene subset.
  *   out [n_genes][S][PPCX_LOO_MM_EXACT_FIELDS(C)]: the ten fields of ppcx_fit_loo_predict_exact with khat the final one, then
@@ -404,11 +404,43 @@ PPCX_API int ppcx_fit_loo_predict_exact_moment_match_split(ppcx_fit* f, int n_ge
  *   one, then khat_before, iterations, cov_iterations, khat_split (NaN without split or with iterations = 0), transform
  *   [C + 1][C + 1] row-major and shift [C + 1]. A cell with iterations = 0 holds ppcx_fit_loo_predict_exact's ten fields bit for
  *   bit. A proposal point with invalid parameters, or no finite ratio: every statistic of the cell is NaN, khat and khat_split
- *   included. Left out: mcse / n_eff of a matched cell, ADVI fits. The same bits on every call, for any gene subset.          */
+ *   included. Left out: mcse / n_eff of a matched cell, the covariance step for ADVI fits. The same bits on every call, for any gene subset.          */
 #define PPCX_LOO_MM_COV_EXACT_FIELDS(C) (14 + ((C) + 1) * ((C) + 1) + ((C) + 1))
 PPCX_API int ppcx_fit_loo_predict_exact_moment_match_cov(ppcx_fit* f, int n_genes, const int32_t* genes, const double* r_eff,
                                                          double k_threshold, int max_iters, int split,
                                                          double truncation_compensation, double p_lo, double p_hi, double* out);
+/* ppcx_fit_loo_approx with a second attempt at the cells whose khat exceeds k_threshold: the gene-local moment matching of
+ * ppcx_fit_loo_moment_match for draws that come from the approximation g of an ADVI fit (ppcx_loo_mm_ap.h). An affine map of the
+ * gene's own coordinates is an implicit change of proposal with a constant Jacobian, and given the hyper-parameters the posterior
+ * factorises over the genes, so the log ratio of a candidate state is (log_p_i - log_g_i) + q(t_i) - q(draw_i) - log_lik(t_i), q
+ * the gene's local log density: ppcx_fit_loo_moment_match's ratio plus the cached array of ppcx_fit_psis. Neither log_g at a new
+ * point nor the approximation's (mu, omega) is needed. loo::loo_moment_match has no approximate-posterior form: a deliberate
+ * deviation from loo, restated from Paananen et al. (2021) and Magnusson et al. (2019), not run against R. Candidates (shift;
+ * shift and scale), gate (a strictly lower khat), tail and tie rule as ppcx_fit_loo_moment_match; r_eff = 1.
+ * Fits, genes, limits and refusals as ppcx_fit_loo_approx (a NUTS fit, or one made by ppcx_fit_from_draws: PPCX_ERR_ARG); also
+ * PPCX_ERR_ARG for a k_threshold that is not finite or max_iters < 0.
+ * out [n_genes][S][PPCX_LOO_MM_FIELDS(C)], the layout of ppcx_fit_loo_moment_match. A cell that is excluded (its khat is the
+ * overall k-hat), NaN, at or below the threshold, run with max_iters = 0, or on which no step was accepted holds
+ * ppcx_fit_loo_approx's four fields bit for bit, khat_before = khat, iterations 0, scale 1, shift 0.
+ * Left out: the split transformation (for a proposal g it needs log_g at inverse-mapped points), the covariance step, mcse /
+ * n_eff, passes over several ranks. A matched khat below the threshold is therefore necessary, not sufficient; and the matching
+ * moves one gene's coordinates only -- where the overall k-hat of log_p - log_g is itself above the threshold the mismatch sits in
+ * the hyper-parameters as well, which no map of a gene's coordinates repairs: a cell's khat below the threshold does not speak
+ * for that part (it is an estimate of the cell's own ratios and can lie below the overall one). The same bits on every call, for
+ * any gene subset.                                                                                                              */
+PPCX_API int ppcx_fit_loo_moment_match_approx(ppcx_fit* f, int n_genes, const int32_t* genes, double k_threshold, int max_iters,
+                                              double* out);
+/* ppcx_fit_loo_predict_exact_approx with the cells above k_threshold matched first as ppcx_fit_loo_moment_match_approx matches them
+ * (the same kernels, so khat, khat_before, iterations, scale and shift are that entry's bits), then the predictive under those
+ * weights with eta_i, phi_i of the negative binomials evaluated at the matched draws, as ppcx_fit_loo_predict_exact_moment_match
+ * does for a NUTS fit. Genes (checked ones), probabilities and truncation compensation as ppcx_fit_loo_predict_exact_approx;
+ * k_threshold, max_iters, refusals and what is left out as ppcx_fit_loo_moment_match_approx.
+ *   out [n_genes][S][PPCX_LOO_MM_EXACT_FIELDS(C)], the layout of ppcx_fit_loo_predict_exact_moment_match. A cell with
+ *   iterations = 0 holds ppcx_fit_loo_predict_exact_approx's ten fields bit for bit. The same bits on every call, for any gene
+ *   subset.                                                                                                                    */
+PPCX_API int ppcx_fit_loo_predict_exact_moment_match_approx(ppcx_fit* f, int n_genes, const int32_t* genes, double k_threshold,
+                                                            int max_iters, double truncation_compensation, double p_lo, double p_hi,
+                                                            double* out);
 /* lp: [chains][n_keep]; the rest [chains][iter] (warmup included); any pointer may be NULL */
 PPCX_API int ppcx_fit_get_diagnostics(ppcx_fit* f, double* lp, double* stepsize, int32_t* treedepth,
                              int32_t* n_leapfrog, int32_t* divergent, double* accept);

@@ -30,6 +30,7 @@ EXPORTS = [
     "ppcx_fit_loo_predict_exact_moment_match", "ppcx_fit_loo_moment_match_split", "ppcx_fit_loo_predict_exact_moment_match_split",
     "ppcx_fit_loo_moment_match_cov", "ppcx_fit_loo_predict_exact_moment_match_cov",
     "ppcx_model_create_ex", "ppcx_model_get_per_sample",
+    "ppcx_fit_loo_moment_match_approx", "ppcx_fit_loo_predict_exact_moment_match_approx",
 ]
 PER_SAMPLE = {"lds": 0, "stream": 1, "auto": 2}     # PPCX_PER_SAMPLE_*
 ABI_VERSION = 400           # include/ppcx.h PPCX_VERSION this binding was written for
@@ -142,6 +143,10 @@ def load() -> C.CDLL:
     if "ppcx_fit_loo_predict_exact_moment_match_cov" not in _LACKING:
         lib.ppcx_fit_loo_predict_exact_moment_match_cov.argtypes = [C.c_void_p, C.c_int, ip, dp, C.c_double, C.c_int, C.c_int, C.c_double,
                                                                     C.c_double, C.c_double, dp]
+    if "ppcx_fit_loo_moment_match_approx" not in _LACKING:
+        lib.ppcx_fit_loo_moment_match_approx.argtypes = [C.c_void_p, C.c_int, ip, C.c_double, C.c_int, dp]
+        lib.ppcx_fit_loo_predict_exact_moment_match_approx.argtypes = [C.c_void_p, C.c_int, ip, C.c_double, C.c_int, C.c_double,
+                                                                       C.c_double, C.c_double, dp]
     lib.ppcx_fit_get_diagnostics.argtypes = [C.c_void_p, dp, dp, ip, ip, ip, dp]
     lib.ppcx_fit_get_timing.argtypes = [C.c_void_p, dp, C.POINTER(C.c_longlong), dp, C.POINTER(C.c_longlong), dp]
     lib.ppcx_fit_get_kernel_times.argtypes = [C.c_void_p, dp, dp, dp, C.POINTER(C.c_longlong)]
@@ -187,6 +192,8 @@ def load() -> C.CDLL:
         lib.ppcx_testing_ppc_exact.argtypes = [C.c_int, C.c_int, dp, dp, ip, ip, C.c_double, C.c_double, C.c_double, dp]
     if hasattr(lib, "ppcx_testing_loo_exact"):
         lib.ppcx_testing_loo_exact.argtypes = [C.c_int, C.c_int, dp, dp, dp, ip, ip, dp, dp, C.c_double, C.c_double, C.c_double, dp]
+    if hasattr(lib, "ppcx_testing_fit_from_draws_approx"):
+        lib.ppcx_testing_fit_from_draws_approx.argtypes = [C.c_void_p, C.c_int, dp, dp, C.POINTER(C.c_void_p)]
     lib.ppcx_fit_free.restype = None
     lib.ppcx_advi_config_default.argtypes = [C.POINTER(AdviConfig)]
     lib.ppcx_advi_config_default.restype = None
@@ -596,6 +603,18 @@ class Model:
         _check(load().ppcx_fit_from_draws(self._h, draws.shape[0], draws.shape[1], _p(draws, C.c_double), C.byref(h)))
         return Fit(self, h)
 
+    def testing_fit_from_draws_approx(self, draws, log_ratio) -> "Fit":
+        """Testing build only (csrc/ppcx_testing.h ppcx_testing_fit_from_draws_approx): a Fit over host-given draws [n_keep, D] and
+        host-given log ratios log_p - log_g [n_keep] that the approximate-posterior methods accept."""
+        draws = np.ascontiguousarray(draws, dtype=np.float64)
+        log_ratio = np.ascontiguousarray(log_ratio, dtype=np.float64)
+        if draws.ndim != 2 or draws.shape[1] != self.D or log_ratio.shape != (draws.shape[0],):
+            raise ValueError("draws must be [n_keep, D] and log_ratio [n_keep]")
+        h = C.c_void_p()
+        _check(_testing_entry("ppcx_testing_fit_from_draws_approx")(self._h, draws.shape[0], _p(draws, C.c_double),
+                                                                     _p(log_ratio, C.c_double), C.byref(h)))
+        return Fit(self, h)
+
     def fit_nuts_comm(self, comm: "Comm", **kw) -> "Fit":
         """This process's gene shard of a multi-GPU fit; partial sums all-reduced over RCCL every leapfrog."""
         cfg = _make_cfg(**kw)
@@ -867,7 +886,8 @@ class Fit:
         and `shift` [n_genes, S, C + 1] (the matched draws of the gene are scale * draw + shift, rows intercept, slopes,
         sigma_raw; 1 and 0 for a row the gene does not have) and `k_threshold`. A cell with iterations == 0 holds Fit.loo's
         bits. k_threshold=None: inference.loo_threshold(n_draws). Without the keywords below there is no covariance step and no
-        split transformation: a matched khat is necessary, not sufficient; no mcse / n_eff. Not for an ADVI fit. r_eff as Fit.loo.
+        split transformation: a matched khat is necessary, not sufficient; no mcse / n_eff. Not for an ADVI fit
+        (Fit.loo_moment_match_approximate_posterior). r_eff as Fit.loo.
         split=True (ppcx_fit_loo_moment_match_split): the split transformation of loo::loo_moment_match on the matched cells --
         the first n_draws // 2 draws in the fit's order (whole leading chains) are transformed, the others kept, and all are
         weighted against the mixture they come from, so elpd_loo, p_loo, looic and `estimates` no longer rest on the matched
@@ -880,7 +900,8 @@ class Fit:
         affine map: in place of `scale` the dict has `transform` [n_genes, S, C + 1, C + 1] (the matched draws are
         transform @ draw + shift; a row or column the gene does not have is the identity's) and `cov_iterations` (the accepted
         steps of that kind, int64); with split=True also `elpd_loo_matched` and `khat_split` as above. The predictive under these
-        weights is Fit.loo_predict_exact_moment_match_cov. Still left out: mcse / n_eff of a matched cell, ADVI fits."""
+        weights is Fit.loo_predict_exact_moment_match_cov. Still left out: mcse / n_eff of a matched cell, the covariance
+        step for ADVI fits."""
         if k_threshold is None:
             from .inference import loo_threshold
             k_threshold = loo_threshold(self.chains * self.n_keep)
@@ -938,6 +959,34 @@ class Fit:
         still needs the correction for g: elpd_loo under the weights of log_p - log_g, p_loo 0, khat = khat_approximation.
         genes=None: all G genes. Not for a NUTS fit (Fit.loo); no mcse / n_eff."""
         _, res, last = self._loo_cells(genes, None, LOO_FIELDS, lambda n, g, re, out: load().ppcx_fit_loo_approx(self._h, n, g, out))
+        res.update(last)
+        res["estimates"] = loo_estimates(res, res["excluded"])
+        res["khat_approximation"] = float(self.psis(cols=[], overall=True)["khat"][-1])
+        return res
+
+    def loo_moment_match_approximate_posterior(self, genes=None, k_threshold=None, max_iters=30):
+        """Fit.loo_approximate_posterior with gene-local moment matching of the cells whose khat exceeds k_threshold
+        (ppcx_fit_loo_moment_match_approx): Fit.loo_moment_match's construction for draws that come from the approximation of an
+        ADVI fit -- a candidate's log ratios are (log_p - log_g) plus those of Fit.loo_moment_match, on the cached array of Fit.psis
+        (loo::loo_moment_match has no approximate-posterior form: a deliberate deviation, restated from Paananen et al. 2021 and
+        Magnusson et al. 2019, not run against R). Fit.loo_moment_match's dict -- `estimates` over the new values, `khat_before`,
+        `iterations` (int64), `scale` and `shift` [n_genes, S, C + 1], `k_threshold` -- plus `khat_approximation`. A cell with
+        iterations == 0 holds Fit.loo_approximate_posterior's bits. k_threshold=None: inference.loo_threshold(n_draws). Left out:
+        the split transformation, the covariance step, mcse / n_eff. A matched khat below the threshold is necessary, not
+        sufficient; and where `khat_approximation` is itself above the threshold the mismatch sits in the hyper-parameters as
+        well, which a gene's own coordinates cannot repair. Not for a NUTS fit (Fit.loo_moment_match)."""
+        if k_threshold is None:
+            from .inference import loo_threshold
+            k_threshold = loo_threshold(self.chains * self.n_keep)
+        k_threshold, max_iters = float(k_threshold), int(max_iters)
+        nc = self.model.C + 1
+        fields = LOO_MM_HEAD + tuple(f"scale{c}" for c in range(nc)) + tuple(f"shift{c}" for c in range(nc))
+        _, res, last = self._loo_cells(genes, None, fields, lambda n, g, re, out: load().ppcx_fit_loo_moment_match_approx(
+            self._h, n, g, k_threshold, max_iters, out))
+        res["scale"] = np.stack([res.pop(f"scale{c}") for c in range(nc)], axis=-1)
+        res["shift"] = np.stack([res.pop(f"shift{c}") for c in range(nc)], axis=-1)
+        res["iterations"] = res["iterations"].astype(np.int64)
+        res["k_threshold"] = k_threshold
         res.update(last)
         res["estimates"] = loo_estimates(res, res["excluded"])
         res["khat_approximation"] = float(self.psis(cols=[], overall=True)["khat"][-1])
@@ -1009,7 +1058,7 @@ class Fit:
         `iterations` (int64), `scale` and `shift` [n_genes, S, C + 1] (the same bits as that method's) and `k_threshold`. A cell
         with iterations == 0 holds Fit.loo_predict_exact's bits. k_threshold=None: inference.loo_threshold(n_draws). No covariance
         step (Fit.loo_predict_exact_moment_match_cov has it) and no split transformation: a matched khat is necessary, not
-        sufficient. Not for an ADVI fit.
+        sufficient. Not for an ADVI fit (Fit.loo_predict_exact_moment_match_approximate_posterior).
         split=True (ppcx_fit_loo_predict_exact_moment_match_split): the split transformation as in Fit.loo_moment_match -- the
         negative binomials are evaluated at the matched draws for the first n_draws // 2 draws in the fit's order and at the
         original draws for the others, under the PSIS weights of the split ratios. `khat` and the matching's record stay its
@@ -1072,6 +1121,33 @@ class Fit:
         is weighted too (by log_p - log_g); its khat is the overall k-hat."""
         res = self._loo_exact(genes, None, lambda n, g, re, out: load().ppcx_fit_loo_predict_exact_approx(
             self._h, n, g, float(truncation_compensation), float(p_lo), float(p_hi), out))
+        res["khat_approximation"] = float(self.psis(cols=[], overall=True)["khat"][-1])
+        return res
+
+    def loo_predict_exact_moment_match_approximate_posterior(self, genes=None, k_threshold=None, max_iters=30, p_lo=0.025, p_hi=0.975,
+                                                             truncation_compensation=1.0):
+        """Fit.loo_predict_exact_approximate_posterior with the cells whose khat exceeds k_threshold matched first as
+        Fit.loo_moment_match_approximate_posterior matches them (ppcx_fit_loo_predict_exact_moment_match_approx): their predictive
+        is taken under the matched weights with the negative binomials evaluated at the matched draws; nothing is sampled.
+        Fit.loo_predict_exact_approximate_posterior's dict (`khat` is the final one; `khat_approximation`), plus `khat_before`,
+        `iterations` (int64), `scale` and `shift` [n_genes, S, C + 1] (the same bits as that method's) and `k_threshold`. A cell
+        with iterations == 0 holds Fit.loo_predict_exact_approximate_posterior's bits. What is left out, and what a matched khat
+        does not say, as Fit.loo_moment_match_approximate_posterior. Not for a NUTS fit (Fit.loo_predict_exact_moment_match)."""
+        if k_threshold is None:
+            from .inference import loo_threshold
+            k_threshold = loo_threshold(self.chains * self.n_keep)
+        k_threshold, max_iters = float(k_threshold), int(max_iters)
+        nc = self.model.C + 1
+
+        def tail(res, more):
+            res["khat_before"] = more[..., 0].copy()
+            res["iterations"] = more[..., 1].astype(np.int64)
+            res["scale"] = more[..., 2:2 + nc].copy()
+            res["shift"] = more[..., 2 + nc:2 + 2 * nc].copy()
+            res["k_threshold"] = k_threshold
+        res = self._loo_exact(genes, None, lambda n, g, re, out: load().ppcx_fit_loo_predict_exact_moment_match_approx(
+            self._h, n, g, k_threshold, max_iters, float(truncation_compensation), float(p_lo), float(p_hi), out),
+            more=2 + 2 * nc, tail=tail)
         res["khat_approximation"] = float(self.psis(cols=[], overall=True)["khat"][-1])
         return res
 

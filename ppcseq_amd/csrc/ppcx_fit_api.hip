@@ -163,7 +163,9 @@ static int loo_mm_prepare(const char* who, ppcx_fit* f, int n_genes, const int32
   if (probs && !f) return fail(PPCX_ERR_ARG, "fit is NULL");
   if (f && f->advi)
     return fail(PPCX_ERR_ARG, std::string(who) + " needs the draws of a NUTS fit: moment matching under the weights of an ADVI fit "
-                                                 "(loo_approximate_posterior) is not available");
+                                                 "(loo_approximate_posterior) is ppcx_fit_loo_moment_match_approx and "
+                                                 "ppcx_fit_loo_predict_exact_moment_match_approx, without the split transformation "
+                                                 "and the covariance step");
   if (!isfinite(k_threshold)) return fail(PPCX_ERR_ARG, std::string(who) + ": k_threshold must be finite");
   if (max_iters < 0) return fail(PPCX_ERR_ARG, std::string(who) + ": max_iters must be >= 0");
   int rc = probs ? loo_exact_check(f, n_genes, genes, probs[0], probs[1], probs[2]) : PPCX_OK;
@@ -416,8 +418,58 @@ extern "C" int ppcx_fit_loo_predict_exact_moment_match_cov(ppcx_fit* f, int n_ge
   return hip_done(who, loo_mm_cov_exact_fit_cells(fc, k_threshold, max_iters, split != 0, truncation_compensation, p_lo, p_hi, out,
                                                   loo_scratch_bytes(), f->m->stream.s));
 }
+// ---- gene-local moment matching of the cells of an ADVI fit with a high k-hat (ppcx_loo_mm_ap.h): the matching's kernels in
+// their approximate-posterior instantiation, the ratios carrying log_p - log_g (psis_ratios), r_eff = 1
+static int loo_mm_approx_prepare(const char* who, ppcx_fit* f, int n_genes, const int32_t* genes, double k_threshold, int max_iters,
+                                 const double* probs, const void* out, std::vector<int>& yenc, FitCells& fc) {
+  if (!f) return fail(PPCX_ERR_ARG, "fit is NULL");
+  int rc = loo_approx_prepare(who, f, n_genes, genes, out, yenc, fc);
+  if (rc != PPCX_OK) return rc;
+  if (!isfinite(k_threshold)) return fail(PPCX_ERR_ARG, std::string(who) + ": k_threshold must be finite");
+  if (max_iters < 0) return fail(PPCX_ERR_ARG, std::string(who) + ": max_iters must be >= 0");
+  if (probs && (rc = loo_exact_check(f, n_genes, genes, probs[0], probs[1], probs[2])) != PPCX_OK) return rc;
+  return loo_approx_ratios(f, fc);
+}
+extern "C" int ppcx_fit_loo_moment_match_approx(ppcx_fit* f, int n_genes, const int32_t* genes, double k_threshold, int max_iters,
+                                                double* out) {
+  const char* who = "ppcx_fit_loo_moment_match_approx";
+  std::vector<int> yenc; FitCells fc;
+  const int rc = loo_mm_approx_prepare(who, f, n_genes, genes, k_threshold, max_iters, nullptr, out, yenc, fc);
+  if (rc != PPCX_OK) return rc;
+  return hip_done(who, loo_mm_fit_cells(fc, k_threshold, max_iters, out, loo_scratch_bytes(), f->m->stream.s));
+}
+extern "C" int ppcx_fit_loo_predict_exact_moment_match_approx(ppcx_fit* f, int n_genes, const int32_t* genes, double k_threshold,
+                                                              int max_iters, double truncation_compensation, double p_lo, double p_hi,
+                                                              double* out) {
+  const char* who = "ppcx_fit_loo_predict_exact_moment_match_approx";
+  const double probs[3] = {truncation_compensation, p_lo, p_hi};
+  std::vector<int> yenc; FitCells fc;
+  const int rc = loo_mm_approx_prepare(who, f, n_genes, genes, k_threshold, max_iters, probs, out, yenc, fc);
+  if (rc != PPCX_OK) return rc;
+  return hip_done(who, loo_mm_exact_fit_cells(fc, k_threshold, max_iters, truncation_compensation, p_lo, p_hi, out, loo_scratch_bytes(),
+                                              f->m->stream.s));
+}
 #ifdef PPCX_TESTING
-// testing build only (ppcx_testing.h): the kernel of the two above on host-given columns, on the current device
+// testing build only (ppcx_testing.h): a fit over host-given draws and host-given log ratios that the _approx entries accept -- it
+// holds zeros in the approximation's place and the log ratios as psis_ratios would have cached them
+extern "C" int ppcx_testing_fit_from_draws_approx(ppcx_model* m, int n_keep, const double* draws, const double* log_ratio, ppcx_fit** out) {
+  if (!log_ratio) return fail(PPCX_ERR_ARG, "bad arguments");
+  const int rc = ppcx_fit_from_draws(m, 1, n_keep, draws, out);
+  if (rc != PPCX_OK) return rc;
+  ppcx_fit* f = *out;
+  f->advi = true;
+  const size_t D = (size_t)m->d.D;
+  hipError_t e = f->d_mu.alloc(D);
+  if (e == hipSuccess) e = f->d_omega.alloc(D);
+  if (e == hipSuccess) e = hipMemset(f->d_mu.p, 0, sizeof(double) * D);
+  if (e == hipSuccess) e = hipMemset(f->d_omega.p, 0, sizeof(double) * D);
+  if (e == hipSuccess) e = f->d_r.alloc((size_t)n_keep);
+  if (e == hipSuccess) e = hipMemcpy(f->d_r.p, log_ratio, sizeof(double) * (size_t)n_keep, hipMemcpyHostToDevice);
+  if (e != hipSuccess) { ppcx_fit_free(f); *out = nullptr; return fail(PPCX_ERR_HIP, hipGetErrorString(e)); }
+  return PPCX_OK;
+}
+// testing build only (ppcx_testing.h): the kernel of ppcx_fit_loo_predict_exact and ppcx_fit_loo_predict_exact_approx on host-given
+// columns, on the current device
 extern "C" int ppcx_testing_loo_exact(int n, int n_cols, const double* ll, const double* eta, const double* sigma_raw, const int32_t* y,
                                       const int32_t* excluded, const double* r_eff, const double* log_ratio,
                                       double truncation_compensation, double p_lo, double p_hi, double* out) {

@@ -25,6 +25,7 @@
 // requested and however the work is batched.
 #include <hip/hip_runtime.h>
 #include "ppcx_loo_mm_dev.h"
+#include "ppcx_loo_mm_ap.h"
 
 namespace ppcx {
 
@@ -35,7 +36,8 @@ __global__ __launch_bounds__(256) void ppcx_loo_mm_hyper_kernel(const double* dr
   U[(long)k * n_draws + j] = draws[j * (long)d.D + hyper_index(d, k)];
 }
 
-template <bool LDS>
+// AP: the cells of an ADVI fit (ppcx_loo_mm_ap.h): ppcx_loo_ap_kernel has run before it, the ratios carry a.lr, r_eff is 1
+template <bool LDS, bool AP>
 __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_kernel(LooMmArgs p) {
 #pragma clang fp contract(off)
   extern __shared__ uint64_t lds_u[];
@@ -49,12 +51,12 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_kernel(LooMmArgs p)
   uint64_t* K = m.K; double* X = m.X;
   double* V = m.V;                                       // [n] the ratios (of the last candidate)
   double* W = V + n;                                     // [n] the current log weights
-  double* Q0 = W + n;                                    // [n] the local density at the original draws
+  double* Q0 = W + n;                                    // [n] the local density at the original draws (AP: minus a.lr)
   const LooCell c = loo_cell<false>(a);
   const int cell = c.cell, gi = c.gi, s = c.s;
   double* o = p.out + (long)cell * loo_mm_fields(C);
   const double* lo = p.loo + (long)cell * kLooFields;
-  // ---- step 0: ppcx_loo_kernel's fields; a finished cell leaves
+  // ---- step 0: ppcx_loo_kernel's fields (AP: ppcx_loo_ap_kernel's); a finished cell leaves
   const double khat0 = lo[3];
   if (tid == 0) {
     o[0] = lo[0]; o[1] = lo[1]; o[2] = lo[2]; o[3] = khat0;
@@ -62,11 +64,18 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_kernel(LooMmArgs p)
   }
   if (loo_mm_finished(c.excluded, khat0, p.k_threshold, p.max_iters)) return;
   CellRatios cr;
-  if (loo_cell_ratios<false, false>(a, c, false, V, nullptr, sh, &cr)) return;
+  if (loo_cell_ratios<false, AP>(a, c, false, V, AP ? Q0 : nullptr, sh, &cr)) return;   // (AP: ll into Q0's place until lpd is formed)
   const long N = cr.N;
   if (N == 0) return;
-  const double lpd = loo_mm_lpd(V, n, cr, sh);
-  const double re = a.r_eff ? a.r_eff[cell] : 1.0;
+  double lpd, re;
+  if constexpr (AP) {                                    // ppcx_loo_ap.h step 4, as ppcx_loo_ap_kernel forms it; a thread reads its own ll
+    const double sl = draws_sum(n, sh.red, [&](long i) { return V[i] != -INFINITY ? exp(Q0[i] - cr.lmax) : 0.0; });
+    lpd = loo_ap_lse(cr.lmax, sl) - log((double)N);
+    re = 1.0;
+  } else {
+    lpd = loo_mm_lpd(V, n, cr, sh);
+    re = a.r_eff ? a.r_eff[cell] : 1.0;
+  }
   double k;
   {
     const int M = psis_tail_len(N, re);
@@ -78,7 +87,12 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_kernel(LooMmArgs p)
   const LooMmGene g = loo_mm_gene(p, gi);
   if (tid < nc) { ms.A[tid] = 1.0; ms.B[tid] = 0.0; }
   __syncthreads();
-  for (long i = tid; i < n; i += kBlockThreads) { double l; Q0[i] = loo_mm_density(g, i, ms.A, ms.B, s, &l); }
+  for (long i = tid; i < n; i += kBlockThreads) {
+    double l;
+    const double q0 = loo_mm_density(g, i, ms.A, ms.B, s, &l);
+    if constexpr (AP) Q0[i] = loo_mm_ap_qa(q0, a.lr[i]);
+    else Q0[i] = q0;
+  }
   // ---- step 3
   int iters = 0;
   while (k > p.k_threshold && iters < p.max_iters) {
@@ -167,7 +181,9 @@ LooMmArgs LooMmWalk::args(const FitCells& fc, const LooArgs& a, const int* genes
 }
 hipError_t launch_loo_mm_kernels(const LooMmArgs& q, const CellLaunch& c, hipStream_t st) {
   const hipError_t e1 = launch_loo_kernel(q.l, kLooFields, c.n_blocks, st);
-  return e1 == hipSuccess ? launch_cell_kernel(pick_kernel<ppcx_loo_mm_kernel_of>(c.lds), q, c, q.l.sel_pad, loo_slice3(q.l.n), st) : e1;
+  return e1 == hipSuccess ? launch_cell_kernel(pick_kernel<ppcx_loo_mm_kernel_of>(c.lds, q.l.lr != nullptr), q, c, q.l.sel_pad,
+                                               loo_slice3(q.l.n), st)
+                          : e1;
 }
 
 hipError_t loo_mm_fit_cells(const FitCells& fc, double k_threshold, int max_iters, double* out, size_t scratch_bytes, hipStream_t st) {

@@ -24,12 +24,15 @@
 #include <hip/hip_runtime.h>
 #include "ppcx_loo_mm_dev.h"
 #include "ppcx_loo_mm_exact.h"
+#include "ppcx_loo_mm_ap.h"
 
 namespace ppcx {
 
 struct LooMmExactShared { double A[kMaxC + 1], B[kMaxC + 1], one[kMaxC + 1], zero[kMaxC + 1]; };
 
-template <bool LDS>
+// AP: the cells of an ADVI fit (ppcx_loo_mm_ap.h step 5): the matching's approximate-posterior instantiation has run before it,
+// an unmatched cell is ppcx_loo_exact_kernel's approximate-posterior cell, a matched cell's ratios carry a.lr, r_eff is 1
+template <bool LDS, bool AP>
 __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_exact_kernel(LooMmThenArgs p) {
 #pragma clang fp contract(off)
   extern __shared__ uint64_t lds_u[];
@@ -51,15 +54,18 @@ __global__ __launch_bounds__(kBlockThreads) void ppcx_loo_mm_exact_kernel(LooMmT
   const bool matched = rec[5] > 0.0;                     // uniform: every thread reads the same word
   if (tid == 0) loo_mm_exact_store_state(o, C, rec);
   // ---- a cell that was not matched: ppcx_loo_exact_kernel's cell
-  if (!matched) { loo_exact_cell<false, false>(a, c, m, nullptr, nullptr, p.log_tc, p.p_lo, p.p_hi, o, sh); return; }
+  if (!matched) { loo_exact_cell<false, AP>(a, c, m, nullptr, nullptr, p.log_tc, p.p_lo, p.p_hi, o, sh); return; }
   auto all_nan = [&]() { if (tid == 0) loo_exact_store_nan(o, y, excluded); };
   // ---- the state, the ratios under it, their tail and the normalised weights; (eta, ln phi) at the transformed draws
   if (tid < nc) { ms.A[tid] = rec[kLooMmHead + tid]; ms.B[tid] = rec[kLooMmHead + nc + tid]; ms.one[tid] = 1.0; ms.zero[tid] = 0.0; }
   __syncthreads();
   const LooMmGene g = loo_mm_gene(p.m, gi);
-  const CountedRatios cr = loo_mm_count_ratios(n, m.V, sh, [&](long i) { return loo_mm_exact_ratio(g, i, ms.A, ms.B, ms.one, ms.zero, s); });
+  const CountedRatios cr = loo_mm_count_ratios(n, m.V, sh, [&](long i) {
+    if constexpr (AP) return loo_mm_ap_exact_ratio(g, a.lr[i], i, ms.A, ms.B, ms.one, ms.zero, s);
+    else return loo_mm_exact_ratio(g, i, ms.A, ms.B, ms.one, ms.zero, s);
+  });
   if (cr.N == 0) { all_nan(); return; }
-  const int M = psis_tail_len(cr.N, a.r_eff ? a.r_eff[cell] : 1.0);
+  const int M = psis_tail_len(cr.N, !AP && a.r_eff ? a.r_eff[cell] : 1.0);
   const LooTail lt = loo_cell_tail(m.V, n, cr.N, M, m.K, m.X, a.sel_pad, sh);
   loo_cell_lw<true>(m.V, W, n, cr.rmax, lt, M, m.K, sh);
   __syncthreads();                                       // no thread reads a ratio any more: V becomes E
@@ -75,7 +81,8 @@ PPCX_KERNEL_OF(ppcx_loo_mm_exact_kernel);
 hipError_t loo_mm_exact_fit_cells(const FitCells& fc, double k_threshold, int max_iters, double tc, double p_lo, double p_hi, double* out,
                                   size_t scratch_bytes, hipStream_t st) {
   return loo_mm_then_fit_cells(fc, LooMmDiagMatching{}, k_threshold, max_iters, tc, p_lo, p_hi, loo_mm_exact_fields(fc.d.C), out,
-                               scratch_bytes, st, [](bool lds) { return pick_kernel<ppcx_loo_mm_exact_kernel_of>(lds); });
+                               scratch_bytes, st,
+                               [ap = fc.log_ratio != nullptr](bool lds) { return pick_kernel<ppcx_loo_mm_exact_kernel_of>(lds, ap); });
 }
 
 }  // namespace ppcx

@@ -86,6 +86,10 @@ PPCX_API int ppcx_testing_ppc_exact(int n, int n_cols, const double* eta, const 
 PPCX_API int ppcx_testing_loo_exact(int n, int n_cols, const double* ll, const double* eta, const double* sigma_raw, const int32_t* y,
                                     const int32_t* excluded, const double* r_eff, const double* log_ratio,
                                     double truncation_compensation, double p_lo, double p_hi, double* out);
+/* A fit over host-given draws [n_keep][D] and host-given log ratios log_ratio [n_keep] (log_p - log_g, -Inf allowed) that the
+ * _approx entries accept (ppcx_fit_loo_approx, ppcx_fit_loo_moment_match_approx, ...): designed draw sets reach their kernels this
+ * way. The fit counts as an ADVI fit of one chain; its approximation (ppcx_fit_get_approximation) is zeros and means nothing. */
+PPCX_API int ppcx_testing_fit_from_draws_approx(ppcx_model* m, int n_keep, const double* draws, const double* log_ratio, ppcx_fit** out);
 #ifdef __cplusplus
 }
 #endif

@@ -232,6 +232,9 @@ class CheckContext:
     exact_loo_moment_match_split: bool = False   # Fit.loo_predict_exact_moment_match is read with split=True
     loo_moment_match_cov: bool = False           # Fit.loo_moment_match is read with cov=True
     exact_loo_moment_match_cov: bool = False     # exact_loo_moment_match reads Fit.loo_predict_exact_moment_match_cov
+    approximation_loo_moment_match: bool = False         # check_approximation_loo reads Fit.loo_moment_match_approximate_posterior
+    exact_approximation_loo_moment_match: bool = False   # exact_approximation_loo_intervals reads
+                                                         # Fit.loo_predict_exact_moment_match_approximate_posterior
 
 
 @dataclass(frozen=True)
@@ -282,6 +285,21 @@ def _read_exact_loo(fit, ctx):
     return read(np.arange(ctx.K), r_eff=ctx.loo_r_eff, **_interval(ctx), **split)
 
 
+def _read_approximation_loo(fit, ctx):
+    """check_approximation_loo's read: Fit.loo_approximate_posterior, or with approximation_loo_moment_match
+    Fit.loo_moment_match_approximate_posterior (its khat is the final one)"""
+    read = fit.loo_moment_match_approximate_posterior if ctx.approximation_loo_moment_match else fit.loo_approximate_posterior
+    return read(np.arange(ctx.K))
+
+
+def _read_exact_approximation_loo(fit, ctx):
+    """exact_approximation_loo_intervals' read: Fit.loo_predict_exact_approximate_posterior at the pass's interval, or with
+    exact_approximation_loo_moment_match Fit.loo_predict_exact_moment_match_approximate_posterior with the same keywords"""
+    read = (fit.loo_predict_exact_moment_match_approximate_posterior if ctx.exact_approximation_loo_moment_match
+            else fit.loo_predict_exact_approximate_posterior)
+    return read(np.arange(ctx.K), **_interval(ctx))
+
+
 CHECKS = (          # in the order of the reads
     Check("check_approximation", "approximation", 2, "advi", False, False,
           "check_approximation needs an ADVI pass (approximate_posterior_inference = True): the Pareto k diagnostic judges the "
@@ -291,7 +309,7 @@ CHECKS = (          # in the order of the reads
     Check("check_approximation_loo", "approximation_loo", 5, "advi", False, False,
           "check_approximation_loo needs an ADVI pass (approximate_posterior_inference = True): it corrects PSIS-LOO for the "
           "variational approximation; PSIS-LOO of a NUTS pass is check_loo",
-          lambda fit, ctx: fit.loo_approximate_posterior(np.arange(ctx.K)), _loo_warnings),
+          _read_approximation_loo, _loo_warnings),
     Check("check_approximation_loo_intervals", "approximation_loo_intervals", 6, "advi", False, False,
           "check_approximation_loo_intervals needs an ADVI pass (approximate_posterior_inference = True): the leave-one-out "
           "intervals of a NUTS pass are check_loo_intervals",
@@ -299,7 +317,7 @@ CHECKS = (          # in the order of the reads
     Check("exact_approximation_loo_intervals", "exact_approximation_loo_intervals", 9, "advi", False, False,
           "exact_approximation_loo_intervals needs an ADVI pass (approximate_posterior_inference = True): the exact leave-one-out "
           "intervals of a NUTS pass are exact_loo_intervals",
-          lambda fit, ctx: fit.loo_predict_exact_approximate_posterior(np.arange(ctx.K), **_interval(ctx))),
+          _read_exact_approximation_loo),
     Check("check_convergence", "convergence", 1, "nuts", True, False,
           "check_convergence needs a NUTS pass: the draws of an ADVI fit are independent (rstan::vb reports no R-hat or ESS)",
           lambda fit, ctx: fit.summary(_alpha_sub_1(fit, ctx.K), lp=not ctx.pooled),
@@ -336,6 +354,12 @@ MODIFIERS = (       # (option, the options of which it needs one, what it is tol
      "loo_moment_match_cov needs loo_moment_match: it is the covariance step of the matching of its cells"),
     ("exact_loo_moment_match_cov", ("exact_loo_moment_match",),
      "exact_loo_moment_match_cov needs exact_loo_moment_match: it is the covariance step of the matching of its cells"),
+    ("approximation_loo_moment_match", ("check_approximation_loo",),
+     "approximation_loo_moment_match needs check_approximation_loo: it matches the moments of the cells whose k-hat its PSIS-LOO "
+     "finds too high"),
+    ("exact_approximation_loo_moment_match", ("exact_approximation_loo_intervals",),
+     "exact_approximation_loo_moment_match needs exact_approximation_loo_intervals: it matches the moments of the cells whose "
+     "k-hat their PSIS finds too high"),
 )
 LOO_MOMENT_MATCH_MCSE = ("loo_mcse cannot be combined with loo_moment_match: the Monte-Carlo standard error and n_eff are those of "
                          "plain PSIS weights and are not given for a matched cell")
@@ -412,6 +436,8 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                  exact_loo_moment_match_split=False,
                  loo_moment_match_cov=False,
                  exact_loo_moment_match_cov=False,
+                 approximation_loo_moment_match=False,
+                 exact_approximation_loo_moment_match=False,
                  per_sample="lds"):
     """One inference pass (discovery or test) of ppcseq on the GPU.
 
@@ -501,6 +527,17 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                       `res.exact_loo_intervals` then carries `transform` in place of `scale`, and `cov_iterations`. Free to
                       combine with exact_loo_moment_match_split. devices=[...]: over the pooled chains. Needs
                       exact_loo_moment_match.
+    approximation_loo_moment_match  True: `res.approximation_loo` comes from Fit.loo_moment_match_approximate_posterior: the cells
+                      whose k-hat exceeds loo_threshold get the gene-local moment matching of loo_moment_match under the weights
+                      of the approximation (no split transformation, no covariance step: a matched k-hat is necessary, not
+                      sufficient, and says nothing of a mismatch in the hyper-parameters, which an overall k-hat that is itself
+                      too high reports); the result then also carries
+                      `khat_before`, `iterations`, `scale`, `shift` and `k_threshold`, and the k-hat warning reads the final
+                      `khat`. Flags and frame are those of the call without it. Needs check_approximation_loo.
+    exact_approximation_loo_moment_match  True: `res.exact_approximation_loo_intervals` comes from
+                      Fit.loo_predict_exact_moment_match_approximate_posterior: the interval and tail probabilities of those
+                      cells are taken under the matched weights at the matched draws; the result carries the same further keys.
+                      Flags and frame are those of the call without it. Needs exact_approximation_loo_intervals.
     per_sample        "lds" | "stream" | "auto": where the log-likelihood kernel keeps the per-sample constants, for every model
                       this pass creates (_lib.Model). "lds" refuses a design whose S * C doubles do not fit LDS beside the
                       tables (S <= 8 704 at two columns, 1 088 at sixteen); "auto" streams them from global memory there.
@@ -571,7 +608,10 @@ def do_inference(counts, X, exposure_rate, how_many_to_check, *,
                                               loo_moment_match_split=bool(checks.get("loo_moment_match_split", False)),
                                               exact_loo_moment_match_split=bool(checks.get("exact_loo_moment_match_split", False)),
                                               loo_moment_match_cov=bool(checks.get("loo_moment_match_cov", False)),
-                                              exact_loo_moment_match_cov=bool(checks.get("exact_loo_moment_match_cov", False))),
+                                              exact_loo_moment_match_cov=bool(checks.get("exact_loo_moment_match_cov", False)),
+                                              approximation_loo_moment_match=bool(checks.get("approximation_loo_moment_match", False)),
+                                              exact_approximation_loo_moment_match=bool(
+                                                  checks.get("exact_approximation_loo_moment_match", False))),
                                   checks, res)
         for msg in msgs:
             warnings.warn(msg, RuntimeWarning, stacklevel=2)
@@ -670,7 +710,10 @@ def pooled_summary(counts, X, exposure_rate, K, draws_checked, *, lambda_mu_mu, 
                                               loo_moment_match_split=bool(checks.get("loo_moment_match_split", False)),
                                               exact_loo_moment_match_split=bool(checks.get("exact_loo_moment_match_split", False)),
                                               loo_moment_match_cov=bool(checks.get("loo_moment_match_cov", False)),
-                                              exact_loo_moment_match_cov=bool(checks.get("exact_loo_moment_match_cov", False))),
+                                              exact_loo_moment_match_cov=bool(checks.get("exact_loo_moment_match_cov", False)),
+                                              approximation_loo_moment_match=bool(checks.get("approximation_loo_moment_match", False)),
+                                              exact_approximation_loo_moment_match=bool(
+                                                  checks.get("exact_approximation_loo_moment_match", False))),
                                   checks, res)
         finally:
             fit.close()

@@ -130,7 +130,8 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                       check_approximation_loo=False, check_approximation_loo_intervals=False, exact_intervals=False,
                       exact_loo_intervals=False, exact_approximation_loo_intervals=False, exact_loo_moment_match=False,
                       loo_moment_match_split=False, exact_loo_moment_match_split=False, loo_moment_match_cov=False,
-                      exact_loo_moment_match_cov=False, per_sample="lds"):
+                      exact_loo_moment_match_cov=False, approximation_loo_moment_match=False,
+                      exact_approximation_loo_moment_match=False, per_sample="lds"):
     """Mirror of ppcseq::identify_outliers (R/methods.R:74-367): same arguments, same defaults.
 
     data is a tidy pandas DataFrame (one row per transcript x sample); column arguments are strings. As in the
@@ -169,6 +170,10 @@ def identify_outliers(data, formula="~ 1", sample="sample", transcript="transcri
                                                      the same attrs
     `exact_loo_moment_match_cov` = True           -> exact_loo_moment_match reads Fit.loo_predict_exact_moment_match_cov (the
                                                      covariance step); in the same attrs
+    `approximation_loo_moment_match` = True (ADVI) -> check_approximation_loo's results come from
+                                                     Fit.loo_moment_match_approximate_posterior; in the same attrs
+    `exact_approximation_loo_moment_match` = True (ADVI) -> exact_approximation_loo_intervals' results come from
+                                                     Fit.loo_predict_exact_moment_match_approximate_posterior; in the same attrs
     `per_sample` = "lds" | "stream" | "auto": where the log-likelihood kernel keeps the per-sample constants, for every model of
     both passes (inference.do_inference; "auto" lifts the bound that LDS puts on the number of samples). Passes over several ranks
     (ppcseq_amd.distributed) take "lds" only.
